@@ -1,29 +1,35 @@
 #!/usr/bin/env python
 """Benchmark of the Noise Flow hot path on MI355X — driver contract.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: either under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`, or plain
     `python bench.py --gpus N`, which then launches its own N ranks that way on a free local port)
+
+A plain run sets up, warms up, times exactly K steps in one block and prints the result line.  Everything else the line
+can carry (the sections below, the parity check against the CPU oracle, the CPU baseline) runs only with --full.
+--dump-outputs DIR writes what the timed path computed to DIR/*.npy after the timed steps (N = 1: the per-patch NLL of the
+last step and the (sum nll, sum sd_z, count) accumulated over the K timed steps; N > 1: the last evaluation's
+(mean nll, mean sd_z, count)).  The inputs are a pure function of the arguments, so two builds can be compared file for file.
 
 N = 1 (the headline, BASELINE configs[1] — the configuration the metric is quoted on): a "step" is one
 pass of the fused likelihood-direction kernel (per-patch NLL written to HBM + log|det J| + batch sums)
 over ONE batch of 1024 synthetic 32x32x4 raw patches with the shipped Noise Flow checkpoint, inputs
-resident in HBM.  With --steps < 200 the K-step block is timed R = 11 times back to back and the MEDIAN
-block is reported (a 20-step block is ~1.1 ms of device time; one block is a noisy sample).
+resident in HBM.
 
 N > 1 (BASELINE configs[3]): a "step" is one COMPLETE evaluation of the 2^20-patch range, sharded in
 contiguous blocks of the patch index over the ranks (strong scaling: the total work is fixed).  Every
 rank keeps its block resident in HBM (34 GB / N), evaluates it with the persistent fused kernel and the
 evaluation ends with ONE RCCL all-reduce of (sum nll, sum sd_z, count) — 24 bytes, the only collective;
-no barrier and no read-back inside the timed region.  NF_BENCH_FORCE_DIST=1 runs this leg on one rank.  The same line
-carries BASELINE configs[4] (2^18 patches of 64x64x4, fp16 coupling CNN / fp32 log-det, sharded the same way) as the nested
-section `fp16_cnn_64x64_sharded` with its own roofline; `--config c5` makes it the headline instead.  `cpu_baseline` is timed
-on rank 0 after the timed regions.
+no barrier and no read-back inside the timed region.  NF_BENCH_FORCE_DIST=1 runs this leg on one rank.  With --full the
+same line carries BASELINE configs[4] (2^18 patches of 64x64x4, fp16 coupling CNN / fp32 log-det, sharded the same way) as the
+nested section `fp16_cnn_64x64_sharded` with its own roofline; `--config c5` makes it the headline instead.  With --full
+`cpu_baseline` is timed on rank 0 after the timed regions.
 
 Patches are a pure function of (seed, global patch index), so any sharding evaluates the same data.
 Rank 0 prints ONE JSON line.  Besides the contract keys it carries
   roofline      the dominant kernel against the dense fp32 matrix/vector peak (the binding roofline:
                 algorithmic flops / wall-clock step time), with the HBM view nested
+and, with --full only,
   cpu_baseline  CPU ports of the reference arithmetic (oracle/): fused plain-C/OpenMP (the
                 reported value) and the op-per-layer torch-CPU restatement of the TF1 graph,
                 timed on this box's host cores on bounded samples (N = 1 only)
@@ -88,7 +94,7 @@ def _usable_cores(threads: int) -> int:
     return int(n)
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: 0.11 s of timed work after 13 ms of warm-up — a 20-step warm-up (1.3 ms) ends before the
@@ -111,9 +117,23 @@ def parse_args():
                          "a short W does not leave the GPU at its idle clocks (0 disables)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target duration of the CPU-baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no extra sections (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra sections, the parity check against the CPU oracle and the CPU baseline "
+                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed to DIR/<name>.npy")
     ap.add_argument("--seed", type=int, default=0)
-    return ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def dump_outputs(out_dir, arrays) -> None:
+    """Write {name: array} as out_dir/<name>.npy (float32 stays float32, every other dtype becomes float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def _kernel_source_sha() -> str:
@@ -391,8 +411,10 @@ def sharded_leg(ctx):
     head = "c5" if args.config == "c5" else "c4"
     spec = sharded_workload(head, args.total_patches)
     run = _run_sharded(ctx, spec, K, Wm)
+    if args.dump_outputs and rank == 0:                # the last evaluation's all-reduced (mean nll, mean sd_z, count)
+        dump_outputs(args.dump_outputs, {"mean_nll_sd_z_count": run["res"]["results"][-1]})
     nested = None
-    if head == "c4":                                   # BASELINE configs[4] rides along as a nested section
+    if head == "c4" and args.full:                     # BASELINE configs[4] rides along as a nested section
         spec5 = sharded_workload("c5", max(0, args.total_patches // 4))
         k5 = max(1, min(K, 10))
         try:
@@ -425,7 +447,7 @@ def sharded_leg(ctx):
         out["fp16_cnn_64x64_sharded"] = {"error": "%s: %s" % (type(nested).__name__, nested)}
     # CPU baseline: rank 0 only, AFTER the timed regions (the other ranks wait in main()'s closing barrier)
     out["cpu_baseline"] = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from noise_flow_amd.patches import synth_patches
         xs, ys = synth_patches(args.seed, 0, 1024, device=ctx["local_rank"])       # patches [0, 1024) of configs[3]'s range
         out["cpu_baseline"] = _cpu_baseline(args, ctx["variables"], xs.cpu().numpy(), ys.cpu().numpy(), 1024)
@@ -444,7 +466,7 @@ def single_gpu_leg(ctx):
     args, local_rank, dev, model, variables = ctx["args"], ctx["local_rank"], ctx["dev"], ctx["model"], ctx["variables"]
     lib = _lib.load()
     B, K, Wm = args.batch, args.steps, args.warmup
-    R = 1 if K >= 200 else 11               # short blocks are repeated and the median block reported
+    R = 1                                   # exactly K timed steps: one K-step block
     cond = _lib.nf_cond(100.0, 2.0, 0.000479, 0.000002)      # ISO 100, S6 (train_noise_flow.py:143-147)
 
     # ---- resident synthetic data: batch j holds patches [j*B, +B) ----
@@ -495,9 +517,13 @@ def single_gpu_leg(ctx):
     assert int(round(s[2])) == B * K * R, (s, B * K * R)
     value = B * K / elapsed
     ms_step = 1e3 * elapsed / K
+    if args.dump_outputs:
+        # what a caller of nf_nll receives: the per-patch NLL of the last timed step (batch (K-1) % pool) and the
+        # (sum nll, sum sd_z, count) the K timed steps accumulated
+        dump_outputs(args.dump_outputs, {"nll": nll_buf.cpu().numpy(), "sums": s})
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         for name, fn in (("two_streams", _two_streams), ("sampling", _sampling), ("fp16_cnn_64x64", _fp16_cnn),
                          ("wide_cnn", _wide_cnn), ("sharded_1m", _sharded_1m), ("training", _training),
                          ("large_patches", _large_patches)):
@@ -506,19 +532,20 @@ def single_gpu_leg(ctx):
             except Exception as e:           # the headline metric must not depend on an optional section
                 extras[name] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    # ---- parity + CPU baseline (oracle/ is the checker, never the product) ----
-    from oracle.nf_oracle import NoiseFlowOracle
-    x0, y0 = batches[0]
-    nb = 64
-    nll_gpu, _ = model._loss(x0[:nb], y0[:nb], [0.0], [0.0], [100.0], [2.0])
-    ref = NoiseFlowOracle(ARCH_LABEL, variables).nll(x0[:nb].cpu().numpy(), y0[:nb].cpu().numpy(), 100.0, 2.0)[0]
-    g = nll_gpu.double().cpu().numpy()
-    nll_check = {"patches": nb, "gpu_mean_nll": float(g.mean()), "cpu_fp64_mean_nll": float(ref.mean()),
-                 "rel_err_mean": float(abs(g.mean() - ref.mean()) / abs(ref.mean())),
-                 "max_rel_err_per_patch": float(np.max(np.abs(g - ref) / np.abs(ref))), "tolerance": 1e-5}
-    cpu_baseline = None
-    if not args.no_cpu_baseline:
-        cpu_baseline = _cpu_baseline(args, variables, x0.cpu().numpy(), y0.cpu().numpy(), B)
+    nll_check = cpu_baseline = None
+    if args.full:
+        # ---- parity + CPU baseline (oracle/ is the checker, never the product) ----
+        from oracle.nf_oracle import NoiseFlowOracle
+        x0, y0 = batches[0]
+        nb = 64
+        nll_gpu, _ = model._loss(x0[:nb], y0[:nb], [0.0], [0.0], [100.0], [2.0])
+        ref = NoiseFlowOracle(ARCH_LABEL, variables).nll(x0[:nb].cpu().numpy(), y0[:nb].cpu().numpy(), 100.0, 2.0)[0]
+        g = nll_gpu.double().cpu().numpy()
+        nll_check = {"patches": nb, "gpu_mean_nll": float(g.mean()), "cpu_fp64_mean_nll": float(ref.mean()),
+                     "rel_err_mean": float(abs(g.mean() - ref.mean()) / abs(ref.mean())),
+                     "max_rel_err_per_patch": float(np.max(np.abs(g - ref) / np.abs(ref))), "tolerance": 1e-5}
+        if not args.no_cpu_baseline:
+            cpu_baseline = _cpu_baseline(args, variables, x0.cpu().numpy(), y0.cpu().numpy(), B)
 
     traffic, traffic_src = _traffic()
     # roofline from the WALL-CLOCK step time (what the driver's clock can confirm); the HIP-event figure is nested

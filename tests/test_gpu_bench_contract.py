@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--ramp-ms", "0",
-                          "--no-cpu-baseline"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                          "--no-cpu-baseline", "--full"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     lines = [l for l in out.stdout.decode().split("\n") if l.strip()]
     assert len(lines) == 1, lines
@@ -50,6 +50,42 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert w512["finite"] and w512["value"] > 0 and "nf_gemm_kernel" in w512["kernel_path"] and w512["roofline"]["frac"] > 0.3
     lp = d["large_patches"]          # 256x256 images as overlapping tiles
     assert lp["finite"] and lp["segments"] >= 1 and lp["pixels_per_s"] > 1e9, lp
+
+
+def test_bench_plain_run_times_exactly_k_steps_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the headline only, exactly --steps steps, and --dump-outputs writes what the timed path
+    computed: the per-patch NLL of the last timed step and the sums the K timed steps accumulated."""
+    import numpy as np
+    K, Wm, B = 7, 3, 1024
+    out_dir = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(Wm),
+                          "--dump-outputs", str(out_dir)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    lines = [l for l in out.stdout.decode().split("\n") if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == K and d["warmup"] == Wm and d["timing"]["repetitions"] == 1 and len(d["timing"]["block_ms"]) == 1
+    assert abs(d["ms_per_step"] - d["timing"]["block_ms"][0] / K) <= 1e-9 * d["ms_per_step"]
+    assert abs(d["value"] - B / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for sec in ("two_streams", "sampling", "fp16_cnn_64x64", "wide_cnn", "sharded_1m", "training", "large_patches"):
+        assert sec not in d, sec
+    assert d["cpu_baseline"] is None and d["nll_check"] is None
+    nll, sums = np.load(str(out_dir / "nll.npy")), np.load(str(out_dir / "sums.npy"))
+    assert nll.dtype == np.float32 and nll.shape == (B,) and np.isfinite(nll).all()
+    assert sums.dtype == np.float64 and sums.shape == (3,) and int(round(sums[2])) == B * K
+    assert abs(sums[0] / sums[2] - d["mean_nll"]) <= 1e-12 * abs(d["mean_nll"])
+    # the last timed step evaluated batch (K - 1) % pool = patches [(K - 1) * B, K * B) of the seeded range
+    from conftest import SHIPPED_CKPT
+    from noise_flow_amd import NoiseFlow, default_hps
+    from noise_flow_amd.ckpt import load_checkpoint
+    from noise_flow_amd.patches import synth_patches
+    m = NoiseFlow([32, 32, 4], False, default_hps(), variables=load_checkpoint(SHIPPED_CKPT))
+    x, y = synth_patches(0, (K - 1) * B, B, device=0)
+    want, _ = m._loss(x, y, [0.0], [0.0], [100.0], [2.0])
+    want = want.double().cpu().numpy()
+    assert np.abs(nll - want).max() <= 1e-5 * np.abs(want).max()
 
 
 def test_bench_multi_rank_leg_under_torchrun_on_one_gpu():
@@ -89,12 +125,12 @@ def test_bench_multi_rank_leg_under_torchrun_on_one_gpu():
 
 def test_bench_multi_rank_leg_without_torchrun_self_spawns():
     """Plain `python bench.py --gpus 2` (no torch.distributed.run, no WORLD_SIZE): bench.py launches its own two ranks.  On this
-    one-GPU box both ranks share GPU 0 and gloo carries the all-reduce.  The line carries configs[3] as the headline, configs[4]
-    (64x64, fp16 CNN, sharded the same way) as a nested section with its own roofline, and rank 0's CPU baseline."""
+    one-GPU box both ranks share GPU 0 and gloo carries the all-reduce.  With --full the line carries configs[3] as the headline,
+    configs[4] (64x64, fp16 CNN, sharded the same way) as a nested section with its own roofline, and rank 0's CPU baseline."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(NF_BENCH_BACKEND="gloo", NF_BENCH_ONE_GPU="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--total-patches", "32768", "--ramp-ms", "0", "--cpu-seconds", "2"], cwd=ROOT, env=env,
+                          "--total-patches", "32768", "--ramp-ms", "0", "--cpu-seconds", "2", "--full"], cwd=ROOT, env=env,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().split("\n") if l.strip().startswith("{")]

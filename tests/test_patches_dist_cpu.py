@@ -209,6 +209,20 @@ def test_bench_launches_its_own_ranks_when_not_under_torchrun():
         assert not [l for l in out.stdout.decode().split("\n") if l.strip().startswith("{")]
 
 
+def test_bench_options_plain_by_default(tmp_path):
+    """A plain run is lean (--full is off unless asked for) and dumps nothing unless --dump-outputs names a directory;
+    dump_outputs writes float32 as float32 and everything else as float64."""
+    import numpy as np
+    bench = _bench_module()
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    a = bench.parse_args(["--steps", "5", "--full", "--dump-outputs", str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    bench.dump_outputs(str(tmp_path / "d"), {"a": np.ones(3, np.float32), "b": (1.5, 2.5, 3)})
+    a32, b64 = np.load(str(tmp_path / "d" / "a.npy")), np.load(str(tmp_path / "d" / "b.npy"))
+    assert a32.dtype == np.float32 and b64.dtype == np.float64 and b64.tolist() == [1.5, 2.5, 3.0]
+
+
 def test_sharded_workload_specs():
     bench = _bench_module()
     c4, c5 = bench.sharded_workload("c4"), bench.sharded_workload("c5")

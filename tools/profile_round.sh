@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --steps 20 --warmup 5"
+BENCH="python $R/bench.py --steps 20 --warmup 5 --full"
 if [ "${2:-all}" = "traffic" ]; then
   # bash tools/profile_round.sh <tag> traffic: only the HBM-traffic passes of the headline kernel + the bench line that quotes
   # them (after a change to the kernel sources that cannot have changed the other evidence, e.g. a comment)
