@@ -133,6 +133,8 @@ typedef struct nf_config {
                               for full 32x32 / 64x64 patches (BASELINE configs[4]), any other shape on
                               the width-32 kernel, zero-padded; widths 8 / 16 / 32: any patch up to 64x64
                               (v_mfma_f32_32x32x16_f16); widths 33 .. 512: any patch up to 64x64. */
+#define NF_CFG_EXACT_FP32 2 /* width 4, full 32x32 patches: keep the exact-fp32 kernel (every conv on
+                              v_mfma_f32_4x4x1) instead of the default split-bf16 one (NF_PATH_SPLIT_BF16) */
 
 /* Per-call conditioning: ONE value per call, not per patch — the reference
  * feeds length-1 lists (MiniBatchSampler.py:61-64, NoiseFlowWrapper.py:85-86).
@@ -416,6 +418,7 @@ int nf_fold_layout(const nf_config *cfg, const nf_layer_desc *layers,
 #define NF_PATH_WIDE32_FP16 5   /* NF_CFG_FP16_CNN at width 8 / 16 / 32 (and width 4 off the full shapes): v_mfma_f32_32x32x16_f16 */
 #define NF_PATH_GEMM 6          /* widths 33 .. 512: LDS-staged GEMM on v_mfma_f32_32x32x2_f32 (csrc/nf_gemm.hip) */
 #define NF_PATH_GEMM_FP16 7     /* NF_CFG_FP16_CNN at widths 33 .. 512: the same on v_mfma_f32_32x32x16_f16 (csrc/nf_gemm16.hip) */
+#define NF_PATH_SPLIT_BF16 8    /* width 4, full 32x32 patches, fp32: l_1 / l_last as "bf16 x 6" on v_mfma_f32_16x16x32_bf16 */
 /* Both GEMM families have two variants, picked by nf_create from the padded width: weights resident in LDS with one pixel tile per
  * wavefront (<= 128) or bands of pixels with the weights streamed from L2 (256 / 512); the environment variables NF_GEMM=a /
  * NF_GEMM16=a (read at nf_create) force the band variant everywhere — an A/B aid, like NF_KERNEL=valu. */

@@ -23,6 +23,7 @@ NF_LAYER_GAIN1, NF_LAYER_GAIN2, NF_LAYER_GAIN3 = 12, 13, 14
 NF_LAYER_CONV1X1_NONE, NF_LAYER_CONV1X1_LU2, NF_LAYER_PERMUTE = 15, 16, 17
 
 NF_CFG_FP16_CNN = 1
+NF_CFG_EXACT_FP32 = 2
 
 NF_ACCUMULATE = 1
 NF_NO_PRIOR = 2
@@ -175,6 +176,7 @@ EXPORTED_SYMBOLS = (
     "nf_trainer_get_params", "nf_trainer_set_params", "nf_trainer_steps", "nf_trainer_set_sync",
 )
 NF_PATH_SCALAR, NF_PATH_MFMA4, NF_PATH_FP16, NF_PATH_WIDE32, NF_PATH_WIDE16, NF_PATH_WIDE32_FP16, NF_PATH_GEMM, NF_PATH_GEMM_FP16 = 0, 1, 2, 3, 4, 5, 6, 7
+NF_PATH_SPLIT_BF16 = 8
 NF_HOST_F32, NF_HOST_F64 = 0, 1
 NF_OPT_ADAM = 0
 NF_OPT_MOMENTUM = 1

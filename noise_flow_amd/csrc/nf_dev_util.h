@@ -15,6 +15,8 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 typedef _Float16 v4h __attribute__((ext_vector_type(4)));
 typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef _Float16 v2h __attribute__((ext_vector_type(2)));
+typedef __bf16 nf_v8bf __attribute__((ext_vector_type(8)));
+typedef __bf16 nf_v2bf __attribute__((ext_vector_type(2)));
 
 // --------------------------------------------------------------------------
 // Philox4x32-10 counter-based RNG (Salmon et al. 2011) — keyed by

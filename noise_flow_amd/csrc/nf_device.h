@@ -146,6 +146,42 @@ __host__ __device__ constexpr int nf11_l3_row(int gk, int m3) { return 2 * (gk &
 #endif
 __host__ __device__ constexpr int nf11_pitch(int side) { return side == 64 ? NF11_PITCH64 : 48; }   // tile row pitch in pixels
 
+// ---- split-bf16 layout (fp32 results, width 4, full 32x32 patches; nf_flow_kernel PREC = 3) -----------------------------------
+// l_1 and l_last run as "bf16 x 6" on v_mfma_f32_16x16x32_bf16 with the NF11_* unit / lane geometry: every fp32 operand is split
+// into three bf16 pieces v = v_h + v_m + v_l (round to nearest even, each piece the rounded remainder of the one before), and the
+// six products hh, hm, mh, hl, lh, mm are accumulated in fp32 — the dropped ones are below 2^-26 of |a b|.  l_2 and the 1x1 mixes
+// stay exact fp32 on v_mfma_f32_4x4x1.
+// LDS: one 24-byte-per-pixel buffer, three regions R0 R1 R2 of [34 x NF12_PITCH] 8-byte slots, shared by the two exchanges:
+//   z0 (2 channels):         R0 slot = (z_h, z_m), R1 slot = (z_l, z_h)  (one bf16x2 word each)
+//   relu(h2) (4 channels):   R_p slot = piece p (4 x bf16)
+// so that a 16-byte read of two slots is a finished B operand: l_1 needs TWO instructions per product pair (a K slot = 2 window
+// columns), and the pairs are (a_h | a_h) x R0 = hh + hm, (a_m | a_m) x R0 = mh + mm, (a_h | a_l) x R1 = hl + lh.
+// l_1 element e of K slot gk, instruction `half`: window row nf11_l1_row(gk), column 2 half + (e >> 2), channel e & 1, and word
+// (e >> 1) & 1 of the slot.  l_last as NF11 (element e = 4 px + c), one instruction per piece pair and m3.
+//   LDS part  MIX  Mt [4][4] (as NF2), COUPLING E [16][4] @0, B1 @64, B2 @68, S @72 (as NF2_*), W2t [4][4] @76 (as NF2_CPL_W2T),
+//             AOFF @92 (int: float offset of the coupling's A image from the start of the block), pad
+//   global    A image of a coupling (behind the LDS part, NOT staged in LDS: each wavefront loads it into registers per coupling,
+//             L1 / L2 hits), 32-bit words:
+//             A1 [3 pair][2 half][64 lanes][4]  pair 0: (a_h | a_h), 1: (a_m | a_m), 2: (a_h | a_l) by the slot word
+//             A3 [3 piece][2 m3][64 lanes][4]   @1536
+#define NF12_CPL_E 0
+#define NF12_CPL_B1 64
+#define NF12_CPL_B2 68
+#define NF12_CPL_S 72
+#define NF12_CPL_W2T 76
+#define NF12_CPL_AOFF 92
+#define NF12_CPL_SIZE 96
+#define NF12_A_A1 0
+#define NF12_A_A3 1536
+#define NF12_A_SIZE 3072
+#define NF12_PITCH 34             // slots per tile row
+// column pair of lane column n (the pixel columns 2 nf12_col(n) + {0, 1}): ds_read_b128 serves a wavefront in the lane groups
+// {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+ 32), i.e. lane columns {0-3, 12-15} of one K slot with {4-11} of the next, whose
+// window row is 2 rows (2 x 17 = 2 bank quads mod 16 at pitch 34) further: even pairs for the one set, odd for the other make the
+// 16 reads of a group hit 16 distinct quads
+__host__ __device__ constexpr int nf12_col(int n) { return ((n + 12) & 15) < 8 ? 2 * ((n + 12) & 15) : 2 * (((n + 12) & 15) - 8) + 1; }
+#define NF12_MAX_FLOATS 2048      // the LDS part (8 KiB): tiles 27.1 KiB + this keep 4 workgroups per CU
+
 // ---- wide-CNN layout (coupling width 32, nf_wide.hip) ------------------------------------------
 // The three convs of a width-32 coupling CNN run on v_mfma_f32_32x32x2_f32 with the PIXELS on the N
 // axis (a tile = 32 consecutive pixels of one image row, lanes n = lane & 31; the two lane halves
@@ -265,6 +301,7 @@ enum : uint32_t {
     // img_H x img_W image, see NfLaunch::tile_* below
     NF_K_TILED     = 256u,
     NF_K_FP16_BIG  = 512u, // with NF_K_FP16_CNN: the parameter block is the NF11_* layout (v_mfma_f32_16x16x32_f16)
+    NF_K_SPLIT_BF16 = 1024u, // the parameter block is the NF12_* layout (split-bf16 convs, fp32 results); n_params = its LDS part
 };
 
 // ---- images beyond 64 x 64: overlapping tiles -------------------------------------------------------

@@ -410,6 +410,58 @@ void relayout_coupling_v11(const float *v1, float *out, bool with_a2)
     }
 }
 
+// split-bf16 re-layout (nf_device.h, NF12_*): v = p[0] + p[1] + p[2], each piece the round-to-nearest-even bf16 of what the pieces
+// before it left (the same split the kernel applies to its activations; every subtraction is exact in fp32)
+void split_bf16x3_host(float v, uint16_t (&p)[3])
+{
+    float r = v;
+    for (int q = 0; q < 3; ++q) {
+        uint32_t u;
+        memcpy(&u, &r, 4);
+        const uint32_t hb = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;   // finite values only (folded weights)
+        p[q] = (uint16_t)hb;
+        const uint32_t back = hb << 16;
+        float f;
+        memcpy(&f, &back, 4);
+        r -= f;
+    }
+}
+
+// The LDS part of a coupling (E, B1, B2, S, W2t: the fp32 values of NF2_*) and its A image (l_1 / l_last weights split into three
+// bf16 pieces, in the order the lanes of v_mfma_f32_16x16x32_bf16 fetch them).  AOFF is filled in by the caller.
+void relayout_coupling_v12(const float *v1, float *lds, uint32_t *img)
+{
+    std::vector<float> v2(NF2_CPL_SIZE);
+    relayout_coupling_v2(v1, v2.data());   // the exact-fp32 kernel's values: E and W3 carry 2 log2(e) in their raw columns
+    memcpy(lds + NF12_CPL_E, v2.data() + NF2_CPL_E, 64 * sizeof(float));
+    memcpy(lds + NF12_CPL_B1, v2.data() + NF2_CPL_B1, 4 * sizeof(float));
+    memcpy(lds + NF12_CPL_B2, v2.data() + NF2_CPL_B2, 4 * sizeof(float));
+    memcpy(lds + NF12_CPL_S, v2.data() + NF2_CPL_S, 4 * sizeof(float));
+    memcpy(lds + NF12_CPL_W2T, v2.data() + NF2_CPL_W2T, 16 * sizeof(float));
+    for (int q = NF12_CPL_AOFF; q < NF12_CPL_SIZE; ++q) lds[q] = 0.0f;
+    uint16_t *a1 = reinterpret_cast<uint16_t *>(img + NF12_A_A1);
+    uint16_t *a3 = reinterpret_cast<uint16_t *>(img + NF12_A_A3);
+    auto tap_ok = [](int d) { return d >= 0 && d <= 2; };
+    for (int l = 0; l < 64; ++l) {
+        const int gk = l >> 4, m = l & 15, a = m >> 3, p = (m >> 2) & 1, j = m & 3;
+        for (int e = 0; e < 8; ++e) {
+            for (int half = 0; half < 2; ++half) {   // l_1: window row nf11_l1_row(gk), column 2 half + (e >> 2), slot word (e >> 1) & 1
+                const int wc = 2 * half + (e >> 2), ws = (e >> 1) & 1, c = e & 1, di = nf11_l1_row(gk) - a, dj = wc - p;
+                uint16_t pc[3] = {0, 0, 0};
+                if (tap_ok(di) && tap_ok(dj)) split_bf16x3_host(v2[NF2_CPL_W1T + 24 * j + 8 * di + 2 * dj + c], pc);
+                const uint16_t pick[3] = {pc[0], pc[1], ws == 0 ? pc[0] : pc[2]};   // pairs (h | h), (m | m), (h | l)
+                for (int pr = 0; pr < 3; ++pr) a1[((pr * 2 + half) * 64 + l) * 8 + e] = pick[pr];
+            }
+            for (int m3 = 0; m3 < 2; ++m3) {   // l_last: as NF11 (element e = 4 px + c of window row nf11_l3_row(gk, m3), column pair gk >> 1)
+                const int wc = 2 * (gk >> 1) + (e >> 2), c = e & 3, di = nf11_l3_row(gk, m3) - a, dj = wc - p;
+                uint16_t pc[3] = {0, 0, 0};
+                if (tap_ok(di) && tap_ok(dj)) split_bf16x3_host(v2[NF2_CPL_W3T + 36 * j + (di * 3 + dj) * 4 + c], pc);
+                for (int q = 0; q < 3; ++q) a3[((q * 2 + m3) * 64 + l) * 8 + e] = pc[q];
+            }
+        }
+    }
+}
+
 // Wide-CNN re-layout (nf_device.h, NF4_*; coupling width 32): every weight in the order the lanes of
 // v_mfma_f32_32x32x2_f32 / v_mfma_f32_4x4x1 fetch their A operands (nf_wide.hip).
 // `w` = the coupling's own width (8, 16 or 32): narrower CNNs are zero-padded to 32 hidden channels (exact: a padded
@@ -842,6 +894,9 @@ struct Built {
     std::vector<float> block;
     NfProgram prog2;             // matrix-core (MFMA) layout, width 4 only
     std::vector<float> block2;   // empty when unavailable
+    NfProgram prog9;             // split-bf16 layout (NF12_*): width 4 in fp32 on full 32x32 patches unless NF_CFG_EXACT_FP32
+    std::vector<float> block9;   // the LDS part (n_lds9 floats), then the couplings' A images
+    int n_lds9 = 0;
     NfProgram prog3;             // fp16-CNN layout (NF_CFG_FP16_CNN), width 4 only
     std::vector<float> block3;
     bool fp16_big = false;       // block3 is the NF11_* layout (v_mfma_f32_16x16x32_f16) instead of NF3_* (4x4x4)
@@ -935,7 +990,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     out.tile_w = tw;
     out.segs.clear();
     if (cfg->n_layers < 1) return fail(NF_EINVAL, "n_layers must be >= 1");
-    if (cfg->flags & ~NF_CFG_FP16_CNN) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
+    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
     const double HW = (double)cfg->height * cfg->width;
 
     // intermediate list in NLL order
@@ -1140,6 +1195,49 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
         }
         if (out.block2.empty()) out.block2.assign(4, 0.0f);
         if (out.block2.size() > NF2_MAX_FLOATS) out.block2.clear();   // too large for LDS: scalar path only
+    }
+    // split-bf16 layout: the default kernel of the fp32 width-4 model on full 32x32 patches
+    out.block9.clear();
+    out.n_lds9 = 0;
+    memset(&out.prog9, 0, sizeof(out.prog9));
+    if (out.prog.width == 4 && !out.block2.empty() && cfg->height == 32 && cfg->width == 32 &&
+        !(cfg->flags & (NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32))) {
+        out.prog9.width = 4;
+        std::vector<uint32_t> img;
+        std::vector<int> aoff_at;   // LDS-part offsets of the couplings' AOFF fields
+        for (int i = 0; i < out.prog.n_ops; ++i) {
+            const NfOp &src = out.prog.ops[i];
+            NfOp &dst = out.prog9.ops[out.prog9.n_ops++];
+            dst.type = src.type;
+            dst.off = (int32_t)out.block9.size();
+            const float *v1 = out.block.data() + src.off;
+            if (src.type == NF_OP_MIX) {
+                for (int j = 0; j < 4; ++j)
+                    for (int c = 0; c < 4; ++c) out.block9.push_back(v1[c * 4 + j]);
+            } else if (src.type == NF_OP_COUPLING_FWD || src.type == NF_OP_COUPLING_REV) {
+                out.block9.resize(out.block9.size() + NF12_CPL_SIZE);
+                img.resize(img.size() + NF12_A_SIZE);
+                relayout_coupling_v12(v1, out.block9.data() + dst.off, img.data() + img.size() - NF12_A_SIZE);
+                aoff_at.push_back(dst.off + NF12_CPL_AOFF);
+            } else if (src.type == NF_OP_SCALE) {
+                out.block9.insert(out.block9.end(), v1, v1 + 4);
+            } else {
+                dst.off = src.off;   // conditioning slot
+            }
+        }
+        if (out.block9.empty()) out.block9.assign(4, 0.0f);
+        out.n_lds9 = (int)out.block9.size();   // a multiple of 4: every section is
+        for (size_t c = 0; c < aoff_at.size(); ++c) {
+            const int32_t off = out.n_lds9 + (int32_t)(c * NF12_A_SIZE);
+            memcpy(out.block9.data() + aoff_at[c], &off, 4);
+        }
+        const size_t n0 = out.block9.size();
+        out.block9.resize(n0 + img.size());
+        if (!img.empty()) memcpy(out.block9.data() + n0, img.data(), img.size() * 4);
+        if (out.n_lds9 > NF12_MAX_FLOATS) {   // LDS image too large for 4 workgroups per CU: the exact-fp32 kernel
+            out.block9.clear();
+            out.n_lds9 = 0;
+        }
     }
     out.block4.clear();
     memset(&out.prog4, 0, sizeof(out.prog4));
@@ -1378,6 +1476,8 @@ struct nf_handle {
     float *d_rev = nullptr;
     float *d_fwd2 = nullptr;   // matrix-core layout (null when unavailable)
     float *d_rev2 = nullptr;
+    float *d_fwd9 = nullptr;   // split-bf16 layout (NF12_*)
+    float *d_rev9 = nullptr;
     float *d_fwd3 = nullptr;   // fp16-CNN layout (NF_CFG_FP16_CNN)
     float *d_rev3 = nullptr;
     float *d_fwd4 = nullptr;   // wide-CNN layout (width 32)
@@ -1479,6 +1579,7 @@ int nf_fold_layout(const nf_config *cfg, const nf_layer_desc *layers, const floa
     case NF_PATH_WIDE16: pg = &b.prog6; blk = &b.block6; break;
     case NF_PATH_GEMM: pg = &b.prog7; blk = &b.block7; break;
     case NF_PATH_GEMM_FP16: pg = &b.prog8; blk = &b.block8; break;
+    case NF_PATH_SPLIT_BF16: pg = &b.prog9; blk = &b.block9; break;
     default: return fail(NF_EINVAL, "unknown kernel path %d", path);
     }
     if (blk->empty()) return fail(NF_EINVAL, "this model has no parameter block for kernel path %d", path);
@@ -1572,12 +1673,12 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
             return fail(NF_EINVAL, "NF_CFG_FP16_CNN: no half-precision kernel for this width / patch shape");
         }
     }
-    for (int d = 0; d < 14; ++d) {
-        const std::vector<float> &b2 = d == 0 ? h->fwd.block2 : d == 1 ? h->rev.block2 : d == 2 ? h->fwd.block3 : d == 3 ? h->rev.block3
+    for (int d = 0; d < 16; ++d) {
+        const std::vector<float> &b2 = d == 14 ? h->fwd.block9 : d == 15 ? h->rev.block9 : d == 0 ? h->fwd.block2 : d == 1 ? h->rev.block2 : d == 2 ? h->fwd.block3 : d == 3 ? h->rev.block3
                                        : d == 4 ? h->fwd.block4 : d == 5 ? h->rev.block4 : d == 6 ? h->fwd.block5 : d == 7 ? h->rev.block5
                                        : d == 8 ? h->fwd.block6 : d == 9 ? h->rev.block6 : d == 10 ? h->fwd.block7 : d == 11 ? h->rev.block7
                                        : d == 12 ? h->fwd.block8 : h->rev.block8;
-        float **dst = d == 0 ? &h->d_fwd2 : d == 1 ? &h->d_rev2 : d == 2 ? &h->d_fwd3 : d == 3 ? &h->d_rev3 : d == 4 ? &h->d_fwd4
+        float **dst = d == 14 ? &h->d_fwd9 : d == 15 ? &h->d_rev9 : d == 0 ? &h->d_fwd2 : d == 1 ? &h->d_rev2 : d == 2 ? &h->d_fwd3 : d == 3 ? &h->d_rev3 : d == 4 ? &h->d_fwd4
                       : d == 5 ? &h->d_rev4 : d == 6 ? &h->d_fwd5 : d == 7 ? &h->d_rev5 : d == 8 ? &h->d_fwd6 : d == 9 ? &h->d_rev6
                       : d == 10 ? &h->d_fwd7 : d == 11 ? &h->d_rev7 : d == 12 ? &h->d_fwd8 : &h->d_rev8;
         if (b2.empty()) continue;
@@ -1601,6 +1702,8 @@ int nf_destroy(nf_handle *h)
     if (h->d_rev) (void)hipFree(h->d_rev);
     if (h->d_fwd2) (void)hipFree(h->d_fwd2);
     if (h->d_rev2) (void)hipFree(h->d_rev2);
+    if (h->d_fwd9) (void)hipFree(h->d_fwd9);
+    if (h->d_rev9) (void)hipFree(h->d_rev9);
     if (h->d_fwd3) (void)hipFree(h->d_fwd3);
     if (h->d_rev3) (void)hipFree(h->d_rev3);
     if (h->d_fwd4) (void)hipFree(h->d_fwd4);
@@ -1942,6 +2045,15 @@ static int launch_resident(nf_handle *h, int direction, NfLaunch &a, hipStream_t
         return NF_OK;
     }
     const bool mc = d3 || (d2 && use_matrix_core());
+    float *d9 = direction == 0 ? h->d_fwd9 : h->d_rev9;
+    if (d9 && use_matrix_core() && !d3) {   // width 4, fp32, full 32x32 patches: split-bf16 convs (nf_device.h, NF12_*)
+        a.params = d9;
+        a.n_params = (int32_t)b.n_lds9;
+        a.flags |= NF_K_SPLIT_BF16;
+        hipError_t e = nf_launch_flow(b.prog9, a, h->n_cu, st, true);
+        if (e != hipSuccess) return fail_hip(e, what);
+        return NF_OK;
+    }
     a.params = d1;
     if (d3) {
         a.params = d3;
@@ -1998,6 +2110,7 @@ int nf_kernel_path(const nf_handle *h, int32_t direction)
     if ((direction == 0 ? h->d_fwd6 : h->d_rev6) && mcore) return NF_PATH_WIDE16;
     if ((direction == 0 ? h->d_fwd4 : h->d_rev4) && mcore) return NF_PATH_WIDE32;
     if (direction == 0 ? h->d_fwd3 : h->d_rev3) return NF_PATH_FP16;
+    if ((direction == 0 ? h->d_fwd9 : h->d_rev9) && use_matrix_core()) return NF_PATH_SPLIT_BF16;
     if ((direction == 0 ? h->d_fwd2 : h->d_rev2) && use_matrix_core()) return NF_PATH_MFMA4;
     return NF_PATH_SCALAR;
 }

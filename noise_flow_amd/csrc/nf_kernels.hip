@@ -115,6 +115,26 @@ __device__ __forceinline__ void stats_flush(const float (&s1)[WIDTH], const floa
     }
 }
 
+// split-bf16 mode (nf_device.h, NF12_*): x = x_h + x_m + x_l for two values at once, each piece the round-to-nearest-even bf16
+// of what the pieces before it left (v_cvt_pk_bf16_f32); the subtractions are exact, the remainder below 2^-24 |x|
+__device__ __forceinline__ void nf_split3(float x0, float x1, uint32_t &h, uint32_t &m, uint32_t &l)
+{
+    const nf_v2bf ph = {(__bf16)x0, (__bf16)x1};
+    x0 -= (float)ph[0];
+    x1 -= (float)ph[1];
+    const nf_v2bf pm = {(__bf16)x0, (__bf16)x1};
+    x0 -= (float)pm[0];
+    x1 -= (float)pm[1];
+    const nf_v2bf pl = {(__bf16)x0, (__bf16)x1};
+    h = __builtin_bit_cast(uint32_t, ph);
+    m = __builtin_bit_cast(uint32_t, pm);
+    l = __builtin_bit_cast(uint32_t, pl);
+}
+__device__ __forceinline__ v4f nf_mfma_bf16(const uint4 a, const uint4 b, const v4f c)
+{
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(nf_v8bf, a), __builtin_bit_cast(nf_v8bf, b), c, 0, 0, 0);
+}
+
 // --------------------------------------------------------------------------
 // The fused flow kernel.
 //   WIDTH   coupling CNN width
@@ -138,9 +158,11 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     static_assert(WIDTH % 4 == 0, "WIDTH must be a multiple of 4");
     static_assert(!MFMA || WIDTH == 4, "the matrix-core path is the width-4 specialisation");
     static_assert(PREC == 0 || (MFMA && FULL && PX == 4), "the fp16-CNN mode exists for full 2x2-blocked patches only");
+    static_assert(PREC != 3 || (THREADS == 256 && !TF && !BS), "the split-bf16 mode exists for full 32x32 patches only");
     constexpr bool H16 = PREC == 1;   // coupling-CNN convs on fp16 matrix cores (fp32 accumulate): v_mfma_f32_4x4x4_16b_f16
     constexpr bool HB = PREC == 2;    // the same on v_mfma_f32_16x16x32_f16 (nf_device.h, NF11_*)
-    constexpr bool HALF = PREC != 0;
+    constexpr bool SB = PREC == 3;    // fp32 results, l_1 / l_last as "bf16 x 6" on v_mfma_f32_16x16x32_bf16 (nf_device.h, NF12_*)
+    constexpr bool HALF = PREC == 1 || PREC == 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     // FULL = square patch that fills the workgroup exactly (32x32 or 64x64): the geometry is a
@@ -150,7 +172,7 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     const int H = FULL ? SIDE : a.H, W = FULL ? SIDE : a.W, HW = H * W;
     // row pitch of the plain row-major tiles; fp16 mode at 32x32: 48 entries so that the next
     // block row (2 tile rows down) starts a multiple of 128 B (half2) / 256 B (4 x half) away
-    const int Wp = HB ? nf11_pitch(SIDE) : (H16 && SIDE == 32) ? 48 : W + 2;
+    const int Wp = SB ? NF12_PITCH : HB ? nf11_pitch(SIDE) : (H16 && SIDE == 32) ? 48 : W + 2;
     const int tile_px = ((H + 2) * Wp + 1) & ~1;         // even -> 16-byte aligned sections
     // MFMA: a 4x4 identity behind the model (the `mix` of a coupling that has none in front: the pair loop below has ONE shape)
     [[maybe_unused]] const int ident_off = (a.n_params + 3) & ~3;
@@ -158,8 +180,8 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     // weight read of a coupling is then `coupling base + lane term` plus an immediate below 64 KiB (behind 63 KiB of tiles the
     // A3 / A2 operands were not, and cost a v_add_u32 each), while the tile accesses keep their compile-time immediates relative to
     // lane addresses that carry the (run-time) tile base
-    constexpr bool WFIRST = HB;
-    constexpr int TILE_WORDS = HALF ? 3 : 2 + WIDTH;                  // 32-bit words per tile pixel
+    constexpr bool WFIRST = HB || SB;
+    constexpr int TILE_WORDS = SB ? 6 : HALF ? 3 : 2 + WIDTH;          // 32-bit words per tile pixel
     constexpr int RED_WORDS = (6 * (THREADS / 64) + 3) & ~3;
     float *const tiles = WFIRST ? smem + ident_off + 16 : smem;
     float2 *const t0 = reinterpret_cast<float2 *>(tiles);  // z0 tile  [tile_px] float2
@@ -167,6 +189,10 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     // fp16-CNN mode: the same two tiles hold half2 / 4 x half per pixel, plain row-major
     uint32_t *const t0h = reinterpret_cast<uint32_t *>(tiles);         // [tile_px] half2
     uint2 *const thh = reinterpret_cast<uint2 *>(tiles + tile_px);     // [tile_px] 4 x half
+    // split-bf16 mode: three regions of [tile_px] 8-byte slots (nf_device.h, NF12_*)
+    [[maybe_unused]] uint2 *const sr0 = reinterpret_cast<uint2 *>(tiles);
+    [[maybe_unused]] uint2 *const sr1 = reinterpret_cast<uint2 *>(tiles + 2 * tile_px);
+    [[maybe_unused]] uint2 *const sr2 = reinterpret_cast<uint2 *>(tiles + 4 * tile_px);
     float *const red = tiles + TILE_WORDS * tile_px;       // reduction scratch [2][3][THREADS/64] (+pad), alternating by patch
     float *const wl = WFIRST ? smem : red + RED_WORDS;     // MFMA: the whole folded model, j-major
     // BS: [THREADS/64][8] per-wavefront statistics partials, then 8 doubles (scale[4], mean[4]) of the pending re-fold
@@ -194,10 +220,13 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     [[maybe_unused]] int prow[PX], pcol[PX];   // masked instantiations: row / column of the pixel inside the patch (tile)
     int wbase = 0;     // BLK: tile entry of the window origin (r' = 2*br, c' = 2*bc)
     [[maybe_unused]] int wbase3 = 0;   // HB: first entry of this lane's l_last B operand (unit 0, instruction 0)
-    if constexpr (HB) {
+    if constexpr (HB || SB) {
         // nf_device.h, NF11_*: a wavefront owns 8 rows x 32 columns = 4 units of 2 rows; lane 16 g + n is pixel
         // (a, p) = (g >> 1, g & 1) of the 2x2 block of lane column n in each of them
-        const int wv = t >> 6, g = (t >> 4) & 3, n = t & 15;
+        const int wv = t >> 6, g = (t >> 4) & 3;
+        // SB: lane column n takes column pair nf12_col(n) — lanes 4 .. 11 the even pairs, the others the odd ones — so that the two
+        // K slots (window rows 2 apart) that share a ds_read_b128 lane group read complementary bank quads at pitch 34
+        const int n = SB ? nf12_col(t & 15) : (t & 15);
         const int q = SIDE == 64 ? (wv & 1) : 0, band = SIDE == 64 ? (wv >> 1) : wv;
         const int c = 32 * q + 2 * n + (g & 1);
         wbase = (band * 8 + nf11_l1_row(g)) * Wp + 32 * q + 2 * n;
@@ -366,6 +395,26 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 const int e = (rp * 2 + (cp & 1)) * PW + (cp >> 1);
                 t0[e] = make_float2(0.f, 0.f);
                 *reinterpret_cast<float4 *>(th + (size_t)e * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        } else if constexpr (SB) {
+            // as below, for the three regions (every interior slot is written by its owner before anyone reads it)
+            const int nb = 2 * (W + 2) + 2 * H;
+            for (int i = t; i < nb; i += THREADS) {
+                int rp, cp;
+                if (i < W + 2) {
+                    rp = 0;
+                    cp = i;
+                } else if (i < 2 * (W + 2)) {
+                    rp = H + 1;
+                    cp = i - (W + 2);
+                } else {
+                    const int j = i - 2 * (W + 2);
+                    rp = 1 + (j >> 1);
+                    cp = (j & 1) ? W + 1 : 0;
+                }
+                sr0[rp * Wp + cp] = make_uint2(0u, 0u);
+                sr1[rp * Wp + cp] = make_uint2(0u, 0u);
+                sr2[rp * Wp + cp] = make_uint2(0u, 0u);
             }
         } else if constexpr (NF_HB_ZB && HB) {
             // every interior entry of both tiles has an owner that writes it before anyone reads it, and no operand read reaches
@@ -770,6 +819,18 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
 #endif
                 constexpr bool L2B = NF_HB_L2BIG && HB && THREADS == 1024;
                 [[maybe_unused]] float4 hb_b1, hb_b2, hb_e[PX];
+                // SB: this lane's A operands of l_1 (pairs x halves) and l_last (pieces x m3), from the coupling's A image in global
+                // memory (the same bytes for every wavefront: L1 / L2 hits); l_last's are requested while l_1 runs
+                [[maybe_unused]] uint4 sb_a1[6], sb_a3[6];
+                [[maybe_unused]] const uint4 *sb_ag = nullptr;
+                if constexpr (SB) {
+                    const int aoff = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wl[coff + NF12_CPL_AOFF]));
+                    sb_ag = reinterpret_cast<const uint4 *>(a.params + aoff) + (t & 63);
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) sb_a1[q] = sb_ag[NF12_A_A1 / 4 + 64 * q];
+                    hb_b1 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_B1);
+                    hb_b2 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_B2);
+                }
                 if constexpr (HB) {
                     const float *wb = wl + coff;
                     const uint32_t *wbw = reinterpret_cast<const uint32_t *>(wb);
@@ -786,9 +847,16 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                     }
                 }
                 // 1) publish the pass-through half
+                // SB: the regions still hold the previous coupling's h2 until every wavefront has read it
+                if constexpr (SB) __syncthreads();
 #pragma unroll
                 for (int k = 0; k < PX; ++k) {
-                    if constexpr (HALF) {
+                    if constexpr (SB) {
+                        uint32_t zh, zm, zl;
+                        nf_split3(z[k][0], z[k][1], zh, zm, zl);
+                        sr0[lidx[k]] = make_uint2(zh, zm);
+                        sr1[lidx[k]] = make_uint2(zl, zh);
+                    } else if constexpr (HALF) {
                         const v2h zh = {(_Float16)z[k][0], (_Float16)z[k][1]};
                         t0h[lidx[k]] = __builtin_bit_cast(uint32_t, zh);
                     } else {
@@ -798,7 +866,53 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 __syncthreads();
 
                 // 2) l_1 (3x3 SAME, BN folded) -> ReLU -> l_2 (1x1, BN folded) -> ReLU
-                if constexpr (HB) {
+                if constexpr (SB) {
+                    const float4 b1 = hb_b1, b2 = hb_b2;
+                    const float4 w2 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_W2T + 4 * j4);
+                    v4f h1[PX];
+#pragma unroll
+                    for (int k = 0; k < PX; ++k) {
+                        // K slot of this lane: one window row, two columns per instruction (16-byte reads of two slots)
+                        const uint4 q00 = *reinterpret_cast<const uint4 *>(sr0 + wbase + 2 * k * Wp);
+                        const uint4 q01 = *reinterpret_cast<const uint4 *>(sr0 + wbase + 2 * k * Wp + 2);
+                        const uint4 q10 = *reinterpret_cast<const uint4 *>(sr1 + wbase + 2 * k * Wp);
+                        const uint4 q11 = *reinterpret_cast<const uint4 *>(sr1 + wbase + 2 * k * Wp + 2);
+                        // smallest products first: hl + lh, mh + mm, hh + hm
+                        v4f acc = v4f{b1.x, b1.y, b1.z, b1.w};
+                        acc = nf_mfma_bf16(sb_a1[4], q10, acc);
+                        acc = nf_mfma_bf16(sb_a1[5], q11, acc);
+                        acc = nf_mfma_bf16(sb_a1[2], q00, acc);
+                        acc = nf_mfma_bf16(sb_a1[3], q01, acc);
+                        acc = nf_mfma_bf16(sb_a1[0], q00, acc);
+                        acc = nf_mfma_bf16(sb_a1[1], q01, acc);
+                        h1[k] = acc;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) sb_a3[q] = sb_ag[NF12_A_A3 / 4 + 64 * q];
+                    uint2 hs[PX][3];   // relu(h2) of the lane's pixels, three pieces
+#pragma unroll
+                    for (int k = 0; k < PX; ++k) {
+                        v4f h2 = {b2.x, b2.y, b2.z, b2.w};
+                        h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.x, nf_relu(h1[k][0]), h2, 0, 0, 0);
+                        h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.y, nf_relu(h1[k][1]), h2, 0, 0, 0);
+                        h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.z, nf_relu(h1[k][2]), h2, 0, 0, 0);
+                        h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.w, nf_relu(h1[k][3]), h2, 0, 0, 0);
+                        uint32_t p01[3], p23[3];
+                        nf_split3(nf_relu(h2[0]), nf_relu(h2[1]), p01[0], p01[1], p01[2]);
+                        nf_split3(nf_relu(h2[2]), nf_relu(h2[3]), p23[0], p23[1], p23[2]);
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) hs[k][q] = make_uint2(p01[q], p23[q]);
+                    }
+#pragma unroll
+                    for (int k = 0; k < PX; ++k) hb_e[k] = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_E + 4 * bmask[k]);
+                    __syncthreads();   // every wavefront has read z0: the regions take h2
+#pragma unroll
+                    for (int k = 0; k < PX; ++k) {
+                        sr0[lidx[k]] = hs[k][0];
+                        sr1[lidx[k]] = hs[k][1];
+                        sr2[lidx[k]] = hs[k][2];
+                    }
+                } else if constexpr (HB) {
                     const float *wb = wl + coff;
                     const uint32_t *wbw = reinterpret_cast<const uint32_t *>(wb);
                     if (!NF_HB_EARLY) {
@@ -1099,7 +1213,28 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 {
                     float o[PX][4];
                     float sc;
-                    if constexpr (HB) {
+                    if constexpr (SB) {
+                        sc = 0.0f;
+                        uint2 *const srp[3] = {sr0, sr1, sr2};
+#pragma unroll
+                        for (int k = 0; k < PX; ++k) {
+                            uint4 qb[3][2];   // [piece][m3]: K slot = two adjacent window pixels x 4 channels, one 16-byte read
+#pragma unroll
+                            for (int p = 0; p < 3; ++p)
+#pragma unroll
+                                for (int m3 = 0; m3 < 2; ++m3) qb[p][m3] = *reinterpret_cast<const uint4 *>(srp[p] + wbase3 + (2 * k + m3) * Wp);
+                            const float4 e = hb_e[k];
+                            v4f acc = v4f{e.x, e.y, e.z, e.w};
+                            // smallest products first: (h l, l h, m m), (h m, m h), h h — weight piece x activation piece
+                            constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+#pragma unroll
+                            for (int t6 = 0; t6 < 6; ++t6)
+#pragma unroll
+                                for (int m3 = 0; m3 < 2; ++m3) acc = nf_mfma_bf16(sb_a3[2 * PA[t6] + m3], qb[PB[t6]][m3], acc);
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) o[k][j] = acc[j];
+                        }
+                    } else if constexpr (HB) {
                         const float *wb = wl + coff;
                         const uint32_t *wbw = reinterpret_cast<const uint32_t *>(wb);
                         sc = 0.0f;
@@ -1475,6 +1610,14 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(NF_MIN_
     nf_flow_body<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, PREC, BS, false>(prog, a);
 }
 
+// split-bf16 convs (NF_K_SPLIT_BF16, nf_device.h NF12_*): full 32x32 patches, 4 workgroups of 4 wavefronts per CU, i.e. at most 128
+// registers a lane
+template <bool PHILOX>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void nf_flow_split_kernel(const NfProgram prog, const NfLaunch a)
+{
+    nf_flow_body<4, 256, 4, PHILOX, true, true, 3, false, false>(prog, a);
+}
+
 // NF_K_TILED launches over full 64x64 tiles: the full-patch matrix-core geometry of nf_flow_kernel<4, 1024, 4, ., true, true, PREC, false>
 // (PREC = 0: fp32, 2x2-blocked lanes; PREC = 2: fp16 CNN on v_mfma_f32_16x16x32_f16)
 template <bool PHILOX, int PREC>
@@ -1651,12 +1794,14 @@ hipError_t launch_flow_p(const NfProgram &prog, const NfLaunch &a, int n_cu, hip
     size_t lds_f = (size_t)tile_px * (PREC != 0 ? 3 : 2 + WIDTH) + ((6 * (THREADS / 64) + 3) & ~3);
     if (PREC == 1 && a.H == 32) lds_f = (size_t)(34 * 48) * 3 + ((6 * (THREADS / 64) + 3) & ~3);   // padded row pitch
     if (PREC == 2) lds_f = (size_t)((a.H + 2) * nf11_pitch(a.H)) * 3 + ((6 * (THREADS / 64) + 3) & ~3);
+    if (PREC == 3) lds_f = (size_t)((a.H + 2) * NF12_PITCH) * 6 + ((6 * (THREADS / 64) + 3) & ~3);
     if (MFMA) lds_f += (size_t)((a.n_params + 3) & ~3) + 16;   // + the identity block
     if (BS) lds_f += (size_t)(THREADS / 64) * 8 + 16;
     const size_t lds = sizeof(float) * lds_f;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     void (*const kern)(const NfProgram, const NfLaunch) = [] {
         if constexpr (TF) return &nf_flow_tile64_kernel<PHILOX, PREC>;
+        else if constexpr (PREC == 3) return &nf_flow_split_kernel<PHILOX>;
         else return &nf_flow_kernel<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, PREC, BS>;
     }();
     const void *fn = reinterpret_cast<const void *>(kern);
@@ -1693,6 +1838,11 @@ hipError_t launch_flow_p(const NfProgram &prog, const NfLaunch &a, int n_cu, hip
 template <int WIDTH, int THREADS, int PX, bool PHILOX, bool MFMA, bool FULL>
 hipError_t launch_flow_f(const NfProgram &prog, const NfLaunch &a, int n_cu, hipStream_t stream)
 {
+    if constexpr (MFMA && FULL && PX == 4 && THREADS == 256 && WIDTH == 4) {
+        if ((a.flags & NF_K_SPLIT_BF16) && !(a.flags & (NF_K_FP16_CNN | NF_K_BATCHSTATS | NF_K_TILED)))
+            return launch_flow_p<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, 3>(prog, a, n_cu, stream);
+    }
+    if (a.flags & NF_K_SPLIT_BF16) return hipErrorInvalidValue;   // the NF12_* block fits no other kernel
     if constexpr (MFMA && FULL && PX == 4) {
         if (a.flags & NF_K_FP16_BIG) return launch_flow_p<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, 2>(prog, a, n_cu, stream);
         if (a.flags & NF_K_FP16_CNN) return launch_flow_p<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, 1>(prog, a, n_cu, stream);
@@ -1738,6 +1888,8 @@ const void *nf_isa_probe_kernels[] = {
     reinterpret_cast<const void *>(&nf_flow_kernel<4, 1024, 4, false, true, true, 2, false>),
     reinterpret_cast<const void *>(&nf_flow_kernel<4, 256, 4, false, true, true, 2, false>),
     reinterpret_cast<const void *>(&nf_flow_kernel<4, 256, 4, false, true, true, 0, false>),
+    reinterpret_cast<const void *>(&nf_flow_split_kernel<false>),
+    reinterpret_cast<const void *>(&nf_flow_split_kernel<true>),
 };
 #else
 template <int WIDTH, bool MFMA>

@@ -145,9 +145,9 @@ class FlowHandle:
             self.layers, descs, flat = _params.pack_layers(layers, variables, width, tmpl or {})
         H, W, Cc = (int(v) for v in x_shape)
         self.x_shape = (H, W, Cc)
-        if cnn_dtype not in ("fp32", "fp16"):
-            raise ValueError("cnn_dtype must be 'fp32' or 'fp16'")
-        flags = _lib.NF_CFG_FP16_CNN if cnn_dtype == "fp16" else 0
+        if cnn_dtype not in ("fp32", "fp16", "fp32_exact"):
+            raise ValueError("cnn_dtype must be 'fp32', 'fp16' or 'fp32_exact'")
+        flags = {"fp32": 0, "fp16": _lib.NF_CFG_FP16_CNN, "fp32_exact": _lib.NF_CFG_EXACT_FP32}[cnn_dtype]
         cfg = _lib.nf_config(H, W, Cc, len(self.layers), -1 if device is None else int(device), flags)
         h = C.c_void_p()
         _lib.check(self.lib.nf_create(C.byref(cfg), descs, flat.ctypes.data_as(C.POINTER(C.c_float)), flat.size,
@@ -194,7 +194,8 @@ class NoiseFlow(object):
           n_levels`` (and optionally ``seed``).
     variables : optional ``{name: ndarray}`` under the reference's checkpoint
           names; default = fresh initialisation with the reference initialisers.
-    cnn_dtype : 'fp32' (default) | 'fp16' — precision of the coupling-CNN convolutions.
+    cnn_dtype : 'fp32' (default) | 'fp16' — precision of the coupling-CNN convolutions; 'fp32_exact' keeps every conv of the
+          width-4 model on the fp32 matrix instruction where 'fp32' would use the fp32-accurate split-bf16 kernel (32x32 patches).
     binding : 'loss_first' | 'sample_first' — template→layer binding (quirk Q1).
     """
 
