@@ -1234,6 +1234,11 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
         const size_t n0 = out.block9.size();
         out.block9.resize(n0 + img.size());
         if (!img.empty()) memcpy(out.block9.data() + n0, img.data(), img.size() * 4);
+        // Not reachable today: this layout exists only where block2 fits NF2_MAX_FLOATS (above), an op costs here at most what it
+        // costs there, and a coupling 96 floats against 332 — with c couplings, m mixes (m <= c) and s scales in NF_MAX_OPS = 64
+        // ops, 332 c + 16 m + 4 s <= 6144 gives c <= 17 (18 without mixes) and 96 c + 16 m + 4 s <= 2024 (tests/test_split_bf16.py
+        // finds the boundary through nf_fold_layout for flow_permutation 0 / 1 / 2).  Kept as the guard of the kernel's LDS budget
+        // should either limit or a section size change.
         if (out.n_lds9 > NF12_MAX_FLOATS) {   // LDS image too large for 4 workgroups per CU: the exact-fp32 kernel
             out.block9.clear();
             out.n_lds9 = 0;

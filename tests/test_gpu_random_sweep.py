@@ -115,6 +115,31 @@ def test_random_model_wide_couplings_match_oracle(seed):
     assert m._flow.lib.nf_kernel_path(m._flow.ptr, 0) == _lib.NF_PATH_GEMM
 
 
+@pytest.mark.parametrize("seed", list(range(900, 940)))
+def test_random_model_on_the_split_bf16_kernel_and_the_exact_one(seed):
+    """The sweep aimed at the default kernel of the headline shape: width 4 and 32x32 forced (the plain draw meets them together in
+    about 3 % of its cases), batch from {1, 2, 5, 33}, everything else as drawn; at least one coupling.  Each case on the split-bf16
+    kernel and on the exact-fp32 one, each against the oracle with _check_case's tolerances; and the two kernels' latents agree to
+    max(1e-6 of scale, twice the distance of the oracle's fp32 flavour from fp64)."""
+    from noise_flow_amd import _lib
+    arch, _, _, fp, decomp, iso, cam, _ = _draw_case(seed)
+    if "unc" not in arch.split("|"):
+        arch = arch + "|unc"
+    B = int(np.random.RandomState(seed).choice([1, 2, 5, 33]))
+    case = (arch, 4, (32, 32), fp, decomp, iso, cam, B)
+    got = {}
+    for cnn_dtype, path in (("fp32", _lib.NF_PATH_SPLIT_BF16), ("fp32_exact", _lib.NF_PATH_MFMA4)):
+        keep = {}
+        m = _check_case(seed, case, cnn_dtype=cnn_dtype, keep=keep)
+        for direction in (0, 1):
+            assert m._flow.lib.nf_kernel_path(m._flow.ptr, direction) == path, (case, cnn_dtype, direction)
+        got[cnn_dtype] = keep
+    a, b = got["fp32"], got["fp32_exact"]
+    tol = max(1e-6 * np.abs(a["z64"]).max(), 2.0 * np.abs(a["z32"] - a["z64"]).max())
+    d = np.abs(a["z"] - b["z"]).max()
+    assert d <= tol, "%r: split vs exact latents %.3e > %.3e" % (case, d, tol)
+
+
 def _large_shape(seed):
     rng = np.random.RandomState(5000 + seed)
     kind = rng.randint(0, 4)
@@ -133,7 +158,8 @@ def test_random_model_large_patches(seed):
     _check_case(seed, (arch, width, _large_shape(seed), fp, decomp, iso, cam, min(B, 2)))
 
 
-def _check_case(seed, case_tuple):
+def _check_case(seed, case_tuple, cnn_dtype=None, keep=None):
+    """``cnn_dtype``: the model's (None = the default kernels); ``keep``: a dict that receives the latents (kernel, fp64, fp32 oracle)."""
     from noise_flow_amd import NoiseFlow, default_hps, params
     from oracle.nf_oracle import NoiseFlowOracle
     arch, width, (H, W), fp, decomp, iso, cam, B = case_tuple
@@ -145,7 +171,7 @@ def _check_case(seed, case_tuple):
             v[k] = base[k]
     v = _condition(v, arch, width, iso, rng)
     hps = default_hps(arch=arch, width=width, flow_permutation=fp, decomp=decomp)
-    m = NoiseFlow([H, W, 4], False, hps, variables=v)
+    m = NoiseFlow([H, W, 4], False, hps, variables=v, cnn_dtype=cnn_dtype)
     o64 = NoiseFlowOracle(arch, v, flow_permutation=fp, decomp=decomp)
     o32 = NoiseFlowOracle(arch, v, dtype=np.float32, flow_permutation=fp, decomp=decomp)
     assert m.get_layer_names() == [L["name"] for L in o64.layers]
@@ -160,6 +186,8 @@ def _check_case(seed, case_tuple):
         assert (np.abs(nll - ref_nll) <= tol).all(), np.abs(nll - ref_nll).max()
         z, obj = m.inverse(x, None, yy, *args)
         _within(z, ref_z, z32, 1e-5)
+        if keep is not None:
+            keep.update(z=np.asarray(z, np.float64), z64=ref_z, z32=z32)
         eps = np.random.RandomState(seed + 3).randn(B, H, W, 4).astype(np.float32)
         xs = m.sample(yy, 0.8, yy, *args, eps=eps)
         _within(xs, o64.sample(eps, 0.8, yy, iso, cam), o32.sample(eps, 0.8, yy, iso, cam), 1e-5)
