@@ -17,6 +17,7 @@ typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef _Float16 v2h __attribute__((ext_vector_type(2)));
 typedef __bf16 nf_v8bf __attribute__((ext_vector_type(8)));
 typedef __bf16 nf_v2bf __attribute__((ext_vector_type(2)));
+typedef float nf_v2f __attribute__((ext_vector_type(2)));
 
 // --------------------------------------------------------------------------
 // Philox4x32-10 counter-based RNG (Salmon et al. 2011) — keyed by
@@ -87,6 +88,30 @@ __device__ __forceinline__ float nf_relu(float x)
     const int b = __float_as_int(x);
     return __int_as_float(b > 0 ? b : 0);
 }
+
+// One stage of the bf16 x 3 split of a value pair: the round-to-nearest-even bf16 of both values in one dword (ONE
+// v_cvt_pk_bf16_f32), and x left as the exact remainders.  The piece goes back to fp32 as a VECTOR conversion of the packed word,
+// which lowers to its two halves moved into place (v_lshlrev_b32 16 / v_and_b32 0xffff0000: the same bits).  Converting back element
+// by element, `x0 -= (float)p[0]`, makes the compiler split the packed conversion up again and round every value a second time
+// with a single-value v_cvt_pk_bf16_f32 (7 conversions per pair instead of 3).  The subtraction of a pair is one v_pk_add_f32;
+// a kernel compiled without packed fp32 (NF_NO_PK_F32) gets two v_sub_f32 instead
+__device__ __forceinline__ uint32_t nf_bf16_peel(nf_v2f &x)
+{
+    const nf_v2bf p = __builtin_convertvector(x, nf_v2bf);
+    x -= __builtin_convertvector(p, nf_v2f);
+    return __builtin_bit_cast(uint32_t, p);
+}
+// the last stage: what is left of the pair, rounded
+__device__ __forceinline__ uint32_t nf_bf16_last(const nf_v2f x)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, nf_v2bf));
+}
+// kernel attribute: no packed fp32 instructions in this kernel (the host pass does not know the feature)
+#ifdef __HIP_DEVICE_COMPILE__
+#define NF_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define NF_NO_PK_F32
+#endif
 
 // Wavefront sum, the total in every lane: four DPP adds finish the 16-lane rows (xor 1 / xor 2 inside the quads, the
 // half-row and row mirrors), four v_readlane + three adds join the rows — ~11 issues instead of the six dependent

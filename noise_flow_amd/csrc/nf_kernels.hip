@@ -116,19 +116,13 @@ __device__ __forceinline__ void stats_flush(const float (&s1)[WIDTH], const floa
 }
 
 // split-bf16 mode (nf_device.h, NF12_*): x = x_h + x_m + x_l for two values at once, each piece the round-to-nearest-even bf16
-// of what the pieces before it left (v_cvt_pk_bf16_f32); the subtractions are exact, the remainder below 2^-24 |x|
+// of what the pieces before it left (nf_dev_util.h, nf_bf16_peel); the subtractions are exact, the remainder below 2^-24 |x|
 __device__ __forceinline__ void nf_split3(float x0, float x1, uint32_t &h, uint32_t &m, uint32_t &l)
 {
-    const nf_v2bf ph = {(__bf16)x0, (__bf16)x1};
-    x0 -= (float)ph[0];
-    x1 -= (float)ph[1];
-    const nf_v2bf pm = {(__bf16)x0, (__bf16)x1};
-    x0 -= (float)pm[0];
-    x1 -= (float)pm[1];
-    const nf_v2bf pl = {(__bf16)x0, (__bf16)x1};
-    h = __builtin_bit_cast(uint32_t, ph);
-    m = __builtin_bit_cast(uint32_t, pm);
-    l = __builtin_bit_cast(uint32_t, pl);
+    nf_v2f x = {x0, x1};
+    h = nf_bf16_peel(x);
+    m = nf_bf16_peel(x);
+    l = nf_bf16_last(x);
 }
 __device__ __forceinline__ v4f nf_mfma_bf16(const uint4 a, const uint4 b, const v4f c)
 {
@@ -657,6 +651,7 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
         float ld2 = 0.0f;   // ... and the part accumulated in log2 units (matrix-core couplings)
         [[maybe_unused]] int n_cpl = 0;
         [[maybe_unused]] int cpl_seen = 0;
+        [[maybe_unused]] int fair_next = 0;   // the coupling count at which the priority level changes next (NF_FAIR, split-bf16 kernel)
 
         // Conv2d1x1 on the matrix cores: per-pixel z <- z @ M   (layers.py:108-124)
         [[maybe_unused]] auto mix_load = [&](int moff) { return *reinterpret_cast<const float4 *>(wl + moff + 4 * j4); };   // M[0..3][j4]
@@ -798,12 +793,18 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 if constexpr (MFMA && !(NF_WAVE_PRIO && THREADS == 1024)) {
                     // lvl = (cpl_seen * 4) / cpl_total, 0 .. 3, wave-uniform — against thresholds formed once per launch (the division
                     // was ~30 scalar instructions per coupling)
-                    const int lvl = (cpl_seen >= fair_t1 ? 1 : 0) + (cpl_seen >= fair_t2 ? 1 : 0) + (cpl_seen >= fair_t3 ? 1 : 0);
+                    // SB: the level changes three times a patch and nothing else sets the priority, so it is written only when cpl_seen
+                    // reaches fair_next, the next threshold (the four-way branch on lvl, formed with two v_cndmask + v_readfirstlane
+                    // pairs, ran in every coupling)
+                    if (!SB || cpl_seen == fair_next) {
+                        const int lvl = (cpl_seen >= fair_t1 ? 1 : 0) + (cpl_seen >= fair_t2 ? 1 : 0) + (cpl_seen >= fair_t3 ? 1 : 0);
+                        if (lvl == 0) __builtin_amdgcn_s_setprio(3);
+                        else if (lvl == 1) __builtin_amdgcn_s_setprio(2);
+                        else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
+                        else __builtin_amdgcn_s_setprio(0);
+                        fair_next = cpl_seen < fair_t1 ? fair_t1 : cpl_seen < fair_t2 ? fair_t2 : cpl_seen < fair_t3 ? fair_t3 : 0x7fffffff;
+                    }
                     ++cpl_seen;
-                    if (lvl == 0) __builtin_amdgcn_s_setprio(3);
-                    else if (lvl == 1) __builtin_amdgcn_s_setprio(2);
-                    else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
-                    else __builtin_amdgcn_s_setprio(0);
                 }
 #endif
                 // HB: every weight operand of the coupling is requested before the barriers, so that after a barrier only the
@@ -824,6 +825,8 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 [[maybe_unused]] uint4 sb_a1[6], sb_a3[6];
                 [[maybe_unused]] const uint4 *sb_ag = nullptr;
                 if constexpr (SB) {
+                    // (the offset is arithmetic in the pair index inside the counted loop; carrying it there instead of reading the field
+                    // costs two more live registers, 8 B more scratch, and measured 1.3 % SLOWER on the headline: left as the LDS read)
                     const int aoff = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wl[coff + NF12_CPL_AOFF]));
                     sb_ag = reinterpret_cast<const uint4 *>(a.params + aoff) + (t & 63);
 #pragma unroll
@@ -1612,8 +1615,20 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(NF_MIN_
 
 // split-bf16 convs (NF_K_SPLIT_BF16, nf_device.h NF12_*): full 32x32 patches, 4 workgroups of 4 wavefronts per CU, i.e. at most 128
 // registers a lane
+// NF_SPLIT_PK_SUB 0: the kernel is compiled without packed fp32, so the 48 subtractions of the operand split (nf_split3) are plain
+// v_sub_f32 and the affine stage's 8 packed multiply-adds 16 plain ones; 1: packed fp32 allowed, 24 v_pk_add_f32 (A/B aid).  Packed
+// fp32 is dear beside matrix instructions and its register pairs cost 24 B more scratch — headline, one box, builds alternated 4 x:
+// double-rounding split 2.125e7 patches/s, this split with v_pk_add_f32 2.089e7, with v_sub_f32 2.200e7 (profiles/r08_ab_split_once.txt)
+#ifndef NF_SPLIT_PK_SUB
+#define NF_SPLIT_PK_SUB 0
+#endif
+#if NF_SPLIT_PK_SUB
+#define NF_SPLIT_KATTR
+#else
+#define NF_SPLIT_KATTR NF_NO_PK_F32
+#endif
 template <bool PHILOX>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void nf_flow_split_kernel(const NfProgram prog, const NfLaunch a)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) NF_SPLIT_KATTR void nf_flow_split_kernel(const NfProgram prog, const NfLaunch a)
 {
     nf_flow_body<4, 256, 4, PHILOX, true, true, 3, false, false>(prog, a);
 }

@@ -35,6 +35,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
+#include "nf_dev_util.h"   // nf_bf16_peel: the convert-once stage of the bf16 x 3 split
 
 #ifndef MM_ABL
 // tools/probes/mm_probe.hip only (timing ablations of k_mm_pix; results are wrong): 1 = no barrier in the K loop, 2 = no global
@@ -120,18 +121,10 @@ typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
 // v = v1 + v2 + v3 per element, each part a bf16 (round to nearest even), packed 4 to a uint2 per part
 __device__ __forceinline__ void split_bf16x3(const float4 v, uint2 (&pl)[3])
 {
-    float r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const v2bf h01 = {(__bf16)r[0], (__bf16)r[1]}, h23 = {(__bf16)r[2], (__bf16)r[3]};
-        pl[q] = make_uint2(__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23));
-        if (q < 2) {
-            r[0] -= (float)h01[0];
-            r[1] -= (float)h01[1];
-            r[2] -= (float)h23[0];
-            r[3] -= (float)h23[1];
-        }
-    }
+    nf_v2f r01 = {v.x, v.y}, r23 = {v.z, v.w};
+    pl[0] = make_uint2(nf_bf16_peel(r01), nf_bf16_peel(r23));
+    pl[1] = make_uint2(nf_bf16_peel(r01), nf_bf16_peel(r23));
+    pl[2] = make_uint2(nf_bf16_last(r01), nf_bf16_last(r23));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
