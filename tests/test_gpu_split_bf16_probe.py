@@ -42,11 +42,16 @@ T = "model/real_nvp_conv_template/"
 
 # ---- the probe model ----------------------------------------------------------------------------------------------------------
 
-def probe_variables(seed, half):
-    """`unc`, width 4, trained-like coupling weights and BN statistics, the 1x1 mix the LU form of the identity; `half` =
-    "shift": the raw channels of l_last are zero, "raw": the shift channels are."""
+def probe_variables(seed, half, width=4):
+    """`unc`, trained-like coupling weights and BN statistics, the 1x1 mix the LU form of the identity; `half` =
+    "shift": the raw channels of l_last are zero, "raw": the shift channels are.  Beyond width 4 the weights of l_2 and l_last are
+    scaled by sqrt(4 / width), as tests/test_gpu_gemm.py::_variables does: activations of O(1) at every width."""
     from oracle.nf_oracle import conv1x1_variable_names
-    v = trained_like_variables("unc", 4, seed=seed)
+    v = trained_like_variables("unc", width, seed=seed)
+    if width > 4:
+        for k in v:
+            if k.endswith("l_2/W") or k.endswith("l_last/W"):
+                v[k] = (v[k] * np.float32((4.0 / width) ** 0.5)).astype(np.float32)
     n = conv1x1_variable_names(0, "LU")
     v[n["P"]] = np.eye(4, dtype=np.float32)
     v[n["sign_S"]] = np.ones(4, np.float32)
@@ -80,7 +85,7 @@ def _folded(p):
 
 
 def abs_terms(p, z0):
-    """A [B, 32, 32, 4] (shift channels, raw channels): the fp64 sum of absolute terms carried through l_1 -> l_2 -> l_last."""
+    """A [B, H, W, 4] (shift channels, raw channels): the fp64 sum of absolute terms carried through l_1 -> l_2 -> l_last."""
     from oracle.nf_oracle import add_edge_padding, conv2d_nhwc
     W1, b1, W2, b2, W3, b3 = (np.abs(a) for a in _folded(p))
     a1 = conv2d_nhwc(np.abs(np.asarray(z0, np.float64)), W1, True) + b1
@@ -93,20 +98,34 @@ def _params64(v):
     return [L for L in bind_variables("unc", v) if L["type"] == "coupling"][0]["p"]
 
 
-def chain_emulated(p, z0, prods1, prods3):
+def chain_emulated(p, z0, prods1, prods3, prods2=None):
     """(shift, raw) of the chain as a split-bf16 kernel evaluates it: folded fp32 weights and fp32 activations in three bf16
     pieces, the listed piece products (weight piece, activation piece) exact and summed in fp64, one fp32 rounding per layer;
-    l_2 in fp32.  prods = SIX for the kernel of DESIGN 4.1, THREE for the mutant."""
+    l_2 in fp32 unless it has a product list of its own.  prods = SIX for the kernel of DESIGN 4.1, THREE for the mutant, None for
+    the layer as an ideal fp32 evaluation (the fp32 operands' exact products, one rounding).  Any width, any patch shape."""
     from oracle.nf_oracle import add_edge_padding, conv2d_nhwc
     W1, b1, W2, b2, W3, b3 = (np.asarray(a, np.float32) for a in _folded(p))
     f32 = lambda a: np.asarray(a, np.float32)   # noqa: E731
-    zp, wp = _split3(z0), _split3(W1)
-    h = sum(conv2d_nhwc(zp[b], wp[a], True) for a, b in prods1) + b1.astype(np.float64)
-    h = np.maximum(f32(h), 0)
-    h = np.maximum(f32(conv2d_nhwc(h.astype(np.float64), W2.astype(np.float64), True) + b2.astype(np.float64)), 0)
-    hp, wp = _split3(h), _split3(W3[:, :, :4, :])
-    edge = conv2d_nhwc(add_edge_padding(np.zeros(h.shape))[..., 4:], W3[:, :, 4:, :].astype(np.float64), False)
-    o = sum(conv2d_nhwc(np.pad(hp[b], [(0, 0), (1, 1), (1, 1), (0, 0)]), wp[a], False) for a, b in prods3)
+    w = W2.shape[-1]
+    pad1 = [(0, 0), (1, 1), (1, 1), (0, 0)]
+    if prods1 is None:
+        h = conv2d_nhwc(np.asarray(z0, np.float64), W1.astype(np.float64), True)
+    else:
+        zp, wp = _split3(z0), _split3(W1)
+        h = sum(conv2d_nhwc(zp[b], wp[a], True) for a, b in prods1)
+    h = np.maximum(f32(h + b1.astype(np.float64)), 0)
+    if prods2 is None:
+        h2 = conv2d_nhwc(h.astype(np.float64), W2.astype(np.float64), True)
+    else:
+        hp, wp = _split3(h), _split3(W2)
+        h2 = sum(conv2d_nhwc(hp[b], wp[a], True) for a, b in prods2)
+    h = np.maximum(f32(h2 + b2.astype(np.float64)), 0)
+    edge = conv2d_nhwc(add_edge_padding(np.zeros(h.shape))[..., w:], W3[:, :, w:, :].astype(np.float64), False)
+    if prods3 is None:
+        o = conv2d_nhwc(np.pad(h.astype(np.float64), pad1), W3[:, :, :w, :].astype(np.float64), False)
+    else:
+        hp, wp = _split3(h), _split3(W3[:, :, :w, :])
+        o = sum(conv2d_nhwc(np.pad(hp[b], pad1), wp[a], False) for a, b in prods3)
     o = f32(o + edge + b3.astype(np.float64)).astype(np.float64)
     return o[..., :2], o[..., 2:]
 
@@ -119,13 +138,14 @@ def _units(err, A):
     return float((np.abs(err) / (U24 * A)).max())
 
 
-def raw_bound(p, A_raw, raw64):
-    """Per-element allowance on ls = rescaling_scale * tanh(raw) as log(out) shows it (module docstring)."""
+def raw_bound(p, A_raw, raw64, units=BOUND_UNITS, raw_t=RAW_T):
+    """Per-element allowance on ls = rescaling_scale * tanh(raw) as log(out) shows it (module docstring); `units` = the conv
+    bound in units of 2^-24 A (BOUND_UNITS here, the per-width table of tests/test_gpu_probe_families.py there)."""
     rs = float(p["rescaling_scale"])
     t = np.tanh(raw64)
     ls = rs * t
-    conv = BOUND_UNITS * U24 * A_raw * rs * (1.0 - t * t)
-    return conv, conv + RAW_T * U24 * (1.0 + np.abs(ls)), ls
+    conv = units * U24 * A_raw * rs * (1.0 - t * t)
+    return conv, conv + raw_t * U24 * (1.0 + np.abs(ls)), ls
 
 
 # ---- CPU: the two conditions that give the bound its meaning ------------------------------------------------------------------

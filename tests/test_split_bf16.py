@@ -60,8 +60,10 @@ FAMILIES = ("lognormal", "bf16_ties", "bf16_exact", "impulse", "wide_range")
 IMPULSES = [(0, 0), (0, 31), (31, 0), (31, 31), (0, 15), (31, 16), (15, 0), (16, 31), (7, 13), (8, 18)]
 
 
-def family(name, seed, B=8, channels=2):
-    """[B, 32, 32, channels] float32 of one input family of the split-bf16 tests: values as a coupling CNN may see them
+def family(name, seed, B=8, channels=2, hw=(32, 32), impulses=None):
+    """[B, H, W, channels] float32 (hw = (H, W), 32x32 unless given; `impulses` = the (row, col) positions of the impulse family,
+    one patch each, IMPULSES unless given — the tests of the other kernels pass the seams of the kernel under test).
+    One input family of the split-bf16 tests: values as a coupling CNN may see them
     (lognormal), low halves that sit on the bf16 rounding ties of the high and of the middle piece and one fp32 ulp either side of
     them (the next piece changes sign across each), exact bf16 values with +-0 (middle and low pieces zero), one impulse per patch
     (corners, edge midpoints, either side of a wavefront's 8-row band: B = len(IMPULSES)), magnitudes 1e-3 .. 1e3 side by side.
@@ -70,7 +72,7 @@ def family(name, seed, B=8, channels=2):
     probe models' BN statistics the oracle's own fp32 flavour is 2.41 units of 2^-24 A from fp64 on that range and 1.95 on
     1e-4 .. 1e4 — beyond, or at, the 2 units the 4-unit bound requires of it.  On 1e-3 .. 1e3 it is at 1.36."""
     rng = np.random.RandomState(100 * seed + FAMILIES.index(name))
-    shape = (B, 32, 32, channels)
+    shape = (B, hw[0], hw[1], channels)
     if name == "lognormal":
         return (rng.randn(*shape) * np.exp(rng.randn(*shape))).astype(np.float32)
     if name == "bf16_ties":
@@ -84,8 +86,9 @@ def family(name, seed, B=8, channels=2):
         z[k == 1] = -0.0
         return z
     if name == "impulse":
-        z = np.zeros((len(IMPULSES), 32, 32, channels), np.float32)
-        for b, (r, c) in enumerate(IMPULSES):
+        impulses = IMPULSES if impulses is None else impulses
+        z = np.zeros((len(impulses), hw[0], hw[1], channels), np.float32)
+        for b, (r, c) in enumerate(impulses):
             z[b, r, c] = (rng.randn(channels) * 3.0).astype(np.float32)
         return z
     if name == "wide_range":
@@ -429,11 +432,11 @@ def test_deepest_split_model_and_the_first_beyond_it_against_the_oracle(n):
     close_elem(m.sample(x, 1.0, None, *args, eps=eps), o64.sample(eps, 1.0), 1e-5)
 
 
-def _mixed_batch(B, seed):
+def _mixed_batch(B, seed, hw=(32, 32)):
     """Patches that differ strongly between neighbours in the batch, so that anything a workgroup keeps from the patch before
     (the shared z0 / relu(h2) buffer, its zero ring, a deferred sum) would show: SIDD-like, all-zero, 30 sigma, low halves on
     bf16 rounding ties, magnitudes spread over six decades — in turn."""
-    x, y = make_inputs(B, seed=seed)
+    x, y = make_inputs(B, hw[0], hw[1], seed=seed)
     rng = np.random.RandomState(seed + 1)
     kind = np.arange(B) % 5
     x[kind == 1] = 0.0
