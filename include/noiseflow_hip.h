@@ -404,6 +404,14 @@ int nf_fold_layout(const nf_config *cfg, const nf_layer_desc *layers,
                    int32_t *ops_out, int32_t ops_cap, int32_t *n_ops, int32_t *layout_width,
                    float *folded, size_t folded_cap, size_t *n_folded);
 
+/* Host-only: how the split-bf16 kernel's launch describes the first counted run of (mix, coupling) pairs of a program in the
+ * NF_PATH_SPLIT_BF16 layout.  `ops` = n_ops (type, offset) pairs and `block` = the n_block floats nf_fold_layout returns for
+ * that path (a test may alter them).  out[8] = run_first (index of the run's first op, -1: no run is described and every
+ * coupling's A offset is read from its NF12_CPL_AOFF field), run_n, run_moff, run_coff, run_stride, run_type, run_aoff,
+ * run_astride: pair i of the run has its mix at run_moff + i * run_stride, its coupling block at run_coff + i * run_stride and
+ * its A image at run_aoff + i * run_astride floats.  No reference counterpart (diagnostic). */
+int nf_split_run_info(const int32_t *ops, int32_t n_ops, const float *block, size_t n_block, int32_t out[8]);
+
 /* Which kernel family nf_nll (direction 0) / nf_sample (direction 1) of this handle launch:
  *   NF_PATH_SCALAR  scalar-weight VALU kernel (any width / shape; also NF_KERNEL=valu)
  *   NF_PATH_MFMA4   width 4 on v_mfma_f32_4x4x1            NF_PATH_FP16 width 4, fp16 CNN (NF_CFG_FP16_CNN)

@@ -148,6 +148,8 @@ def load() -> C.CDLL:
     lib.nf_fold_layout.argtypes = [C.POINTER(nf_config), C.POINTER(nf_layer_desc), C.POINTER(C.c_float), C.c_size_t,
                                    i32, i32, C.POINTER(i32), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float), C.c_size_t,
                                    C.POINTER(C.c_size_t)]
+    lib.nf_split_run_info.restype = C.c_int
+    lib.nf_split_run_info.argtypes = [C.POINTER(i32), i32, C.POINTER(C.c_float), C.c_size_t, C.POINTER(i32)]
     lib.nf_kernel_path.restype = C.c_int
     lib.nf_kernel_path.argtypes = [vp, i32]
     lib.nf_workspace_bytes.restype = i64
@@ -170,7 +172,7 @@ def check(rc: int) -> None:
 
 EXPORTED_SYMBOLS = (
     "nf_abi_version", "nf_last_error", "nf_layer_param_count", "nf_create", "nf_destroy", "nf_nll",
-    "nf_sample", "nf_set_sync", "nf_sample_eps", "nf_tile_plan", "nf_tile_segments", "nf_nll_host", "nf_sample_host", "nf_synth_patches", "nf_fold_params", "nf_fold_layout", "nf_sdn5_scalars",
+    "nf_sample", "nf_set_sync", "nf_sample_eps", "nf_tile_plan", "nf_tile_segments", "nf_nll_host", "nf_sample_host", "nf_synth_patches", "nf_fold_params", "nf_fold_layout", "nf_split_run_info", "nf_sdn5_scalars",
     "nf_nll_batchstats", "nf_sample_batchstats", "nf_sums_reduce", "nf_kernel_path", "nf_workspace_bytes", "nf_reserve_workspace",
     "nf_trainer_create", "nf_trainer_destroy", "nf_trainer_forward_backward", "nf_trainer_forward", "nf_trainer_apply", "nf_trainer_step",
     "nf_trainer_get_params", "nf_trainer_set_params", "nf_trainer_steps", "nf_trainer_set_sync",

@@ -23,7 +23,9 @@
 #include "nf_gemm_layout.h"
 #include "nf_internal.h"
 
-hipError_t nf_launch_flow(const NfProgram &prog, const NfLaunch &a, int n_cu, hipStream_t stream, bool matrix_core);
+hipError_t nf_launch_flow(const NfProgram &prog, const NfLaunch &a, int n_cu, hipStream_t stream, bool matrix_core, const float *block12 = nullptr,
+                          size_t n_block12 = 0);
+void nf_find_run(const NfProgram &prog, const float *block12, size_t n_block12, NfLaunch &a);
 hipError_t nf_launch_wide(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream);
 hipError_t nf_launch_wide16(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream);
 hipError_t nf_launch_gemm(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream);
@@ -1605,6 +1607,25 @@ int nf_fold_layout(const nf_config *cfg, const nf_layer_desc *layers, const floa
     return NF_OK;
 }
 
+int nf_split_run_info(const int32_t *ops, int32_t n_ops, const float *block, size_t n_block, int32_t out[8])
+{
+    if (!ops || !block || !out || n_ops < 0 || n_ops > NF_MAX_OPS) return fail(NF_EINVAL, "bad argument");
+    NfProgram prog;
+    memset(&prog, 0, sizeof(prog));
+    prog.width = 4;
+    prog.n_ops = n_ops;
+    for (int i = 0; i < n_ops; ++i) {
+        prog.ops[i].type = ops[2 * i];
+        prog.ops[i].off = ops[2 * i + 1];
+    }
+    NfLaunch a;
+    memset(&a, 0, sizeof(a));
+    nf_find_run(prog, block, n_block, a);
+    const int32_t v[8] = {a.run_first, a.run_n, a.run_moff, a.run_coff, a.run_stride, a.run_type, a.run_aoff, a.run_astride};
+    memcpy(out, v, sizeof(v));
+    return NF_OK;
+}
+
 int nf_sdn5_scalars(const float *sdn_params, const nf_cond *cond, double out[2])
 {
     if (!sdn_params || !out) return fail(NF_EINVAL, "null argument");
@@ -2055,7 +2076,7 @@ static int launch_resident(nf_handle *h, int direction, NfLaunch &a, hipStream_t
         a.params = d9;
         a.n_params = (int32_t)b.n_lds9;
         a.flags |= NF_K_SPLIT_BF16;
-        hipError_t e = nf_launch_flow(b.prog9, a, h->n_cu, st, true);
+        hipError_t e = nf_launch_flow(b.prog9, a, h->n_cu, st, true, b.block9.data(), b.block9.size());
         if (e != hipSuccess) return fail_hip(e, what);
         return NF_OK;
     }

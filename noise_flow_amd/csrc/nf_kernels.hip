@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 #include <atomic>
 #include "../../include/noiseflow_hip.h"   // NF_SUMS_SLOTS / NF_SUMS_STRIDE
 #include "nf_device.h"
@@ -551,6 +552,16 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     // offsets loaded at its door.
     [[maybe_unused]] const int run_first = a.run_first, run_n = a.run_n, run_moff = a.run_moff, run_coff = a.run_coff, run_stride = a.run_stride,
                                run_type = a.run_type;
+    // SB: the A images of the run's pairs sit a constant stride apart as well (verified on the host: nf_find_run), so the offset of
+    // the image is a scalar that the counted loop advances, and the A operands are buffer loads — descriptor and offset in SGPRs, one
+    // 32-bit lane offset — instead of global loads from three 64-bit vector addresses formed per coupling behind an LDS read of the
+    // field.  The range check covers the whole block.  NF_SB_AOFF 0: the field read and the global loads (A/B aid).
+#ifndef NF_SB_AOFF
+#define NF_SB_AOFF 1
+#endif
+    [[maybe_unused]] const int run_aoff = a.run_aoff, run_astride = a.run_astride;
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t sb_rsrc;
+    if constexpr (SB && NF_SB_AOFF) sb_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.params), 0, a.params_floats * 4, 0x00020000);
 
     // nll / sd / log-det of patch (tile) pb from its three sums: the wavefronts' partials in `rd`, or (one wavefront) r0 r1 r2
     auto finish_patch = [&](const float *rd, int64_t pb, float r0, float r1, float r2) {
@@ -714,6 +725,7 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
             // matrix-core kernels: the counted loop over (mix, coupling) pairs that starts at this op — n pairs, their blocks at
             // moff / coff + i * stride floats, one coupling direction; a coupling without a mix in front takes the identity block
             [[maybe_unused]] int pr_n = 1, pr_moff = 0, pr_coff = 0, pr_stride = 0;
+            [[maybe_unused]] int pr_aoff = 0, pr_astride = 0;   // SB: float offset of the pair's A image and its step
             if constexpr (MFMA) {
                 if (type == NF_OP_MIX) {
 #ifdef NF_TIMELINE
@@ -721,6 +733,7 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
 #endif
                     if (op == run_first) {
                         pr_n = run_n; pr_moff = run_moff; pr_coff = run_coff; pr_stride = run_stride;
+                        pr_aoff = run_aoff; pr_astride = run_astride;
                         type = run_type;
                     } else {
                         const int nt = op + 1 < n_ops ? prog.ops[op + 1].type : 0;
@@ -736,6 +749,10 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 } else if (type == NF_OP_COUPLING_FWD || type == NF_OP_COUPLING_REV) {
                     pr_moff = ident_off;
                     pr_coff = prog.ops[op].off;
+                }
+                if constexpr (SB && NF_SB_AOFF) {   // a pair outside the counted run: its field, read once at the door of the loop
+                    if (pr_n == 1 && (type == NF_OP_COUPLING_FWD || type == NF_OP_COUPLING_REV))
+                        pr_aoff = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wl[pr_coff + NF12_CPL_AOFF]));
                 }
             }
             [[maybe_unused]] int coff = prog.ops[op].off;   // parameter block of the op (of the current coupling inside the pair loop)
@@ -824,9 +841,22 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 // memory (the same bytes for every wavefront: L1 / L2 hits); l_last's are requested while l_1 runs
                 [[maybe_unused]] uint4 sb_a1[6], sb_a3[6];
                 [[maybe_unused]] const uint4 *sb_ag = nullptr;
-                if constexpr (SB) {
-                    // (the offset is arithmetic in the pair index inside the counted loop; carrying it there instead of reading the field
-                    // costs two more live registers, 8 B more scratch, and measured 1.3 % SLOWER on the headline: left as the LDS read)
+                // operand q of section `sec` (NF12_A_A1 / NF12_A_A3) of the image at byte offset ab: 1 KiB per operand, all of it in the
+                // scalar offset (a constant added to the lane offset is loop-invariant and would be hoisted into a register of its own)
+                [[maybe_unused]] int sb_ab = 0;
+                [[maybe_unused]] auto sb_aload = [&](int ab, int sec, int q) {
+                    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(sb_rsrc, (t & 63) * 16, ab + sec * 4 + q * 1024, 0));
+                };
+                if constexpr (SB && NF_SB_AOFF) {
+                    sb_ab = pr_aoff * 4;
+                    pr_aoff += pr_astride;
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) sb_a1[q] = sb_aload(sb_ab, NF12_A_A1, q);
+                    hb_b1 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_B1);
+                    hb_b2 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_B2);
+                } else if constexpr (SB) {
+                    // (the field read: NF_SB_AOFF 0.  Carrying the offset as a VECTOR address in the counted loop cost two more live
+                    // registers, 8 B more scratch, and measured 1.3 % SLOWER on the headline)
                     const int aoff = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wl[coff + NF12_CPL_AOFF]));
                     sb_ag = reinterpret_cast<const uint4 *>(a.params + aoff) + (t & 63);
 #pragma unroll
@@ -873,33 +903,82 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                     const float4 b1 = hb_b1, b2 = hb_b2;
                     const float4 w2 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_W2T + 4 * j4);
                     v4f h1[PX];
+                    // K slot of this lane: one window row, two columns per instruction (16-byte reads of two slots): [region][half]
+                    // NF_SB_RDAHEAD: the operand reads of unit k + 1 are requested while the chain of unit k is being issued instead
+                    // of behind its last instruction — 1: each into the registers the chain has just finished with (region 1's pair
+                    // behind the chain's second instruction, region 0's behind its last), 2: all of them behind the second instruction
+                    // (a second operand set).  0: where the compiler puts them (behind the chain).  The barriers let plain VALU and
+                    // SALU instructions pass (mask 0x406) and hold matrix and LDS instructions in the order written.
+                    // Measured and left at 0: 1 LOSES 0.8 % against 0 and 2 (16 registers more, scratch 12 -> 84 B)
+                    // 6 % — with four wavefronts per SIMD the reads behind a chain are already covered by the other wavefronts'
+                    // chains, and the pinned order costs more than the exposed round trips
+#ifndef NF_SB_RDAHEAD
+#define NF_SB_RDAHEAD 0
+#endif
+                    constexpr int RDA = NF_SB_RDAHEAD;
+                    uint4 q1[PX][2][2];
+                    auto rd1 = [&](int k, int r) {
+#pragma unroll
+                        for (int hf = 0; hf < 2; ++hf) q1[k][r][hf] = *reinterpret_cast<const uint4 *>((r ? sr1 : sr0) + wbase + 2 * k * Wp + 2 * hf);
+                    };
+                    if (RDA) { rd1(0, 1); rd1(0, 0); }
 #pragma unroll
                     for (int k = 0; k < PX; ++k) {
-                        // K slot of this lane: one window row, two columns per instruction (16-byte reads of two slots)
-                        const uint4 q00 = *reinterpret_cast<const uint4 *>(sr0 + wbase + 2 * k * Wp);
-                        const uint4 q01 = *reinterpret_cast<const uint4 *>(sr0 + wbase + 2 * k * Wp + 2);
-                        const uint4 q10 = *reinterpret_cast<const uint4 *>(sr1 + wbase + 2 * k * Wp);
-                        const uint4 q11 = *reinterpret_cast<const uint4 *>(sr1 + wbase + 2 * k * Wp + 2);
+                        if (!RDA) { rd1(k, 0); rd1(k, 1); }
                         // smallest products first: hl + lh, mh + mm, hh + hm
                         v4f acc = v4f{b1.x, b1.y, b1.z, b1.w};
-                        acc = nf_mfma_bf16(sb_a1[4], q10, acc);
-                        acc = nf_mfma_bf16(sb_a1[5], q11, acc);
-                        acc = nf_mfma_bf16(sb_a1[2], q00, acc);
-                        acc = nf_mfma_bf16(sb_a1[3], q01, acc);
-                        acc = nf_mfma_bf16(sb_a1[0], q00, acc);
-                        acc = nf_mfma_bf16(sb_a1[1], q01, acc);
+                        acc = nf_mfma_bf16(sb_a1[4], q1[k][1][0], acc);
+                        acc = nf_mfma_bf16(sb_a1[5], q1[k][1][1], acc);
+                        if (RDA && k + 1 < PX) {
+                            __builtin_amdgcn_sched_barrier(0x406);
+                            rd1(k + 1, 1);
+                            if (RDA >= 2) rd1(k + 1, 0);
+                            __builtin_amdgcn_sched_barrier(0x406);
+                        }
+                        acc = nf_mfma_bf16(sb_a1[2], q1[k][0][0], acc);
+                        acc = nf_mfma_bf16(sb_a1[3], q1[k][0][1], acc);
+                        acc = nf_mfma_bf16(sb_a1[0], q1[k][0][0], acc);
+                        acc = nf_mfma_bf16(sb_a1[1], q1[k][0][1], acc);
+                        if (RDA == 1 && k + 1 < PX) {
+                            __builtin_amdgcn_sched_barrier(0x406);
+                            rd1(k + 1, 0);
+                            __builtin_amdgcn_sched_barrier(0x406);
+                        }
                         h1[k] = acc;
                     }
 #pragma unroll
-                    for (int q = 0; q < 6; ++q) sb_a3[q] = sb_ag[NF12_A_A3 / 4 + 64 * q];
+                    for (int q = 0; q < 6; ++q) sb_a3[q] = NF_SB_AOFF ? sb_aload(sb_ab, NF12_A_A3, q) : sb_ag[NF12_A_A3 / 4 + 64 * q];
                     uint2 hs[PX][3];   // relu(h2) of the lane's pixels, three pieces
+                    // NF_SB_L2IL 1: the four units' l_2 chains issued side by side (one product of each in turn, held in that order),
+                    // so that no s_nop stands between two dependent v_mfma_f32_4x4x1; each chain's own order is unchanged.  0: unit by
+                    // unit in the source, interleaved where the scheduler sees fit (units 2 and 3).  Measured with NF_SB_RDAHEAD 1: + 0.2 %,
+                    // inside the run-to-run spread (the s_nop that remain wait for the v_max in front of each product): left at 0
+#ifndef NF_SB_L2IL
+#define NF_SB_L2IL 0
+#endif
+                    [[maybe_unused]] v4f h2s[PX];
+                    if (NF_SB_L2IL) {
+                        const float w2v[4] = {w2.x, w2.y, w2.z, w2.w};
+#pragma unroll
+                        for (int k = 0; k < PX; ++k) h2s[k] = v4f{b2.x, b2.y, b2.z, b2.w};
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+                            for (int k = 0; k < PX; ++k) h2s[k] = __builtin_amdgcn_mfma_f32_4x4x1f32(w2v[c], nf_relu(h1[k][c]), h2s[k], 0, 0, 0);
+                            __builtin_amdgcn_sched_barrier(0x406);
+                        }
+                    }
 #pragma unroll
                     for (int k = 0; k < PX; ++k) {
                         v4f h2 = {b2.x, b2.y, b2.z, b2.w};
+                        if (NF_SB_L2IL) {
+                            h2 = h2s[k];
+                        } else {
                         h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.x, nf_relu(h1[k][0]), h2, 0, 0, 0);
                         h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.y, nf_relu(h1[k][1]), h2, 0, 0, 0);
                         h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.z, nf_relu(h1[k][2]), h2, 0, 0, 0);
                         h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.w, nf_relu(h1[k][3]), h2, 0, 0, 0);
+                        }
                         uint32_t p01[3], p23[3];
                         nf_split3(nf_relu(h2[0]), nf_relu(h2[1]), p01[0], p01[1], p01[2]);
                         nf_split3(nf_relu(h2[2]), nf_relu(h2[3]), p23[0], p23[1], p23[2]);
@@ -1216,27 +1295,61 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 {
                     float o[PX][4];
                     float sc;
+                    // SB, NF_SB_AFFINE 1: ls * log2(e) of unit k (two exp2, two rcp, two fma: the part of the affine stage that does not
+                    // depend on the direction) is formed in the source under the chain of unit k + 1, between the same barriers as
+                    // that chain's read-ahead.  0: behind the last chain, where the scheduler moves what it likes.  Measured with
+                    // NF_SB_RDAHEAD 1: no difference (+0.01 %), 16 B more scratch: left at 0
+#ifndef NF_SB_AFFINE
+#define NF_SB_AFFINE 0
+#endif
+                    [[maybe_unused]] float sb_l[PX][2];
+                    [[maybe_unused]] float sb_scl = 0.f, sb_m2scl = 0.f;
                     if constexpr (SB) {
                         sc = 0.0f;
+                        if (NF_SB_AFFINE) {
+                            sb_scl = wl[coff + NF12_CPL_S + 1];
+                            sb_m2scl = wl[coff + NF12_CPL_S + 2];
+                        }
+                        [[maybe_unused]] auto affine_ls = [&](int k) {
+                            sb_l[k][0] = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][2]) + 1.0f), sb_m2scl, sb_scl);
+                            sb_l[k][1] = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][3]) + 1.0f), sb_m2scl, sb_scl);
+                        };
                         uint2 *const srp[3] = {sr0, sr1, sr2};
+                        // smallest products first: (h l, l h, m m), (h m, m h), h h — weight piece x activation piece
+                        constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+                        // NF_SB_RDAHEAD (l_1 above): activation piece 2 is last used by product 0 of a chain, piece 1 by product 3 and
+                        // piece 0 by product 5 — 1: unit k + 1's reads of a piece follow the last use of that piece in unit k's chain,
+                        // 2: all six follow product 0
+                        constexpr int RDA = NF_SB_RDAHEAD;
+                        constexpr int AFTER[3] = {RDA >= 2 ? 0 : 5, RDA >= 2 ? 0 : 3, 0};   // by piece: the product its read-ahead follows
+                        uint4 qb[PX][3][2];   // [unit][piece][m3]: K slot = two adjacent window pixels x 4 channels, one 16-byte read
+                        auto rd3 = [&](int k, int p) {
+#pragma unroll
+                            for (int m3 = 0; m3 < 2; ++m3) qb[k][p][m3] = *reinterpret_cast<const uint4 *>(srp[p] + wbase3 + (2 * k + m3) * Wp);
+                        };
+                        if (RDA) { rd3(0, 2); rd3(0, 0); rd3(0, 1); }
 #pragma unroll
                         for (int k = 0; k < PX; ++k) {
-                            uint4 qb[3][2];   // [piece][m3]: K slot = two adjacent window pixels x 4 channels, one 16-byte read
-#pragma unroll
-                            for (int p = 0; p < 3; ++p)
-#pragma unroll
-                                for (int m3 = 0; m3 < 2; ++m3) qb[p][m3] = *reinterpret_cast<const uint4 *>(srp[p] + wbase3 + (2 * k + m3) * Wp);
+                            if (!RDA) { rd3(k, 0); rd3(k, 1); rd3(k, 2); }
                             const float4 e = hb_e[k];
                             v4f acc = v4f{e.x, e.y, e.z, e.w};
-                            // smallest products first: (h l, l h, m m), (h m, m h), h h — weight piece x activation piece
-                            constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
 #pragma unroll
-                            for (int t6 = 0; t6 < 6; ++t6)
+                            for (int t6 = 0; t6 < 6; ++t6) {
 #pragma unroll
-                                for (int m3 = 0; m3 < 2; ++m3) acc = nf_mfma_bf16(sb_a3[2 * PA[t6] + m3], qb[PB[t6]][m3], acc);
+                                for (int m3 = 0; m3 < 2; ++m3) acc = nf_mfma_bf16(sb_a3[2 * PA[t6] + m3], qb[k][PB[t6]][m3], acc);
+                                if (RDA && k + 1 < PX && (t6 == AFTER[0] || t6 == AFTER[1] || t6 == AFTER[2])) {
+                                    __builtin_amdgcn_sched_barrier(0x406);
+#pragma unroll
+                                    for (int p = 2; p >= 0; --p)
+                                        if (AFTER[p] == t6) rd3(k + 1, p);
+                                    __builtin_amdgcn_sched_barrier(0x406);
+                                }
+                                if (NF_SB_AFFINE && t6 == 0 && k > 0) affine_ls(k - 1);
+                            }
 #pragma unroll
                             for (int j = 0; j < 4; ++j) o[k][j] = acc[j];
                         }
+                        if (NF_SB_AFFINE) affine_ls(PX - 1);
                     } else if constexpr (HB) {
                         const float *wb = wl + coff;
                         const uint32_t *wbw = reinterpret_cast<const uint32_t *>(wb);
@@ -1431,8 +1544,14 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                         if (type == NF_OP_COUPLING_FWD) {
 #pragma unroll
                             for (int k = 0; k < PX; ++k) {
-                                const float l0 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][2]) + 1.0f), m2scl, scl);
-                                const float l1 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][3]) + 1.0f), m2scl, scl);
+                                float l0, l1;
+                                if constexpr (SB && NF_SB_AFFINE) {
+                                    l0 = sb_l[k][0];
+                                    l1 = sb_l[k][1];
+                                } else {
+                                    l0 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][2]) + 1.0f), m2scl, scl);
+                                    l1 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][3]) + 1.0f), m2scl, scl);
+                                }
                                 z[k][2] = fmaf(z[k][2], __builtin_amdgcn_exp2f(l0), o[k][0]);
                                 z[k][3] = fmaf(z[k][3], __builtin_amdgcn_exp2f(l1), o[k][1]);
                                 if (own[k]) ld2 += l0 + l1;
@@ -1440,8 +1559,14 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                         } else {
 #pragma unroll
                             for (int k = 0; k < PX; ++k) {
-                                const float l0 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][2]) + 1.0f), m2scl, scl);
-                                const float l1 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][3]) + 1.0f), m2scl, scl);
+                                float l0, l1;
+                                if constexpr (SB && NF_SB_AFFINE) {
+                                    l0 = sb_l[k][0];
+                                    l1 = sb_l[k][1];
+                                } else {
+                                    l0 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][2]) + 1.0f), m2scl, scl);
+                                    l1 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][3]) + 1.0f), m2scl, scl);
+                                }
                                 z[k][2] = (z[k][2] - o[k][0]) * __builtin_amdgcn_exp2f(-l0);
                                 z[k][3] = (z[k][3] - o[k][1]) * __builtin_amdgcn_exp2f(-l1);
                             }
@@ -1933,12 +2058,15 @@ hipError_t dispatch_geom(const NfProgram &prog, const NfLaunch &a, int n_cu, hip
 }  // namespace
 
 // ---- entry points used by nf_host.hip ----
-hipError_t nf_launch_flow(const NfProgram &prog, const NfLaunch &a_in, int n_cu, hipStream_t stream, bool matrix_core)
+// The first run of `mix, coupling` pairs of a program whose parameter blocks sit a constant stride apart -> a.run_*, a.n_cpl,
+// a.fair_t*.  block12 (host copy of an NF12_* block of n_block12 floats, or null for the other layouts): the pairs' A images must
+// sit at run_aoff + i * run_astride as well, each inside the block; where they do not, NO run is described (run_first = -1).
+void nf_find_run(const NfProgram &prog, const float *block12, size_t n_block12, NfLaunch &a)
 {
-    // what the kernels would otherwise find out with scalar loads, once per workgroup (= once per patch in a one-round launch)
-    NfLaunch a = a_in;
     a.run_first = -1;
     a.run_n = a.run_moff = a.run_coff = a.run_stride = a.run_type = a.n_cpl = 0;
+    a.run_aoff = a.run_astride = 0;
+    a.params_floats = (int32_t)n_block12;
     auto is_cpl = [](int t) { return t == NF_OP_COUPLING_FWD || t == NF_OP_COUPLING_REV; };
     for (int q = 0; q < prog.n_ops; ++q) a.n_cpl += is_cpl(prog.ops[q].type) ? 1 : 0;
     const int ct = a.n_cpl < 1 ? 1 : a.n_cpl;
@@ -1961,6 +2089,39 @@ hipError_t nf_launch_flow(const NfProgram &prog, const NfLaunch &a_in, int n_cu,
             ++a.run_n;
         }
     }
+    if (!block12 || a.run_first < 0) return;
+    auto aoff_of = [&](int i, int64_t &off) {   // the field of pair i; false: the field or the image it names lies outside the block
+        const int64_t at = (int64_t)a.run_coff + (int64_t)i * a.run_stride + NF12_CPL_AOFF;
+        if (at < 0 || (size_t)at >= n_block12) return false;
+        int32_t v;
+        memcpy(&v, block12 + at, 4);
+        off = v;
+        return v >= 0 && (size_t)v + NF12_A_SIZE <= n_block12;
+    };
+    int64_t first = 0, second = 0;
+    bool ok = aoff_of(0, first);
+    if (ok && a.run_n > 1) ok = aoff_of(1, second);
+    const int64_t stride = a.run_n > 1 ? second - first : 0;
+    for (int i = 2; ok && i < a.run_n; ++i) {
+        int64_t v = 0;
+        ok = aoff_of(i, v) && v == first + i * stride;
+    }
+    if (ok) {
+        a.run_aoff = (int32_t)first;
+        a.run_astride = (int32_t)stride;
+    } else {
+        a.run_first = -1;
+        a.run_n = a.run_moff = a.run_coff = a.run_stride = a.run_type = 0;
+    }
+}
+
+hipError_t nf_launch_flow(const NfProgram &prog, const NfLaunch &a_in, int n_cu, hipStream_t stream, bool matrix_core, const float *block12,
+                          size_t n_block12)
+{
+    // what the kernels would otherwise find out with scalar loads, once per workgroup (= once per patch in a one-round launch)
+    NfLaunch a = a_in;
+    nf_find_run(prog, block12, n_block12, a);
+    if ((a.flags & NF_K_SPLIT_BF16) && !block12) return hipErrorInvalidValue;   // the split-bf16 kernel bounds its A loads by the block
     if (matrix_core) return prog.width == 4 ? dispatch_geom<4, true>(prog, a, n_cu, stream) : hipErrorInvalidValue;
     switch (prog.width) {
     case 4: return dispatch_geom<4, false>(prog, a, n_cu, stream);
