@@ -216,6 +216,41 @@ int nf_sample(nf_handle *h, const float *y, const float *eps, uint64_t seed,
 int nf_sample_eps(uint64_t seed, int64_t patch_index_base, int64_t B, int32_t height, int32_t width,
                   float *eps_out, void *stream);
 
+/* Per-PATCH conditioning: a minibatch that mixes cameras and ISOs (a noise generator for denoiser training) in ONE call
+ * instead of one call per (ISO, camera) group.  All a kernel needs of a patch's nf_cond is two scalars per conditional
+ * layer and, in the NLL direction, the patch's share of the constant log-det: one nf_cond_row, made on the host by
+ * nf_cond_rows and read by the kernels once per patch (scalar loads, nothing inside the per-pixel loops).
+ * 48 bytes; an array of rows must start 16-byte aligned. */
+typedef struct nf_cond_row {
+    float  a[4];      /* slot i: SDN kinds scale^2 = a*y + b;  gain kinds z *= a  (already 1/scale in the NLL direction) */
+    float  b[4];
+    double ld;        /* this patch's share of the constant log-det (plain gain kinds), 0 in the sampling direction */
+    double reserved;  /* 0 */
+} nf_cond_row;
+
+/* rows_out[k] (HOST, n rows) = what nf_nll (direction 0) / nf_sample (direction 1) of a model created from the same
+ * arguments would hand its kernels for conds[k]: the same arithmetic, so a patch gets the same bits either way.  Slots the
+ * model does not use hold a = 0, b = 1.  Host-only: no device, no handle (same argument style as nf_fold_params).  A row
+ * is valid for every model with these parameters and this patch size, so callers compute one row per DISTINCT condition and
+ * gather.  An unknown camera in conds[k] returns NF_ECOND and nf_last_error() names k; a non-positive gain scale returns
+ * NF_EINVAL.  n = 0 is fine. */
+int nf_cond_rows(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params,
+                 int32_t direction, const nf_cond *conds, int64_t n, nf_cond_row *rows_out);
+
+/* nf_nll / nf_sample with patch b conditioned by rows[b] (DEVICE memory, [B], 16-byte aligned, on the handle's device;
+ * NULL with B > 0, a misaligned pointer or another device's memory is NF_EINVAL).  Everything else — arguments, kernel
+ * selection (nf_kernel_path), re-entrancy, no synchronisation, no allocation up to 64x64, images beyond 64x64 (the row is
+ * the IMAGE's) — is as for nf_nll / nf_sample, and every output of a patch has the bits the per-call entry gives that
+ * patch under the same condition.  The rows must stay unchanged until the work enqueued on `stream` has run.
+ * There are no per-patch variants of the batch-statistics (nf_*_batchstats), host-fed (nf_*_host) or trainer entries,
+ * and no per-patch temperature (nf_sample_eps above covers it). */
+int nf_nll_percond(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond_row *rows,
+                   float *nll_out, float *sd_out, float *logdet_out, float *z_out,
+                   double *sums_out, uint32_t flags, void *stream);
+int nf_sample_percond(nf_handle *h, const float *y, const float *eps, uint64_t seed,
+                      int64_t patch_index_base, float temp, int64_t B, const nf_cond_row *rows,
+                      float *x_out, void *stream);
+
 /* The tile plan of one image axis (see "Patch sizes"): `size` pixels, tiles of `tile` = min(size, 64) pixels, `halo` =
  * 2 x the number of coupling layers.  Returns the number of tiles n (or a negative NF_E* code) and, for i < min(n, cap),
  * the tile's first pixel origin[i] and the window [core0[i], core1[i]) it reports — a partition of [0, size) with

@@ -70,12 +70,15 @@ class NoiseFlowWrapper:
         self.nf_model.restore(self.model_checkpoint_path)
 
     def sample_noise_nf(self, batch_x, b1, b2, iso, cam):
-        """NoiseFlowWrapper.py:81-87 → float32 [B,32,32,4] noise (unclipped)."""
+        """NoiseFlowWrapper.py:81-87 → float32 [B,32,32,4] noise (unclipped).  ``b1, b2, iso, cam``: one value for the
+        batch as in the reference, or (each on its own) a length-B sequence — one value per patch of a mixed minibatch,
+        still one call (``bn_mode='running'`` only)."""
         return self.sample_sidd_tf(batch_x, b1, b2, iso, cam)
 
     def sample_sidd_tf(self, batch_x, b1=0.0, b2=0.0, iso=100.0, cam=2.0):
         if self.is_cond:
-            x = self.nf_model.sample(batch_x, self.temp, batch_x, [b1], [b2], [iso], [cam])
+            b1, b2, iso, cam = (v if hasattr(v, "__len__") else [v] for v in (b1, b2, iso, cam))
+            x = self.nf_model.sample(batch_x, self.temp, batch_x, b1, b2, iso, cam)
         else:
             x = self.nf_model.sample(batch_x, self.temp)
         return x.astype(np.float32) if isinstance(x, np.ndarray) else x

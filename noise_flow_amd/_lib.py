@@ -54,6 +54,11 @@ class nf_cond(C.Structure):
     _fields_ = [("iso", C.c_float), ("cam", C.c_float), ("nlf0", C.c_float), ("nlf1", C.c_float)]
 
 
+class nf_cond_row(C.Structure):
+    """What one patch's conditional ops read (48 bytes); numpy view: COND_ROW_DTYPE."""
+    _fields_ = [("a", C.c_float * 4), ("b", C.c_float * 4), ("ld", C.c_double), ("reserved", C.c_double)]
+
+
 class NoiseFlowLibError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__("noiseflow_hip error %d: %s" % (code, msg))
@@ -158,6 +163,13 @@ def load() -> C.CDLL:
     lib.nf_reserve_workspace.argtypes = [vp, i64, i32]
     lib.nf_sdn5_scalars.restype = C.c_int
     lib.nf_sdn5_scalars.argtypes = [C.POINTER(C.c_float), C.POINTER(nf_cond), C.POINTER(C.c_double)]
+    lib.nf_cond_rows.restype = C.c_int
+    lib.nf_cond_rows.argtypes = [C.POINTER(nf_config), C.POINTER(nf_layer_desc), C.POINTER(C.c_float), C.c_size_t, i32,
+                                 C.POINTER(nf_cond), i64, C.POINTER(nf_cond_row)]
+    lib.nf_nll_percond.restype = C.c_int
+    lib.nf_nll_percond.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, u32, vp]
+    lib.nf_sample_percond.restype = C.c_int
+    lib.nf_sample_percond.argtypes = [vp, vp, vp, u64, i64, f32, i64, vp, vp, vp]
     if lib.nf_abi_version() != 1:
         raise ImportError("noiseflow_hip ABI version mismatch")
     _lib = lib
@@ -176,6 +188,7 @@ EXPORTED_SYMBOLS = (
     "nf_nll_batchstats", "nf_sample_batchstats", "nf_sums_reduce", "nf_kernel_path", "nf_workspace_bytes", "nf_reserve_workspace",
     "nf_trainer_create", "nf_trainer_destroy", "nf_trainer_forward_backward", "nf_trainer_forward", "nf_trainer_apply", "nf_trainer_step",
     "nf_trainer_get_params", "nf_trainer_set_params", "nf_trainer_steps", "nf_trainer_set_sync",
+    "nf_cond_rows", "nf_nll_percond", "nf_sample_percond",
 )
 NF_PATH_SCALAR, NF_PATH_MFMA4, NF_PATH_FP16, NF_PATH_WIDE32, NF_PATH_WIDE16, NF_PATH_WIDE32_FP16, NF_PATH_GEMM, NF_PATH_GEMM_FP16 = 0, 1, 2, 3, 4, 5, 6, 7
 NF_PATH_SPLIT_BF16 = 8

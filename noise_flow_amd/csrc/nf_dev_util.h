@@ -11,6 +11,40 @@ namespace {
 // the constant address space so that every wave-uniform fetch becomes an s_load
 // (scalar cache, SGPR operands) instead of a per-lane global_load into VGPRs.
 typedef const float __attribute__((address_space(4))) *cfloat_p;
+// The conditioning rows of a per-patch call (NfLaunch::cond_rows) are immutable while it runs: the same address space, for the same
+// reason.  The row index is the patch (or, tiled, the image) of the persistent loop's current iteration — wave-uniform — so the
+// fetches below are scalar loads made once per patch and conditional op, never inside a per-pixel loop.
+// PC is a template flag of every fused kernel body: the per-call kernels (PC = false) compile to the code they were before the
+// rows existed — these kernels sit at their scalar-register limit, and a run-time choice between the two sources moved their
+// register allocation — and each has a twin with PC = true that the launchers pick when cond_rows is set (nf_kernels.hip,
+// nf_wide.hip: `..._pc_kernel` wrappers of the shared body; the GEMM and width-16 kernels carry the flag themselves, because
+// moving their code into a body behind a wrapper changed their spills).
+typedef const nf_cond_row __attribute__((address_space(4))) *nf_crow_p;
+template <bool PC>
+__device__ __forceinline__ nf_crow_p nf_cond_row_of(const NfLaunch &a, int64_t patch)
+{
+    if constexpr (PC) return (nf_crow_p)(a.cond_rows) + patch;
+    else return (nf_crow_p) nullptr;
+}
+template <bool PC>
+__device__ __forceinline__ float nf_cond_a(const NfLaunch &a, nf_crow_p row, int slot)
+{
+    if constexpr (PC) return row->a[slot & 3];
+    else return a.cond_a[slot & 3];
+}
+template <bool PC>
+__device__ __forceinline__ float nf_cond_b(const NfLaunch &a, nf_crow_p row, int slot)
+{
+    if constexpr (PC) return row->b[slot & 3];
+    else return a.cond_b[slot & 3];
+}
+// the constant part of a patch's log-det: the per-call path's host sum `call part + model part`, formed in the same order
+template <bool PC>
+__device__ __forceinline__ double nf_cond_ld(const NfLaunch &a, nf_crow_p row)
+{
+    if constexpr (PC) return row->ld + a.ld_const;
+    else return a.ld_const;
+}
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef _Float16 v4h __attribute__((ext_vector_type(4)));
 typedef _Float16 v8h __attribute__((ext_vector_type(8)));

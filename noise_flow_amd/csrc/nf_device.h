@@ -6,6 +6,7 @@
 // all intermediate tensors in registers / LDS.
 #pragma once
 #include <stdint.h>
+#include "../../include/noiseflow_hip.h"   // nf_cond_row
 
 #define NF_MAX_OPS 64
 
@@ -389,6 +390,10 @@ struct NfLaunch {
     // NF12_CPL_AOFF fields say, verified on the host: a run whose fields are no such progression is not described at all, and its
     // pairs then go through the loop one by one with the field read at its door); params_floats = the whole block, A images included
     int32_t run_aoff, run_astride, params_floats;
+    // per-patch conditioning (nf_nll_percond / nf_sample_percond): [B] rows (per IMAGE with NF_K_TILED), or null = the per-call
+    // cond_a / cond_b above.  When set, a kernel takes cond_a / cond_b from the row of the patch it is working on and forms the
+    // log-det constant as row.ld + ld_const, ld_const then holding the model's part only (nf_dev_util.h, nf_cond_*).
+    const nf_cond_row *cond_rows;
 };
 
 #define NF_STATS_SLOTS 64   // power of two

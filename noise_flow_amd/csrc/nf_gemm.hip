@@ -50,7 +50,8 @@ __device__ __forceinline__ float4 ldg4(const float *p) { return *reinterpret_cas
 //   OWN     pixels per thread: 2 (patches <= 1024 pixels), 4 (<= 2048) or 8 (<= 4096: 64x64)
 //   BRD     the pass-through tile carries a zero border ('SAME' padding by construction).  Beside the 128 KiB band a bordered
 //           64x64 tile does not fit the 160 KiB of a CU by 2 KiB: !BRD keeps the bare H x W planes and masks the taps instead
-template <int WP, bool PHILOX, int OWN, bool BRD>
+//   PC      per-patch conditioning (NfLaunch::cond_rows set; nf_dev_util.h): false compiles to the per-call kernel as it was
+template <int WP, bool PHILOX, int OWN, bool BRD, bool PC = false>
 __global__ __launch_bounds__(GT) void nf_gemm_kernel(const NfProgram prog, const NfLaunch a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(GT) void nf_gemm_kernel(const NfProgram prog, const
     double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const GemmTile T = gemm_tile(a, b, H, W);
+        const GemmTile T = gemm_tile<PC>(a, b, H, W);
         float z[OWN][4];
         gemm_input<OWN, PHILOX>(a, T, pr, pc, act, z);
 
@@ -297,13 +298,13 @@ __global__ __launch_bounds__(GT) void nf_gemm_kernel(const NfProgram prog, const
                 // ---- finish the coupling on the owned pixels ----
                 gemm_finish_coupling<OWN, false>(type, a.params + prog.ops[op].off + NF7_CPL_E, P[NF7_CPL_S + 1], P[NF7_CPL_S + 2], T, pr, pc, act, o, z, ld2);
             } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
-                gemm_sdn<OWN>(type, prog.ops[op].off, a, T, pr, pc, act, z, ld);
+                gemm_sdn<OWN, PC>(type, prog.ops[op].off, a, T, pr, pc, act, z, ld);
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : a.cond_a[prog.ops[op].off & 3], z);
+                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off), z);
             }
         }
 
-        gemm_epilogue<OWN, GT>(a, T, b, HW, pr, pc, act, z, ld, ld2, red, acc_nll, acc_sd);
+        gemm_epilogue<OWN, GT, PC>(a, T, b, HW, pr, pc, act, z, ld, ld2, red, acc_nll, acc_sd);
     }
     gemm_flush_sums(a, acc_nll, acc_sd);
 }
@@ -316,7 +317,8 @@ __global__ __launch_bounds__(GT) void nf_gemm_kernel(const NfProgram prog, const
 // through LDS — one slab per output tile (nf_gemm_layout.h, NF10_*), all slabs of a coupling staged once per patch and resident
 // for its rounds (85 KiB at width 128).  Nothing is re-streamed per band and the band bookkeeping of variant A (4 barriers, a
 // partial-sum gather over WM wavefronts) shrinks to 2 barriers per round.  Beyond 128 the slabs do not fit and variant A runs.
-template <int WP, bool PHILOX, int OWN>
+//   PC      per-patch conditioning (NfLaunch::cond_rows set; nf_dev_util.h): false compiles to the per-call kernel as it was
+template <int WP, bool PHILOX, int OWN, bool PC = false>
 __global__ __launch_bounds__(GT) void nf_gemmb_kernel(const NfProgram prog, const NfLaunch a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -354,7 +356,7 @@ __global__ __launch_bounds__(GT) void nf_gemmb_kernel(const NfProgram prog, cons
     double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const GemmTile T = gemm_tile(a, b, H, W);
+        const GemmTile T = gemm_tile<PC>(a, b, H, W);
         float z[OWN][4];
         gemm_input<OWN, PHILOX>(a, T, pr, pc, act, z);
 
@@ -499,13 +501,13 @@ __global__ __launch_bounds__(GT) void nf_gemmb_kernel(const NfProgram prog, cons
                 // ---- finish the coupling on the owned pixels ----
                 gemm_finish_coupling<OWN, false>(type, a.params + prog.ops[op].off + NF7_CPL_E, P[NF7_CPL_S + 1], P[NF7_CPL_S + 2], T, pr, pc, act, o, z, ld2);
             } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
-                gemm_sdn<OWN>(type, prog.ops[op].off, a, T, pr, pc, act, z, ld);
+                gemm_sdn<OWN, PC>(type, prog.ops[op].off, a, T, pr, pc, act, z, ld);
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : a.cond_a[prog.ops[op].off & 3], z);
+                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off), z);
             }
         }
 
-        gemm_epilogue<OWN, GT>(a, T, b, HW, pr, pc, act, z, ld, ld2, red, acc_nll, acc_sd);
+        gemm_epilogue<OWN, GT, PC>(a, T, b, HW, pr, pc, act, z, ld, ld2, red, acc_nll, acc_sd);
     }
     gemm_flush_sums(a, acc_nll, acc_sd);
 }
@@ -516,11 +518,14 @@ size_t gemmb_lds_bytes(int wp, int H, int W)
     return ((size_t)(wp / 32) * nf10_slab_floats(wp) + (size_t)32 * GW * NF7_P_STRIDE + 2 * (size_t)PL + 3 * GW + 8) * sizeof(float);
 }
 
-template <int WP, bool PHILOX, int OWN>
+template <int WP, bool PHILOX, int OWN, bool PC = false>
 hipError_t launch_gemmb(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
 {
+    if constexpr (!PC) {
+        if (a.cond_rows) return launch_gemmb<WP, PHILOX, OWN, true>(prog, a, n_cu, device, stream);
+    }
     static std::atomic<size_t> lds_set[16];
-    return gemm_launch_per_cu<GT>(&nf_gemmb_kernel<WP, PHILOX, OWN>, gemmb_lds_bytes(WP, a.H, a.W), lds_set, prog, a, n_cu, device, stream);
+    return gemm_launch_per_cu<GT>(&nf_gemmb_kernel<WP, PHILOX, OWN, PC>, gemmb_lds_bytes(WP, a.H, a.W), lds_set, prog, a, n_cu, device, stream);
 }
 
 template <int WP, bool PHILOX>
@@ -535,11 +540,14 @@ size_t gemm_lds_bytes(int H, int W, bool bordered = true)
     return ((size_t)NF7_BAND_FLOATS + 2 * (size_t)PL + (bordered ? 3 * GW + 8 : 0)) * sizeof(float);
 }
 
-template <int WP, bool PHILOX, int OWN, bool BRD = true>
+template <int WP, bool PHILOX, int OWN, bool BRD = true, bool PC = false>
 hipError_t launch_gemm(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
 {
+    if constexpr (!PC) {
+        if (a.cond_rows) return launch_gemm<WP, PHILOX, OWN, BRD, true>(prog, a, n_cu, device, stream);
+    }
     static std::atomic<size_t> lds_set[16];
-    return gemm_launch_per_cu<GT>(&nf_gemm_kernel<WP, PHILOX, OWN, BRD>, gemm_lds_bytes(a.H, a.W, BRD), lds_set, prog, a, n_cu, device, stream);
+    return gemm_launch_per_cu<GT>(&nf_gemm_kernel<WP, PHILOX, OWN, BRD, PC>, gemm_lds_bytes(a.H, a.W, BRD), lds_set, prog, a, n_cu, device, stream);
 }
 
 template <int WP, bool PHILOX>

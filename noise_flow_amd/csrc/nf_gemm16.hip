@@ -46,7 +46,8 @@ __device__ __forceinline__ float4 ldg4(const float *p) { return *reinterpret_cas
 //   WP      padded coupling width: 64, 128, 256, 512
 //   PHILOX  input = in-kernel Philox/Box-Muller draw
 //   OWN     pixels per thread: 2 (patches <= 1024 pixels), 4 (<= 2048) or 8 (<= 4096: 64x64)
-template <int WP, bool PHILOX, int OWN>
+//   PC      per-patch conditioning (NfLaunch::cond_rows set; nf_dev_util.h): false compiles to the per-call kernel as it was
+template <int WP, bool PHILOX, int OWN, bool PC = false>
 __global__ __launch_bounds__(GT) void nf_gemm16_kernel(const NfProgram prog, const NfLaunch a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(GT) void nf_gemm16_kernel(const NfProgram prog, con
     double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const GemmTile T = gemm_tile(a, b, H, W);
+        const GemmTile T = gemm_tile<PC>(a, b, H, W);
         float z[OWN][4];
         gemm_input<OWN, PHILOX>(a, T, pr, pc, act, z);
 
@@ -279,13 +280,13 @@ __global__ __launch_bounds__(GT) void nf_gemm16_kernel(const NfProgram prog, con
                 // ---- finish the coupling on the owned pixels ----
                 gemm_finish_coupling<OWN, true>(type, a.params + prog.ops[op].off + NF8_CPL_E, P[NF8_CPL_S + 1], P[NF8_CPL_S + 2], T, pr, pc, act, o, z, ld2);
             } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
-                gemm_sdn<OWN>(type, prog.ops[op].off, a, T, pr, pc, act, z, ld);
+                gemm_sdn<OWN, PC>(type, prog.ops[op].off, a, T, pr, pc, act, z, ld);
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : a.cond_a[prog.ops[op].off & 3], z);
+                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off), z);
             }
         }
 
-        gemm_epilogue<OWN, GT>(a, T, b, HW, pr, pc, act, z, ld, ld2, red, acc_nll, acc_sd);
+        gemm_epilogue<OWN, GT, PC>(a, T, b, HW, pr, pc, act, z, ld, ld2, red, acc_nll, acc_sd);
     }
     gemm_flush_sums(a, acc_nll, acc_sd);
 }
@@ -301,7 +302,8 @@ __global__ __launch_bounds__(GT) void nf_gemm16_kernel(const NfProgram prog, con
 // and coupling instead of once per band, and the operand every wavefront needs sits in LDS (1 KiB per MFMA and wavefront =
 // 128 of the 256 B/clk ds_read_b128 delivers).  A streamed version for 256 / 512 (slabs double-buffered behind the previous
 // tile's MFMAs, one barrier per tile) was measured below variant A (599 against 795 TFLOP/s at 512) and is not kept.
-template <int WP, bool PHILOX, int OWN>
+//   PC      per-patch conditioning (NfLaunch::cond_rows set; nf_dev_util.h): false compiles to the per-call kernel as it was
+template <int WP, bool PHILOX, int OWN, bool PC = false>
 __global__ __launch_bounds__(GT) void nf_gemm16b_kernel(const NfProgram prog, const NfLaunch a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -343,7 +345,7 @@ __global__ __launch_bounds__(GT) void nf_gemm16b_kernel(const NfProgram prog, co
     double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const GemmTile T = gemm_tile(a, b, H, W);
+        const GemmTile T = gemm_tile<PC>(a, b, H, W);
         float z[OWN][4];
         gemm_input<OWN, PHILOX>(a, T, pr, pc, act, z);
 
@@ -496,13 +498,13 @@ __global__ __launch_bounds__(GT) void nf_gemm16b_kernel(const NfProgram prog, co
                 // ---- finish the coupling on the owned pixels ----
                 gemm_finish_coupling<OWN, true>(type, a.params + prog.ops[op].off + NF8_CPL_E, P[NF8_CPL_S + 1], P[NF8_CPL_S + 2], T, pr, pc, act, o, z, ld2);
             } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
-                gemm_sdn<OWN>(type, prog.ops[op].off, a, T, pr, pc, act, z, ld);
+                gemm_sdn<OWN, PC>(type, prog.ops[op].off, a, T, pr, pc, act, z, ld);
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : a.cond_a[prog.ops[op].off & 3], z);
+                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off), z);
             }
         }
 
-        gemm_epilogue<OWN, GT>(a, T, b, HW, pr, pc, act, z, ld, ld2, red, acc_nll, acc_sd);
+        gemm_epilogue<OWN, GT, PC>(a, T, b, HW, pr, pc, act, z, ld, ld2, red, acc_nll, acc_sd);
     }
     gemm_flush_sums(a, acc_nll, acc_sd);
 }
@@ -513,11 +515,14 @@ size_t gemm16b_lds_bytes(int wp, int H, int W)
     return ((size_t)MT * SLAB + (size_t)32 * GW * PSTR + (size_t)PL + 3 * GW + 8) * sizeof(float);
 }
 
-template <int WP, bool PHILOX, int OWN>
+template <int WP, bool PHILOX, int OWN, bool PC = false>
 hipError_t launch_gemm16b(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
 {
+    if constexpr (!PC) {
+        if (a.cond_rows) return launch_gemm16b<WP, PHILOX, OWN, true>(prog, a, n_cu, device, stream);
+    }
     static std::atomic<size_t> lds_set[16];
-    return gemm_launch_per_cu<GT>(&nf_gemm16b_kernel<WP, PHILOX, OWN>, gemm16b_lds_bytes(WP, a.H, a.W), lds_set, prog, a, n_cu, device, stream);
+    return gemm_launch_per_cu<GT>(&nf_gemm16b_kernel<WP, PHILOX, OWN, PC>, gemm16b_lds_bytes(WP, a.H, a.W), lds_set, prog, a, n_cu, device, stream);
 }
 
 template <int WP, bool PHILOX>
@@ -542,11 +547,14 @@ size_t gemm16_lds_bytes(int H, int W)
     return ((size_t)NF8_BAND_HALVES / 2 + (size_t)PL + 3 * GW + 8) * sizeof(float);
 }
 
-template <int WP, bool PHILOX, int OWN>
+template <int WP, bool PHILOX, int OWN, bool PC = false>
 hipError_t launch_gemm16(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
 {
+    if constexpr (!PC) {
+        if (a.cond_rows) return launch_gemm16<WP, PHILOX, OWN, true>(prog, a, n_cu, device, stream);
+    }
     static std::atomic<size_t> lds_set[16];
-    return gemm_launch_per_cu<GT>(&nf_gemm16_kernel<WP, PHILOX, OWN>, gemm16_lds_bytes(a.H, a.W), lds_set, prog, a, n_cu, device, stream);
+    return gemm_launch_per_cu<GT>(&nf_gemm16_kernel<WP, PHILOX, OWN, PC>, gemm16_lds_bytes(a.H, a.W), lds_set, prog, a, n_cu, device, stream);
 }
 
 template <int WP, bool PHILOX>

@@ -19,6 +19,7 @@ namespace {
 struct GemmTile {
     size_t patch_off;    // floats in front of the patch's / image's tensor
     int64_t patch_id;    // Philox key
+    nf_crow_p crow;      // per-patch conditioning: this patch's (tiled: this image's) row, or null (nf_dev_util.h)
     int oy, ox, IH, IW, cy0, cy1, cx0, cx1;
     bool tiled;
     __device__ __forceinline__ int gi(bool act, int r, int c) const { return act ? (oy + r) * IW + ox + c : 0; }   // index in the tensors
@@ -33,6 +34,7 @@ struct GemmTile {
     }
 };
 
+template <bool PC>
 __device__ __forceinline__ GemmTile gemm_tile(const NfLaunch &a, int64_t b, int H, int W)
 {
     GemmTile T;
@@ -56,6 +58,7 @@ __device__ __forceinline__ GemmTile gemm_tile(const NfLaunch &a, int64_t b, int 
         T.patch_off = (size_t)img * (size_t)T.IH * (size_t)T.IW * 4u;
         T.patch_id = img;
     }
+    T.crow = nf_cond_row_of<PC>(a, T.patch_id);
     return T;
 }
 
@@ -106,12 +109,12 @@ __device__ __forceinline__ void gemm_mix(cfloat_p P, float (&z)[OWN][4])
 }
 
 // AffineCouplingSdnEx5 and its relatives: scale = sqrt(beta1*y/gain + beta2)  (cond_utils.py:238)
-template <int OWN>
+template <int OWN, bool PC>
 __device__ __forceinline__ void gemm_sdn(int type, int slot, const NfLaunch &a, const GemmTile &T, const int (&pr)[OWN], const int (&pc)[OWN],
                                          const bool (&act)[OWN], float (&z)[OWN][4], float &ld)
 {
     const float4 *y4 = reinterpret_cast<const float4 *>(a.y + T.patch_off);
-    const float ck1 = a.cond_a[slot & 3], cb2 = a.cond_b[slot & 3];
+    const float ck1 = nf_cond_a<PC>(a, T.crow, slot), cb2 = nf_cond_b<PC>(a, T.crow, slot);
 #pragma unroll
     for (int m = 0; m < OWN; ++m) {
         float4 yv = make_float4(1.f, 1.f, 1.f, 1.f);
@@ -170,7 +173,7 @@ __device__ __forceinline__ void gemm_finish_coupling(int type, const float *__re
 
 // ---- epilogue (as nf_flow_kernel): outputs, per-patch nll / sd_z / log-det or, tiled, the tile's share of its image's sums ----
 //   red   [3][GW] floats of LDS;  every thread of the workgroup calls this (two barriers)
-template <int OWN, int GT>
+template <int OWN, int GT, bool PC>
 __device__ __forceinline__ void gemm_epilogue(const NfLaunch &a, const GemmTile &T, int64_t b, int HW, const int (&pr)[OWN], const int (&pc)[OWN],
                                               const bool (&act)[OWN], const float (&z)[OWN][4], float ld, float ld2, float *red, double &acc_nll,
                                               double &acc_sd)
@@ -215,7 +218,7 @@ __device__ __forceinline__ void gemm_epilogue(const NfLaunch &a, const GemmTile 
             *reinterpret_cast<float4 *>(a.tile_part + (size_t)b * 4u) = make_float4(r0, r1, r2, 0.f);
         } else if (t == 0) {
             const double npx = (double)HW * 4.0;
-            const double logdet = (double)r0 + a.ld_const;
+            const double logdet = (double)r0 + nf_cond_ld<PC>(a, T.crow);
             double nll = -logdet;   // prior: sum -0.5*(log 2pi + z^2)   (noise_flow_model.py:537-539)
             if (a.flags & NF_K_PRIOR) nll += 0.5 * npx * 1.8378770664093453 + 0.5 * (double)r2;
             const double mean = (double)r1 / npx;

@@ -42,7 +42,8 @@ hipError_t nf_launch_stats_scatter(double *stats, int nvals, const double *buf, 
 hipError_t nf_launch_sums_reduce(const double *wide, double *out3, bool accumulate, hipStream_t stream);
 hipError_t nf_launch_bs_finalize(double *stats, int w, double n, float *Wm, int rows, float *Bv, float *mean_out, float *var_out,
                                  hipStream_t stream);
-hipError_t nf_launch_tile_combine(const float *part, const NfTileParts &tp, int64_t B, double n, double ld_const, uint32_t flags,
+hipError_t nf_launch_tile_combine(const float *part, const NfTileParts &tp, int64_t B, double n, double ld_const, const nf_cond_row *cond_rows,
+                                  uint32_t flags,
                                   float *nll_out, float *sd_out, float *ld_out, double *sums, hipStream_t stream);
 hipError_t nf_launch_gather(float *dst, const float *src, const int32_t *pairs, int n, hipStream_t stream);
 
@@ -1757,9 +1758,57 @@ int nf_destroy(nf_handle *h)
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// What the kernels read of one nf_cond (NfLaunch::cond_a / cond_b and the per-call part of the constant log-det, or one row of a
+// per-patch call): the scalars of the program's conditional layers in slot order.  direction 0 (NLL) divides by a gain layer's
+// scale and carries its log-det; direction 1 (sampling) multiplies.  Unused slots stay a = 0, b = 1.
+static int cond_row_of(const Built &b, int H, int W, int direction, const nf_cond *cond, nf_cond_row &r)
+{
+    for (int i = 0; i < 4; ++i) {
+        r.a[i] = 0.f;
+        r.b[i] = 1.f;
+    }
+    r.ld = 0.0;   // per-call part of the constant log-det (plain `gain` layers)
+    r.reserved = 0.0;
+    for (size_t i = 0; i < b.cond.size(); ++i) {
+        double sc[2];
+        int rc = cond_scalars(b.cond[i], cond, sc);
+        if (rc != NF_OK) return rc;
+        if (direction == 0 && is_gain_kind(b.cond[i].kind)) {
+            r.a[i] = (float)(1.0 / sc[0]);            // NLL direction divides
+            // AffineCouplingGain / GainEx1 / GainEx3 write -log(scale) once per patch (no H*W*C factor, e.g.
+            // AffineCouplingGain.py:113-127); GainEx2 broadcasts the scale first and sums (AffineCouplingGainEx2.py:112-126)
+            r.ld -= (b.cond[i].kind == NF_LAYER_GAIN2 ? (double)H * W * kC : 1.0) * log(sc[0]);
+        } else {
+            r.a[i] = (float)sc[0];                    // sampling direction multiplies
+            r.b[i] = (float)sc[1];
+        }
+    }
+    return NF_OK;
+}
+
+// the rows of a per-patch call: [B] on the handle's device, 16-byte aligned
+static int check_rows(const nf_handle *h, const nf_cond_row *rows, int64_t B)
+{
+    if (B <= 0) return NF_OK;
+    if (!rows) return fail(NF_EINVAL, "rows is NULL");
+    if (!aligned16(rows)) return fail(NF_EINVAL, "rows must be 16-byte aligned");
+    for (const char *q : {(const char *)rows, (const char *)(rows + B) - 1}) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, q) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(NF_EINVAL, "rows is not device memory (all %lld rows)", (long long)B);
+        }
+        if (at.type != hipMemoryTypeDevice || at.device != h->device)
+            return fail(NF_EINVAL, "rows must be memory of the handle's device %d", h->device);
+    }
+    return NF_OK;
+}
+
 // ---- argument checking + NfLaunch assembly shared by the resident and the batch-statistics paths ----
+// (with_rows: a per-patch entry, whose device `rows` stand in for `cond`)
 static int nll_args(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond, float *nll_out,
-                    float *sd_out, float *logdet_out, float *z_out, double *sums_out, uint32_t flags, NfLaunch &a)
+                    float *sd_out, float *logdet_out, float *z_out, double *sums_out, uint32_t flags, NfLaunch &a,
+                    bool with_rows = false, const nf_cond_row *rows = nullptr)
 {
     if (!h) return fail(NF_EINVAL, "handle is NULL");
     if (B < 0) return fail(NF_EINVAL, "B must be >= 0");
@@ -1767,21 +1816,14 @@ static int nll_args(nf_handle *h, const float *x, const float *y, int64_t B, con
     if (h->fwd.has_sdn && B > 0 && !y) return fail(NF_EINVAL, "model has a signal-dependent layer but y is NULL");
     if (!aligned16(x) || !aligned16(y) || !aligned16(z_out))
         return fail(NF_EINVAL, "x, y and z_out must be 16-byte aligned (every pixel is one float4 access)");
-    float ca[4] = {0.f, 0.f, 0.f, 0.f}, cb[4] = {1.f, 1.f, 1.f, 1.f};
-    double ld_call = 0.0;   // per-call part of the constant log-det (plain `gain` layers)
-    for (size_t i = 0; i < h->fwd.cond.size(); ++i) {
-        double sc[2];
-        int rc = cond_scalars(h->fwd.cond[i], cond, sc);
+    nf_cond_row r;
+    if (with_rows) {   // per-patch conditioning: the kernels read rows[b], and ld_const holds the model's part only
+        int rc = check_rows(h, rows, B);
         if (rc != NF_OK) return rc;
-        if (is_gain_kind(h->fwd.cond[i].kind)) {
-            ca[i] = (float)(1.0 / sc[0]);            // NLL direction divides
-            // AffineCouplingGain / GainEx1 / GainEx3 write -log(scale) once per patch (no H*W*C factor, e.g.
-            // AffineCouplingGain.py:113-127); GainEx2 broadcasts the scale first and sums (AffineCouplingGainEx2.py:112-126)
-            ld_call -= (h->fwd.cond[i].kind == NF_LAYER_GAIN2 ? (double)h->cfg.height * h->cfg.width * kC : 1.0) * log(sc[0]);
-        } else {
-            ca[i] = (float)sc[0];
-            cb[i] = (float)sc[1];
-        }
+        memset(&r, 0, sizeof(r));
+    } else {
+        int rc = cond_row_of(h->fwd, h->cfg.height, h->cfg.width, 0, cond, r);
+        if (rc != NF_OK) return rc;
     }
     memset(&a, 0, sizeof(a));
     a.in = x;
@@ -1792,10 +1834,11 @@ static int nll_args(nf_handle *h, const float *x, const float *y, int64_t B, con
     a.ld_out = logdet_out;
     a.sums = sums_out;
     a.B = B;
-    a.ld_const = ld_call;   // + the model's constant part, added by the launcher
+    a.ld_const = r.ld;   // + the model's constant part, added by the launcher
     a.in_scale = 1.0f;
-    memcpy(a.cond_a, ca, sizeof(ca));
-    memcpy(a.cond_b, cb, sizeof(cb));
+    memcpy(a.cond_a, r.a, sizeof(r.a));
+    memcpy(a.cond_b, r.b, sizeof(r.b));
+    a.cond_rows = with_rows ? rows : nullptr;
     a.H = h->cfg.height;
     a.W = h->cfg.width;
     a.flags = (flags & NF_NO_PRIOR) ? 0u : NF_K_PRIOR;
@@ -1804,7 +1847,8 @@ static int nll_args(nf_handle *h, const float *x, const float *y, int64_t B, con
 }
 
 static int sample_args(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base,
-                       float temp, int64_t B, const nf_cond *cond, float *x_out, NfLaunch &a)
+                       float temp, int64_t B, const nf_cond *cond, float *x_out, NfLaunch &a, bool with_rows = false,
+                       const nf_cond_row *rows = nullptr)
 {
     if (!h) return fail(NF_EINVAL, "handle is NULL");
     if (B < 0) return fail(NF_EINVAL, "B must be >= 0");
@@ -1812,13 +1856,14 @@ static int sample_args(nf_handle *h, const float *y, const float *eps, uint64_t 
     if (h->rev.has_sdn && B > 0 && !y) return fail(NF_EINVAL, "model has a signal-dependent layer but y is NULL");
     if (!aligned16(y) || !aligned16(eps) || !aligned16(x_out))
         return fail(NF_EINVAL, "y, eps and x_out must be 16-byte aligned (every pixel is one float4 access)");
-    float ca[4] = {0.f, 0.f, 0.f, 0.f}, cb[4] = {1.f, 1.f, 1.f, 1.f};
-    for (size_t i = 0; i < h->rev.cond.size(); ++i) {
-        double sc[2];
-        int rc = cond_scalars(h->rev.cond[i], cond, sc);
+    nf_cond_row r;
+    if (with_rows) {
+        int rc = check_rows(h, rows, B);
         if (rc != NF_OK) return rc;
-        ca[i] = (float)sc[0];                        // sampling direction multiplies
-        cb[i] = (float)sc[1];
+        memset(&r, 0, sizeof(r));
+    } else {
+        int rc = cond_row_of(h->rev, h->cfg.height, h->cfg.width, 1, cond, r);
+        if (rc != NF_OK) return rc;
     }
     memset(&a, 0, sizeof(a));
     a.in = eps;
@@ -1828,8 +1873,9 @@ static int sample_args(nf_handle *h, const float *y, const float *eps, uint64_t 
     a.patch_base = patch_index_base;
     a.seed = seed;
     a.in_scale = temp;
-    memcpy(a.cond_a, ca, sizeof(ca));
-    memcpy(a.cond_b, cb, sizeof(cb));
+    memcpy(a.cond_a, r.a, sizeof(r.a));
+    memcpy(a.cond_b, r.b, sizeof(r.b));
+    a.cond_rows = with_rows ? rows : nullptr;
     a.H = h->cfg.height;
     a.W = h->cfg.width;
     a.flags = eps ? 0u : NF_K_PHILOX_IN;
@@ -2010,8 +2056,8 @@ static int launch_tiled(nf_handle *h, int direction, NfLaunch &a, hipStream_t st
         cur = t.out;
     }
     if (e == hipSuccess && want)
-        e = nf_launch_tile_combine(part, tp, B, (double)h->cfg.height * h->cfg.width * kC, a.ld_const, a.flags, a.nll_out, a.sd_out, a.ld_out,
-                                   a.sums, st);
+        e = nf_launch_tile_combine(part, tp, B, (double)h->cfg.height * h->cfg.width * kC, a.ld_const, a.cond_rows, a.flags, a.nll_out, a.sd_out,
+                                   a.ld_out, a.sums, st);
     ws_release(h, wsp, st);
     if (e != hipSuccess) return fail_hip(e, what);
     return NF_OK;
@@ -2169,6 +2215,57 @@ int nf_sample(nf_handle *h, const float *y, const float *eps, uint64_t seed, int
     DeviceGuard guard;
     if ((rc = guard.enter(h->device)) != NF_OK) return rc;
     return launch_resident(h, 1, a, (hipStream_t)stream, "nf_sample launch");
+}
+
+// ---- per-patch conditioning: the same launches with NfLaunch::cond_rows set ----
+int nf_cond_rows(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params, int32_t direction,
+                 const nf_cond *conds, int64_t n, nf_cond_row *rows_out)
+{
+    if (direction != 0 && direction != 1) return fail(NF_EINVAL, "direction must be 0 or 1");
+    if (n < 0) return fail(NF_EINVAL, "n must be >= 0");
+    if (n > 0 && (!conds || !rows_out)) return fail(NF_EINVAL, "conds / rows_out is NULL");
+    if (!cfg) return fail(NF_EINVAL, "cfg is NULL");
+    Built b;
+    int rc = build_program(cfg, layers, params, n_params, direction, b);
+    if (rc != NF_OK) return rc;
+    for (int64_t k = 0; k < n; ++k) {
+        rc = cond_row_of(b, cfg->height, cfg->width, direction, &conds[k], rows_out[k]);
+        if (rc != NF_OK) {
+            const std::string why = g_last_error;
+            return fail(rc, "conds[%lld]: %s", (long long)k, why.c_str());
+        }
+    }
+    return NF_OK;
+}
+
+int nf_nll_percond(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond_row *rows, float *nll_out, float *sd_out,
+                   float *logdet_out, float *z_out, double *sums_out, uint32_t flags, void *stream)
+{
+    NfLaunch a;
+    int rc = nll_args(h, x, y, B, nullptr, nll_out, sd_out, logdet_out, z_out, sums_out, flags, a, true, rows);
+    if (rc != NF_OK) return rc;
+    DeviceGuard guard;
+    if ((rc = guard.enter(h->device)) != NF_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (sums_out && !(flags & NF_ACCUMULATE)) {
+        const size_t nb = (flags & NF_SUMS_WIDE) ? (size_t)NF_SUMS_SLOTS * NF_SUMS_STRIDE : 3;
+        hipError_t e = hipMemsetAsync(sums_out, 0, nb * sizeof(double), st);
+        if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(sums)");
+    }
+    if (B == 0) return NF_OK;
+    return launch_resident(h, 0, a, st, "nf_nll_percond launch");
+}
+
+int nf_sample_percond(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp, int64_t B,
+                      const nf_cond_row *rows, float *x_out, void *stream)
+{
+    NfLaunch a;
+    int rc = sample_args(h, y, eps, seed, patch_index_base, temp, B, nullptr, x_out, a, true, rows);
+    if (rc != NF_OK) return rc;
+    if (B == 0) return NF_OK;
+    DeviceGuard guard;
+    if ((rc = guard.enter(h->device)) != NF_OK) return rc;
+    return launch_resident(h, 1, a, (hipStream_t)stream, "nf_sample_percond launch");
 }
 
 // ---- batch-statistics mode (is_training=True graphs: layers.py:386-398) ----
@@ -2610,8 +2707,8 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
                 memset(&tp, 0, sizeof(tp));
                 tp.n_seg = 1;
                 tp.nt[0] = bs_nt;
-                e = nf_launch_tile_combine(part, tp, a.B, (double)h->cfg.height * h->cfg.width * kC, a.ld_const, a.flags, a.nll_out, a.sd_out,
-                                           a.ld_out, a.sums, st);
+                e = nf_launch_tile_combine(part, tp, a.B, (double)h->cfg.height * h->cfg.width * kC, a.ld_const, nullptr, a.flags, a.nll_out,
+                                           a.sd_out, a.ld_out, a.sums, st);
             }
             if (part) {
                 hipError_t e2 = hipFreeAsync(part, st);

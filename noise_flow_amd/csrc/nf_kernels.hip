@@ -145,7 +145,7 @@ __device__ __forceinline__ v4f nf_mfma_bf16(const uint4 a, const uint4 b, const 
 // --------------------------------------------------------------------------
 //   TF      NF_K_TILED launches whose tiles are full 64x64 blocks (FULL geometry, per-tile addresses and border masks);
 //           masked (!FULL) instantiations take tiled launches of any tile shape at run time
-template <int WIDTH, int THREADS, int PX, bool PHILOX, bool MFMA, bool FULL, int PREC, bool BS, bool TF>
+template <int WIDTH, int THREADS, int PX, bool PHILOX, bool MFMA, bool FULL, int PREC, bool BS, bool TF, bool PC = false>
 __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaunch &a)
 {
     static_assert(!BS || (MFMA && PREC == 0), "the batch-statistics variant is the fp32 matrix-core kernel");
@@ -579,7 +579,7 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
             if (t == 0) *reinterpret_cast<float4 *>(a.tile_part + (size_t)pb * 4u) = make_float4(r0, r1, r2, 0.f);
         } else if (t == 0) {
             const double n = (double)HW * 4.0;
-            const double logdet = (double)r0 + a.ld_const;
+            const double logdet = (double)r0 + nf_cond_ld<PC>(a, nf_cond_row_of<PC>(a, pb));   // (not tiled: the patch is the row)
             // prior: sum -0.5*(log 2pi + z^2)   (noise_flow_model.py:537-539)
             double nll = -logdet;
             if (a.flags & NF_K_PRIOR) nll += 0.5 * n * 1.8378770664093453 + 0.5 * (double)r2;
@@ -636,6 +636,8 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
             }
         }
 
+        [[maybe_unused]] const nf_crow_p crow = nf_cond_row_of<PC>(a, patch_id);   // per-patch conditioning: this patch's (tiled: this image's) row, or null
+
         // ---- prologue: the 4 channels of each owned pixel -> registers ----
         float z[PX][4];
         if (PHILOX) {
@@ -682,7 +684,7 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
 
         // AffineCouplingSdnEx5 and its relatives: scale = sqrt(beta1*y/gain + beta2)  (cond_utils.py:238)
         auto sdn_apply = [&](int stype, int slot, const float4 (&yv)[PX]) {
-            const float ck1 = a.cond_a[slot & 3], cb2 = a.cond_b[slot & 3];
+            const float ck1 = nf_cond_a<PC>(a, crow, slot), cb2 = nf_cond_b<PC>(a, crow, slot);
 #pragma unroll
             for (int k = 0; k < PX; ++k) {
                 const float yy[4] = {yv[k].x, yv[k].y, yv[k].z, yv[k].w};
@@ -1604,7 +1606,7 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 }
                 sdn_apply(type, prog.ops[op].off, yv);
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? P[0] : a.cond_a[prog.ops[op].off & 3];
+                const float s = type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, crow, prog.ops[op].off);
 #pragma unroll
                 for (int k = 0; k < PX; ++k)
 #pragma unroll
@@ -1738,6 +1740,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(NF_MIN_
     nf_flow_body<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, PREC, BS, false>(prog, a);
 }
 
+// per-patch conditioning (NfLaunch::cond_rows set): the same body with PC = true, under a name of its own
+template <int WIDTH, int THREADS, int PX, bool PHILOX, bool MFMA, bool FULL, int PREC>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(NF_MIN_WAVES(THREADS, PX, MFMA)))) void nf_flow_pc_kernel(const NfProgram prog, const NfLaunch a)
+{
+    nf_flow_body<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, PREC, false, false, true>(prog, a);
+}
+
 // split-bf16 convs (NF_K_SPLIT_BF16, nf_device.h NF12_*): full 32x32 patches, 4 workgroups of 4 wavefronts per CU, i.e. at most 128
 // registers a lane
 // NF_SPLIT_PK_SUB 0: the kernel is compiled without packed fp32, so the 48 subtractions of the operand split (nf_split3) are plain
@@ -1758,12 +1767,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) NF_SPL
     nf_flow_body<4, 256, 4, PHILOX, true, true, 3, false, false>(prog, a);
 }
 
+template <bool PHILOX>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) NF_SPLIT_KATTR void nf_flow_split_pc_kernel(const NfProgram prog, const NfLaunch a)
+{
+    nf_flow_body<4, 256, 4, PHILOX, true, true, 3, false, false, true>(prog, a);
+}
+
 // NF_K_TILED launches over full 64x64 tiles: the full-patch matrix-core geometry of nf_flow_kernel<4, 1024, 4, ., true, true, PREC, false>
 // (PREC = 0: fp32, 2x2-blocked lanes; PREC = 2: fp16 CNN on v_mfma_f32_16x16x32_f16)
 template <bool PHILOX, int PREC>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(NF_MIN_WAVES(1024, 4, true)))) void nf_flow_tile64_kernel(const NfProgram prog, const NfLaunch a)
 {
     nf_flow_body<4, 1024, 4, PHILOX, true, true, PREC, false, true>(prog, a);
+}
+
+template <bool PHILOX, int PREC>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(NF_MIN_WAVES(1024, 4, true)))) void nf_flow_tile64_pc_kernel(const NfProgram prog, const NfLaunch a)
+{
+    nf_flow_body<4, 1024, 4, PHILOX, true, true, PREC, false, true, true>(prog, a);
 }
 
 // Batch-statistics mode, device side of the re-fold (layers.py:388-391 + the BN-eval folding of fold_coupling):
@@ -1824,7 +1845,8 @@ __global__ __launch_bounds__(64) void nf_sums_reduce_kernel(const double *__rest
 // last one), and the call's (sum nll, sum sd, count) accumulators.  One wavefront per image: lane l adds up tiles l, l + 64, ...
 // of every segment in double, then the fixed-order wavefront sum — the same bits whatever else is in the batch.
 __global__ __launch_bounds__(64) void nf_tile_combine_kernel(const float *__restrict__ part, const NfTileParts tp, int64_t B, double n,
-                                                             double ld_const, uint32_t flags, float *__restrict__ nll_out,
+                                                             double ld_const, const nf_cond_row *__restrict__ cond_rows, uint32_t flags,
+                                                             float *__restrict__ nll_out,
                                                              float *__restrict__ sd_out, float *__restrict__ ld_out, double *__restrict__ sums)
 {
     const int64_t i = blockIdx.x;
@@ -1847,7 +1869,7 @@ __global__ __launch_bounds__(64) void nf_tile_combine_kernel(const float *__rest
     r1 = wave_sum(r1);
     r2 = wave_sum(r2);
     if (lane == 0) {
-        const double logdet = r0 + ld_const;
+        const double logdet = r0 + (cond_rows ? cond_rows[i].ld + ld_const : ld_const);   // per-patch conditioning: the image's row
         double nll = -logdet;
         if (flags & NF_K_PRIOR) nll += 0.5 * n * 1.8378770664093453 + 0.5 * r2;
         const double mean = r1 / n;
@@ -1927,9 +1949,15 @@ inline int env_int(const char *name)
     return e ? atoi(e) : 0;
 }
 
-template <int WIDTH, int THREADS, int PX, bool PHILOX, bool MFMA, bool FULL, int PREC, bool BS = false, bool TF = false>
+template <int WIDTH, int THREADS, int PX, bool PHILOX, bool MFMA, bool FULL, int PREC, bool BS = false, bool TF = false, bool PC = false>
 hipError_t launch_flow_p(const NfProgram &prog, const NfLaunch &a, int n_cu, hipStream_t stream)
 {
+    if constexpr (!PC) {   // per-patch conditioning: the PC twin of the same kernel (none for the batch-statistics passes)
+        if (a.cond_rows) {
+            if constexpr (BS) return hipErrorInvalidValue;
+            else return launch_flow_p<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, PREC, false, TF, true>(prog, a, n_cu, stream);
+        }
+    }
     const int tile_px = ((a.H + 2) * (a.W + 2) + 1) & ~1;
     size_t lds_f = (size_t)tile_px * (PREC != 0 ? 3 : 2 + WIDTH) + ((6 * (THREADS / 64) + 3) & ~3);
     if (PREC == 1 && a.H == 32) lds_f = (size_t)(34 * 48) * 3 + ((6 * (THREADS / 64) + 3) & ~3);   // padded row pitch
@@ -1940,7 +1968,10 @@ hipError_t launch_flow_p(const NfProgram &prog, const NfLaunch &a, int n_cu, hip
     const size_t lds = sizeof(float) * lds_f;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     void (*const kern)(const NfProgram, const NfLaunch) = [] {
-        if constexpr (TF) return &nf_flow_tile64_kernel<PHILOX, PREC>;
+        if constexpr (PC && TF) return &nf_flow_tile64_pc_kernel<PHILOX, PREC>;
+        else if constexpr (PC && PREC == 3) return &nf_flow_split_pc_kernel<PHILOX>;
+        else if constexpr (PC) return &nf_flow_pc_kernel<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, PREC>;
+        else if constexpr (TF) return &nf_flow_tile64_kernel<PHILOX, PREC>;
         else if constexpr (PREC == 3) return &nf_flow_split_kernel<PHILOX>;
         else return &nf_flow_kernel<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, PREC, BS>;
     }();
@@ -2152,12 +2183,13 @@ hipError_t nf_launch_sums_reduce(const double *wide, double *out3, bool accumula
     return hipGetLastError();
 }
 
-hipError_t nf_launch_tile_combine(const float *part, const NfTileParts &tp, int64_t B, double n, double ld_const, uint32_t flags,
+hipError_t nf_launch_tile_combine(const float *part, const NfTileParts &tp, int64_t B, double n, double ld_const, const nf_cond_row *cond_rows,
+                                  uint32_t flags,
                                   float *nll_out, float *sd_out, float *ld_out, double *sums, hipStream_t stream)
 {
     if (B <= 0) return hipSuccess;
     if (B > 0x7fffffff) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nf_tile_combine_kernel, dim3((unsigned)B), dim3(64), 0, stream, part, tp, B, n, ld_const, flags,
+    hipLaunchKernelGGL(nf_tile_combine_kernel, dim3((unsigned)B), dim3(64), 0, stream, part, tp, B, n, ld_const, cond_rows, flags,
                        nll_out, sd_out, ld_out, sums);
     return hipGetLastError();
 }

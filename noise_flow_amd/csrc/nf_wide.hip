@@ -113,7 +113,7 @@ __device__ __forceinline__ float half_sums(float a, float b)
 // it does their global I/O, 1x1 mixes, signal-dependent scaling, affine update and log-det.
 //   TILED    NF_K_TILED launches (nf_device.h): its own kernels (nf_wide32_tiled_kernel), so that the per-tile geometry costs
 //            the whole-patch kernels neither scalar registers nor instructions
-template <int THREADS, bool PHILOX, int TPR, int PREC, bool TILED>
+template <int THREADS, bool PHILOX, int TPR, int PREC, bool TILED, bool PC = false>
 __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLaunch &a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -200,6 +200,7 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
             patch_off = (size_t)img * (size_t)IH * (size_t)IW * 4u;
             patch_id = img;
         }
+        [[maybe_unused]] const nf_crow_p crow = nf_cond_row_of<PC>(a, patch_id);   // per-patch conditioning: this patch's (tiled: this image's) row, or null
         const int C = ox + c;                                               // image column of this lane's pixels
         const bool col_own = col_on && C >= cx0 && C < cx1;
         const int cmask = (C == 0 ? 4 : 0) | (C == IW - 1 ? 8 : 0);
@@ -532,7 +533,7 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
             } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
                 // AffineCouplingSdnEx5: scale = sqrt(beta1*y/gain + beta2)  (cond_utils.py:238)
                 const float4 *y4 = reinterpret_cast<const float4 *>(a.y + patch_off);
-                const float ck1 = a.cond_a[prog.ops[op].off & 3], cb2 = a.cond_b[prog.ops[op].off & 3];
+                const float ck1 = nf_cond_a<PC>(a, crow, prog.ops[op].off), cb2 = nf_cond_b<PC>(a, crow, prog.ops[op].off);
 #pragma unroll
                 for (int m = 0; m < OWN; ++m) {
                     const int r = row0 + 2 * m + g;
@@ -554,7 +555,7 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
                     }
                 }
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? P[0] : a.cond_a[prog.ops[op].off & 3];
+                const float s = type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, crow, prog.ops[op].off);
 #pragma unroll
                 for (int m = 0; m < OWN; ++m)
 #pragma unroll
@@ -604,7 +605,7 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
                 *reinterpret_cast<float4 *>(a.tile_part + (size_t)b * 4u) = make_float4(r0, r1, r2, 0.f);
             } else if (t == 0) {
                 const double npx = (double)HW * 4.0;
-                const double logdet = (double)r0 + a.ld_const;
+                const double logdet = (double)r0 + nf_cond_ld<PC>(a, crow);
                 double nll = -logdet;   // prior: sum -0.5*(log 2pi + z^2)   (noise_flow_model.py:537-539)
                 if (a.flags & NF_K_PRIOR) nll += 0.5 * npx * 1.8378770664093453 + 0.5 * (double)r2;
                 const double mean = (double)r1 / npx;
@@ -645,6 +646,19 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
     nf_wide32_body<THREADS, PHILOX, TPR, PREC, true>(prog, a);
 }
 
+// per-patch conditioning (NfLaunch::cond_rows set): the same body with PC = true (nf_dev_util.h), under a name of its own
+template <int THREADS, bool PHILOX, int TPR, int PREC>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS == 256 ? (PREC == 1 ? NF_WIDE_WPE16 : NF_WIDE_WPE) : 1))) void nf_wide32_pc_kernel(const NfProgram prog, const NfLaunch a)
+{
+    nf_wide32_body<THREADS, PHILOX, TPR, PREC, false, true>(prog, a);
+}
+
+template <int THREADS, bool PHILOX, int TPR, int PREC>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS == 256 ? NF_WIDE_WPE : 1))) void nf_wide32_tiled_pc_kernel(const NfProgram prog, const NfLaunch a)
+{
+    nf_wide32_body<THREADS, PHILOX, TPR, PREC, true, true>(prog, a);
+}
+
 size_t wide_lds_bytes(int H, int W, int threads, int tpr, int prec)
 {
     const int Wp = W + 2, PL = ((H + 2) * Wp + 3) & ~3, NW = threads / 64;
@@ -653,14 +667,18 @@ size_t wide_lds_bytes(int H, int W, int threads, int tpr, int prec)
     return f * sizeof(float);
 }
 
-template <int THREADS, bool PHILOX, int TPR, int PREC>
+template <int THREADS, bool PHILOX, int TPR, int PREC, bool PC = false>
 hipError_t launch_wide_p(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
 {
+    if constexpr (!PC) {
+        if (a.cond_rows) return launch_wide_p<THREADS, PHILOX, TPR, PREC, true>(prog, a, n_cu, device, stream);
+    }
     const size_t lds = wide_lds_bytes(a.H, a.W, THREADS, TPR, PREC);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const bool tiled = (a.flags & NF_K_TILED) != 0;
     void (*const kern)(const NfProgram, const NfLaunch) =
-        tiled ? &nf_wide32_tiled_kernel<THREADS, PHILOX, TPR, PREC> : &nf_wide32_kernel<THREADS, PHILOX, TPR, PREC>;
+        PC ? (tiled ? &nf_wide32_tiled_pc_kernel<THREADS, PHILOX, TPR, PREC> : &nf_wide32_pc_kernel<THREADS, PHILOX, TPR, PREC>)
+           : (tiled ? &nf_wide32_tiled_kernel<THREADS, PHILOX, TPR, PREC> : &nf_wide32_kernel<THREADS, PHILOX, TPR, PREC>);
     const void *fn = reinterpret_cast<const void *>(kern);
     // (tiled << 48 | device << 40 | lds bytes << 8 | resident workgroups per CU) of the last query; racy but idempotent
     static std::atomic<uint64_t> cache{0};

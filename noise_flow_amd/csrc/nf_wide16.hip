@@ -68,7 +68,8 @@ __host__ __device__ inline int nf_w16_plane(int px)
     return pl;
 }
 
-template <int THREADS, int TPW, bool PHILOX>
+//   PC      per-patch conditioning (NfLaunch::cond_rows set; nf_dev_util.h): false compiles to the per-call kernel as it was
+template <int THREADS, int TPW, bool PHILOX, bool PC = false>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS == 512 ? NF_W16_WPE : 1))) void nf_wide16_kernel(const NfProgram prog, const NfLaunch a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
     double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const GemmTile T = gemm_tile(a, b, H, W);      // the patch on its own, or (NF_K_TILED) a tile of an image: nf_gemm_common.h
+        const GemmTile T = gemm_tile<PC>(a, b, H, W);      // the patch on its own, or (NF_K_TILED) a tile of an image: nf_gemm_common.h
         const size_t patch_off = T.patch_off;
 
         float z[OWN][4];
@@ -299,7 +300,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
             } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
                 // AffineCouplingSdnEx5: scale = sqrt(beta1*y/gain + beta2)  (cond_utils.py:238)
                 const float4 *y4 = reinterpret_cast<const float4 *>(a.y + patch_off);
-                const float ck1 = a.cond_a[prog.ops[op].off & 3], cb2 = a.cond_b[prog.ops[op].off & 3];
+                const float ck1 = nf_cond_a<PC>(a, T.crow, prog.ops[op].off), cb2 = nf_cond_b<PC>(a, T.crow, prog.ops[op].off);
 #pragma unroll
                 for (int m = 0; m < OWN; ++m) {
                     const int r = row0 + 4 * m + g;
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
                     }
                 }
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? P[0] : a.cond_a[prog.ops[op].off & 3];
+                const float s = type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off);
 #pragma unroll
                 for (int m = 0; m < OWN; ++m)
 #pragma unroll
@@ -369,7 +370,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
                 *reinterpret_cast<float4 *>(a.tile_part + (size_t)b * 4u) = make_float4(r0, r1, r2, 0.f);
             } else if (t == 0) {
                 const double npx = (double)HW * 4.0;
-                const double logdet = (double)r0 + a.ld_const;
+                const double logdet = (double)r0 + nf_cond_ld<PC>(a, T.crow);
                 double nll = -logdet;   // prior: sum -0.5*(log 2pi + z^2)   (noise_flow_model.py:537-539)
                 if (a.flags & NF_K_PRIOR) nll += 0.5 * npx * 1.8378770664093453 + 0.5 * (double)r2;
                 const double mean = (double)r1 / npx;
@@ -402,12 +403,16 @@ size_t wide16_lds_bytes(int H, int W, int threads)
     return f * sizeof(float);
 }
 
-template <int THREADS, int TPW, bool PHILOX>
+template <int THREADS, int TPW, bool PHILOX, bool PC = false>
 hipError_t launch_wide16(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
 {
+    if constexpr (!PC) {
+        if (a.cond_rows) return launch_wide16<THREADS, TPW, PHILOX, true>(prog, a, n_cu, device, stream);
+    }
+    void (*const kern)(const NfProgram, const NfLaunch) = &nf_wide16_kernel<THREADS, TPW, PHILOX, PC>;
     const size_t lds = wide16_lds_bytes(a.H, a.W, THREADS);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const void *fn = reinterpret_cast<const void *>(&nf_wide16_kernel<THREADS, TPW, PHILOX>);
+    const void *fn = reinterpret_cast<const void *>(kern);
     static std::atomic<uint64_t> cache{0};   // (device << 40 | lds bytes << 8 | resident workgroups per CU) of the last query
     const uint64_t key = ((uint64_t)(device & 0xff) << 40) | ((uint64_t)lds << 8);
     uint64_t cv = cache.load(std::memory_order_relaxed);
@@ -429,7 +434,7 @@ hipError_t launch_wide16(const NfProgram &prog, const NfLaunch &a, int n_cu, int
     int64_t groups = (int64_t)n_cu * occ;
     if (a.B < groups) groups = a.B;
     if (groups < 1) groups = 1;
-    hipLaunchKernelGGL((nf_wide16_kernel<THREADS, TPW, PHILOX>), dim3((unsigned)groups), dim3(THREADS), lds, stream, prog, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(THREADS), lds, stream, prog, a);
     return hipGetLastError();
 }
 

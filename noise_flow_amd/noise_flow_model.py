@@ -3,7 +3,8 @@
 Mirrors ``borealisflows/noise_flow_model.py::NoiseFlow`` (reference file:line in
 each docstring): same constructor arguments, same method names, argument order
 and conditioning convention (``iso`` / ``cam`` / ``nlf0`` / ``nlf1`` are
-length-1 lists or scalars — ONE value per call, ``MiniBatchSampler.py:61-64``).
+length-1 lists or scalars — ONE value per call, ``MiniBatchSampler.py:61-64`` —
+or, beyond the reference, length-B sequences: one value per patch of a mixed minibatch).
 The TF graph tensors become eager arrays: numpy in → numpy out, torch (CUDA)
 tensor in → torch tensor out (zero-copy).  Every method runs the fused HIP
 kernels through the C ABI; there is no CPU execution path.
@@ -36,6 +37,52 @@ def _first(v, default=0.0) -> float:
         raise ValueError("conditioning is per call, not per patch: expected one value, got %d "
                          "(reference feeds length-1 lists)" % a.size)
     return float(a[0])
+
+
+def _cond_values(v):
+    """A conditioning argument as a flat float64 array (None stays None)."""
+    if v is None:
+        return None
+    return np.asarray(v if not hasattr(v, "detach") else v.detach().cpu().numpy(), dtype=np.float64).reshape(-1)
+
+
+def _batch_of(a) -> int:
+    return int(a.shape[0]) if hasattr(a, "shape") else len(a)
+
+
+COND_ROW_DTYPE = np.dtype([("a", "<f4", (4,)), ("b", "<f4", (4,)), ("ld", "<f8"), ("reserved", "<f8")])   # nf_cond_row
+
+
+class PatchCond:
+    """Per-patch conditioning of one call: ``table[b] = (iso, cam, nlf0, nlf1)`` of patch b, float32 [B, 4]."""
+
+    def __init__(self, table: np.ndarray):
+        self.table = table
+
+    def rows(self, flow: "FlowHandle", direction: int) -> np.ndarray:
+        """``nf_cond_row[B]``: ``nf_cond_rows`` on the distinct tuples, gathered to the patches."""
+        uniq, inv = np.unique(self.table, axis=0, return_inverse=True)
+        return flow.cond_rows(direction, uniq)[np.asarray(inv).reshape(-1)]
+
+
+def patch_cond(nlf0, nlf1, iso, cam, B, is_training=False):
+    """The conditioning of a call on B patches: ``None`` when every argument is a scalar / length-1 list (today's per-call
+    path), a :class:`PatchCond` when some argument holds one value per patch (length-1 arguments are broadcast);
+    any other length is a ``ValueError``, and so is a length-B argument under batch statistics."""
+    vals = [_cond_values(v) for v in (iso, cam, nlf0, nlf1)]
+    if all(a is None or a.size == 1 for a in vals):
+        return None
+    for a in vals:
+        if a is not None and a.size not in (1, B):
+            raise ValueError("conditioning is one value per call or one per patch: expected 1 or %d values, got %d" % (B, a.size))
+    if is_training:
+        raise ValueError("per-patch conditioning is not available with is_training=True (batch statistics couple the "
+                         "patches of a call; the library has no per-patch batch-statistics entry)")
+    table = np.zeros((B, 4), np.float32)
+    for k, a in enumerate(vals):
+        if a is not None:
+            table[:, k] = a
+    return PatchCond(table)
 
 
 _NARROW_POOL = None
@@ -149,6 +196,7 @@ class FlowHandle:
             raise ValueError("cnn_dtype must be 'fp32', 'fp16' or 'fp32_exact'")
         flags = {"fp32": 0, "fp16": _lib.NF_CFG_FP16_CNN, "fp32_exact": _lib.NF_CFG_EXACT_FP32}[cnn_dtype]
         cfg = _lib.nf_config(H, W, Cc, len(self.layers), -1 if device is None else int(device), flags)
+        self._model_args = (cfg, descs, flat)   # what nf_cond_rows takes (kept alive with the handle)
         h = C.c_void_p()
         _lib.check(self.lib.nf_create(C.byref(cfg), descs, flat.ctypes.data_as(C.POINTER(C.c_float)), flat.size,
                                       C.byref(h)))
@@ -159,6 +207,16 @@ class FlowHandle:
         tb = tmpl if layers is not None else _params.template_binding(self.layers, binding)
         self.coupling_scopes = [_params.template_scope((tb or {}).get(L.arch_index, 0))
                                 for L in self.layers if L.kind == "coupling"]
+
+    def cond_rows(self, direction: int, conds: np.ndarray) -> np.ndarray:
+        """``nf_cond_rows``: conds float32 [n, 4] = (iso, cam, nlf0, nlf1) → ``COND_ROW_DTYPE[n]`` (host only)."""
+        cfg, descs, flat = self._model_args
+        conds = np.ascontiguousarray(conds, np.float32).reshape(-1, 4)
+        rows = np.zeros(conds.shape[0], COND_ROW_DTYPE)
+        _lib.check(self.lib.nf_cond_rows(C.byref(cfg), descs, flat.ctypes.data_as(C.POINTER(C.c_float)), flat.size, int(direction),
+                                         C.cast(conds.ctypes.data, C.POINTER(_lib.nf_cond)), conds.shape[0],
+                                         C.cast(rows.ctypes.data, C.POINTER(_lib.nf_cond_row))))
+        return rows
 
     def close(self):
         if getattr(self, "_h", None):
@@ -315,8 +373,18 @@ class NoiseFlow(object):
         return [L.name for L in self.model[0]]
 
     # ------------------------------------------------------------------ helpers
-    def _cond(self, nlf0, nlf1, iso, cam):
+    def _cond(self, nlf0, nlf1, iso, cam, B=None):
+        """One ``nf_cond`` for the call, or — some argument holding one value per patch — a :class:`PatchCond`."""
+        if B is not None:
+            pc = patch_cond(nlf0, nlf1, iso, cam, B, self._is_training)
+            if pc is not None:
+                return pc
         return _lib.nf_cond(_first(iso), _first(cam), _first(nlf0), _first(nlf1))
+
+    def _rows_to_dev(self, cond: PatchCond, direction: int):
+        """The call's ``nf_cond_row[B]`` as one device tensor (uint8 [B, 48])."""
+        rows = cond.rows(self._flow, direction)
+        return self._dev.torch.from_numpy(rows.view(np.uint8).reshape(rows.shape[0], COND_ROW_DTYPE.itemsize)).to(self._dev.device)
 
     def _check_mode(self):
         if self._is_training not in (True, False):
@@ -369,7 +437,8 @@ class NoiseFlow(object):
     def _run_nll(self, x, y, cond, want_z: bool, flags: int = 0, want_sums: bool = False):
         dev = self._dev
         tail = tuple(self.x_shape)
-        if not self._is_training and not isinstance(x, dev.torch.Tensor) and not isinstance(y, dev.torch.Tensor):
+        per_patch = isinstance(cond, PatchCond)
+        if not per_patch and not self._is_training and not isinstance(x, dev.torch.Tensor) and not isinstance(y, dev.torch.Tensor):
             return self._run_nll_host(x, y, cond, want_z, flags, want_sums)
         xt, was_np = dev.to_dev(x, tail)
         yt = None
@@ -387,11 +456,15 @@ class NoiseFlow(object):
         if want_sums:   # slotted layout: the per-workgroup atomics spread over 64 cache lines
             sums = torch.empty((_lib.NF_SUMS_SLOTS * _lib.NF_SUMS_STRIDE,), dtype=torch.float64, device=dev.device)
             flags |= _lib.NF_SUMS_WIDE
-        args = (self._flow.ptr, xt.data_ptr(), yt.data_ptr() if yt is not None else None, B, C.byref(cond),
+        rows = self._rows_to_dev(cond, 0) if per_patch else None
+        args = (self._flow.ptr, xt.data_ptr(), yt.data_ptr() if yt is not None else None, B,
+                rows.data_ptr() if per_patch else C.byref(cond),
                 nll.data_ptr(), sd.data_ptr(), ld.data_ptr(), z.data_ptr() if z is not None else None,
                 sums.data_ptr() if sums is not None else None, flags)
         with torch.cuda.device(dev.device):
-            if self._is_training:
+            if per_patch:
+                _lib.check(self._flow.lib.nf_nll_percond(*args, dev.stream_ptr()))
+            elif self._is_training:
                 mom = self._moments_buffer()
                 self._check_equal_shards(int(xt.shape[0]))
                 _lib.check(self._flow.lib.nf_nll_batchstats(*args, mom.ctypes.data, dev.stream_ptr()))
@@ -407,7 +480,7 @@ class NoiseFlow(object):
         self._check_mode()
         if yy is None and self._flow.has_sdn:
             raise ValueError("this architecture has a signal-dependent layer: the clean image yy is required")
-        nll, sd, ld, z, _, was_np = self._run_nll(x, yy, self._cond(nlf0, nlf1, iso, cam), True, _lib.NF_NO_PRIOR)
+        nll, sd, ld, z, _, was_np = self._run_nll(x, yy, self._cond(nlf0, nlf1, iso, cam, _batch_of(x)), True, _lib.NF_NO_PRIOR)
         if objective is None:
             obj = ld
         elif isinstance(objective, self._dev.torch.Tensor):
@@ -421,7 +494,7 @@ class NoiseFlow(object):
         self._check_mode()
         cond_on = getattr(self.hps, "sidd_cond", "mix") not in (None, "uncond")
         yy = y if (cond_on or self._flow.has_sdn) else None
-        nll, sd, _, _, _, was_np = self._run_nll(x, yy, self._cond(nlf0, nlf1, iso, cam), False)
+        nll, sd, _, _, _, was_np = self._run_nll(x, yy, self._cond(nlf0, nlf1, iso, cam, _batch_of(x)), False)
         self.hps.top_shape = list(self.x_shape)
         sd_z = sd.double().mean().float()
         return self._dev.back(nll, was_np), (float(sd_z) if was_np else sd_z)
@@ -431,7 +504,7 @@ class NoiseFlow(object):
         self._check_mode()
         cond_on = getattr(self.hps, "sidd_cond", "mix") not in (None, "uncond")
         yy = y if (cond_on or self._flow.has_sdn) else None
-        _, _, _, _, sums, was_np = self._run_nll(x, yy, self._cond(nlf0, nlf1, iso, cam), False, 0, True)
+        _, _, _, _, sums, was_np = self._run_nll(x, yy, self._cond(nlf0, nlf1, iso, cam, _batch_of(x)), False, 0, True)
         sums = self.fold_sums(sums)
         mean = sums[:2] / sums[2]
         if was_np:
@@ -456,11 +529,15 @@ class NoiseFlow(object):
         if sums is None:
             sums = self.new_sums()
         flags = _lib.NF_ACCUMULATE | (_lib.NF_SUMS_WIDE if sums.numel() != 3 else 0)
-        cond = self._cond(nlf0, nlf1, iso, cam)
+        cond = self._cond(nlf0, nlf1, iso, cam, int(xt.shape[0]))
+        per_patch = isinstance(cond, PatchCond)
+        rows = self._rows_to_dev(cond, 0) if per_patch else None
         args = (self._flow.ptr, xt.data_ptr(), yt.data_ptr() if yt is not None else None, int(xt.shape[0]),
-                C.byref(cond), None, None, None, None, sums.data_ptr(), flags)
+                rows.data_ptr() if per_patch else C.byref(cond), None, None, None, None, sums.data_ptr(), flags)
         with torch.cuda.device(dev.device):
-            if self._is_training:
+            if per_patch:
+                _lib.check(self._flow.lib.nf_nll_percond(*args, dev.stream_ptr()))
+            elif self._is_training:
                 mom = self._moments_buffer()
                 self._check_equal_shards(int(xt.shape[0]))
                 _lib.check(self._flow.lib.nf_nll_batchstats(*args, mom.ctypes.data, dev.stream_ptr()))
@@ -497,7 +574,7 @@ class NoiseFlow(object):
         """noise_flow_model.py:430-447: bijectors in reverse order, ``_forward`` each.
         ``eps_std`` only matters for multi-level split priors (unused at n_levels = 1)."""
         self._check_mode()
-        return self._run_sample(z, 1.0, yy, self._cond(nlf0, nlf1, iso, cam), z_is_eps=True)
+        return self._run_sample(z, 1.0, yy, self._cond(nlf0, nlf1, iso, cam, _batch_of(z)), z_is_eps=True)
 
     def sample(self, y, eps_std=None, yy=None, nlf0=None, nlf1=None, iso=None, cam=None, eps=None, seed=None):
         """noise_flow_model.py:449-456: ``z = ε·eps_std`` (prior.sample, :499-504), then
@@ -508,7 +585,7 @@ class NoiseFlow(object):
         Without it ε is generated in-kernel (Philox4x32-10 keyed by ``seed``, a
         running patch counter and the pixel index)."""
         self._check_mode()
-        cond = self._cond(nlf0, nlf1, iso, cam)
+        cond = self._cond(nlf0, nlf1, iso, cam, _batch_of(y))
         tv = None if eps_std is None else np.asarray(eps_std.detach().cpu() if hasattr(eps_std, "detach") else eps_std,
                                                      np.float32).reshape(-1)
         if tv is not None and tv.size > 1 and not np.all(tv == tv[0]):
@@ -544,7 +621,8 @@ class NoiseFlow(object):
         tail = tuple(self.x_shape)
         if yy is None and self._flow.has_sdn:
             raise ValueError("this architecture has a signal-dependent layer: the clean image yy is required")
-        if not self._is_training and not isinstance(z_or_y, dev.torch.Tensor) and not isinstance(yy, dev.torch.Tensor):
+        per_patch = isinstance(cond, PatchCond)
+        if not per_patch and not self._is_training and not isinstance(z_or_y, dev.torch.Tensor) and not isinstance(yy, dev.torch.Tensor):
             # numpy in → numpy out through nf_sample_host (chunked, full duplex: y goes down while x comes up)
             za, zdt = _host_tensor(z_or_y, tail)
             B = int(za.shape[0])
@@ -576,10 +654,13 @@ class NoiseFlow(object):
             with self._lock:
                 base = self._draws
                 self._draws += B
+        rows = self._rows_to_dev(cond, 1) if per_patch else None
         args = (self._flow.ptr, yt.data_ptr() if yt is not None else None, zt.data_ptr() if z_is_eps else None,
-                sd & _U64, base, float(temp), B, C.byref(cond), out.data_ptr())
+                sd & _U64, base, float(temp), B, rows.data_ptr() if per_patch else C.byref(cond), out.data_ptr())
         with dev.torch.cuda.device(dev.device):
-            if self._is_training:
+            if per_patch:
+                _lib.check(self._flow.lib.nf_sample_percond(*args, dev.stream_ptr()))
+            elif self._is_training:
                 mom = self._moments_buffer()
                 self._check_equal_shards(B)
                 _lib.check(self._flow.lib.nf_sample_batchstats(*args, mom.ctypes.data, dev.stream_ptr()))
