@@ -251,6 +251,26 @@ int nf_sample_percond(nf_handle *h, const float *y, const float *eps, uint64_t s
                       int64_t patch_index_base, float temp, int64_t B, const nf_cond_row *rows,
                       float *x_out, void *stream);
 
+/* Input gradients of the likelihood: d nll_b / d x and d nll_b / d y of the nll_b that nf_nll reports (prior included),
+ * evaluation mode (running BN statistics), fp32.  Exactly one of cond / rows is non-NULL: cond = one nf_cond for the call,
+ * rows = DEVICE nf_cond_row[B] made by nf_cond_rows(direction 0), as for nf_nll_percond.
+ *   x, y      [B,H,W,4] device, 16-byte aligned (y NULL only for models without an SDN-kind layer)
+ *   nll_out   [B] or NULL      gx_out [B,H,W,4] or NULL      gy_out [B,H,W,4] or NULL (must be NULL when y is)
+ * Like nf_nll: re-entrant, no synchronisation, no allocation, any B >= 0, only enqueues on `stream`.
+ * One fused kernel (csrc/nf_grad.hip): a forward sweep that records the ReLU gates, then a backward sweep that rebuilds
+ * every layer's input from its output (the flow is invertible), so no activation is stored and HBM traffic is x, y in and
+ * gx, gy out.  Supported set (nf_grad_supported decides, everything else is NF_EINVAL): fp32 handles (NF_CFG_FP16_CNN is
+ * refused, NF_CFG_EXACT_FP32 is ignored), the whole layer vocabulary, patches up to 64x64, coupling widths up to 32 as far
+ * as one workgroup's LDS (160 KiB) holds the patch: width 4 up to 64x64, widths 8 and 16 at least up to 32x32.
+ * Not covered: images beyond 64x64 (tiled evaluation), widths beyond 32 (the GEMM families), batch-statistics mode, and
+ * host-fed variants. */
+int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond,
+                const nf_cond_row *rows, float *nll_out, float *gx_out, float *gy_out, void *stream);
+
+/* Host-only (no device, same argument style as nf_fold_params): 0 when nf_nll_grad supports this model and patch
+ * size, NF_EINVAL otherwise, with nf_last_error() naming the limit that was hit. */
+int nf_grad_supported(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params);
+
 /* The tile plan of one image axis (see "Patch sizes"): `size` pixels, tiles of `tile` = min(size, 64) pixels, `halo` =
  * 2 x the number of coupling layers.  Returns the number of tiles n (or a negative NF_E* code) and, for i < min(n, cap),
  * the tile's first pixel origin[i] and the window [core0[i], core1[i]) it reports — a partition of [0, size) with

@@ -83,6 +83,14 @@ class NoiseFlowWrapper:
             x = self.nf_model.sample(batch_x, self.temp)
         return x.astype(np.float32) if isinstance(x, np.ndarray) else x
 
+    def nll_and_grad(self, x, y, b1=0.0, b2=0.0, iso=100.0, cam=2.0):
+        """``NoiseFlow.nll_and_grad``: ``(nll[B], d nll / d x, d nll / d y)`` (``bn_mode='running'`` only)."""
+        return self.nf_model.nll_and_grad(x, y, b1, b2, iso, cam)
+
+    def nll_torch(self, x, y, b1=0.0, b2=0.0, iso=100.0, cam=2.0):
+        """``NoiseFlow.nll_torch``: the NLL as a ``torch.autograd`` function of CUDA tensors (``bn_mode='running'`` only)."""
+        return self.nf_model.nll_torch(x, y, b1, b2, iso, cam)
+
     @staticmethod
     def hps_loader(path):
         return hps_loader(path)

@@ -170,6 +170,10 @@ def load() -> C.CDLL:
     lib.nf_nll_percond.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, u32, vp]
     lib.nf_sample_percond.restype = C.c_int
     lib.nf_sample_percond.argtypes = [vp, vp, vp, u64, i64, f32, i64, vp, vp, vp]
+    lib.nf_nll_grad.restype = C.c_int
+    lib.nf_nll_grad.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.nf_grad_supported.restype = C.c_int
+    lib.nf_grad_supported.argtypes = [C.POINTER(nf_config), C.POINTER(nf_layer_desc), C.POINTER(C.c_float), C.c_size_t]
     if lib.nf_abi_version() != 1:
         raise ImportError("noiseflow_hip ABI version mismatch")
     _lib = lib
@@ -189,6 +193,7 @@ EXPORTED_SYMBOLS = (
     "nf_trainer_create", "nf_trainer_destroy", "nf_trainer_forward_backward", "nf_trainer_forward", "nf_trainer_apply", "nf_trainer_step",
     "nf_trainer_get_params", "nf_trainer_set_params", "nf_trainer_steps", "nf_trainer_set_sync",
     "nf_cond_rows", "nf_nll_percond", "nf_sample_percond",
+    "nf_nll_grad", "nf_grad_supported",
 )
 NF_PATH_SCALAR, NF_PATH_MFMA4, NF_PATH_FP16, NF_PATH_WIDE32, NF_PATH_WIDE16, NF_PATH_WIDE32_FP16, NF_PATH_GEMM, NF_PATH_GEMM_FP16 = 0, 1, 2, 3, 4, 5, 6, 7
 NF_PATH_SPLIT_BF16 = 8

@@ -396,6 +396,44 @@ struct NfLaunch {
     const nf_cond_row *cond_rows;
 };
 
+// ---- input gradients of the NLL (nf_grad.hip, nf_nll_grad) ------------------------------------------
+// The kernel interprets the NLL-order program over a parameter block of its own ("gradient block"), the generic layout
+// with the inverse of every 1x1 matrix beside it:
+//   MIX       A [4][4] @0 (row-major [c][k], as the generic block), Ainv [4][4] @16
+//   COUPLING  the generic block (nf_cpl_off_*)
+//   SCALE     s, 1/s, 0, 0
+// One workgroup per patch: THREADS x PX pixel slots by patch size and width (nf_grad_threads, nf_grad_px), LDS = the forward kernel's two
+// tiles (2 + w words per tile pixel), the gate record and the reduction scratch.
+// Gate record: one bit per hidden channel, ReLU and coupling — gate set s = 2 c + layer of coupling c is `width` bits,
+// 32 / width sets per 32-bit word, word-major over the pixel slots ([word][THREADS * PX]: a lane reads and writes only its own).
+struct NfGradLaunch {
+    const float *params;   // gradient block (device)
+    const float *x;        // [B,H,W,4]
+    const float *y;        // [B,H,W,4] or null
+    float *nll_out;        // [B] or null
+    float *gx_out;         // [B,H,W,4] or null
+    float *gy_out;         // [B,H,W,4] or null
+    int64_t B;
+    double ld_const;       // constant part of the log-det (model + per-call part; with cond_rows the model's part only)
+    float cond_a[4];
+    float cond_b[4];
+    const nf_cond_row *cond_rows;   // [B] or null (as NfLaunch::cond_rows)
+    int32_t H, W;
+    int32_t first_cpl;     // index of the first coupling op (n_ops when the model has none)
+    int32_t gate_words;    // 32-bit words of gate record per pixel slot
+};
+__host__ __device__ constexpr int nf_grad_threads(int hw, int width)
+{
+    return hw <= 64 ? 64 : hw <= 256 ? 256 : hw <= 1024 ? (width >= 32 ? 1024 : 256) : 1024;
+}
+__host__ __device__ constexpr int nf_grad_px(int hw, int width) { return hw <= 256 || (hw <= 1024 && width >= 32) ? 1 : 4; }
+__host__ __device__ constexpr int nf_grad_gate_words(int n_cpl, int width) { return (2 * n_cpl * width + 31) / 32; }
+__host__ __device__ constexpr size_t nf_grad_lds_floats(int H, int W, int width, int n_cpl)
+{
+    return (size_t)((((H + 2) * (W + 2)) + 1) & ~1) * (size_t)(2 + width) +
+           (size_t)nf_grad_gate_words(n_cpl, width) * (size_t)(nf_grad_threads(H * W, width) * nf_grad_px(H * W, width)) + 32;
+}
+
 #define NF_STATS_SLOTS 64   // power of two
 
 // Philox stream ids (4th counter word)

@@ -46,6 +46,7 @@ hipError_t nf_launch_tile_combine(const float *part, const NfTileParts &tp, int6
                                   uint32_t flags,
                                   float *nll_out, float *sd_out, float *ld_out, double *sums, hipStream_t stream);
 hipError_t nf_launch_gather(float *dst, const float *src, const int32_t *pairs, int n, hipStream_t stream);
+hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 
 namespace {
 
@@ -1428,6 +1429,65 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     return NF_OK;
 }
 
+// ---- input gradients (nf_nll_grad, nf_grad.hip) ---------------------------------------------------
+// THE place that decides what nf_nll_grad supports: `fwd` = the NLL-direction program of the model.
+int grad_support(const nf_config *cfg, const Built &fwd)
+{
+    if (cfg->flags & NF_CFG_FP16_CNN) return fail(NF_EINVAL, "nf_nll_grad: fp32 handles only (NF_CFG_FP16_CNN is set)");
+    if (cfg->height > 64 || cfg->width > 64)
+        return fail(NF_EINVAL, "nf_nll_grad: patches of up to 64x64 (%dx%d given; no tiled evaluation)", cfg->height, cfg->width);
+    const int w = fwd.prog.width, hw = cfg->height * cfg->width;
+    if (w > 32) return fail(NF_EINVAL, "nf_nll_grad: coupling widths up to 32 (%d given; the GEMM families have no gradient kernel)", fwd.raw_width);
+    int n_cpl = 0;
+    for (int i = 0; i < fwd.prog.n_ops; ++i) n_cpl += fwd.prog.ops[i].type == NF_OP_COUPLING_FWD ? 1 : 0;
+    // registers: beyond 32x32 a lane of the 1 024-thread workgroup holds 4 pixels inside 128 VGPRs.  No width fits that without
+    // scratch (width 4 spills 167 VGPRs, width 8 269: both run, slower); widths 16 and 32 would keep most of their hidden
+    // vectors in scratch and are refused.  Width 32 keeps one pixel per lane (12 spilled VGPRs at 1 024 threads)
+    if (hw > 1024 && w > 8)
+        return fail(NF_EINVAL, "nf_nll_grad: coupling width %d covers patches of up to 1024 pixels (%dx%d given): registers", fwd.raw_width,
+                    cfg->height, cfg->width);
+    const size_t lds = sizeof(float) * nf_grad_lds_floats(cfg->height, cfg->width, w, n_cpl);
+    if (lds > 160 * 1024)
+        return fail(NF_EINVAL, "nf_nll_grad: a %dx%d patch with coupling width %d and %d couplings needs %zu KiB of LDS (> 160)", cfg->height,
+                    cfg->width, w, n_cpl, (lds + 1023) / 1024);
+    return NF_OK;
+}
+
+// The gradient block (nf_device.h, NfGradLaunch): the NLL-order generic block with A^-1 beside every 1x1 matrix — op i of
+// the NLL program is op n - 1 - i of the sampling program, whose block holds the inverse — and 1/s beside every scale.
+void build_grad_block(const Built &fwd, const Built &rev, NfProgram &gp, std::vector<float> &blk, int &n_cpl, int &first_cpl)
+{
+    memset(&gp, 0, sizeof(gp));
+    gp.width = fwd.prog.width;
+    gp.n_ops = fwd.prog.n_ops;
+    blk.clear();
+    n_cpl = 0;
+    first_cpl = fwd.prog.n_ops;
+    for (int i = 0; i < fwd.prog.n_ops; ++i) {
+        const NfOp &src = fwd.prog.ops[i];
+        const NfOp &inv = rev.prog.ops[fwd.prog.n_ops - 1 - i];
+        const float *v = fwd.block.data() + src.off;
+        gp.ops[i].type = src.type;
+        gp.ops[i].off = (int32_t)blk.size();
+        if (src.type == NF_OP_MIX) {
+            blk.insert(blk.end(), v, v + 16);
+            blk.insert(blk.end(), rev.block.data() + inv.off, rev.block.data() + inv.off + 16);
+        } else if (src.type == NF_OP_COUPLING_FWD) {
+            blk.insert(blk.end(), v, v + nf_cpl_size(gp.width));
+            if (n_cpl == 0) first_cpl = i;
+            ++n_cpl;
+        } else if (src.type == NF_OP_SCALE) {
+            blk.push_back(v[0]);
+            blk.push_back(rev.block[inv.off]);
+            blk.push_back(0.f);
+            blk.push_back(0.f);
+        } else {
+            gp.ops[i].off = src.off;   // conditioning slot
+        }
+    }
+    if (blk.empty()) blk.assign(4, 0.0f);
+}
+
 // NF_KERNEL=valu forces the scalar-weight VALU kernel (A/B testing); default = matrix core
 bool use_matrix_core()
 {
@@ -1499,6 +1559,12 @@ struct nf_handle {
     float *d_fwd8 = nullptr;   // fp16-CNN GEMM layout
     float *d_rev8 = nullptr;
     bool scalar_ok = true;     // the scalar-weight kernel's LDS tiles fit this patch shape / width
+    // nf_nll_grad: its program and block (nf_device.h, NfGradLaunch), or why this handle has none (grad_support)
+    NfProgram gprog;
+    float *d_grad = nullptr;
+    int grad_n_cpl = 0, grad_first_cpl = 0;
+    int grad_rc = NF_EINVAL;
+    std::string grad_why;
     // scratch of the tiled calls (images beyond 64x64): the per-tile sums and the tensors between two segments.  A small set of
     // device buffers owned by the handle, one per call in flight; a call takes a free one (waiting, on ITS stream, for the work
     // that last used it), so nf_nll / nf_sample allocate only when a call needs more than any earlier one did, or when more
@@ -1715,6 +1781,21 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
             return fail_hip(e, "hipMalloc/hipMemcpy(matrix-core params)");
         }
     }
+    {   // the gradient kernel's block, where nf_nll_grad supports the model (otherwise the call reports grad_why)
+        const std::string keep = g_last_error;
+        h->grad_rc = grad_support(cfg, h->fwd);
+        h->grad_why = g_last_error;
+        g_last_error = keep;
+        if (h->grad_rc == NF_OK) {
+            std::vector<float> gb;
+            build_grad_block(h->fwd, h->rev, h->gprog, gb, h->grad_n_cpl, h->grad_first_cpl);
+            if ((e = hipMalloc((void **)&h->d_grad, gb.size() * sizeof(float))) != hipSuccess ||
+                (e = hipMemcpy(h->d_grad, gb.data(), gb.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) {
+                nf_destroy(h);
+                return fail_hip(e, "hipMalloc/hipMemcpy(gradient params)");
+            }
+        }
+    }
     *out = h;
     return NF_OK;
 }
@@ -1743,6 +1824,7 @@ int nf_destroy(nf_handle *h)
     if (h->d_rev7) (void)hipFree(h->d_rev7);
     if (h->d_fwd8) (void)hipFree(h->d_fwd8);
     if (h->d_rev8) (void)hipFree(h->d_rev8);
+    if (h->d_grad) (void)hipFree(h->d_grad);
     nf_bs_destroy(h->bs);
     for (nf_handle::Workspace *w : h->ws) {
         if (w->ev) {
@@ -2266,6 +2348,62 @@ int nf_sample_percond(nf_handle *h, const float *y, const float *eps, uint64_t s
     DeviceGuard guard;
     if ((rc = guard.enter(h->device)) != NF_OK) return rc;
     return launch_resident(h, 1, a, (hipStream_t)stream, "nf_sample_percond launch");
+}
+
+// ---- input gradients: d nll / d x, d nll / d y (nf_grad.hip) ----
+int nf_grad_supported(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params)
+{
+    Built b;
+    int rc = build_program(cfg, layers, params, n_params, 0, b);
+    if (rc != NF_OK) return rc;
+    return grad_support(cfg, b);
+}
+
+int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond, const nf_cond_row *rows, float *nll_out,
+                float *gx_out, float *gy_out, void *stream)
+{
+    if (!h) return fail(NF_EINVAL, "handle is NULL");
+    if (h->grad_rc != NF_OK) return fail(h->grad_rc, "%s", h->grad_why.c_str());
+    if (B < 0) return fail(NF_EINVAL, "B must be >= 0");
+    if ((cond != nullptr) == (rows != nullptr)) return fail(NF_EINVAL, "nf_nll_grad: exactly one of cond / rows must be given");
+    if (B > 0 && !x) return fail(NF_EINVAL, "x is NULL");
+    if (h->fwd.has_sdn && B > 0 && !y) return fail(NF_EINVAL, "model has a signal-dependent layer but y is NULL");
+    if (!y && gy_out) return fail(NF_EINVAL, "gy_out must be NULL when y is");
+    if (!aligned16(x) || !aligned16(y) || !aligned16(gx_out) || !aligned16(gy_out))
+        return fail(NF_EINVAL, "x, y, gx_out and gy_out must be 16-byte aligned (every pixel is one float4 access)");
+    nf_cond_row r;
+    memset(&r, 0, sizeof(r));
+    if (rows) {
+        int rc = check_rows(h, rows, B);
+        if (rc != NF_OK) return rc;
+    } else {
+        int rc = cond_row_of(h->fwd, h->cfg.height, h->cfg.width, 0, cond, r);
+        if (rc != NF_OK) return rc;
+    }
+    if (B == 0) return NF_OK;
+    NfGradLaunch a;
+    memset(&a, 0, sizeof(a));
+    a.params = h->d_grad;
+    a.x = x;
+    a.y = y;
+    a.nll_out = nll_out;
+    a.gx_out = gx_out;
+    a.gy_out = gy_out;
+    a.B = B;
+    a.ld_const = r.ld + h->fwd.ld_const;
+    memcpy(a.cond_a, r.a, sizeof(r.a));
+    memcpy(a.cond_b, r.b, sizeof(r.b));
+    a.cond_rows = rows;
+    a.H = h->cfg.height;
+    a.W = h->cfg.width;
+    a.first_cpl = h->grad_first_cpl;
+    a.gate_words = nf_grad_gate_words(h->grad_n_cpl, h->gprog.width);
+    DeviceGuard guard;
+    int rc = guard.enter(h->device);
+    if (rc != NF_OK) return rc;
+    hipError_t e = nf_launch_grad(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "nf_nll_grad launch");
+    return NF_OK;
 }
 
 // ---- batch-statistics mode (is_training=True graphs: layers.py:386-398) ----

@@ -499,6 +499,53 @@ class NoiseFlow(object):
         sd_z = sd.double().mean().float()
         return self._dev.back(nll, was_np), (float(sd_z) if was_np else sd_z)
 
+    # ------------------------------------------------------------------ input gradients
+    def _run_nll_grad(self, xt, yt, cond, want_gx=True, want_gy=True):
+        """One ``nf_nll_grad`` call on device tensors, on the current stream → (nll, gx | None, gy | None)."""
+        dev = self._dev
+        B = int(xt.shape[0])
+        nll = dev.empty((B,))
+        gx = dev.empty(xt.shape) if want_gx else None
+        gy = dev.empty(yt.shape) if (want_gy and yt is not None) else None
+        per_patch = isinstance(cond, PatchCond)
+        rows = self._rows_to_dev(cond, 0) if per_patch else None
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        with dev.torch.cuda.device(dev.device):
+            _lib.check(self._flow.lib.nf_nll_grad(self._flow.ptr, xt.data_ptr(), ptr(yt), B, None if per_patch else C.byref(cond),
+                                                  ptr(rows), nll.data_ptr(), ptr(gx), ptr(gy), dev.stream_ptr()))
+        return nll, gx, gy
+
+    def _grad_inputs(self, x, y):
+        if self._is_training:
+            raise NotImplementedError("input gradients exist in evaluation mode only (is_training=False): batch statistics "
+                                      "couple the patches of a call")
+        tail = tuple(self.x_shape)
+        xt, was_np = self._dev.to_dev(x, tail)
+        yt = None
+        if y is not None and self._flow.has_sdn:
+            yt, _ = self._dev.to_dev(y, tail)
+            if yt.shape[0] != xt.shape[0]:
+                raise ValueError("x and y batch sizes differ")
+        elif self._flow.has_sdn:
+            raise ValueError("this architecture has a signal-dependent layer: the clean image y is required")
+        return xt, yt, was_np
+
+    def nll_and_grad(self, x, y, nlf0=None, nlf1=None, iso=None, cam=None):
+        """``(nll[B], d nll_b / d x, d nll_b / d y)`` of the ``nll`` that :meth:`_loss` reports, in one fused kernel
+        (evaluation mode, fp32).  numpy in → numpy out, CUDA tensors in → CUDA tensors out; length-B ``iso`` / ``cam`` lists
+        condition per patch.  ``gy`` is ``None`` for a model without a signal-dependent layer."""
+        xt, yt, was_np = self._grad_inputs(x, y)
+        nll, gx, gy = self._run_nll_grad(xt, yt, self._cond(nlf0, nlf1, iso, cam, int(xt.shape[0])))
+        back = self._dev.back
+        return back(nll, was_np), back(gx, was_np), (back(gy, was_np) if gy is not None else None)
+
+    def nll_torch(self, x, y, nlf0=None, nlf1=None, iso=None, cam=None):
+        """``nll[B]`` as a differentiable function of the CUDA tensors ``x`` and ``y`` (``torch.autograd``): a denoiser loss
+        is ``nf.nll_torch(noisy - f(noisy), f(noisy), iso=..., cam=...).mean()``.  One ``nf_nll_grad`` call when an input
+        requires grad, plain ``nf_nll`` otherwise; issued on the current stream, no host synchronisation."""
+        from .autograd import nll_torch
+        return nll_torch(self, x, y, nlf0, nlf1, iso, cam)
+
     def loss(self, x, y, nlf0=None, nlf1=None, iso=None, cam=None, reuse=False):
         """noise_flow_model.py:482-484 → ``(mean_b nll_b, sd_z)``."""
         self._check_mode()
