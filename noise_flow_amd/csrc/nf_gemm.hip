@@ -25,11 +25,14 @@
 //    output pixels it owns:  o[r][c] += sum_taps P[r+di-1][c+dj-1][tap] over the pixels of THIS band.  'SAME' padding falls
 //    out of the bounds checks, the edge-indicator channel is the 16-entry border table of the other kernels.
 //
+// This file holds the two fp32 kernels, their LDS sizes and entry points.  nf_gemmb_kernel (variant B below) is its LDS carve-up,
+// lane constants and CNN on the frame of nf_gemm_common.h; nf_gemm_kernel (the bands above) keeps its own frame, gather and pixel
+// table — on the shared frame it lost 1 - 5 % at 8 pixels per thread — and shares the per-pixel helpers and the launcher.
+//
 // Replaces (reference, /root/reference): layers.py:251-375 (AffineCoupling), :452-498 (real_nvp_conv_template), :555-613,
 // :651-674 (conv2d / add_edge_padding / conv2d_zeros) at hps.width > 32 (sidd/ArgParser.py:43: default 512).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <atomic>
 #include "../../include/noiseflow_hip.h"   // NF_SUMS_SLOTS / NF_SUMS_STRIDE
 #include "nf_device.h"
 #include "nf_gemm_layout.h"
@@ -37,13 +40,6 @@
 #include "nf_gemm_common.h"
 
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-constexpr int GT = 512;          // threads per workgroup
-constexpr int GW = GT / 64;      // wavefronts
-
-__device__ __forceinline__ float4 ldg4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 
 //   WP      padded coupling width: 64, 128, 256, 512
 //   PHILOX  input = in-kernel Philox/Box-Muller draw
@@ -96,7 +92,7 @@ __global__ __launch_bounds__(GT) void nf_gemm_kernel(const NfProgram prog, const
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
         const GemmTile T = gemm_tile<PC>(a, b, H, W);
         float z[OWN][4];
-        gemm_input<OWN, PHILOX>(a, T, pr, pc, act, z);
+        gemm_input<OWN, PHILOX>(a, T, GemmPixTable<OWN>{pr, pc, act}, z);
 
         float ld = 0.0f, ld2 = 0.0f;   // natural-log / log2 parts of this thread's log-det share
 
@@ -296,15 +292,15 @@ __global__ __launch_bounds__(GT) void nf_gemm_kernel(const NfProgram prog, const
                 }
 
                 // ---- finish the coupling on the owned pixels ----
-                gemm_finish_coupling<OWN, false>(type, a.params + prog.ops[op].off + NF7_CPL_E, P[NF7_CPL_S + 1], P[NF7_CPL_S + 2], T, pr, pc, act, o, z, ld2);
+                gemm_finish_coupling<OWN, false>(type, a.params + prog.ops[op].off + NF7_CPL_E, P[NF7_CPL_S + 1], P[NF7_CPL_S + 2], T, GemmPixTable<OWN>{pr, pc, act}, o, z, ld2);
             } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
-                gemm_sdn<OWN, PC>(type, prog.ops[op].off, a, T, pr, pc, act, z, ld);
+                gemm_sdn<OWN, PC>(type, prog.ops[op].off, a, T, GemmPixTable<OWN>{pr, pc, act}, z, ld);
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
                 gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off), z);
             }
         }
 
-        gemm_epilogue<OWN, GT, PC>(a, T, b, HW, pr, pc, act, z, ld, ld2, red, acc_nll, acc_sd);
+        gemm_epilogue<OWN, PC>(a, T, b, HW, GemmPixTable<OWN>{pr, pc, act}, z, ld, ld2, red, acc_nll, acc_sd);
     }
     gemm_flush_sums(a, acc_nll, acc_sd);
 }
@@ -337,201 +333,102 @@ __global__ __launch_bounds__(GT) void nf_gemmb_kernel(const NfProgram prog, cons
 
     const int t = threadIdx.x;
     const int wv = t >> 6, lane = t & 63, n = lane & 31, g = lane >> 5;
+    const int n_rounds = (HW + RND - 1) / RND;
 
     for (int i = t; i < 2 * PL; i += GT) z0s[i] = 0.0f;
     __syncthreads();
-    // the pixels this thread owns: p = t + GT m
-    int pr[OWN], pc[OWN];
-    bool act[OWN];
+
+    gemm_frame<OWN, PHILOX, PC>(prog, a, red, [&](int type, int off, cfloat_p P, const GemmTile &T, const GemmPix<OWN> &pix, float (&z)[OWN][4],
+                                                  float (&o)[OWN][4], float &ld2) __attribute__((always_inline)) {
+        const float *const img = a.params + off + NF7_CPL_IMG;
+        // publish the pass-through half, stage this coupling's slabs
+        gemm_publish<OWN>(z0s, PL, Wp, 1, pix, z);
+        for (int i = t; i < MT * (SLAB / 4); i += GT)
+            reinterpret_cast<float4 *>(wb)[i] = reinterpret_cast<const float4 *>(img + nf10_img_SLAB(WP))[i];
+        __syncthreads();
+
+        for (int rnd = 0; rnd < n_rounds; ++rnd) {
+            const int p0 = rnd * RND;
+            // ---- l_1: relu(W1 z0 + b1) for this wavefront's 32 pixels, all channels, into registers ----
+            float hr[MT][16];
+            {
+                int p = p0 + 32 * wv + n;
+                p = p < HW ? p : HW - 1;   // columns past the patch: never gathered
+                const int r = p / W, c = p - r * W;
+                const float *zb = z0s + g * PL + r * Wp + c;   // tap (di,dj) at + di*Wp + dj
+                float bt[9];
 #pragma unroll
-    for (int m = 0; m < OWN; ++m) {
-        const int p = t + GT * m;
-        act[m] = p < HW;
-        pr[m] = act[m] ? p / W : 0;
-        pc[m] = act[m] ? p - pr[m] * W : 0;
-    }
-
-    const int n_ops = prog.n_ops;
-    const int n_rounds = (HW + RND - 1) / RND;
-    double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
-
-    for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const GemmTile T = gemm_tile<PC>(a, b, H, W);
-        float z[OWN][4];
-        gemm_input<OWN, PHILOX>(a, T, pr, pc, act, z);
-
-        float ld = 0.0f, ld2 = 0.0f;   // natural-log / log2 parts of this thread's log-det share
-
-        for (int op = 0; op < n_ops; ++op) {
-            const int type = prog.ops[op].type;
-            const cfloat_p P = (cfloat_p)(a.params + prog.ops[op].off);   // wave-uniform, scalar loads
-
-            if (type == NF_OP_MIX) {
-                gemm_mix<OWN>(P, z);
-            } else if (type == NF_OP_COUPLING_FWD || type == NF_OP_COUPLING_REV) {
-                const float *const img = a.params + prog.ops[op].off + NF7_CPL_IMG;
-                // ---- publish the pass-through half, stage this coupling's slabs ----
+                for (int tap = 0; tap < 9; ++tap) bt[tap] = zb[(tap / 3) * Wp + tap % 3];
 #pragma unroll
-                for (int m = 0; m < OWN; ++m)
-                    if (act[m]) {
-                        z0s[(pr[m] + 1) * Wp + pc[m] + 1] = z[m][0];
-                        z0s[PL + (pr[m] + 1) * Wp + pc[m] + 1] = z[m][1];
+                for (int m = 0; m < MT; ++m) {
+                    v16f d = gemm_acc_bias(img + nf7_img_B1(WP) + m * 32 + g * 16);
+#pragma unroll
+                    for (int grp = 0; grp < 3; ++grp) {
+                        const float4 aw = ldg4(img + nf7_img_A1(WP) + ((m * 3 + grp) * 64 + lane) * 4);
+                        const float as[4] = {aw.x, aw.y, aw.z, aw.w};
+#pragma unroll
+                        for (int s = 0; s < 4; ++s)
+                            if (grp * 4 + s < 9) d = __builtin_amdgcn_mfma_f32_32x32x2f32(as[s], bt[grp * 4 + s], d, 0, 0, 0);
                     }
-                float o[OWN][4];
 #pragma unroll
-                for (int m = 0; m < OWN; ++m)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) o[m][j] = 0.0f;
-                for (int i = t; i < MT * (SLAB / 4); i += GT)
-                    reinterpret_cast<float4 *>(wb)[i] = reinterpret_cast<const float4 *>(img + nf10_img_SLAB(WP))[i];
-                __syncthreads();
-
-                for (int rnd = 0; rnd < n_rounds; ++rnd) {
-                    const int p0 = rnd * RND;
-                    // ---- l_1: relu(W1 z0 + b1) for this wavefront's 32 pixels, all channels, into registers ----
-                    float hr[MT][16];
-                    {
-                        int p = p0 + 32 * wv + n;
-                        p = p < HW ? p : HW - 1;   // columns past the patch: never gathered
-                        const int r = p / W, c = p - r * W;
-                        const float *zb = z0s + g * PL + r * Wp + c;   // tap (di,dj) at + di*Wp + dj
-                        float bt[9];
-#pragma unroll
-                        for (int tap = 0; tap < 9; ++tap) bt[tap] = zb[(tap / 3) * Wp + tap % 3];
-#pragma unroll
-                        for (int m = 0; m < MT; ++m) {
-                            v16f d;
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const float4 bb = ldg4(img + nf7_img_B1(WP) + m * 32 + g * 16 + 4 * q);
-                                d[4 * q + 0] = bb.x; d[4 * q + 1] = bb.y; d[4 * q + 2] = bb.z; d[4 * q + 3] = bb.w;
-                            }
-#pragma unroll
-                            for (int grp = 0; grp < 3; ++grp) {
-                                const float4 aw = ldg4(img + nf7_img_A1(WP) + ((m * 3 + grp) * 64 + lane) * 4);
-                                const float as[4] = {aw.x, aw.y, aw.z, aw.w};
-#pragma unroll
-                                for (int s = 0; s < 4; ++s)
-                                    if (grp * 4 + s < 9) d = __builtin_amdgcn_mfma_f32_32x32x2f32(as[s], bt[grp * 4 + s], d, 0, 0, 0);
-                            }
-#pragma unroll
-                            for (int v = 0; v < 16; ++v) hr[m][v] = nf_relu(d[v]);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    }
-                    // ---- per output tile: l_2 over the whole K from the slab in LDS, then its share of P = W3^T relu(h2) ----
-                    v16f pa;
-                    v4f p8 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) pa[v] = 0.0f;
-#pragma unroll 1
-                    for (int m = 0; m < MT; ++m) {
-                        const float *sl = wb + m * SLAB;
-                        v16f acc;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const float4 bb = *reinterpret_cast<const float4 *>(sl + nf10_slab_B2(WP) + g * 16 + 4 * q);
-                            acc[4 * q + 0] = bb.x; acc[4 * q + 1] = bb.y; acc[4 * q + 2] = bb.z; acc[4 * q + 3] = bb.w;
-                        }
-                        const float4 *ap = reinterpret_cast<const float4 *>(sl) + lane;   // chunk kc (K steps 4 kc .. 4 kc + 3) at + 64 kc
-                        float4 ca = ap[0], na = ca;
-#pragma unroll
-                        for (int kc = 0; kc < KC; ++kc) {
-                            if (kc + 1 < KC) na = ap[64 * (kc + 1)];
-                            __builtin_amdgcn_sched_barrier(0);
-                            const float as[4] = {ca.x, ca.y, ca.z, ca.w};
-#pragma unroll
-                            for (int s = 0; s < 4; ++s) {
-                                const int kk = 4 * kc + s;   // consumes register kk % 16 of input tile kk / 16
-                                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[s], hr[kk >> 4][kk & 15], acc, 0, 0, 0);
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            ca = na;
-                        }
-                        // h2 tile m complete: ReLU and straight into P (taps 0 .. 7: one 32-row tile; tap 8: 4x4x1)
-#pragma unroll
-                        for (int grp = 0; grp < 4; ++grp) {
-                            const float4 w0 = *reinterpret_cast<const float4 *>(sl + nf10_slab_A3(WP) + (grp * 64 + lane) * 4);
-                            const float4 wc = *reinterpret_cast<const float4 *>(sl + nf10_slab_A3C(WP) + (grp * 8 + g * 4 + (lane & 3)) * 4);
-                            const float ws0[4] = {w0.x, w0.y, w0.z, w0.w}, wcs[4] = {wc.x, wc.y, wc.z, wc.w};
-#pragma unroll
-                            for (int s = 0; s < 4; ++s) {
-                                const float h = nf_relu(acc[grp * 4 + s]);
-                                pa = __builtin_amdgcn_mfma_f32_32x32x2f32(ws0[s], h, pa, 0, 0, 0);
-                                p8 = __builtin_amdgcn_mfma_f32_4x4x1f32(wcs[s], h, p8, 0, 0, 0);
-                            }
-                        }
-                    }
-                    // ---- P records of the round ----
-                    {
-                        float *dst = prec + (size_t)(32 * wv + n) * NF7_P_STRIDE;
-#pragma unroll
-                        for (int aa = 0; aa < 4; ++aa)
-                            *reinterpret_cast<float4 *>(dst + (2 * aa + g) * 4) = make_float4(pa[4 * aa + 0], pa[4 * aa + 1], pa[4 * aa + 2], pa[4 * aa + 3]);
-                        *reinterpret_cast<float4 *>(dst + 32 + 4 * g) = make_float4(p8[0], p8[1], p8[2], p8[3]);
-                    }
-                    __syncthreads();
-                    // gather: the taps of this round's pixels that fall on the output pixels this thread owns
-#pragma unroll
-                    for (int m = 0; m < OWN; ++m) {
-                        const int q = t + GT * m;
-                        if (!act[m] || q + W + 1 < p0 || q >= p0 + RND + W + 1) continue;
-#pragma unroll
-                        for (int di = 0; di < 3; ++di) {
-                            const int rr = pr[m] + di - 1;
-                            if (rr < 0 || rr >= H) continue;
-#pragma unroll
-                            for (int dj = 0; dj < 3; ++dj) {
-                                const int cc = pc[m] + dj - 1;
-                                const int src = rr * W + cc - p0;
-                                if (cc < 0 || cc >= W || src < 0 || src >= RND) continue;
-                                const float *rp = prec + (size_t)src * NF7_P_STRIDE;
-                                float4 v = *reinterpret_cast<const float4 *>(rp + (di * 3 + dj) * 4);
-                                if (di * 3 + dj == 8) {   // tap 8: the two lane halves' partial sums
-                                    const float4 u = *reinterpret_cast<const float4 *>(rp + 36);
-                                    v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-                                }
-                                o[m][0] += v.x; o[m][1] += v.y; o[m][2] += v.z; o[m][3] += v.w;
-                            }
-                        }
-                    }
-                    __syncthreads();   // the next round overwrites the records
+                    for (int v = 0; v < 16; ++v) hr[m][v] = nf_relu(d[v]);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
-
-                // ---- finish the coupling on the owned pixels ----
-                gemm_finish_coupling<OWN, false>(type, a.params + prog.ops[op].off + NF7_CPL_E, P[NF7_CPL_S + 1], P[NF7_CPL_S + 2], T, pr, pc, act, o, z, ld2);
-            } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
-                gemm_sdn<OWN, PC>(type, prog.ops[op].off, a, T, pr, pc, act, z, ld);
-            } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off), z);
             }
+            // ---- per output tile: l_2 over the whole K from the slab in LDS, then its share of P = W3^T relu(h2) ----
+            v16f pa;
+            v4f p8 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int v = 0; v < 16; ++v) pa[v] = 0.0f;
+#pragma unroll 1
+            for (int m = 0; m < MT; ++m) {
+                const float *sl = wb + m * SLAB;
+                v16f acc = gemm_acc_bias(sl + nf10_slab_B2(WP) + g * 16);
+                const float4 *ap = reinterpret_cast<const float4 *>(sl) + lane;   // chunk kc (K steps 4 kc .. 4 kc + 3) at + 64 kc
+                float4 ca = ap[0], na = ca;
+#pragma unroll
+                for (int kc = 0; kc < KC; ++kc) {
+                    if (kc + 1 < KC) na = ap[64 * (kc + 1)];
+                    __builtin_amdgcn_sched_barrier(0);
+                    const float as[4] = {ca.x, ca.y, ca.z, ca.w};
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        const int kk = 4 * kc + s;   // consumes register kk % 16 of input tile kk / 16
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[s], hr[kk >> 4][kk & 15], acc, 0, 0, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    ca = na;
+                }
+                // h2 tile m complete: ReLU and straight into P (taps 0 .. 7: one 32-row tile; tap 8: 4x4x1)
+#pragma unroll
+                for (int grp = 0; grp < 4; ++grp) {
+                    const float4 w0 = *reinterpret_cast<const float4 *>(sl + nf10_slab_A3(WP) + (grp * 64 + lane) * 4);
+                    const float4 wc = *reinterpret_cast<const float4 *>(sl + nf10_slab_A3C(WP) + (grp * 8 + g * 4 + (lane & 3)) * 4);
+                    const float ws0[4] = {w0.x, w0.y, w0.z, w0.w}, wcs[4] = {wc.x, wc.y, wc.z, wc.w};
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        const float h = nf_relu(acc[grp * 4 + s]);
+                        pa = __builtin_amdgcn_mfma_f32_32x32x2f32(ws0[s], h, pa, 0, 0, 0);
+                        p8 = __builtin_amdgcn_mfma_f32_4x4x1f32(wcs[s], h, p8, 0, 0, 0);
+                    }
+                }
+            }
+            // ---- P records of the round, gathered onto the output pixels this thread owns ----
+            gemm_store_p(prec + (size_t)(32 * wv + n) * NF7_P_STRIDE, g, pa, p8);
+            __syncthreads();
+            gemm_gather<OWN, 1>(prec, 0, p0, RND, H, W, pix, o);
+            __syncthreads();   // the next round overwrites the records
         }
 
-        gemm_epilogue<OWN, GT, PC>(a, T, b, HW, pr, pc, act, z, ld, ld2, red, acc_nll, acc_sd);
-    }
-    gemm_flush_sums(a, acc_nll, acc_sd);
+        gemm_finish_coupling<OWN, false>(type, a.params + off + NF7_CPL_E, P[NF7_CPL_S + 1], P[NF7_CPL_S + 2], T, pix, o, z, ld2);
+    });
 }
 
+// ---- launching ---------------------------------------------------------------------------------------------------------------------
 size_t gemmb_lds_bytes(int wp, int H, int W)
 {
     const int Wp = W + 2, PL = ((H + 2) * Wp + 3) & ~3;
     return ((size_t)(wp / 32) * nf10_slab_floats(wp) + (size_t)32 * GW * NF7_P_STRIDE + 2 * (size_t)PL + 3 * GW + 8) * sizeof(float);
-}
-
-template <int WP, bool PHILOX, int OWN, bool PC = false>
-hipError_t launch_gemmb(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
-{
-    if constexpr (!PC) {
-        if (a.cond_rows) return launch_gemmb<WP, PHILOX, OWN, true>(prog, a, n_cu, device, stream);
-    }
-    static std::atomic<size_t> lds_set[16];
-    return gemm_launch_per_cu<GT>(&nf_gemmb_kernel<WP, PHILOX, OWN, PC>, gemmb_lds_bytes(WP, a.H, a.W), lds_set, prog, a, n_cu, device, stream);
-}
-
-template <int WP, bool PHILOX>
-hipError_t dispatch_ownb(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
-{
-    return gemm_by_own<GT>(a.H * a.W, [&](auto own) { return launch_gemmb<WP, PHILOX, decltype(own)::value>(prog, a, n_cu, device, stream); });
 }
 
 size_t gemm_lds_bytes(int H, int W, bool bordered = true)
@@ -540,63 +437,46 @@ size_t gemm_lds_bytes(int H, int W, bool bordered = true)
     return ((size_t)NF7_BAND_FLOATS + 2 * (size_t)PL + (bordered ? 3 * GW + 8 : 0)) * sizeof(float);
 }
 
-template <int WP, bool PHILOX, int OWN, bool BRD = true, bool PC = false>
-hipError_t launch_gemm(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
-{
-    if constexpr (!PC) {
-        if (a.cond_rows) return launch_gemm<WP, PHILOX, OWN, BRD, true>(prog, a, n_cu, device, stream);
-    }
-    static std::atomic<size_t> lds_set[16];
-    return gemm_launch_per_cu<GT>(&nf_gemm_kernel<WP, PHILOX, OWN, BRD, PC>, gemm_lds_bytes(a.H, a.W, BRD), lds_set, prog, a, n_cu, device, stream);
-}
-
 template <int WP, bool PHILOX>
-hipError_t dispatch_own(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
-{
-    if (a.H * a.W <= 2 * GT) return launch_gemm<WP, PHILOX, 2>(prog, a, n_cu, device, stream);
-    if (a.H * a.W <= 4 * GT) return launch_gemm<WP, PHILOX, 4>(prog, a, n_cu, device, stream);
-    // up to 64x64: 8 pixels per thread; the bordered tile of the largest shapes does not fit beside the band
-    if (gemm_lds_bytes(a.H, a.W, true) <= 160 * 1024) return launch_gemm<WP, PHILOX, 8>(prog, a, n_cu, device, stream);
-    return launch_gemm<WP, PHILOX, 8, false>(prog, a, n_cu, device, stream);
-}
-
-template <bool PHILOX>
-hipError_t dispatch_gemm(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
-{
-    switch (prog.width) {
-    case 64: return dispatch_own<64, PHILOX>(prog, a, n_cu, device, stream);
-    case 128: return dispatch_own<128, PHILOX>(prog, a, n_cu, device, stream);
-    case 256: return dispatch_own<256, PHILOX>(prog, a, n_cu, device, stream);
-    case 512: return dispatch_own<512, PHILOX>(prog, a, n_cu, device, stream);
-    }
-    return hipErrorInvalidValue;
-}
+struct GemmB {
+    template <int OWN, bool PC> static auto kernel() { return &nf_gemmb_kernel<WP, PHILOX, OWN, PC>; }
+};
+template <int WP, bool PHILOX, bool BRD>
+struct GemmA {
+    template <int OWN, bool PC> static auto kernel() { return &nf_gemm_kernel<WP, PHILOX, OWN, BRD, PC>; }
+};
 
 }  // namespace
 
 // variant B: programs in the NF10 layout (widths <= 128)
 bool nf_gemmb_shape_ok(int wp, int H, int W)
 {
-    return wp <= 128 && H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemmb_lds_bytes(wp, H, W) <= 160 * 1024;
+    return wp <= 128 && H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemmb_lds_bytes(wp, H, W) <= GEMM_LDS_MAX;
 }
 hipError_t nf_launch_gemmb(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
 {
     if (!nf_gemmb_shape_ok(prog.width, a.H, a.W)) return hipErrorInvalidValue;
-    const bool ph = (a.flags & NF_K_PHILOX_IN) != 0;
-    if (prog.width == 64) return ph ? dispatch_ownb<64, true>(prog, a, n_cu, device, stream) : dispatch_ownb<64, false>(prog, a, n_cu, device, stream);
-    return ph ? dispatch_ownb<128, true>(prog, a, n_cu, device, stream) : dispatch_ownb<128, false>(prog, a, n_cu, device, stream);
+    return gemm_by_width<128>(prog.width, a, [&](auto wp, auto philox) {
+        return gemm_launch<GemmB<decltype(wp)::value, decltype(philox)::value>>(gemmb_lds_bytes(prog.width, a.H, a.W), prog, a, n_cu, device, stream);
+    });
 }
 
 // whether a patch shape fits the GEMM kernel (nf_create asks before accepting a width > 32)
 bool nf_gemm_shape_ok(int H, int W)
 {
-    return H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemm_lds_bytes(H, W, false) <= 160 * 1024;
+    return H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemm_lds_bytes(H, W, false) <= GEMM_LDS_MAX;
 }
 
 // entry point used by nf_host.hip: programs in the NF7 layout (coupling width padded to 64 / 128 / 256 / 512)
 hipError_t nf_launch_gemm(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
 {
     if (!nf_gemm_shape_ok(a.H, a.W)) return hipErrorInvalidValue;
-    if (a.flags & NF_K_PHILOX_IN) return dispatch_gemm<true>(prog, a, n_cu, device, stream);
-    return dispatch_gemm<false>(prog, a, n_cu, device, stream);
+    return gemm_by_width<512>(prog.width, a, [&](auto wp, auto philox) {
+        constexpr int WP = decltype(wp)::value;
+        constexpr bool PHILOX = decltype(philox)::value;
+        // 8 pixels per thread (beyond 2048 pixels, up to 64x64): the bordered tile of the largest shapes does not fit beside the band
+        if (a.H * a.W > 4 * GT && gemm_lds_bytes(a.H, a.W, true) > GEMM_LDS_MAX)
+            return gemm_launch_own<GemmA<WP, PHILOX, false>, 8>(gemm_lds_bytes(a.H, a.W, false), prog, a, n_cu, device, stream);
+        return gemm_launch<GemmA<WP, PHILOX, true>>(gemm_lds_bytes(a.H, a.W, true), prog, a, n_cu, device, stream);
+    });
 }

@@ -34,6 +34,7 @@ hipError_t nf_launch_gemm16b(const NfProgram &prog, const NfLaunch &a, int n_cu,
 bool nf_gemm_shape_ok(int H, int W);
 hipError_t nf_launch_gemmb(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream);
 bool nf_gemmb_shape_ok(int wp, int H, int W);
+bool nf_gemm16b_shape_ok(int wp, int H, int W);
 hipError_t nf_launch_synth(uint64_t seed, int64_t patch_base, int64_t B, int HW, float beta1, float beta2,
                            float *y_out, float *x_out, hipStream_t stream);
 hipError_t nf_launch_eps(uint64_t seed, int64_t patch_base, int64_t B, int HW, float *eps_out, hipStream_t stream);
@@ -1310,7 +1311,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
         out.prog8.width = wp;
         {   // variant B (weights resident in LDS, pixel tiles per wavefront) where its slabs fit: widths <= 128; NF_GEMM16=a: A/B aid
             const char *e = getenv("NF_GEMM16");
-            out.gemm16_b = wp <= 128 && !(e && e[0] == 'a');
+            out.gemm16_b = nf_gemm16b_shape_ok(wp, th, tw) && !(e && e[0] == 'a');
         }
         for (int i = 0; i < out.prog.n_ops; ++i) {
             const NfOp &src = out.prog.ops[i];

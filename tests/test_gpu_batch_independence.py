@@ -8,7 +8,7 @@ module generalises that test to one small ragged shape on each of the other path
 
 Batch size: 2.4 x the number of workgroups the kernel keeps resident, so that workgroups get two and three patches.  The grid of
 every launch site is  min(B, multi_processor_count x occ):
-  * nf_launch_gemm / gemmb / gemm16 / gemm16b (nf_gemm_common.h, gemm_launch_per_cu): occ = 1, one workgroup per CU;
+  * nf_launch_gemm / gemmb / gemm16 / gemm16b (nf_gemm_common.h, gemm_launch_own): occ = 1, one workgroup per CU;
   * launch_flow_p (nf_kernels.hip), launch_wide_p (nf_wide.hip), launch_wide16 (nf_wide16.hip): occ is what
     hipOccupancyMaxActiveBlocksPerMultiprocessor reports for the kernel, clamped to 1 .. 32.  The test cannot ask for that number,
     so it takes the largest value the hardware allows for the workgroup size the dispatcher picks at the shape (2048 threads per

@@ -1,4 +1,5 @@
-"""Quick GPU check + timing of the GEMM kernel (csrc/nf_gemm.hip): `[B=..] [DTYPE=fp16] [SIDE=64] python tools/check_gemm.py [widths...]`."""
+"""Quick GPU check + timing of the GEMM kernels (csrc/nf_gemm.hip, nf_gemm16.hip): `[B=..] [DTYPE=fp16] [SIDE=64] [N=..] python tools/check_gemm.py [widths...]`
+(N = launches in the timed loop, default 3: raise it for an A/B whose windows have to be long enough to compare)."""
 import ctypes as C
 import os
 import sys
@@ -13,6 +14,9 @@ import torch  # noqa: E402
 from conftest import FULL_ARCH, make_inputs, trained_like_variables  # noqa: E402
 from noise_flow_amd import NoiseFlow, default_hps, _lib  # noqa: E402
 from oracle.nf_oracle import NoiseFlowOracle  # noqa: E402
+
+if os.environ.get("NF_TOOL_LIB"):   # A/B a differently-built library (this tool only)
+    _lib.LIB_PATH = os.path.abspath(os.environ["NF_TOOL_LIB"])
 
 widths = [int(a) for a in sys.argv[1:]] or [64, 128, 256, 512]
 B = int(os.environ.get("B", "512"))
@@ -40,7 +44,7 @@ for w in widths:
         _lib.check(lib.nf_nll(m._flow.ptr, xb.data_ptr(), yb.data_ptr(), B, C.byref(cond), out.data_ptr(), None, None, None, None, 0, st))
     step(); step()
     torch.cuda.synchronize()
-    n = 3
+    n = int(os.environ.get("N", "3"))
     t0 = time.perf_counter()
     for _ in range(n):
         step()
@@ -48,5 +52,5 @@ for w in widths:
     ms = (time.perf_counter() - t0) / n * 1e3
     mac = 16 + 18 * w + w * w + 36 * (w + 1)
     flop = (8 * (2 * mac + 56) + 40) * S * S * B
-    print("%dx%d " % (S, S) + "width %d %s: path %d nll rel err %.2e | B=%d %.2f ms = %.0f patches/s = %.1f TFLOP/s = %.3f of the %s matrix peak" % (
+    print("%dx%d " % (S, S) + "width %d %s: path %d nll rel err %.2e | B=%d %.4f ms = %.0f patches/s = %.1f TFLOP/s = %.3f of the %s matrix peak" % (
         w, DT, lib.nf_kernel_path(m._flow.ptr, 0), err, B, ms, B / ms * 1e3, flop / ms / 1e9, flop / ms / 1e9 / PEAK, DT), flush=True)
