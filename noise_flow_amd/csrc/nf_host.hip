@@ -222,7 +222,9 @@ bool fold_conv1x1_lu2(const float *p, Mat4 &A, Mat4 &Ainv, double &log_abs_det)
 }
 
 // ---- coupling CNN folding ---------------------------------------------------
-void fold_coupling(const float *p, int w, float *out)
+// `w` = width of the variables, `wk` >= w = width (and strides) of the block written: `out` arrives zeroed, the hidden channels
+// w .. wk-1 keep zero weights and zero bias
+void fold_coupling(const float *p, int w, int wk, float *out)
 {
     const float *W1 = p;
     const float *b1 = W1 + 18 * w;
@@ -245,7 +247,7 @@ void fold_coupling(const float *p, int w, float *out)
     double es[4];
     for (int j = 0; j < 4; ++j) es[j] = exp(kLogscaleFactor * (double)logs[j]);
 
-    float *E = out + nf_cpl_off_E(w);
+    float *E = out + nf_cpl_off_E(wk);
     for (int mask = 0; mask < 16; ++mask) {
         const bool top = mask & 1, bottom = mask & 2, left = mask & 4, right = mask & 8;
         for (int j = 0; j < 4; ++j) {
@@ -258,26 +260,56 @@ void fold_coupling(const float *p, int w, float *out)
             E[mask * 4 + j] = (float)(s * es[j]);
         }
     }
-    float *W3o = out + nf_cpl_off_W3(w);
+    float *W3o = out + nf_cpl_off_W3(wk);
     for (int tap = 0; tap < 9; ++tap)
         for (int i = 0; i < w; ++i)
             for (int j = 0; j < 4; ++j)
-                W3o[(tap * w + i) * 4 + j] = (float)((double)W3[(tap * (w + 1) + i) * 4 + j] * es[j]);
-    float *W1o = out + nf_cpl_off_W1(w);
+                W3o[(tap * wk + i) * 4 + j] = (float)((double)W3[(tap * (w + 1) + i) * 4 + j] * es[j]);
+    float *W1o = out + nf_cpl_off_W1(wk);
     for (int tap = 0; tap < 9; ++tap)
         for (int c = 0; c < 2; ++c)
             for (int j = 0; j < w; ++j)
-                W1o[(tap * 2 + c) * w + j] = (float)((double)W1[(tap * 2 + c) * w + j] * s1[j]);
-    float *B1o = out + nf_cpl_off_B1(w);
+                W1o[(tap * 2 + c) * wk + j] = (float)((double)W1[(tap * 2 + c) * w + j] * s1[j]);
+    float *B1o = out + nf_cpl_off_B1(wk);
     for (int j = 0; j < w; ++j) B1o[j] = (float)(((double)b1[j] - (double)m1[j]) * s1[j]);
-    float *W2o = out + nf_cpl_off_W2(w);
+    float *W2o = out + nf_cpl_off_W2(wk);
     for (int i = 0; i < w; ++i)
-        for (int j = 0; j < w; ++j) W2o[i * w + j] = (float)((double)W2[i * w + j] * s2[j]);
-    float *B2o = out + nf_cpl_off_B2(w);
+        for (int j = 0; j < w; ++j) W2o[i * wk + j] = (float)((double)W2[i * w + j] * s2[j]);
+    float *B2o = out + nf_cpl_off_B2(wk);
     for (int j = 0; j < w; ++j) B2o[j] = (float)(((double)b2[j] - (double)m2[j]) * s2[j]);
-    float *S = out + nf_cpl_off_S(w);
+    float *S = out + nf_cpl_off_S(wk);
     S[0] = resc[0];
     S[1] = S[2] = S[3] = 0.0f;
+}
+
+constexpr double kLog2e = 1.4426950408889634, k2Log2e = 2.0 * kLog2e;
+
+// What every re-layout opens with: the border table E (16 masks x 4 channels) with 2*log2(e) folded into its raw columns, which
+// feed exp2() directly, and the four scalars S of a generic coupling block of width `w`.
+void relayout_ES(const float *v1, int w, float *E, float *S)
+{
+    for (int m = 0; m < 16; ++m)
+        for (int j = 0; j < 4; ++j) {
+            const float e = v1[nf_cpl_off_E(w) + 4 * m + j];
+            E[4 * m + j] = j >= 2 ? (float)((double)e * k2Log2e) : e;
+        }
+    const double sc = v1[nf_cpl_off_S(w)];
+    S[0] = (float)sc;
+    S[1] = (float)(sc * kLog2e);          // scl:   ls*log2(e) = scl*tanh(raw)
+    S[2] = (float)(-2.0 * sc * kLog2e);   // -2*scl
+    S[3] = 0.0f;
+}
+
+// The two bias tables of the families that hold 32 hidden channels per tile (register v of lane half g = channel base +
+// nf4_chan(v, g)); channels beyond the model's width `w` are zero.
+void bias_tables32(const float *B1, const float *B2, int base, int w, float *o1, float *o2)
+{
+    for (int g = 0; g < 2; ++g)
+        for (int v = 0; v < 16; ++v) {
+            const int ch = base + nf4_chan(v, g);
+            o1[g * 16 + v] = ch < w ? B1[ch] : 0.0f;
+            o2[g * 16 + v] = ch < w ? B2[ch] : 0.0f;
+        }
 }
 
 // The same folded coupling block re-laid out j-major for the matrix-core kernel
@@ -285,18 +317,10 @@ void fold_coupling(const float *p, int w, float *out)
 void relayout_coupling_v2(const float *v1, float *out)
 {
     const int w = 4;
-    const double k2 = 2.0 * 1.4426950408889634;   // 2*log2(e): raw columns feed exp2() directly
-    const double log2e = 1.4426950408889634;
-    memcpy(out + NF2_CPL_E, v1 + nf_cpl_off_E(w), 64 * sizeof(float));
-    for (int m = 0; m < 16; ++m)
-        for (int j = 2; j < 4; ++j) out[NF2_CPL_E + 4 * m + j] = (float)((double)v1[nf_cpl_off_E(w) + 4 * m + j] * k2);
+    const double k2 = k2Log2e;
+    relayout_ES(v1, w, out + NF2_CPL_E, out + NF2_CPL_S);
     memcpy(out + NF2_CPL_B1, v1 + nf_cpl_off_B1(w), 4 * sizeof(float));
     memcpy(out + NF2_CPL_B2, v1 + nf_cpl_off_B2(w), 4 * sizeof(float));
-    const double sc = v1[nf_cpl_off_S(w)];
-    out[NF2_CPL_S + 0] = (float)sc;
-    out[NF2_CPL_S + 1] = (float)(sc * log2e);          // scl:   ls*log2(e) = scl*tanh(raw)
-    out[NF2_CPL_S + 2] = (float)(-2.0 * sc * log2e);   // -2*scl
-    out[NF2_CPL_S + 3] = 0.0f;
     for (int j = 0; j < 4; ++j) {
         for (int di = 0; di < 3; ++di)
             for (int q = 0; q < 8; ++q)
@@ -324,8 +348,7 @@ uint16_t to_half(float f)
 // rounds at the same point).
 uint16_t to_half_w3(float wv, int j)
 {
-    const double k2 = 2.0 * 1.4426950408889634;
-    _Float16 h = (_Float16)(j >= 2 ? (double)wv * k2 : (double)wv);
+    _Float16 h = (_Float16)(j >= 2 ? (double)wv * k2Log2e : (double)wv);
     uint16_t u;
     memcpy(&u, &h, 2);
     return u;
@@ -334,19 +357,9 @@ uint16_t to_half_w3(float wv, int j)
 void relayout_coupling_v3(const float *v1, float *out)
 {
     const int w = 4;
-    const double log2e = 1.4426950408889634, k2 = 2.0 * log2e;
-    for (int m = 0; m < 16; ++m)
-        for (int j = 0; j < 4; ++j) {
-            const double e = v1[nf_cpl_off_E(w) + 4 * m + j];
-            out[NF3_CPL_E + 4 * m + j] = (float)(j >= 2 ? e * k2 : e);   // raw columns feed exp2() directly
-        }
+    relayout_ES(v1, w, out + NF3_CPL_E, out + NF3_CPL_S);
     memcpy(out + NF3_CPL_B1, v1 + nf_cpl_off_B1(w), 4 * sizeof(float));
     memcpy(out + NF3_CPL_B2, v1 + nf_cpl_off_B2(w), 4 * sizeof(float));
-    const double sc = v1[nf_cpl_off_S(w)];
-    out[NF3_CPL_S + 0] = (float)sc;
-    out[NF3_CPL_S + 1] = (float)(sc * log2e);
-    out[NF3_CPL_S + 2] = (float)(-2.0 * sc * log2e);
-    out[NF3_CPL_S + 3] = 0.0f;
     uint16_t *h1 = reinterpret_cast<uint16_t *>(out + NF3_CPL_W1H);
     uint16_t *h2 = reinterpret_cast<uint16_t *>(out + NF3_CPL_W2H);
     uint16_t *h3 = reinterpret_cast<uint16_t *>(out + NF3_CPL_W3H);
@@ -372,19 +385,9 @@ void relayout_coupling_v3(const float *v1, float *out)
 void relayout_coupling_v11(const float *v1, float *out, bool with_a2)
 {
     const int w = 4;
-    const double log2e = 1.4426950408889634, k2 = 2.0 * log2e;
-    for (int m = 0; m < 16; ++m)
-        for (int j = 0; j < 4; ++j) {
-            const double e = v1[nf_cpl_off_E(w) + 4 * m + j];
-            out[NF11_CPL_E + 4 * m + j] = (float)(j >= 2 ? e * k2 : e);   // raw columns feed exp2() directly
-        }
+    relayout_ES(v1, w, out + NF11_CPL_E, out + NF11_CPL_S);
     memcpy(out + NF11_CPL_B1, v1 + nf_cpl_off_B1(w), 4 * sizeof(float));
     memcpy(out + NF11_CPL_B2, v1 + nf_cpl_off_B2(w), 4 * sizeof(float));
-    const double sc = v1[nf_cpl_off_S(w)];
-    out[NF11_CPL_S + 0] = (float)sc;
-    out[NF11_CPL_S + 1] = (float)(sc * log2e);
-    out[NF11_CPL_S + 2] = (float)(-2.0 * sc * log2e);
-    out[NF11_CPL_S + 3] = 0.0f;
     uint16_t *h2 = reinterpret_cast<uint16_t *>(out + NF11_CPL_W2H);
     uint16_t *a1 = reinterpret_cast<uint16_t *>(out + NF11_CPL_A1);
     uint16_t *a3 = reinterpret_cast<uint16_t *>(out + NF11_CPL_A3);
@@ -473,17 +476,8 @@ void relayout_coupling_v12(const float *v1, float *lds, uint32_t *img)
 // channel has zero weights and zero bias in l_1 / l_2, hence zero activation, and zero l_last weights).
 void relayout_coupling_wide32(const float *v1, int w, float *out)
 {
-    const double k2 = 2.0 * 1.4426950408889634, log2e = 1.4426950408889634;
-    for (int m = 0; m < 16; ++m)
-        for (int j = 0; j < 4; ++j) {
-            const double e = v1[nf_cpl_off_E(w) + 4 * m + j];
-            out[NF4_CPL_E + 4 * m + j] = (float)(j >= 2 ? e * k2 : e);   // raw columns feed exp2() directly
-        }
-    const double sc = v1[nf_cpl_off_S(w)];
-    out[NF4_CPL_S + 0] = (float)sc;
-    out[NF4_CPL_S + 1] = (float)(sc * log2e);
-    out[NF4_CPL_S + 2] = (float)(-2.0 * sc * log2e);
-    out[NF4_CPL_S + 3] = 0.0f;
+    const double k2 = k2Log2e;
+    relayout_ES(v1, w, out + NF4_CPL_E, out + NF4_CPL_S);
     float *img = out + NF4_CPL_IMG;
     const float *W1 = v1 + nf_cpl_off_W1(w), *B1 = v1 + nf_cpl_off_B1(w), *W2 = v1 + nf_cpl_off_W2(w);
     const float *B2 = v1 + nf_cpl_off_B2(w), *W3 = v1 + nf_cpl_off_W3(w);
@@ -491,12 +485,7 @@ void relayout_coupling_wide32(const float *v1, int w, float *out)
         for (int l = 0; l < 64; ++l)
             img[NF4_IMG_A1 + ((step >> 2) * 64 + l) * 4 + (step & 3)] =
                 (step < 9 && (l & 31) < w) ? W1[(step * 2 + (l >> 5)) * w + (l & 31)] : 0.0f;
-    for (int g = 0; g < 2; ++g)
-        for (int v = 0; v < 16; ++v) {
-            const int ch = nf4_chan(v, g);
-            img[NF4_IMG_B1 + g * 16 + v] = ch < w ? B1[ch] : 0.0f;
-            img[NF4_IMG_B2 + g * 16 + v] = ch < w ? B2[ch] : 0.0f;
-        }
+    bias_tables32(B1, B2, 0, w, img + NF4_IMG_B1, img + NF4_IMG_B2);
     // taps (di,dj) of the 8 off-centre rows groups of P, by (a, g')
     static const int tap_of[4][2] = {{0 * 3 + 0, 2 * 3 + 0}, {0 * 3 + 2, 2 * 3 + 2}, {0 * 3 + 1, 2 * 3 + 1}, {1 * 3 + 0, 1 * 3 + 2}};
     for (int s = 0; s < 16; ++s)
@@ -519,18 +508,9 @@ void relayout_coupling_wide32(const float *v1, int w, float *out)
 // wavefront that consumes it fetches it from L2 (nf_gemm.hip).
 void relayout_coupling_gemm(const float *v1, int w, int wp, float *out)
 {
-    const double k2 = 2.0 * 1.4426950408889634, log2e = 1.4426950408889634;
+    const double k2 = k2Log2e;
     const int MT = wp / 32, KC = wp / 8;
-    for (int m = 0; m < 16; ++m)
-        for (int j = 0; j < 4; ++j) {
-            const double e = v1[nf_cpl_off_E(w) + 4 * m + j];
-            out[NF7_CPL_E + 4 * m + j] = (float)(j >= 2 ? e * k2 : e);   // raw columns feed exp2() directly
-        }
-    const double sc = v1[nf_cpl_off_S(w)];
-    out[NF7_CPL_S + 0] = (float)sc;
-    out[NF7_CPL_S + 1] = (float)(sc * log2e);
-    out[NF7_CPL_S + 2] = (float)(-2.0 * sc * log2e);
-    out[NF7_CPL_S + 3] = 0.0f;
+    relayout_ES(v1, w, out + NF7_CPL_E, out + NF7_CPL_S);
     float *img = out + NF7_CPL_IMG;
     const float *W1 = v1 + nf_cpl_off_W1(w), *B1 = v1 + nf_cpl_off_B1(w), *W2 = v1 + nf_cpl_off_W2(w);
     const float *B2 = v1 + nf_cpl_off_B2(w), *W3 = v1 + nf_cpl_off_W3(w);
@@ -541,12 +521,7 @@ void relayout_coupling_gemm(const float *v1, int w, int wp, float *out)
                 img[nf7_img_A1(wp) + ((m * 3 + (step >> 2)) * 64 + l) * 4 + (step & 3)] =
                     (step < 9 && oc < w) ? W1[(step * 2 + (l >> 5)) * w + oc] : 0.0f;
             }
-        for (int g = 0; g < 2; ++g)
-            for (int v = 0; v < 16; ++v) {
-                const int ch = 32 * m + nf4_chan(v, g);
-                img[nf7_img_B1(wp) + m * 32 + g * 16 + v] = ch < w ? B1[ch] : 0.0f;
-                img[nf7_img_B2(wp) + m * 32 + g * 16 + v] = ch < w ? B2[ch] : 0.0f;
-            }
+        bias_tables32(B1, B2, 32 * m, w, img + nf7_img_B1(wp) + m * 32, img + nf7_img_B2(wp) + m * 32);
         for (int kc = 0; kc < KC; ++kc)                // l_2: K step kk = 4 kc + s consumes input tile kk / 16, register kk % 16
             for (int l = 0; l < 64; ++l)
                 for (int s2 = 0; s2 < 4; ++s2) {
@@ -599,18 +574,8 @@ void relayout_coupling_gemmb(const float *v1, int w, int wp, float *out)
 // folded weights rounded to half once (the oracle's rounding points), biases / border table fp32.
 void relayout_coupling_gemm16(const float *v1, int w, int wp, float *out)
 {
-    const double k2 = 2.0 * 1.4426950408889634, log2e = 1.4426950408889634;
     const int MT = wp / 32, KS = wp / 16;
-    for (int m = 0; m < 16; ++m)
-        for (int j = 0; j < 4; ++j) {
-            const double e = v1[nf_cpl_off_E(w) + 4 * m + j];
-            out[NF8_CPL_E + 4 * m + j] = (float)(j >= 2 ? e * k2 : e);
-        }
-    const double sc = v1[nf_cpl_off_S(w)];
-    out[NF8_CPL_S + 0] = (float)sc;
-    out[NF8_CPL_S + 1] = (float)(sc * log2e);
-    out[NF8_CPL_S + 2] = (float)(-2.0 * sc * log2e);
-    out[NF8_CPL_S + 3] = 0.0f;
+    relayout_ES(v1, w, out + NF8_CPL_E, out + NF8_CPL_S);
     float *img = out + NF8_CPL_IMG;
     memset(img, 0, (size_t)nf8_img_size(wp) * sizeof(float));
     uint16_t *h = reinterpret_cast<uint16_t *>(img);   // half index = 2 * dword index
@@ -635,12 +600,7 @@ void relayout_coupling_gemm16(const float *v1, int w, int wp, float *out)
                 }
             }
         }
-        for (int g = 0; g < 2; ++g)
-            for (int v = 0; v < 16; ++v) {
-                const int ch = 32 * m + nf4_chan(v, g);
-                img[nf8_img_B1(wp) + m * 32 + g * 16 + v] = ch < w ? B1[ch] : 0.0f;
-                img[nf8_img_B2(wp) + m * 32 + g * 16 + v] = ch < w ? B2[ch] : 0.0f;
-            }
+        bias_tables32(B1, B2, 32 * m, w, img + nf8_img_B1(wp) + m * 32, img + nf8_img_B2(wp) + m * 32);
         for (int q4 = 0; q4 < 4; ++q4)                 // tap 8 on v_mfma_f32_4x4x4_16b_f16
             for (int g = 0; g < 2; ++g)
                 for (int j = 0; j < 4; ++j)
@@ -673,17 +633,8 @@ void relayout_coupling_gemm16b(const float *v1, int w, int wp, float *out)
 // Width-16 re-layout (nf_device.h, NF6_*; `w` = 16, or 8 zero-padded): fetch order of v_mfma_f32_16x16x4_f32.
 void relayout_coupling_wide16(const float *v1, int w, float *out)
 {
-    const double k2 = 2.0 * 1.4426950408889634, log2e = 1.4426950408889634;
-    for (int m = 0; m < 16; ++m)
-        for (int j = 0; j < 4; ++j) {
-            const double e = v1[nf_cpl_off_E(w) + 4 * m + j];
-            out[NF4_CPL_E + 4 * m + j] = (float)(j >= 2 ? e * k2 : e);
-        }
-    const double sc = v1[nf_cpl_off_S(w)];
-    out[NF4_CPL_S + 0] = (float)sc;
-    out[NF4_CPL_S + 1] = (float)(sc * log2e);
-    out[NF4_CPL_S + 2] = (float)(-2.0 * sc * log2e);
-    out[NF4_CPL_S + 3] = 0.0f;
+    const double k2 = k2Log2e;
+    relayout_ES(v1, w, out + NF4_CPL_E, out + NF4_CPL_S);
     float *img = out + NF4_CPL_IMG;
     memset(img, 0, NF6_IMG_SIZE * sizeof(float));
     const float *W1 = v1 + nf_cpl_off_W1(w), *B1 = v1 + nf_cpl_off_B1(w), *W2 = v1 + nf_cpl_off_W2(w);
@@ -722,17 +673,7 @@ void relayout_coupling_wide16(const float *v1, int w, float *out)
 // v_mfma_f32_32x32x16_f16 (8 halves per lane and instruction) / v_mfma_f32_4x4x4_16b_f16 (centre tap).
 void relayout_coupling_wide32_fp16(const float *v1, int w, float *out)
 {
-    const double k2 = 2.0 * 1.4426950408889634, log2e = 1.4426950408889634;
-    for (int m = 0; m < 16; ++m)
-        for (int j = 0; j < 4; ++j) {
-            const double e = v1[nf_cpl_off_E(w) + 4 * m + j];
-            out[NF4_CPL_E + 4 * m + j] = (float)(j >= 2 ? e * k2 : e);
-        }
-    const double sc = v1[nf_cpl_off_S(w)];
-    out[NF4_CPL_S + 0] = (float)sc;
-    out[NF4_CPL_S + 1] = (float)(sc * log2e);
-    out[NF4_CPL_S + 2] = (float)(-2.0 * sc * log2e);
-    out[NF4_CPL_S + 3] = 0.0f;
+    relayout_ES(v1, w, out + NF4_CPL_E, out + NF4_CPL_S);
     float *img = out + NF4_CPL_IMG;
     memset(img, 0, NF5_IMG_SIZE * sizeof(float));
     uint16_t *h = reinterpret_cast<uint16_t *>(img);   // half index = 2 * dword index
@@ -754,12 +695,7 @@ void relayout_coupling_wide32_fp16(const float *v1, int w, float *out)
             }
         }
     }
-    for (int g = 0; g < 2; ++g)
-        for (int v = 0; v < 16; ++v) {
-            const int ch = nf4_chan(v, g);
-            img[NF5_IMG_B1 + g * 16 + v] = ch < w ? B1[ch] : 0.0f;
-            img[NF5_IMG_B2 + g * 16 + v] = ch < w ? B2[ch] : 0.0f;
-        }
+    bias_tables32(B1, B2, 0, w, img + NF5_IMG_B1, img + NF5_IMG_B2);
     for (int q = 0; q < 4; ++q)
         for (int g = 0; g < 2; ++g)
             for (int j = 0; j < 4; ++j)
@@ -893,31 +829,32 @@ int cond_scalars(const CondLayer &L, const nf_cond *cond, double out[2])
 }
 
 // ---- program construction -----------------------------------------------------
+constexpr int NF_PATH_COUNT = 9;   // the NF_PATH_* values of noiseflow_hip.h index every per-family table of this file
+
+struct Layout {
+    NfProgram prog = {};
+    std::vector<float> block;   // empty: the model has no such layout
+};
+
 struct Built {
     std::vector<CondLayer> cond;   // conditioning slots, in the order the ops reference them
-    NfProgram prog;
-    std::vector<float> block;
-    NfProgram prog2;             // matrix-core (MFMA) layout, width 4 only
-    std::vector<float> block2;   // empty when unavailable
-    NfProgram prog9;             // split-bf16 layout (NF12_*): width 4 in fp32 on full 32x32 patches unless NF_CFG_EXACT_FP32
-    std::vector<float> block9;   // the LDS part (n_lds9 floats), then the couplings' A images
+    // One program + parameter block per kernel family, all the same op sequence:
+    //   NF_PATH_SCALAR       the generic layout every other one is made from (always there)
+    //   NF_PATH_MFMA4        matrix-core layout (NF2_*: j-major weights), width 4 only
+    //   NF_PATH_SPLIT_BF16   NF12_*: width 4 in fp32 on full 32x32 patches unless NF_CFG_EXACT_FP32; the LDS part (n_lds9 floats),
+    //                        then the couplings' A images
+    //   NF_PATH_FP16         fp16-CNN layout (NF_CFG_FP16_CNN), width 4 only
+    //   NF_PATH_WIDE32       wide-CNN layout (NF4_*), width 32 (8 / 16 zero-padded on large patches)
+    //   NF_PATH_WIDE32_FP16  wide-CNN fp16 layout (NF5_*): NF_CFG_FP16_CNN at widths 8 / 16 / 32
+    //   NF_PATH_WIDE16       width-16 layout (NF6_*)
+    //   NF_PATH_GEMM         NF7_*: widths 33 .. 512, zero-padded to 64 / 128 / 256 / 512
+    //   NF_PATH_GEMM_FP16    NF8_*: NF_CFG_FP16_CNN at widths 33 .. 512
+    Layout lay[NF_PATH_COUNT];
     int n_lds9 = 0;
-    NfProgram prog3;             // fp16-CNN layout (NF_CFG_FP16_CNN), width 4 only
-    std::vector<float> block3;
-    bool fp16_big = false;       // block3 is the NF11_* layout (v_mfma_f32_16x16x32_f16) instead of NF3_* (4x4x4)
-    int raw_width = 4;           // coupling width of the model's variables; prog.width is the (zero-padded) width the kernels run
-    NfProgram prog4;             // wide-CNN layout (NF4_*), width 32 (8 / 16 zero-padded on large patches)
-    std::vector<float> block4;
-    NfProgram prog5;             // wide-CNN fp16 layout (NF5_*): NF_CFG_FP16_CNN at widths 8 / 16 / 32
-    std::vector<float> block5;
-    NfProgram prog6;             // width-16 layout (NF6_*)
-    std::vector<float> block6;
-    NfProgram prog7;             // GEMM layout (NF7_*): widths 33 .. 512, zero-padded to 64 / 128 / 256 / 512
-    std::vector<float> block7;
-    bool gemm_b = false;         // block7 is in the variant-B layout (NF10_*: widths <= 128, weights resident in LDS)
-    NfProgram prog8;             // fp16-CNN GEMM layout (NF8_*): NF_CFG_FP16_CNN at widths 33 .. 512
-    std::vector<float> block8;
-    bool gemm16_b = false;       // block8 is in the variant-B layout (NF9_*: widths <= 128)
+    bool fp16_big = false;       // the NF_PATH_FP16 block is the NF11_* layout (v_mfma_f32_16x16x32_f16) instead of NF3_* (4x4x4)
+    int raw_width = 4;           // coupling width of the model's variables; lay[0].prog.width is the (zero-padded) width the kernels run
+    bool gemm_b = false;         // the NF_PATH_GEMM block is in the variant-B layout (NF10_*: widths <= 128, weights resident in LDS)
+    bool gemm16_b = false;       // the NF_PATH_GEMM_FP16 block is in the variant-B layout (NF9_*: widths <= 128)
     double ld_const = 0.0;
     bool has_sdn = false;      // some op reads the clean image y
     // images beyond 64x64 (nf_device.h, NF_K_TILED): the kernels run on overlapping tile_h x tile_w tiles, the program cut
@@ -979,6 +916,32 @@ static int plan_tile_segments(const NfProgram &prog, int H, int W, int th, int t
     return NF_OK;
 }
 
+// One family's program and block from the generic ones — the same op sequence: a 1x1 matrix copied, or stored transposed
+// (`mix_t`: j-major, the width-4 matrix-core kernels), `cpl_floats` reserved per coupling and filled by
+// relayout(the coupling's generic block, its place in the new block), a scale copied, a conditioning slot passed through.
+template <class Relayout>
+void build_layout(const Layout &gen, Layout &out, int width, bool mix_t, size_t cpl_floats, Relayout relayout)
+{
+    out.prog.width = width;
+    for (int i = 0; i < gen.prog.n_ops; ++i) {
+        const NfOp &src = gen.prog.ops[i];
+        NfOp &dst = out.prog.ops[out.prog.n_ops++];
+        dst.type = src.type;
+        dst.off = (int32_t)out.block.size();
+        const float *v1 = gen.block.data() + src.off;
+        if (src.type == NF_OP_MIX) {
+            for (int q = 0; q < 16; ++q) out.block.push_back(mix_t ? v1[(q & 3) * 4 + (q >> 2)] : v1[q]);
+        } else if (src.type == NF_OP_COUPLING_FWD || src.type == NF_OP_COUPLING_REV) {
+            out.block.resize(out.block.size() + cpl_floats);
+            relayout(v1, out.block.data() + dst.off);
+        } else if (src.type == NF_OP_SCALE) {
+            out.block.insert(out.block.end(), v1, v1 + 4);
+        } else {
+            dst.off = src.off;   // conditioning slot
+        }
+    }
+    if (out.block.empty()) out.block.assign(4, 0.0f);
+}
 
 int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params,
                   int direction, Built &out)
@@ -1060,25 +1023,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
             it.type = NF_OP_COUPLING_FWD;
             it.w = wk;
             it.blk.assign(nf_cpl_size(wk), 0.0f);
-            if (wk == L.width) {
-                fold_coupling(p, L.width, it.blk.data());
-            } else {
-                const int w = L.width;
-                std::vector<float> f(nf_cpl_size(w));
-                fold_coupling(p, w, f.data());
-                float *o = it.blk.data();
-                memcpy(o + nf_cpl_off_E(wk), f.data() + nf_cpl_off_E(w), 64 * sizeof(float));
-                for (int tap = 0; tap < 9; ++tap) {
-                    memcpy(o + nf_cpl_off_W3(wk) + tap * wk * 4, f.data() + nf_cpl_off_W3(w) + tap * w * 4, (size_t)w * 4 * sizeof(float));
-                    for (int c = 0; c < 2; ++c)
-                        memcpy(o + nf_cpl_off_W1(wk) + (tap * 2 + c) * wk, f.data() + nf_cpl_off_W1(w) + (tap * 2 + c) * w, (size_t)w * sizeof(float));
-                }
-                memcpy(o + nf_cpl_off_B1(wk), f.data() + nf_cpl_off_B1(w), (size_t)w * sizeof(float));
-                memcpy(o + nf_cpl_off_B2(wk), f.data() + nf_cpl_off_B2(w), (size_t)w * sizeof(float));
-                for (int i = 0; i < w; ++i)
-                    memcpy(o + nf_cpl_off_W2(wk) + i * wk, f.data() + nf_cpl_off_W2(w) + i * w, (size_t)w * sizeof(float));
-                memcpy(o + nf_cpl_off_S(wk), f.data() + nf_cpl_off_S(w), 4 * sizeof(float));
-            }
+            fold_coupling(p, L.width, wk, it.blk.data());
             break;
         }
         case NF_LAYER_SDN5:
@@ -1135,24 +1080,26 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     if (direction == 1) std::vector<Item *>(order.rbegin(), order.rend()).swap(order);
     if (order.size() > NF_MAX_OPS) return fail(NF_EINVAL, "too many layers (%zu > %d)", order.size(), NF_MAX_OPS);
 
-    memset(&out.prog, 0, sizeof(out.prog));
-    out.prog.width = width ? width : 4;
+    for (Layout &l : out.lay) l = Layout();
+    out.n_lds9 = 0;
+    out.fp16_big = out.gemm_b = out.gemm16_b = false;
+    Layout &gen = out.lay[NF_PATH_SCALAR];
+    gen.prog.width = width ? width : 4;
     out.raw_width = raw_width ? raw_width : 4;
-    out.block.clear();
     for (Item *it : order) {
-        NfOp &op = out.prog.ops[out.prog.n_ops++];
-        op.off = (int32_t)out.block.size();
+        NfOp &op = gen.prog.ops[gen.prog.n_ops++];
+        op.off = (int32_t)gen.block.size();
         switch (it->type) {
         case NF_OP_MIX: {
             op.type = NF_OP_MIX;
             const Mat4 &M = direction == 0 ? it->A : it->Ainv;
             for (int r = 0; r < 4; ++r)
-                for (int c = 0; c < 4; ++c) out.block.push_back((float)M.m[r][c]);
+                for (int c = 0; c < 4; ++c) gen.block.push_back((float)M.m[r][c]);
             break;
         }
         case NF_OP_COUPLING_FWD:
             op.type = direction == 0 ? NF_OP_COUPLING_FWD : NF_OP_COUPLING_REV;
-            out.block.insert(out.block.end(), it->blk.begin(), it->blk.end());
+            gen.block.insert(gen.block.end(), it->blk.begin(), it->blk.end());
             break;
         case NF_OP_SDN_DIV:
             op.type = direction == 0 ? NF_OP_SDN_DIV : NF_OP_SDN_MUL;
@@ -1165,205 +1112,79 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
         case NF_OP_SCALE: {
             op.type = NF_OP_SCALE;
             const double s = direction == 0 ? 1.0 / it->scale : it->scale;
-            out.block.push_back((float)s);
-            out.block.push_back(0.f);
-            out.block.push_back(0.f);
-            out.block.push_back(0.f);
+            gen.block.push_back((float)s);
+            gen.block.push_back(0.f);
+            gen.block.push_back(0.f);
+            gen.block.push_back(0.f);
             break;
         }
         }
     }
-    if (out.block.empty()) out.block.assign(4, 0.0f);
+    if (gen.block.empty()) gen.block.assign(4, 0.0f);
 
-    // matrix-core re-layout (same op sequence, j-major weights), when the model qualifies
-    out.block2.clear();
-    memset(&out.prog2, 0, sizeof(out.prog2));
-    if (out.prog.width == 4) {
-        out.prog2.width = 4;
-        for (int i = 0; i < out.prog.n_ops; ++i) {
-            const NfOp &src = out.prog.ops[i];
-            NfOp &dst = out.prog2.ops[out.prog2.n_ops++];
-            dst.type = src.type;
-            dst.off = (int32_t)out.block2.size();
-            const float *v1 = out.block.data() + src.off;
-            if (src.type == NF_OP_MIX) {
-                for (int j = 0; j < 4; ++j)
-                    for (int c = 0; c < 4; ++c) out.block2.push_back(v1[c * 4 + j]);
-            } else if (src.type == NF_OP_COUPLING_FWD || src.type == NF_OP_COUPLING_REV) {
-                out.block2.resize(out.block2.size() + NF2_CPL_SIZE);
-                relayout_coupling_v2(v1, out.block2.data() + dst.off);
-            } else if (src.type == NF_OP_SCALE) {
-                out.block2.insert(out.block2.end(), v1, v1 + 4);
-            } else {
-                dst.off = src.off;   // conditioning slot
-            }
-        }
-        if (out.block2.empty()) out.block2.assign(4, 0.0f);
-        if (out.block2.size() > NF2_MAX_FLOATS) out.block2.clear();   // too large for LDS: scalar path only
+    // Every other family, where the model qualifies: the condition under which its layout exists, then build_layout
+    const int w = gen.prog.width;
+    const bool fp16_cnn = (cfg->flags & NF_CFG_FP16_CNN) != 0;
+    // matrix-core re-layout (j-major weights)
+    Layout &mfma4 = out.lay[NF_PATH_MFMA4];
+    if (w == 4) {
+        build_layout(gen, mfma4, 4, true, NF2_CPL_SIZE, relayout_coupling_v2);
+        if (mfma4.block.size() > NF2_MAX_FLOATS) mfma4.block.clear();   // too large for LDS: scalar path only
     }
     // split-bf16 layout: the default kernel of the fp32 width-4 model on full 32x32 patches
-    out.block9.clear();
-    out.n_lds9 = 0;
-    memset(&out.prog9, 0, sizeof(out.prog9));
-    if (out.prog.width == 4 && !out.block2.empty() && cfg->height == 32 && cfg->width == 32 &&
-        !(cfg->flags & (NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32))) {
-        out.prog9.width = 4;
+    if (w == 4 && !mfma4.block.empty() && cfg->height == 32 && cfg->width == 32 && !(cfg->flags & (NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32))) {
+        Layout &split = out.lay[NF_PATH_SPLIT_BF16];
         std::vector<uint32_t> img;
         std::vector<int> aoff_at;   // LDS-part offsets of the couplings' AOFF fields
-        for (int i = 0; i < out.prog.n_ops; ++i) {
-            const NfOp &src = out.prog.ops[i];
-            NfOp &dst = out.prog9.ops[out.prog9.n_ops++];
-            dst.type = src.type;
-            dst.off = (int32_t)out.block9.size();
-            const float *v1 = out.block.data() + src.off;
-            if (src.type == NF_OP_MIX) {
-                for (int j = 0; j < 4; ++j)
-                    for (int c = 0; c < 4; ++c) out.block9.push_back(v1[c * 4 + j]);
-            } else if (src.type == NF_OP_COUPLING_FWD || src.type == NF_OP_COUPLING_REV) {
-                out.block9.resize(out.block9.size() + NF12_CPL_SIZE);
-                img.resize(img.size() + NF12_A_SIZE);
-                relayout_coupling_v12(v1, out.block9.data() + dst.off, img.data() + img.size() - NF12_A_SIZE);
-                aoff_at.push_back(dst.off + NF12_CPL_AOFF);
-            } else if (src.type == NF_OP_SCALE) {
-                out.block9.insert(out.block9.end(), v1, v1 + 4);
-            } else {
-                dst.off = src.off;   // conditioning slot
-            }
-        }
-        if (out.block9.empty()) out.block9.assign(4, 0.0f);
-        out.n_lds9 = (int)out.block9.size();   // a multiple of 4: every section is
+        build_layout(gen, split, 4, true, NF12_CPL_SIZE, [&](const float *v1, float *o) {
+            img.resize(img.size() + NF12_A_SIZE);
+            relayout_coupling_v12(v1, o, img.data() + img.size() - NF12_A_SIZE);
+            aoff_at.push_back((int)(o - split.block.data()) + NF12_CPL_AOFF);
+        });
+        out.n_lds9 = (int)split.block.size();   // a multiple of 4: every section is
         for (size_t c = 0; c < aoff_at.size(); ++c) {
             const int32_t off = out.n_lds9 + (int32_t)(c * NF12_A_SIZE);
-            memcpy(out.block9.data() + aoff_at[c], &off, 4);
+            memcpy(split.block.data() + aoff_at[c], &off, 4);
         }
-        const size_t n0 = out.block9.size();
-        out.block9.resize(n0 + img.size());
-        if (!img.empty()) memcpy(out.block9.data() + n0, img.data(), img.size() * 4);
-        // Not reachable today: this layout exists only where block2 fits NF2_MAX_FLOATS (above), an op costs here at most what it
+        const size_t n0 = split.block.size();
+        split.block.resize(n0 + img.size());
+        if (!img.empty()) memcpy(split.block.data() + n0, img.data(), img.size() * 4);
+        // Not reachable today: this layout exists only where the NF_PATH_MFMA4 block fits NF2_MAX_FLOATS (above), an op costs here at most what it
         // costs there, and a coupling 96 floats against 332 — with c couplings, m mixes (m <= c) and s scales in NF_MAX_OPS = 64
         // ops, 332 c + 16 m + 4 s <= 6144 gives c <= 17 (18 without mixes) and 96 c + 16 m + 4 s <= 2024 (tests/test_split_bf16.py
         // finds the boundary through nf_fold_layout for flow_permutation 0 / 1 / 2).  Kept as the guard of the kernel's LDS budget
         // should either limit or a section size change.
         if (out.n_lds9 > NF12_MAX_FLOATS) {   // LDS image too large for 4 workgroups per CU: the exact-fp32 kernel
-            out.block9.clear();
+            split.block.clear();
             out.n_lds9 = 0;
         }
     }
-    out.block4.clear();
-    memset(&out.prog4, 0, sizeof(out.prog4));
     // width 32: the product path; width 8 only where the scalar-weight kernel's LDS tile does not fit (patches larger
-    // than 48x48): zero-padded to 32 channels.  Width 16 has its own kernel (prog6).
-    {
-        const size_t tile_px = ((size_t)(th + 2) * (tw + 2) + 1) & ~(size_t)1;
-        const bool scalar_fits = sizeof(float) * (tile_px * (2 + (size_t)out.prog.width) + 64) <= 160 * 1024;
-        if (out.prog.width == 32 || (out.prog.width == 8 && !scalar_fits)) out.prog4.width = 32;
-        // tiled images (nf_device.h): width 8 runs zero-padded on the width-32 kernel; width 16 on its own (fp32; its fp16-CNN
-        // mode is the width-32 fp16 kernel's, tiled or not)
-        if (out.tiled && out.prog.width == 8) out.prog4.width = 32;
+    // than 48x48): zero-padded to 32 channels.  Width 16 has its own kernel (NF_PATH_WIDE16).
+    // tiled images (nf_device.h): width 8 runs zero-padded on the width-32 kernel; width 16 on its own (fp32; its fp16-CNN
+    // mode is the width-32 fp16 kernel's, tiled or not)
+    const size_t tile_px = ((size_t)(th + 2) * (tw + 2) + 1) & ~(size_t)1;
+    const bool scalar_fits = sizeof(float) * (tile_px * (2 + (size_t)w) + 64) <= 160 * 1024;
+    if (w == 32 || (w == 8 && !scalar_fits) || (out.tiled && w == 8))
+        build_layout(gen, out.lay[NF_PATH_WIDE32], 32, false, NF4_CPL_SIZE, [&](const float *v1, float *o) { relayout_coupling_wide32(v1, w, o); });
+    if (w == 16)
+        build_layout(gen, out.lay[NF_PATH_WIDE16], 16, false, NF6_CPL_SIZE, [&](const float *v1, float *o) { relayout_coupling_wide16(v1, w, o); });
+    if (w > 32 && fp16_cnn) {
+        const int wp = nf7_pad_width(w);
+        // variant B (weights resident in LDS, pixel tiles per wavefront) where its slabs fit: widths <= 128; NF_GEMM16=a: A/B aid
+        const char *e = getenv("NF_GEMM16");
+        const bool vb = out.gemm16_b = nf_gemm16b_shape_ok(wp, th, tw) && !(e && e[0] == 'a');
+        build_layout(gen, out.lay[NF_PATH_GEMM_FP16], wp, false, vb ? nf9_cpl_size(wp) : nf8_cpl_size(wp),
+                     [&](const float *v1, float *o) { vb ? relayout_coupling_gemm16b(v1, w, wp, o) : relayout_coupling_gemm16(v1, w, wp, o); });
     }
-    if (out.prog4.width == 32) {
-        for (int i = 0; i < out.prog.n_ops; ++i) {
-            const NfOp &src = out.prog.ops[i];
-            NfOp &dst = out.prog4.ops[out.prog4.n_ops++];
-            dst.type = src.type;
-            dst.off = (int32_t)out.block4.size();
-            const float *v1 = out.block.data() + src.off;
-            if (src.type == NF_OP_MIX) {
-                out.block4.insert(out.block4.end(), v1, v1 + 16);
-            } else if (src.type == NF_OP_COUPLING_FWD || src.type == NF_OP_COUPLING_REV) {
-                out.block4.resize(out.block4.size() + NF4_CPL_SIZE);
-                relayout_coupling_wide32(v1, out.prog.width, out.block4.data() + dst.off);
-            } else if (src.type == NF_OP_SCALE) {
-                out.block4.insert(out.block4.end(), v1, v1 + 4);
-            } else {
-                dst.off = src.off;   // conditioning slot
-            }
-        }
-        if (out.block4.empty()) out.block4.assign(4, 0.0f);
+    if (w > 32 && !fp16_cnn) {
+        const int wp = nf7_pad_width(w);
+        // variant B where its slabs fit beside the patch's tiles; NF_GEMM=a: A/B aid
+        const char *e = getenv("NF_GEMM");
+        const bool vb = out.gemm_b = nf_gemmb_shape_ok(wp, th, tw) && !(e && e[0] == 'a');
+        build_layout(gen, out.lay[NF_PATH_GEMM], wp, false, vb ? nf10_cpl_size(wp) : nf7_cpl_size(wp),
+                     [&](const float *v1, float *o) { vb ? relayout_coupling_gemmb(v1, w, wp, o) : relayout_coupling_gemm(v1, w, wp, o); });
     }
-    out.block6.clear();
-    memset(&out.prog6, 0, sizeof(out.prog6));
-    if (out.prog.width == 16) {
-        out.prog6.width = 16;
-        for (int i = 0; i < out.prog.n_ops; ++i) {
-            const NfOp &src = out.prog.ops[i];
-            NfOp &dst = out.prog6.ops[out.prog6.n_ops++];
-            dst.type = src.type;
-            dst.off = (int32_t)out.block6.size();
-            const float *v1 = out.block.data() + src.off;
-            if (src.type == NF_OP_MIX) {
-                out.block6.insert(out.block6.end(), v1, v1 + 16);
-            } else if (src.type == NF_OP_COUPLING_FWD || src.type == NF_OP_COUPLING_REV) {
-                out.block6.resize(out.block6.size() + NF6_CPL_SIZE);
-                relayout_coupling_wide16(v1, out.prog.width, out.block6.data() + dst.off);
-            } else if (src.type == NF_OP_SCALE) {
-                out.block6.insert(out.block6.end(), v1, v1 + 4);
-            } else {
-                dst.off = src.off;   // conditioning slot
-            }
-        }
-        if (out.block6.empty()) out.block6.assign(4, 0.0f);
-    }
-    out.block8.clear();
-    memset(&out.prog8, 0, sizeof(out.prog8));
-    if (out.prog.width > 32 && (cfg->flags & NF_CFG_FP16_CNN)) {
-        const int wp = nf7_pad_width(out.prog.width);
-        out.prog8.width = wp;
-        {   // variant B (weights resident in LDS, pixel tiles per wavefront) where its slabs fit: widths <= 128; NF_GEMM16=a: A/B aid
-            const char *e = getenv("NF_GEMM16");
-            out.gemm16_b = nf_gemm16b_shape_ok(wp, th, tw) && !(e && e[0] == 'a');
-        }
-        for (int i = 0; i < out.prog.n_ops; ++i) {
-            const NfOp &src = out.prog.ops[i];
-            NfOp &dst = out.prog8.ops[out.prog8.n_ops++];
-            dst.type = src.type;
-            dst.off = (int32_t)out.block8.size();
-            const float *v1 = out.block.data() + src.off;
-            if (src.type == NF_OP_MIX) {
-                out.block8.insert(out.block8.end(), v1, v1 + 16);
-            } else if (src.type == NF_OP_COUPLING_FWD || src.type == NF_OP_COUPLING_REV) {
-                out.block8.resize(out.block8.size() + (out.gemm16_b ? nf9_cpl_size(wp) : nf8_cpl_size(wp)));
-                if (out.gemm16_b) relayout_coupling_gemm16b(v1, out.prog.width, wp, out.block8.data() + dst.off);
-                else relayout_coupling_gemm16(v1, out.prog.width, wp, out.block8.data() + dst.off);
-            } else if (src.type == NF_OP_SCALE) {
-                out.block8.insert(out.block8.end(), v1, v1 + 4);
-            } else {
-                dst.off = src.off;   // conditioning slot
-            }
-        }
-        if (out.block8.empty()) out.block8.assign(4, 0.0f);
-    }
-    out.block7.clear();
-    memset(&out.prog7, 0, sizeof(out.prog7));
-    if (out.prog.width > 32 && !(cfg->flags & NF_CFG_FP16_CNN)) {
-        const int wp = nf7_pad_width(out.prog.width);
-        out.prog7.width = wp;
-        {   // variant B where its slabs fit beside the patch's tiles; NF_GEMM=a: A/B aid
-            const char *e = getenv("NF_GEMM");
-            out.gemm_b = nf_gemmb_shape_ok(wp, th, tw) && !(e && e[0] == 'a');
-        }
-        for (int i = 0; i < out.prog.n_ops; ++i) {
-            const NfOp &src = out.prog.ops[i];
-            NfOp &dst = out.prog7.ops[out.prog7.n_ops++];
-            dst.type = src.type;
-            dst.off = (int32_t)out.block7.size();
-            const float *v1 = out.block.data() + src.off;
-            if (src.type == NF_OP_MIX) {
-                out.block7.insert(out.block7.end(), v1, v1 + 16);
-            } else if (src.type == NF_OP_COUPLING_FWD || src.type == NF_OP_COUPLING_REV) {
-                out.block7.resize(out.block7.size() + (out.gemm_b ? nf10_cpl_size(wp) : nf7_cpl_size(wp)));
-                if (out.gemm_b) relayout_coupling_gemmb(v1, out.prog.width, wp, out.block7.data() + dst.off);
-                else relayout_coupling_gemm(v1, out.prog.width, wp, out.block7.data() + dst.off);
-            } else if (src.type == NF_OP_SCALE) {
-                out.block7.insert(out.block7.end(), v1, v1 + 4);
-            } else {
-                dst.off = src.off;   // conditioning slot
-            }
-        }
-        if (out.block7.empty()) out.block7.assign(4, 0.0f);
-    }
-    out.block5.clear();
-    memset(&out.prog5, 0, sizeof(out.prog5));
     // width 4 has its own fp16 kernel for the two full shapes (nf_kernels.hip); on any other shape it runs here, zero-padded
     // to 32 channels (exact: same rounding points, a padded channel is identically zero)
     // NF_H16=4x4 (read at nf_create) keeps the v_mfma_f32_4x4x4_16b_f16 formulation of the width-4 fp16 kernel — an A/B aid
@@ -1371,60 +1192,20 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     // width 4 in fp16-CNN mode has its own kernel for full 32x32 / 64x64 patches — and, on v_mfma_f32_16x16x32_f16, for images
     // tiled into full 64x64 tiles; everything else rides the width-32 fp16 kernel zero-padded
     const bool w4_full = ((th == 32 && tw == 32) || (th == 64 && tw == 64)) && (!out.tiled || (fp16_big && th == 64 && tw == 64));
-    if ((cfg->flags & NF_CFG_FP16_CNN) &&
-        (out.prog.width == 8 || out.prog.width == 16 || out.prog.width == 32 || (out.prog.width == 4 && !w4_full))) {
-        out.prog5.width = 32;
-        for (int i = 0; i < out.prog.n_ops; ++i) {
-            const NfOp &src = out.prog.ops[i];
-            NfOp &dst = out.prog5.ops[out.prog5.n_ops++];
-            dst.type = src.type;
-            dst.off = (int32_t)out.block5.size();
-            const float *v1 = out.block.data() + src.off;
-            if (src.type == NF_OP_MIX) {
-                out.block5.insert(out.block5.end(), v1, v1 + 16);
-            } else if (src.type == NF_OP_COUPLING_FWD || src.type == NF_OP_COUPLING_REV) {
-                out.block5.resize(out.block5.size() + NF5_CPL_SIZE);
-                relayout_coupling_wide32_fp16(v1, out.prog.width, out.block5.data() + dst.off);
-            } else if (src.type == NF_OP_SCALE) {
-                out.block5.insert(out.block5.end(), v1, v1 + 4);
-            } else {
-                dst.off = src.off;   // conditioning slot
-            }
-        }
-        if (out.block5.empty()) out.block5.assign(4, 0.0f);
-    }
-    out.block3.clear();
-    memset(&out.prog3, 0, sizeof(out.prog3));
-    if (out.prog.width == 4 && (cfg->flags & NF_CFG_FP16_CNN)) {
-        out.prog3.width = 4;
+    if (fp16_cnn && (w == 8 || w == 16 || w == 32 || (w == 4 && !w4_full)))
+        build_layout(gen, out.lay[NF_PATH_WIDE32_FP16], 32, false, NF5_CPL_SIZE, [&](const float *v1, float *o) { relayout_coupling_wide32_fp16(v1, w, o); });
+    if (w == 4 && fp16_cnn) {
         out.fp16_big = fp16_big;
-        for (int i = 0; i < out.prog.n_ops; ++i) {
-            const NfOp &src = out.prog.ops[i];
-            NfOp &dst = out.prog3.ops[out.prog3.n_ops++];
-            dst.type = src.type;
-            dst.off = (int32_t)out.block3.size();
-            const float *v1 = out.block.data() + src.off;
-            if (src.type == NF_OP_MIX) {
-                for (int j = 0; j < 4; ++j)
-                    for (int c = 0; c < 4; ++c) out.block3.push_back(v1[c * 4 + j]);
-            } else if (src.type == NF_OP_COUPLING_FWD || src.type == NF_OP_COUPLING_REV) {
-                // 64x64 patches / tiles: l_2's operands for v_mfma_f32_16x16x32_f16 ride along (NF11_CPL_A2)
-                const bool with_a2 = th == 64 && tw == 64;
-                out.block3.resize(out.block3.size() + (out.fp16_big ? (with_a2 ? NF11_CPL_SIZE_L2 : NF11_CPL_SIZE) : NF3_CPL_SIZE));
-                if (out.fp16_big) relayout_coupling_v11(v1, out.block3.data() + dst.off, with_a2);
-                else relayout_coupling_v3(v1, out.block3.data() + dst.off);
-            } else if (src.type == NF_OP_SCALE) {
-                out.block3.insert(out.block3.end(), v1, v1 + 4);
-            } else {
-                dst.off = src.off;   // conditioning slot
-            }
-        }
-        if (out.block3.empty()) out.block3.assign(4, 0.0f);
-        if (out.block3.size() > (size_t)(out.fp16_big ? NF11_MAX_FLOATS : NF2_MAX_FLOATS)) return fail(NF_EINVAL, "model too large for the fp16-CNN LDS image");
+        // 64x64 patches / tiles: l_2's operands for v_mfma_f32_16x16x32_f16 ride along (NF11_CPL_A2)
+        const bool with_a2 = th == 64 && tw == 64;
+        Layout &fp16 = out.lay[NF_PATH_FP16];
+        build_layout(gen, fp16, 4, true, fp16_big ? (with_a2 ? NF11_CPL_SIZE_L2 : NF11_CPL_SIZE) : NF3_CPL_SIZE,
+                     [&](const float *v1, float *o) { fp16_big ? relayout_coupling_v11(v1, o, with_a2) : relayout_coupling_v3(v1, o); });
+        if (fp16.block.size() > (size_t)(fp16_big ? NF11_MAX_FLOATS : NF2_MAX_FLOATS)) return fail(NF_EINVAL, "model too large for the fp16-CNN LDS image");
     }
     if (out.tiled) {
         // every coupling widens the dependence of a pixel by 2 (3x3, 1x1, 3x3): nf_device.h, "overlapping tiles"
-        int rc = plan_tile_segments(out.prog, cfg->height, cfg->width, th, tw, out.segs);
+        int rc = plan_tile_segments(gen.prog, cfg->height, cfg->width, th, tw, out.segs);
         if (rc != NF_OK) return rc;
     }
     return NF_OK;
@@ -1437,10 +1218,11 @@ int grad_support(const nf_config *cfg, const Built &fwd)
     if (cfg->flags & NF_CFG_FP16_CNN) return fail(NF_EINVAL, "nf_nll_grad: fp32 handles only (NF_CFG_FP16_CNN is set)");
     if (cfg->height > 64 || cfg->width > 64)
         return fail(NF_EINVAL, "nf_nll_grad: patches of up to 64x64 (%dx%d given; no tiled evaluation)", cfg->height, cfg->width);
-    const int w = fwd.prog.width, hw = cfg->height * cfg->width;
+    const NfProgram &prog = fwd.lay[NF_PATH_SCALAR].prog;
+    const int w = prog.width, hw = cfg->height * cfg->width;
     if (w > 32) return fail(NF_EINVAL, "nf_nll_grad: coupling widths up to 32 (%d given; the GEMM families have no gradient kernel)", fwd.raw_width);
     int n_cpl = 0;
-    for (int i = 0; i < fwd.prog.n_ops; ++i) n_cpl += fwd.prog.ops[i].type == NF_OP_COUPLING_FWD ? 1 : 0;
+    for (int i = 0; i < prog.n_ops; ++i) n_cpl += prog.ops[i].type == NF_OP_COUPLING_FWD ? 1 : 0;
     // registers: beyond 32x32 a lane of the 1 024-thread workgroup holds 4 pixels inside 128 VGPRs.  No width fits that without
     // scratch (width 4 spills 167 VGPRs, width 8 269: both run, slower); widths 16 and 32 would keep most of their hidden
     // vectors in scratch and are refused.  Width 32 keeps one pixel per lane (12 spilled VGPRs at 1 024 threads)
@@ -1456,7 +1238,8 @@ int grad_support(const nf_config *cfg, const Built &fwd)
 
 // The gradient block (nf_device.h, NfGradLaunch): the NLL-order generic block with A^-1 beside every 1x1 matrix — op i of
 // the NLL program is op n - 1 - i of the sampling program, whose block holds the inverse — and 1/s beside every scale.
-void build_grad_block(const Built &fwd, const Built &rev, NfProgram &gp, std::vector<float> &blk, int &n_cpl, int &first_cpl)
+// (`fwd`, `rev` = the generic layouts of the two directions)
+void build_grad_block(const Layout &fwd, const Layout &rev, NfProgram &gp, std::vector<float> &blk, int &n_cpl, int &first_cpl)
 {
     memset(&gp, 0, sizeof(gp));
     gp.width = fwd.prog.width;
@@ -1487,6 +1270,25 @@ void build_grad_block(const Built &fwd, const Built &rev, NfProgram &gp, std::ve
         }
     }
     if (blk.empty()) blk.assign(4, 0.0f);
+}
+
+// a layout through the C ABI (nf_fold_params, nf_fold_layout): sizes always, contents where the caller gave room
+int export_layout(const Layout &l, int32_t *ops_out, int32_t ops_cap, int32_t *n_ops, float *folded, size_t folded_cap, size_t *n_folded)
+{
+    if (n_ops) *n_ops = l.prog.n_ops;
+    if (n_folded) *n_folded = l.block.size();
+    if (ops_out) {
+        if (ops_cap < l.prog.n_ops) return fail(NF_EINVAL, "ops_cap too small");
+        for (int i = 0; i < l.prog.n_ops; ++i) {
+            ops_out[2 * i] = l.prog.ops[i].type;
+            ops_out[2 * i + 1] = l.prog.ops[i].off;
+        }
+    }
+    if (folded) {
+        if (folded_cap < l.block.size()) return fail(NF_EINVAL, "folded_cap too small");
+        memcpy(folded, l.block.data(), l.block.size() * sizeof(float));
+    }
+    return NF_OK;
 }
 
 // NF_KERNEL=valu forces the scalar-weight VALU kernel (A/B testing); default = matrix core
@@ -1541,25 +1343,8 @@ struct nf_handle {
     int device = 0;
     int n_cu = 256;
     Built fwd, rev;
-    float *d_fwd = nullptr;
-    float *d_rev = nullptr;
-    float *d_fwd2 = nullptr;   // matrix-core layout (null when unavailable)
-    float *d_rev2 = nullptr;
-    float *d_fwd9 = nullptr;   // split-bf16 layout (NF12_*)
-    float *d_rev9 = nullptr;
-    float *d_fwd3 = nullptr;   // fp16-CNN layout (NF_CFG_FP16_CNN)
-    float *d_rev3 = nullptr;
-    float *d_fwd4 = nullptr;   // wide-CNN layout (width 32)
-    float *d_rev4 = nullptr;
-    float *d_fwd5 = nullptr;   // wide-CNN fp16 layout
-    float *d_rev5 = nullptr;
-    float *d_fwd6 = nullptr;   // width-16 layout
-    float *d_rev6 = nullptr;
-    float *d_fwd7 = nullptr;   // GEMM layout (widths 33 .. 512)
-    float *d_rev7 = nullptr;
-    float *d_fwd8 = nullptr;   // fp16-CNN GEMM layout
-    float *d_rev8 = nullptr;
-    bool scalar_ok = true;     // the scalar-weight kernel's LDS tiles fit this patch shape / width
+    float *d_lay[2][NF_PATH_COUNT] = {};   // [direction][NF_PATH_*]: the layouts' blocks on the device (null: the model has none)
+    bool scalar_ok = true;    // the scalar-weight kernel's LDS tiles fit this patch shape / width
     // nf_nll_grad: its program and block (nf_device.h, NfGradLaunch), or why this handle has none (grad_support)
     NfProgram gprog;
     float *d_grad = nullptr;
@@ -1618,21 +1403,8 @@ int nf_fold_params(const nf_config *cfg, const nf_layer_desc *layers, const floa
     Built b;
     int rc = build_program(cfg, layers, params, n_params, direction, b);
     if (rc != NF_OK) return rc;
-    if (n_ops) *n_ops = b.prog.n_ops;
-    if (n_folded) *n_folded = b.block.size();
     if (ld_const) *ld_const = b.ld_const;
-    if (ops_out) {
-        if (ops_cap < b.prog.n_ops) return fail(NF_EINVAL, "ops_cap too small");
-        for (int i = 0; i < b.prog.n_ops; ++i) {
-            ops_out[2 * i] = b.prog.ops[i].type;
-            ops_out[2 * i + 1] = b.prog.ops[i].off;
-        }
-    }
-    if (folded) {
-        if (folded_cap < b.block.size()) return fail(NF_EINVAL, "folded_cap too small");
-        memcpy(folded, b.block.data(), b.block.size() * sizeof(float));
-    }
-    return NF_OK;
+    return export_layout(b.lay[NF_PATH_SCALAR], ops_out, ops_cap, n_ops, folded, folded_cap, n_folded);
 }
 
 int nf_fold_layout(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params, int32_t direction,
@@ -1643,36 +1415,11 @@ int nf_fold_layout(const nf_config *cfg, const nf_layer_desc *layers, const floa
     Built b;
     int rc = build_program(cfg, layers, params, n_params, direction, b);
     if (rc != NF_OK) return rc;
-    const NfProgram *pg = nullptr;
-    const std::vector<float> *blk = nullptr;
-    switch (path) {
-    case NF_PATH_SCALAR: pg = &b.prog; blk = &b.block; break;
-    case NF_PATH_MFMA4: pg = &b.prog2; blk = &b.block2; break;
-    case NF_PATH_FP16: pg = &b.prog3; blk = &b.block3; break;
-    case NF_PATH_WIDE32: pg = &b.prog4; blk = &b.block4; break;
-    case NF_PATH_WIDE32_FP16: pg = &b.prog5; blk = &b.block5; break;
-    case NF_PATH_WIDE16: pg = &b.prog6; blk = &b.block6; break;
-    case NF_PATH_GEMM: pg = &b.prog7; blk = &b.block7; break;
-    case NF_PATH_GEMM_FP16: pg = &b.prog8; blk = &b.block8; break;
-    case NF_PATH_SPLIT_BF16: pg = &b.prog9; blk = &b.block9; break;
-    default: return fail(NF_EINVAL, "unknown kernel path %d", path);
-    }
-    if (blk->empty()) return fail(NF_EINVAL, "this model has no parameter block for kernel path %d", path);
-    if (n_ops) *n_ops = pg->n_ops;
-    if (layout_width) *layout_width = pg->width;
-    if (n_folded) *n_folded = blk->size();
-    if (ops_out) {
-        if (ops_cap < pg->n_ops) return fail(NF_EINVAL, "ops_cap too small");
-        for (int i = 0; i < pg->n_ops; ++i) {
-            ops_out[2 * i] = pg->ops[i].type;
-            ops_out[2 * i + 1] = pg->ops[i].off;
-        }
-    }
-    if (folded) {
-        if (folded_cap < blk->size()) return fail(NF_EINVAL, "folded_cap too small");
-        memcpy(folded, blk->data(), blk->size() * sizeof(float));
-    }
-    return NF_OK;
+    if (path < 0 || path >= NF_PATH_COUNT) return fail(NF_EINVAL, "unknown kernel path %d", path);
+    const Layout &l = b.lay[path];
+    if (l.block.empty()) return fail(NF_EINVAL, "this model has no parameter block for kernel path %d", path);
+    if (layout_width) *layout_width = l.prog.width;
+    return export_layout(l, ops_out, ops_cap, n_ops, folded, folded_cap, n_folded);
 }
 
 int nf_split_run_info(const int32_t *ops, int32_t n_ops, const float *block, size_t n_block, int32_t out[8])
@@ -1717,11 +1464,13 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
     h->raw.assign(params, params + n_params);
     {   // the two LDS tiles of the scalar-weight kernel must fit one CU (160 KiB)
         const size_t tile_px = ((size_t)(h->fwd.tile_h + 2) * (h->fwd.tile_w + 2) + 1) & ~(size_t)1;
-        const size_t lds = sizeof(float) * (tile_px * (2 + (size_t)h->fwd.prog.width) + 64);
-        h->scalar_ok = lds <= 160 * 1024 && h->fwd.prog.width <= 32;
-        if (lds > 160 * 1024 && h->fwd.block2.empty() && h->fwd.block4.empty() && h->fwd.block5.empty() && h->fwd.block6.empty() &&
-            h->fwd.block7.empty() && h->fwd.block8.empty()) {
-            const int w = h->fwd.prog.width;
+        const int w = h->fwd.lay[NF_PATH_SCALAR].prog.width;
+        const size_t lds = sizeof(float) * (tile_px * (2 + (size_t)w) + 64);
+        h->scalar_ok = lds <= 160 * 1024 && w <= 32;
+        bool other = false;   // a family that takes the patch instead (NF_PATH_FP16 and NF_PATH_SPLIT_BF16 are not asked)
+        for (int p : {NF_PATH_MFMA4, NF_PATH_WIDE32, NF_PATH_WIDE32_FP16, NF_PATH_WIDE16, NF_PATH_GEMM, NF_PATH_GEMM_FP16})
+            other = other || !h->fwd.lay[p].block.empty();
+        if (lds > 160 * 1024 && !other) {
             delete h;
             return fail(NF_EINVAL, "a %dx%d patch with coupling width %d needs %zu KiB of LDS (> 160): unsupported",
                         cfg->height, cfg->width, w, lds / 1024);
@@ -1745,43 +1494,30 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
         return fail_hip(e, "hipDeviceGetAttribute");
     }
     h->n_cu = n_cu > 0 ? n_cu : 256;
-    const size_t nb_f = h->fwd.block.size() * sizeof(float), nb_r = h->rev.block.size() * sizeof(float);
-    if ((e = hipMalloc((void **)&h->d_fwd, nb_f)) != hipSuccess || (e = hipMalloc((void **)&h->d_rev, nb_r)) != hipSuccess) {
-        if (h->d_fwd) (void)hipFree(h->d_fwd);
-        delete h;
-        return fail_hip(e, "hipMalloc(params)");
-    }
-    if ((e = hipMemcpy(h->d_fwd, h->fwd.block.data(), nb_f, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(h->d_rev, h->rev.block.data(), nb_r, hipMemcpyHostToDevice)) != hipSuccess) {
-        (void)hipFree(h->d_fwd);
-        (void)hipFree(h->d_rev);
-        delete h;
-        return fail_hip(e, "hipMemcpy(params)");
-    }
     if (cfg->flags & NF_CFG_FP16_CNN) {
         const int hw = cfg->height * cfg->width;
-        const bool w4_ok = !h->fwd.block3.empty() && ((cfg->height == 32 && cfg->width == 32) || (cfg->height == 64 && cfg->width == 64) ||
-                                                      (h->fwd.tiled && h->fwd.fp16_big && h->fwd.tile_h == 64 && h->fwd.tile_w == 64));
-        if ((!w4_ok && h->fwd.block5.empty() && h->fwd.block8.empty()) || hw == 0) {
-            nf_destroy(h);   // the scalar-layout blocks are already on the device
+        const bool w4_ok = !h->fwd.lay[NF_PATH_FP16].block.empty() &&
+                           ((cfg->height == 32 && cfg->width == 32) || (cfg->height == 64 && cfg->width == 64) ||
+                            (h->fwd.tiled && h->fwd.fp16_big && h->fwd.tile_h == 64 && h->fwd.tile_w == 64));
+        if ((!w4_ok && h->fwd.lay[NF_PATH_WIDE32_FP16].block.empty() && h->fwd.lay[NF_PATH_GEMM_FP16].block.empty()) || hw == 0) {
+            nf_destroy(h);
             return fail(NF_EINVAL, "NF_CFG_FP16_CNN: no half-precision kernel for this width / patch shape");
         }
     }
-    for (int d = 0; d < 16; ++d) {
-        const std::vector<float> &b2 = d == 14 ? h->fwd.block9 : d == 15 ? h->rev.block9 : d == 0 ? h->fwd.block2 : d == 1 ? h->rev.block2 : d == 2 ? h->fwd.block3 : d == 3 ? h->rev.block3
-                                       : d == 4 ? h->fwd.block4 : d == 5 ? h->rev.block4 : d == 6 ? h->fwd.block5 : d == 7 ? h->rev.block5
-                                       : d == 8 ? h->fwd.block6 : d == 9 ? h->rev.block6 : d == 10 ? h->fwd.block7 : d == 11 ? h->rev.block7
-                                       : d == 12 ? h->fwd.block8 : h->rev.block8;
-        float **dst = d == 14 ? &h->d_fwd9 : d == 15 ? &h->d_rev9 : d == 0 ? &h->d_fwd2 : d == 1 ? &h->d_rev2 : d == 2 ? &h->d_fwd3 : d == 3 ? &h->d_rev3 : d == 4 ? &h->d_fwd4
-                      : d == 5 ? &h->d_rev4 : d == 6 ? &h->d_fwd5 : d == 7 ? &h->d_rev5 : d == 8 ? &h->d_fwd6 : d == 9 ? &h->d_rev6
-                      : d == 10 ? &h->d_fwd7 : d == 11 ? &h->d_rev7 : d == 12 ? &h->d_fwd8 : &h->d_rev8;
-        if (b2.empty()) continue;
-        if ((e = hipMalloc((void **)dst, b2.size() * sizeof(float))) != hipSuccess ||
-            (e = hipMemcpy(*dst, b2.data(), b2.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) {
-            nf_destroy(h);
-            return fail_hip(e, "hipMalloc/hipMemcpy(matrix-core params)");
+    for (int p = 0; p < NF_PATH_COUNT; ++p)   // every layout the model has, both directions
+        for (int d = 0; d < 2; ++d) {
+            const std::vector<float> &blk = (d == 0 ? h->fwd : h->rev).lay[p].block;
+            if (blk.empty()) continue;
+            const bool gen = p == NF_PATH_SCALAR;
+            if ((e = hipMalloc((void **)&h->d_lay[d][p], blk.size() * sizeof(float))) != hipSuccess) {
+                nf_destroy(h);
+                return fail_hip(e, gen ? "hipMalloc(params)" : "hipMalloc/hipMemcpy(matrix-core params)");
+            }
+            if ((e = hipMemcpy(h->d_lay[d][p], blk.data(), blk.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) {
+                nf_destroy(h);
+                return fail_hip(e, gen ? "hipMemcpy(params)" : "hipMalloc/hipMemcpy(matrix-core params)");
+            }
         }
-    }
     {   // the gradient kernel's block, where nf_nll_grad supports the model (otherwise the call reports grad_why)
         const std::string keep = g_last_error;
         h->grad_rc = grad_support(cfg, h->fwd);
@@ -1789,7 +1525,7 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
         g_last_error = keep;
         if (h->grad_rc == NF_OK) {
             std::vector<float> gb;
-            build_grad_block(h->fwd, h->rev, h->gprog, gb, h->grad_n_cpl, h->grad_first_cpl);
+            build_grad_block(h->fwd.lay[NF_PATH_SCALAR], h->rev.lay[NF_PATH_SCALAR], h->gprog, gb, h->grad_n_cpl, h->grad_first_cpl);
             if ((e = hipMalloc((void **)&h->d_grad, gb.size() * sizeof(float))) != hipSuccess ||
                 (e = hipMemcpy(h->d_grad, gb.data(), gb.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) {
                 nf_destroy(h);
@@ -1807,24 +1543,9 @@ int nf_destroy(nf_handle *h)
     nf_hostpipe_release(h);
     DeviceGuard guard;
     (void)guard.enter(h->device);
-    if (h->d_fwd) (void)hipFree(h->d_fwd);
-    if (h->d_rev) (void)hipFree(h->d_rev);
-    if (h->d_fwd2) (void)hipFree(h->d_fwd2);
-    if (h->d_rev2) (void)hipFree(h->d_rev2);
-    if (h->d_fwd9) (void)hipFree(h->d_fwd9);
-    if (h->d_rev9) (void)hipFree(h->d_rev9);
-    if (h->d_fwd3) (void)hipFree(h->d_fwd3);
-    if (h->d_rev3) (void)hipFree(h->d_rev3);
-    if (h->d_fwd4) (void)hipFree(h->d_fwd4);
-    if (h->d_rev4) (void)hipFree(h->d_rev4);
-    if (h->d_fwd5) (void)hipFree(h->d_fwd5);
-    if (h->d_rev5) (void)hipFree(h->d_rev5);
-    if (h->d_fwd6) (void)hipFree(h->d_fwd6);
-    if (h->d_rev6) (void)hipFree(h->d_rev6);
-    if (h->d_fwd7) (void)hipFree(h->d_fwd7);
-    if (h->d_rev7) (void)hipFree(h->d_rev7);
-    if (h->d_fwd8) (void)hipFree(h->d_fwd8);
-    if (h->d_rev8) (void)hipFree(h->d_rev8);
+    for (auto &dir : h->d_lay)
+        for (float *p : dir)
+            if (p) (void)hipFree(p);
     if (h->d_grad) (void)hipFree(h->d_grad);
     nf_bs_destroy(h->bs);
     for (nf_handle::Workspace *w : h->ws) {
@@ -2031,6 +1752,61 @@ static void ws_release(nf_handle *h, nf_handle::Workspace *w, hipStream_t st, bo
     w->busy = false;
 }
 
+// THE place that decides which kernel family a handle launches in a direction (nf_kernel_path reports it, launch_resident and
+// launch_tiled dispatch on it).  A layout the model lacks has no device block.
+static int select_path(const nf_handle *h, int direction)
+{
+    const Built &b = direction == 0 ? h->fwd : h->rev;
+    float *const *d = h->d_lay[direction];
+    // NF_KERNEL=valu (A/B aid) selects the scalar-weight kernel only where that kernel can hold the patch
+    const bool mcore = use_matrix_core() || !h->scalar_ok;
+    if (d[NF_PATH_WIDE32_FP16]) return NF_PATH_WIDE32_FP16;   // NF_CFG_FP16_CNN at width 8 / 16 / 32: v_mfma_f32_32x32x16_f16
+    if (d[NF_PATH_GEMM_FP16]) return NF_PATH_GEMM_FP16;       // ... at widths 33 .. 512: the GEMM kernel on the same instruction (nf_gemm16.hip)
+    if (d[NF_PATH_GEMM]) return NF_PATH_GEMM;                 // widths 33 .. 512: LDS-staged GEMMs on v_mfma_f32_32x32x2_f32 (nf_gemm.hip); no other kernel holds these widths
+    if (b.tiled) {   // images beyond 64x64: the GEMM and width-16 kernels take tiles as they take patches
+        const int w = b.lay[NF_PATH_SCALAR].prog.width;
+        if (d[NF_PATH_WIDE16] && w == 16 && mcore) return NF_PATH_WIDE16;
+        if (d[NF_PATH_FP16] && b.fp16_big) return NF_PATH_FP16;   // width 4, fp16 CNN, full 64x64 tiles: the fused kernel on v_mfma_f32_16x16x32_f16
+        if (d[NF_PATH_WIDE32] && w > 4) return NF_PATH_WIDE32;    // kept as found: `w > 4` and no `mcore` here, `mcore` and no width test below
+        return d[NF_PATH_MFMA4] && mcore ? NF_PATH_MFMA4 : NF_PATH_SCALAR;   // kept as found: also without the matrix core when the scalar kernel cannot hold the tile
+    }
+    if (d[NF_PATH_WIDE16] && mcore) return NF_PATH_WIDE16;   // width 16: v_mfma_f32_16x16x4_f32 (nf_wide16.hip)
+    if (d[NF_PATH_WIDE32] && mcore) return NF_PATH_WIDE32;   // width 32: the three convs on v_mfma_f32_32x32x2_f32 (nf_wide.hip)
+    if (d[NF_PATH_FP16]) return NF_PATH_FP16;
+    if (d[NF_PATH_SPLIT_BF16] && use_matrix_core()) return NF_PATH_SPLIT_BF16;   // width 4, fp32, full 32x32 patches: split-bf16 convs (nf_device.h, NF12_*)
+    return d[NF_PATH_MFMA4] && use_matrix_core() ? NF_PATH_MFMA4 : NF_PATH_SCALAR;   // kept as found: MFMA4 only under use_matrix_core(), whatever scalar_ok says
+}
+
+// One launch of `prog` — the path's program or, tiled, a segment of it — on the path's kernel family: the path's device block,
+// its size and its NF_K_* flags go into `a`.
+static hipError_t launch_path(const nf_handle *h, int direction, int path, const NfProgram &prog, NfLaunch &a, hipStream_t st)
+{
+    const Built &b = direction == 0 ? h->fwd : h->rev;
+    const std::vector<float> &blk = b.lay[path].block;
+    a.params = h->d_lay[direction][path];
+    if (path != NF_PATH_SCALAR) a.n_params = (int32_t)blk.size();   // (the scalar-weight kernel: n_params stays what the caller set)
+    switch (path) {
+    case NF_PATH_WIDE32_FP16:
+        a.flags |= NF_K_FP16_CNN;
+        return nf_launch_wide(prog, a, h->n_cu, h->device, st);
+    case NF_PATH_WIDE32: return nf_launch_wide(prog, a, h->n_cu, h->device, st);
+    case NF_PATH_WIDE16: return nf_launch_wide16(prog, a, h->n_cu, h->device, st);
+    case NF_PATH_GEMM_FP16:
+        a.flags |= NF_K_FP16_CNN;
+        return b.gemm16_b ? nf_launch_gemm16b(prog, a, h->n_cu, h->device, st) : nf_launch_gemm16(prog, a, h->n_cu, h->device, st);
+    case NF_PATH_GEMM: return b.gemm_b ? nf_launch_gemmb(prog, a, h->n_cu, h->device, st) : nf_launch_gemm(prog, a, h->n_cu, h->device, st);
+    case NF_PATH_SPLIT_BF16:   // the kernel holds the LDS part; the launcher reads the host block to find the couplings' A images
+        a.n_params = (int32_t)b.n_lds9;
+        a.flags |= NF_K_SPLIT_BF16;
+        return nf_launch_flow(prog, a, h->n_cu, st, true, blk.data(), blk.size());
+    case NF_PATH_FP16:
+        a.flags |= NF_K_FP16_CNN | (b.fp16_big ? NF_K_FP16_BIG : 0u);
+        return nf_launch_flow(prog, a, h->n_cu, st, true);
+    case NF_PATH_MFMA4: return nf_launch_flow(prog, a, h->n_cu, st, true);
+    default: return nf_launch_flow(prog, a, h->n_cu, st, false);
+    }
+}
+
 // Images beyond 64x64 (nf_device.h, "overlapping tiles"): per segment of the program one launch of the fused width-4 kernel
 // (or, at widths 8 / 16 / 32 and in fp16-CNN mode, of the width-32 matrix-core kernel) over B x tiles tile-sized "patches" that reads and writes image-shaped tensors in place (the caller's, and between two
 // segments a scratch tensor), then — in the NLL direction — a one-wavefront-per-image kernel that adds the tiles' sums up.  Scratch
@@ -2038,8 +1814,6 @@ static void ws_release(nf_handle *h, nf_handle::Workspace *w, hipStream_t st, bo
 static int launch_tiled(nf_handle *h, int direction, NfLaunch &a, hipStream_t st, const char *what)
 {
     const Built &b = direction == 0 ? h->fwd : h->rev;
-    float *d1 = direction == 0 ? h->d_fwd : h->d_rev;
-    float *d2 = direction == 0 ? h->d_fwd2 : h->d_rev2;
     const int64_t B = a.B;
     const int S = (int)b.segs.size();
     const bool want = direction == 0 && (a.nll_out || a.sd_out || a.ld_out || a.sums);
@@ -2068,19 +1842,9 @@ static int launch_tiled(nf_handle *h, int direction, NfLaunch &a, hipStream_t st
         for (int i = 0; i < 2 && i < S - 1; ++i, q += img_bytes) scratch[i] = reinterpret_cast<float *>(q);
     }
     // kernel family: fp16-CNN mode and widths 8 / 16 / 32 on the width-32 matrix-core kernel (zero-padded), width 4 in fp32 on
-    // the fused width-4 kernels
-    float *d4 = direction == 0 ? h->d_fwd4 : h->d_rev4;
-    float *d5 = direction == 0 ? h->d_fwd5 : h->d_rev5;
-    float *d3 = direction == 0 ? h->d_fwd3 : h->d_rev3;
-    float *d7 = direction == 0 ? h->d_fwd7 : h->d_rev7;   // widths 33 .. 512: the GEMM kernels take tiles as they take patches
-    float *d8 = direction == 0 ? h->d_fwd8 : h->d_rev8;
-    const int gemm = d8 ? 2 : d7 ? 1 : 0;
-    float *d6 = direction == 0 ? h->d_fwd6 : h->d_rev6;   // width 16 in fp32: nf_wide16.hip takes tiles as well
-    const bool w16 = !gemm && !d5 && d6 && b.prog.width == 16 && (use_matrix_core() || !h->scalar_ok);
-    const bool hb = !gemm && d3 && b.fp16_big && !d5;   // width 4, fp16 CNN, full 64x64 tiles: the fused kernel on v_mfma_f32_16x16x32_f16
-    const int wide = (hb || gemm || w16) ? 0 : d5 ? 2 : (d4 && b.prog.width > 4) ? 1 : 0;
-    const bool mc = hb || (d2 && (use_matrix_core() || !h->scalar_ok));
-    const NfProgram &full = w16 ? b.prog6 : gemm == 2 ? b.prog8 : gemm == 1 ? b.prog7 : hb ? b.prog3 : wide == 2 ? b.prog5 : wide == 1 ? b.prog4 : mc ? b.prog2 : b.prog;
+    // the fused width-4 kernels (select_path)
+    const int path = select_path(h, direction);
+    const NfProgram &full = b.lay[path].prog;
     const float *cur = a.in;
     for (int s = 0; s < S && e == hipSuccess; ++s) {
         const Built::TileSeg &g = b.segs[s];
@@ -2108,34 +1872,7 @@ static int launch_tiled(nf_handle *h, int direction, NfLaunch &a, hipStream_t st
         t.nll_out = t.sd_out = t.ld_out = nullptr;
         t.sums = nullptr;
         t.tile_part = want ? part + tp.off[s] * 4 : nullptr;
-        if (w16) {
-            t.params = d6;
-            t.n_params = (int32_t)b.block6.size();
-            e = nf_launch_wide16(sp, t, h->n_cu, h->device, st);
-        } else if (gemm == 2) {
-            t.params = d8;
-            t.n_params = (int32_t)b.block8.size();
-            t.flags |= NF_K_FP16_CNN;
-            e = b.gemm16_b ? nf_launch_gemm16b(sp, t, h->n_cu, h->device, st) : nf_launch_gemm16(sp, t, h->n_cu, h->device, st);
-        } else if (gemm == 1) {
-            t.params = d7;
-            t.n_params = (int32_t)b.block7.size();
-            e = b.gemm_b ? nf_launch_gemmb(sp, t, h->n_cu, h->device, st) : nf_launch_gemm(sp, t, h->n_cu, h->device, st);
-        } else if (wide) {
-            t.params = wide == 2 ? d5 : d4;
-            t.n_params = (int32_t)(wide == 2 ? b.block5.size() : b.block4.size());
-            if (wide == 2) t.flags |= NF_K_FP16_CNN;
-            e = nf_launch_wide(sp, t, h->n_cu, h->device, st);
-        } else {
-            t.params = hb ? d3 : mc ? d2 : d1;
-            if (hb) {
-                t.n_params = (int32_t)b.block3.size();
-                t.flags |= NF_K_FP16_CNN | NF_K_FP16_BIG;
-            } else if (mc) {
-                t.n_params = (int32_t)b.block2.size();
-            }
-            e = nf_launch_flow(sp, t, h->n_cu, st, mc);
-        }
+        e = launch_path(h, direction, path, sp, t, st);
         cur = t.out;
     }
     if (e == hipSuccess && want)
@@ -2150,75 +1887,10 @@ static int launch_tiled(nf_handle *h, int direction, NfLaunch &a, hipStream_t st
 static int launch_resident(nf_handle *h, int direction, NfLaunch &a, hipStream_t st, const char *what)
 {
     const Built &b = direction == 0 ? h->fwd : h->rev;
-    float *d1 = direction == 0 ? h->d_fwd : h->d_rev;
-    float *d2 = direction == 0 ? h->d_fwd2 : h->d_rev2;
-    float *d3 = direction == 0 ? h->d_fwd3 : h->d_rev3;
-    float *d4 = direction == 0 ? h->d_fwd4 : h->d_rev4;
-    float *d5 = direction == 0 ? h->d_fwd5 : h->d_rev5;
     if (direction == 0) a.ld_const += b.ld_const;
     if (b.tiled) return launch_tiled(h, direction, a, st, what);
-    if (d5) {   // NF_CFG_FP16_CNN at width 8 / 16 / 32: v_mfma_f32_32x32x16_f16
-        a.params = d5;
-        a.n_params = (int32_t)b.block5.size();
-        a.flags |= NF_K_FP16_CNN;
-        hipError_t e = nf_launch_wide(b.prog5, a, h->n_cu, h->device, st);
-        if (e != hipSuccess) return fail_hip(e, what);
-        return NF_OK;
-    }
-    float *d8 = direction == 0 ? h->d_fwd8 : h->d_rev8;
-    if (d8) {   // NF_CFG_FP16_CNN at widths 33 .. 512: the GEMM kernel on v_mfma_f32_32x32x16_f16 (nf_gemm16.hip)
-        a.params = d8;
-        a.n_params = (int32_t)b.block8.size();
-        a.flags |= NF_K_FP16_CNN;
-        hipError_t e = b.gemm16_b ? nf_launch_gemm16b(b.prog8, a, h->n_cu, h->device, st) : nf_launch_gemm16(b.prog8, a, h->n_cu, h->device, st);
-        if (e != hipSuccess) return fail_hip(e, what);
-        return NF_OK;
-    }
-    float *d7 = direction == 0 ? h->d_fwd7 : h->d_rev7;
-    if (d7) {   // widths 33 .. 512: LDS-staged GEMMs on v_mfma_f32_32x32x2_f32 (nf_gemm.hip); no other kernel holds these widths
-        a.params = d7;
-        a.n_params = (int32_t)b.block7.size();
-        hipError_t e = b.gemm_b ? nf_launch_gemmb(b.prog7, a, h->n_cu, h->device, st) : nf_launch_gemm(b.prog7, a, h->n_cu, h->device, st);
-        if (e != hipSuccess) return fail_hip(e, what);
-        return NF_OK;
-    }
-    // NF_KERNEL=valu (A/B aid) selects the scalar-weight kernel only where that kernel can hold the patch
-    const bool mcore = use_matrix_core() || !h->scalar_ok;
-    float *d6 = direction == 0 ? h->d_fwd6 : h->d_rev6;
-    if (d6 && mcore) {   // width 16: v_mfma_f32_16x16x4_f32 (nf_wide16.hip)
-        a.params = d6;
-        a.n_params = (int32_t)b.block6.size();
-        hipError_t e = nf_launch_wide16(b.prog6, a, h->n_cu, h->device, st);
-        if (e != hipSuccess) return fail_hip(e, what);
-        return NF_OK;
-    }
-    if (d4 && mcore) {   // width 32: the three convs on v_mfma_f32_32x32x2_f32 (nf_wide.hip)
-        a.params = d4;
-        a.n_params = (int32_t)b.block4.size();
-        hipError_t e = nf_launch_wide(b.prog4, a, h->n_cu, h->device, st);
-        if (e != hipSuccess) return fail_hip(e, what);
-        return NF_OK;
-    }
-    const bool mc = d3 || (d2 && use_matrix_core());
-    float *d9 = direction == 0 ? h->d_fwd9 : h->d_rev9;
-    if (d9 && use_matrix_core() && !d3) {   // width 4, fp32, full 32x32 patches: split-bf16 convs (nf_device.h, NF12_*)
-        a.params = d9;
-        a.n_params = (int32_t)b.n_lds9;
-        a.flags |= NF_K_SPLIT_BF16;
-        hipError_t e = nf_launch_flow(b.prog9, a, h->n_cu, st, true, b.block9.data(), b.block9.size());
-        if (e != hipSuccess) return fail_hip(e, what);
-        return NF_OK;
-    }
-    a.params = d1;
-    if (d3) {
-        a.params = d3;
-        a.n_params = (int32_t)b.block3.size();
-        a.flags |= NF_K_FP16_CNN | (b.fp16_big ? NF_K_FP16_BIG : 0u);
-    } else if (mc) {
-        a.params = d2;
-        a.n_params = (int32_t)b.block2.size();
-    }
-    hipError_t e = nf_launch_flow(d3 ? b.prog3 : mc ? b.prog2 : b.prog, a, h->n_cu, st, mc);
+    const int path = select_path(h, direction);
+    hipError_t e = launch_path(h, direction, path, b.lay[path].prog, a, st);
     if (e != hipSuccess) return fail_hip(e, what);
     return NF_OK;
 }
@@ -2250,31 +1922,16 @@ int nf_reserve_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight)
 int nf_kernel_path(const nf_handle *h, int32_t direction)
 {
     if (!h || (direction != 0 && direction != 1)) return fail(NF_EINVAL, "bad argument");
-    if (direction == 0 ? h->d_fwd5 : h->d_rev5) return NF_PATH_WIDE32_FP16;
-    if (h->fwd.tiled) {   // images beyond 64x64: launch_tiled's choice
-        if (direction == 0 ? h->d_fwd8 : h->d_rev8) return NF_PATH_GEMM_FP16;
-        if (direction == 0 ? h->d_fwd7 : h->d_rev7) return NF_PATH_GEMM;
-        if ((direction == 0 ? h->d_fwd3 : h->d_rev3) && h->fwd.fp16_big) return NF_PATH_FP16;
-        if ((direction == 0 ? h->d_fwd6 : h->d_rev6) && h->fwd.prog.width == 16 && (use_matrix_core() || !h->scalar_ok)) return NF_PATH_WIDE16;
-        if ((direction == 0 ? h->d_fwd4 : h->d_rev4) && h->fwd.prog.width > 4) return NF_PATH_WIDE32;
-        return (direction == 0 ? h->d_fwd2 : h->d_rev2) && (use_matrix_core() || !h->scalar_ok) ? NF_PATH_MFMA4 : NF_PATH_SCALAR;
-    }
-    if (direction == 0 ? h->d_fwd8 : h->d_rev8) return NF_PATH_GEMM_FP16;
-    if (direction == 0 ? h->d_fwd7 : h->d_rev7) return NF_PATH_GEMM;
-    const bool mcore = use_matrix_core() || !h->scalar_ok;
-    if ((direction == 0 ? h->d_fwd6 : h->d_rev6) && mcore) return NF_PATH_WIDE16;
-    if ((direction == 0 ? h->d_fwd4 : h->d_rev4) && mcore) return NF_PATH_WIDE32;
-    if (direction == 0 ? h->d_fwd3 : h->d_rev3) return NF_PATH_FP16;
-    if ((direction == 0 ? h->d_fwd9 : h->d_rev9) && use_matrix_core()) return NF_PATH_SPLIT_BF16;
-    if ((direction == 0 ? h->d_fwd2 : h->d_rev2) && use_matrix_core()) return NF_PATH_MFMA4;
-    return NF_PATH_SCALAR;
+    return select_path(h, direction);
 }
 
-int nf_nll(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond, float *nll_out, float *sd_out,
-           float *logdet_out, float *z_out, double *sums_out, uint32_t flags, void *stream)
+// nf_nll (one `cond` for the call) and nf_nll_percond (`with_rows`: device `rows`, one per patch)
+static int nll_call(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond, bool with_rows, const nf_cond_row *rows,
+                    float *nll_out, float *sd_out, float *logdet_out, float *z_out, double *sums_out, uint32_t flags, void *stream,
+                    const char *what)
 {
     NfLaunch a;
-    int rc = nll_args(h, x, y, B, cond, nll_out, sd_out, logdet_out, z_out, sums_out, flags, a);
+    int rc = nll_args(h, x, y, B, cond, nll_out, sd_out, logdet_out, z_out, sums_out, flags, a, with_rows, rows);
     if (rc != NF_OK) return rc;
     DeviceGuard guard;
     if ((rc = guard.enter(h->device)) != NF_OK) return rc;
@@ -2285,19 +1942,32 @@ int nf_nll(nf_handle *h, const float *x, const float *y, int64_t B, const nf_con
         if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(sums)");
     }
     if (B == 0) return NF_OK;
-    return launch_resident(h, 0, a, st, "nf_nll launch");
+    return launch_resident(h, 0, a, st, what);
+}
+
+int nf_nll(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond, float *nll_out, float *sd_out,
+           float *logdet_out, float *z_out, double *sums_out, uint32_t flags, void *stream)
+{
+    return nll_call(h, x, y, B, cond, false, nullptr, nll_out, sd_out, logdet_out, z_out, sums_out, flags, stream, "nf_nll launch");
+}
+
+// nf_sample and nf_sample_percond, as nll_call
+static int sample_call(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp, int64_t B,
+                       const nf_cond *cond, bool with_rows, const nf_cond_row *rows, float *x_out, void *stream, const char *what)
+{
+    NfLaunch a;
+    int rc = sample_args(h, y, eps, seed, patch_index_base, temp, B, cond, x_out, a, with_rows, rows);
+    if (rc != NF_OK) return rc;
+    if (B == 0) return NF_OK;
+    DeviceGuard guard;
+    if ((rc = guard.enter(h->device)) != NF_OK) return rc;
+    return launch_resident(h, 1, a, (hipStream_t)stream, what);
 }
 
 int nf_sample(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp,
               int64_t B, const nf_cond *cond, float *x_out, void *stream)
 {
-    NfLaunch a;
-    int rc = sample_args(h, y, eps, seed, patch_index_base, temp, B, cond, x_out, a);
-    if (rc != NF_OK) return rc;
-    if (B == 0) return NF_OK;
-    DeviceGuard guard;
-    if ((rc = guard.enter(h->device)) != NF_OK) return rc;
-    return launch_resident(h, 1, a, (hipStream_t)stream, "nf_sample launch");
+    return sample_call(h, y, eps, seed, patch_index_base, temp, B, cond, false, nullptr, x_out, stream, "nf_sample launch");
 }
 
 // ---- per-patch conditioning: the same launches with NfLaunch::cond_rows set ----
@@ -2324,31 +1994,13 @@ int nf_cond_rows(const nf_config *cfg, const nf_layer_desc *layers, const float 
 int nf_nll_percond(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond_row *rows, float *nll_out, float *sd_out,
                    float *logdet_out, float *z_out, double *sums_out, uint32_t flags, void *stream)
 {
-    NfLaunch a;
-    int rc = nll_args(h, x, y, B, nullptr, nll_out, sd_out, logdet_out, z_out, sums_out, flags, a, true, rows);
-    if (rc != NF_OK) return rc;
-    DeviceGuard guard;
-    if ((rc = guard.enter(h->device)) != NF_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (sums_out && !(flags & NF_ACCUMULATE)) {
-        const size_t nb = (flags & NF_SUMS_WIDE) ? (size_t)NF_SUMS_SLOTS * NF_SUMS_STRIDE : 3;
-        hipError_t e = hipMemsetAsync(sums_out, 0, nb * sizeof(double), st);
-        if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(sums)");
-    }
-    if (B == 0) return NF_OK;
-    return launch_resident(h, 0, a, st, "nf_nll_percond launch");
+    return nll_call(h, x, y, B, nullptr, true, rows, nll_out, sd_out, logdet_out, z_out, sums_out, flags, stream, "nf_nll_percond launch");
 }
 
 int nf_sample_percond(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp, int64_t B,
                       const nf_cond_row *rows, float *x_out, void *stream)
 {
-    NfLaunch a;
-    int rc = sample_args(h, y, eps, seed, patch_index_base, temp, B, nullptr, x_out, a, true, rows);
-    if (rc != NF_OK) return rc;
-    if (B == 0) return NF_OK;
-    DeviceGuard guard;
-    if ((rc = guard.enter(h->device)) != NF_OK) return rc;
-    return launch_resident(h, 1, a, (hipStream_t)stream, "nf_sample_percond launch");
+    return sample_call(h, y, eps, seed, patch_index_base, temp, B, nullptr, true, rows, x_out, stream, "nf_sample_percond launch");
 }
 
 // ---- input gradients: d nll / d x, d nll / d y (nf_grad.hip) ----
@@ -2482,7 +2134,7 @@ static int bs_build_plan(nf_handle *h, int direction, BsPlan &P)
         const nf_layer_desc &L = h->layers[i];
         if (L.type != NF_LAYER_COUPLING) continue;
         ++n_cpl;
-        const int w = L.width, wk = h->fwd.prog.width;   // width of the variables / of the kernels' layout (zero-padded channels:
+        const int w = L.width, wk = h->fwd.lay[NF_PATH_SCALAR].prog.width;   // width of the variables / of the kernels' layout (zero-padded channels:
                                                           // activation 0 on every pixel, batch moments 0, weights and bias stay 0)
         float *lp = p.data() + L.param_offset;
         float *mv[4] = {lp + 19 * w, lp + 20 * w, lp + 22 * w + w * w, lp + 23 * w + w * w};
@@ -2494,7 +2146,7 @@ static int bs_build_plan(nf_handle *h, int direction, BsPlan &P)
     }
     int rc = build_program(&h->cfg, h->layers.data(), p.data(), p.size(), direction, P.ident);
     if (rc != NF_OK) return rc;
-    const NfProgram &prog = P.ident.prog;
+    const NfProgram &prog = P.ident.lay[NF_PATH_SCALAR].prog;
     P.cpl_ops.clear();
     for (int i = 0; i < prog.n_ops; ++i)
         if (prog.ops[i].type == NF_OP_COUPLING_FWD || prog.ops[i].type == NF_OP_COUPLING_REV) P.cpl_ops.push_back(i);
@@ -2529,14 +2181,14 @@ static int bs_build_plan(nf_handle *h, int direction, BsPlan &P)
         if (prog.n_ops - first > NF_MAX_OPS) return fail(NF_EINVAL, "too many layers for the batch-statistics plan");
         for (int i = first; i < prog.n_ops; ++i) P.progF.ops[P.progF.n_ops++] = prog.ops[i];
     }
-    if (!P.ident.block2.empty()) {   // same op sequences, offsets of the matrix-core layout
+    if (!P.ident.lay[NF_PATH_MFMA4].block.empty()) {   // same op sequences, offsets of the matrix-core layout
         auto to_mc = [&](const NfProgram &src) {
             NfProgram dst = src;
             for (int i = 0; i < src.n_ops; ++i) {
                 if (src.ops[i].type == NF_OP_STORE) continue;
                 for (int k = 0; k < prog.n_ops; ++k)   // identify the op in the full program by (type, offset)
                     if (prog.ops[k].type == src.ops[i].type && prog.ops[k].off == src.ops[i].off) {
-                        dst.ops[i].off = P.ident.prog2.ops[k].off;
+                        dst.ops[i].off = P.ident.lay[NF_PATH_MFMA4].prog.ops[k].off;
                         break;
                     }
             }
@@ -2551,17 +2203,17 @@ static int bs_build_plan(nf_handle *h, int direction, BsPlan &P)
         P.progF2 = to_mc(P.progF);
     }
     hipError_t e;
-    const size_t nb = P.ident.block.size() * sizeof(float);
+    const size_t nb = P.ident.lay[NF_PATH_SCALAR].block.size() * sizeof(float);
     if ((e = hipMalloc((void **)&P.d_ident, nb)) != hipSuccess ||
-        (e = hipMemcpy(P.d_ident, P.ident.block.data(), nb, hipMemcpyHostToDevice)) != hipSuccess)
+        (e = hipMemcpy(P.d_ident, P.ident.lay[NF_PATH_SCALAR].block.data(), nb, hipMemcpyHostToDevice)) != hipSuccess)
         return fail_hip(e, "batch-statistics plan upload");
-    if (!P.ident.block2.empty()) {
+    if (!P.ident.lay[NF_PATH_MFMA4].block.empty()) {
         // the normalisation-dependent entries of the matrix-core layout are plain copies of scalar-layout entries
         std::vector<int32_t> pairs;
         const int w = 4;
         for (int i = 0; i < prog.n_ops; ++i) {
             if (prog.ops[i].type != NF_OP_COUPLING_FWD && prog.ops[i].type != NF_OP_COUPLING_REV) continue;
-            const int o1 = prog.ops[i].off, o2 = P.ident.prog2.ops[i].off;
+            const int o1 = prog.ops[i].off, o2 = P.ident.lay[NF_PATH_MFMA4].prog.ops[i].off;
             for (int j = 0; j < 4; ++j) {
                 pairs.push_back(o2 + NF2_CPL_B1 + j); pairs.push_back(o1 + nf_cpl_off_B1(w) + j);
                 pairs.push_back(o2 + NF2_CPL_B2 + j); pairs.push_back(o1 + nf_cpl_off_B2(w) + j);
@@ -2577,9 +2229,9 @@ static int bs_build_plan(nf_handle *h, int direction, BsPlan &P)
             }
         }
         P.n_pairs = (int)(pairs.size() / 2);
-        const size_t nb2 = P.ident.block2.size() * sizeof(float);
+        const size_t nb2 = P.ident.lay[NF_PATH_MFMA4].block.size() * sizeof(float);
         if ((e = hipMalloc((void **)&P.d_ident2, nb2)) != hipSuccess ||
-            (e = hipMemcpy(P.d_ident2, P.ident.block2.data(), nb2, hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemcpy(P.d_ident2, P.ident.lay[NF_PATH_MFMA4].block.data(), nb2, hipMemcpyHostToDevice)) != hipSuccess ||
             (e = hipMalloc((void **)&P.d_pairs, pairs.size() * sizeof(int32_t))) != hipSuccess ||
             (e = hipMemcpy(P.d_pairs, pairs.data(), pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess)
             return fail_hip(e, "batch-statistics plan upload (matrix-core layout)");
@@ -2656,10 +2308,10 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
     {
         // the generic schedule below runs on the scalar-weight kernel: both LDS tiles of a patch on one CU, one pixel per lane at
         // width 32; the width-4 schedule on the matrix-core kernel takes every size (images beyond 64x64 as overlapping tiles)
-        const int pw = h->fwd.prog.width;
+        const int pw = h->fwd.lay[NF_PATH_SCALAR].prog.width;
         const size_t tile_px = ((size_t)(a.H + 2) * (a.W + 2) + 1) & ~(size_t)1;
         const bool scalar_fits = sizeof(float) * (tile_px * (2 + (size_t)pw) + 64) <= 160 * 1024 && !(pw >= 32 && a.H * a.W > 1024) && h->scalar_ok && !h->fwd.tiled;
-        const bool mc4 = pw == 4 && !h->fwd.block2.empty() && use_matrix_core();
+        const bool mc4 = pw == 4 && !h->fwd.lay[NF_PATH_MFMA4].block.empty() && use_matrix_core();
         // NF_BS_WIDE=1: A/B aid; read per call on purpose (tests/test_gpu_batchstats.py flips it inside one process), =0 means off
         const char *bw = getenv("NF_BS_WIDE");
         // width 32 on 32x32 patches (the paper's coupling CNN on the training patch size): the evaluator runs the trainer's patch-resident
@@ -2676,7 +2328,7 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
     // ONE halo for the whole call — 3 = the deepest launch (re-run coupling c-1, then l_1 of coupling c for its statistics) —
     // so that the tile grid, and with it the per-thread log-det carry, is the same in every launch
     const bool tiled = h->fwd.tiled;
-    if (tiled && !(h->fwd.prog.width == 4 && !h->fwd.block2.empty() && use_matrix_core()))
+    if (tiled && !(h->fwd.lay[NF_PATH_SCALAR].prog.width == 4 && !h->fwd.lay[NF_PATH_MFMA4].block.empty() && use_matrix_core()))
         return fail(NF_EINVAL, "batch-statistics mode beyond 64x64 pixels (%dx%d given) runs on the width-4 matrix-core kernels only",
                     h->cfg.height, h->cfg.width);
     const int bs_halo = 3;
@@ -2694,8 +2346,8 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
         if (rc != NF_OK) return rc;
     }
     const int n_cpl = (int)P.cpl_ops.size();
-    const int w = P.ident.prog.width;
-    const size_t nw1 = P.ident.block.size(), nw2 = P.ident.block2.size();
+    const int w = P.ident.lay[NF_PATH_SCALAR].prog.width;
+    const size_t nw1 = P.ident.lay[NF_PATH_SCALAR].block.size(), nw2 = P.ident.lay[NF_PATH_MFMA4].block.size();
     auto grow = [&](float *&ptr, size_t &cap, size_t need) -> hipError_t {
         if (cap >= need) return hipSuccess;
         if (ptr) (void)hipFree(ptr);
@@ -2741,7 +2393,7 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
             f.ld_carry = S.d_carry;
         }
     };
-    if (nw2 && P.ident.prog.width == 4 && use_matrix_core()) {
+    if (nw2 && P.ident.lay[NF_PATH_SCALAR].prog.width == 4 && use_matrix_core()) {
         // ---- width 4: every launch on the matrix-core kernel, the re-fold fused into the consumer's prologue ----
         // launch k gathers the sums of pass k into its own block of `d_stats_mc`; launch k+1 (every workgroup, in LDS)
         // turns them into moments and rescales the layer, workgroup 0 writes the patched image to the OTHER working
@@ -2823,7 +2475,7 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
                     if (rc != NF_OK) return rc;
                 }
                 pend_stats = s.stats;
-                pend_off = P.ident.prog2.ops[P.cpl_ops[c]].off;
+                pend_off = P.ident.lay[NF_PATH_MFMA4].prog.ops[P.cpl_ops[c]].off;
                 pend_stage = stage;
                 pend_mom = mom + (stage == 1 ? 0 : 8);
             }
@@ -2840,7 +2492,7 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
             if (want && (e = hipMallocAsync((void **)&part, (size_t)a.B * bs_nt * 4 * sizeof(float), st)) != hipSuccess)
                 return fail_hip(e, "hipMallocAsync(tile sums)");
             f.tile_part = part;
-            e = launch(n_cpl > 1 ? P.progF2 : P.ident.prog2, f);
+            e = launch(n_cpl > 1 ? P.progF2 : P.ident.lay[NF_PATH_MFMA4].prog, f);
             if (e == hipSuccess && want) {
                 NfTileParts tp;
                 memset(&tp, 0, sizeof(tp));
@@ -2854,7 +2506,7 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
                 if (e == hipSuccess) e = e2;
             }
             if (e != hipSuccess) return fail_hip(e, "batch-statistics final launch");
-        } else if ((e = launch(n_cpl > 1 ? P.progF2 : P.ident.prog2, a)) != hipSuccess) return fail_hip(e, "batch-statistics final launch");
+        } else if ((e = launch(n_cpl > 1 ? P.progF2 : P.ident.lay[NF_PATH_MFMA4].prog, a)) != hipSuccess) return fail_hip(e, "batch-statistics final launch");
         std::vector<float> mom_h((size_t)std::max(n_cpl, 1) * 16);
         if (moments_out && n_cpl &&
             (e = hipMemcpyAsync(mom_h.data(), S.d_mom, (size_t)n_cpl * 16 * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess) {
@@ -2892,7 +2544,7 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
     const float in_scale0 = a.in_scale;
     const uint32_t flags0 = a.flags;
     for (int c = 0; c < n_cpl; ++c) {
-        const int blk = P.ident.prog.ops[P.cpl_ops[c]].off;
+        const int blk = P.ident.lay[NF_PATH_SCALAR].prog.ops[P.cpl_ops[c]].off;
         float *mom = S.d_mom + (size_t)P.cpl_row[c] * 4 * w;
         for (int stage = 1; stage <= 2; ++stage) {
             const NfProgram &prog = stage == 1 ? P.progA[c] : P.progB[c];
@@ -2936,7 +2588,7 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
     a.n_params = mc ? (int32_t)nw2 : 0;
     a.ld_const = ld_call + (direction == 0 ? P.ident.ld_const : 0.0);
     if (!mc) final_args(a);   // (a final pass on the matrix-core kernel maps pixels to threads differently: whole stack, no carry)
-    if ((e = nf_launch_flow(mc ? P.ident.prog2 : n_cpl > 1 ? P.progF : P.ident.prog, a, h->n_cu, st, mc)) != hipSuccess)
+    if ((e = nf_launch_flow(mc ? P.ident.lay[NF_PATH_MFMA4].prog : n_cpl > 1 ? P.progF : P.ident.lay[NF_PATH_SCALAR].prog, a, h->n_cu, st, mc)) != hipSuccess)
         return fail_hip(e, "batch-statistics final launch");
     std::vector<float> mom_h((size_t)std::max(n_cpl, 1) * 4 * w);
     if (moments_out && n_cpl &&
