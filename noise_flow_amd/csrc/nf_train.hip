@@ -25,6 +25,7 @@
 #include <string.h>
 #include <algorithm>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/noiseflow_hip.h"
@@ -1530,6 +1531,35 @@ struct Cpl {      // per-coupling workspace
     int d_st1, d_st2, d_bs1, d_bs2;       // offsets into the double buffer
 };
 
+// Where a coupling's parameters sit in the raw vector (nf_layer_param_count): l_1/W [18][w], l_1/b, BN1 mean + var, l_2/W [w][w],
+// l_2/b, BN2 mean + var, l_last/W [36][w + 1]; tail3: b3 [4], logs [4], scale.  The ONE place these formulas are written.
+struct CplOff {
+    int w1, b1, m1, w2, b2, m2, w3, tail3;
+};
+inline CplOff cpl_off(int off, int w)
+{
+    const int w2 = off + 21 * w, m2 = w2 + w * w + w, w3 = m2 + 2 * w;
+    return CplOff{off, off + 18 * w, off + 19 * w, w2, w2 + w * w, m2, w3, w3 + 36 * (w + 1)};
+}
+
+// Which kernel family runs the couplings of a handle.  The create-time part (train_family: width, patch size, the switches) is stored
+// on the handle and sizes the workspace; train_path() adds the per-call part (the tiled stages' batch terms).
+enum TrainPath {
+    TP_LAYER,   // the layer kernels at the top of this file (widths 4 / 8)
+    TP_TILED,   // nf_train_tiled.h: one workgroup per patch, widths 4 / 8 (falls back to TP_LAYER per call)
+    TP_WIDE,    // widths 16 / 32: the stages of nf_train_wide.h, each behind its NF_TRAIN_WIDE_MFMA bit, else the layer kernel
+    TP_PR,      // nf_train_pr.h: width 32 on 32x32 patches
+    TP_GEMM     // nf_train_gemm.h: every other width (and the batch-statistics evaluator)
+};
+
+// The step plan: what the fixed layer list says about a coupling's neighbours, worked out once at create time.  Layer indices, -1 = none.
+struct CplPlan {
+    int fold;        // the Conv2d1x1 directly below: folded into the coupling's first forward / last backward stage
+    int above;       // the coupling above of the same width, directly or behind ONE Conv2d1x1: its first stage can ride in this one's last launch
+    int above_mix;   // ... that Conv2d1x1 (-1: directly above)
+    int below;       // the coupling of the same width below this one and its folded Conv2d1x1: its stage A can ride in this one's last launch
+};
+
 }  // namespace
 
 struct nf_trainer {
@@ -1542,6 +1572,8 @@ struct nf_trainer {
     int width = 0;
     std::vector<nf_layer_desc> layers;
     TLayers tl;
+    TrainPath family = TP_LAYER;    // train_family(): the create-time part of train_path()
+    CplPlan plan[kMaxLayers];       // by layer index; meaningful at couplings
     std::vector<Cpl> cpl;           // indexed by TLayer::aux of coupling layers
     float *d_params = nullptr, *d_m = nullptr, *d_v = nullptr, *d_gradf = nullptr;
     uint8_t *d_mask = nullptr;
@@ -1564,6 +1596,7 @@ struct nf_trainer {
     size_t part_floats() const { return (n_dbl - 1 - hole_rows) * NSLOT; }
     int d_dA = 0, d_dab = 0, d_dg = 0, d_ld0 = 0, d_ldc = 0;
     float *d_flt = nullptr;         // A matrices, sdn5 (a,b), BN scalars
+    const float *mixA(int l) const { return d_flt + f_A + 16 * tl.l[l].aux; }   // the matrix of the Conv2d1x1 at layer l (k_prep)
     size_t n_flt = 0;
     int f_A = 0, f_ab = 0, f_s = 0;
     float *d_patch = nullptr;       // s1[B], s2[B]
@@ -1576,21 +1609,34 @@ struct nf_trainer {
     hipStream_t side = nullptr;
     hipEvent_t ev_fork[3] = {nullptr, nullptr, nullptr}, ev_done[3] = {nullptr, nullptr, nullptr};
     bool done_pending[3] = {false, false, false};
+    // the side-stream protocol (NF_TRAIN_SERIAL=1: the "side" stream is the caller's)
+    hipStream_t side_of(hipStream_t st) const { return serial ? st : side; }
+    void wait_set(hipStream_t st, int k)   // before buffer set k is written again: the side work of the coupling that used it last
+    {
+        if (done_pending[k]) {
+            (void)hipStreamWaitEvent(st, ev_done[k], 0);
+            done_pending[k] = false;
+        }
+    }
+    void fork_side(hipStream_t st)         // the side stream picks up behind the main stream's last launch
+    {
+        (void)hipEventRecord(ev_fork[0], st);
+        (void)hipStreamWaitEvent(side_of(st), ev_fork[0], 0);
+    }
+    void side_done(hipStream_t st, int k)  // the side launches that read buffer set k are enqueued
+    {
+        (void)hipEventRecord(ev_done[k], side_of(st));
+        done_pending[k] = true;
+    }
+    void join_side(hipStream_t st)         // end of the step: the side stream's slots are read next
+    {
+        for (int k = 0; k < 3; ++k) wait_set(st, k);
+    }
     int band_cap = 320;        // pixels (rows x width, halo included) a band kernel keeps in LDS
     bool serial = false;   // NF_TRAIN_SERIAL=1: everything on the caller's stream (kernel durations without overlap, for profiling)
     int wide_mfma = 4095;   // NF_TRAIN_WIDE_MFMA: width-32 stages on the matrix cores (bit 0 filter gradients, 1 l_2 forward, 2 l_2 backward, 3 statistics finalisers, 4 l_last forward, 5 l_last transposed, 6 l_1 transposed, 7 filter gradients inside the stage that holds their operands, 8 l_1 forward, 11 affine/tanh backward inside the transposed l_last; 0: layer kernels only)
-    int pr = 1;            // NF_TRAIN_PR: width 32 on 32x32 patches on the patch-resident stages of nf_train_pr.h (1: 8 wavefronts per patch, 2: 4; + 4 / + 8: no forward / backward launch fusion, + 16: no side-stream d l_last/W; 0: the stage kernels of nf_train_wide.h)
+    int pr = 1;            // NF_TRAIN_PR as given (whether the family is in use: family == TP_PR): 1: 8 wavefronts per patch, 2: 4; + 4 / + 8: no forward / backward launch fusion, + 16: no side-stream d l_last/W, + 32: d l_last/W only; 0: the stage kernels of nf_train_wide.h
     float *pr_img = nullptr;   // [couplings][PR_SIZE] packed weights of this step (k_pr_pack)
-    // the coupling above the one a patch-resident forward is launched for, when only a Conv2d1x1 lies between them: its stage 0 rides in
-    // this coupling's last launch (set by the layer loop; pr_f0_done: the next call's stage 0 already ran)
-    const TLayer *pr_next = nullptr;
-    const float *pr_next_A = nullptr;
-    float *pr_next_zin = nullptr;
-    bool pr_f0_done = false;
-    // ... and in the backward pass: stage A of the coupling BELOW rides in this coupling's last launch
-    const TLayer *pr_below = nullptr;
-    const float *pr_below_zin = nullptr;
-    bool pr_a_done = false;
     int pr_side_full = 0;      // NF_TRAIN_PR_SIDE_FULL=1 (A/B aid): one side workgroup per patch even when fewer CUs are idle
     int pr_both_max = 0;       // NF_TRAIN_PR_BOTH_MAX=<patches> (A/B aid): up to how many patches both products take the side stream (default CUs / 2)
     int tiled = 3;   // NF_TRAIN_TILED: bit 0 = tiled backward stages, bit 1 = tiled forward stages (0: layer kernels only)
@@ -1691,9 +1737,87 @@ inline int patch_split(const Geo &g)
     return (int)std::max<int64_t>(1, std::min<int64_t>(4, std::min<int64_t>(g.nslot / npatch, 512 / npatch)));
 }
 
+inline Geo make_geo(const nf_trainer *t, int64_t B)
+{
+    Geo g;
+    g.B = (int)B;
+    g.H = t->cfg.height;
+    g.W = t->cfg.width;
+    g.HW = g.H * g.W;
+    g.npix = B * (int64_t)g.HW;
+    g.nloop = (g.npix + 63) & ~(int64_t)63;
+    const unsigned nb = blocks_for(t, g.npix);
+    g.nslot = (t->sync_fn && t->sync_world > 1) ? std::max((int)nb, 2) : (int)nb;   // the synchronised totals occupy slots 0 and 1
+    return g;
+}
+
+// What every driver of a coupling needs, built once per coupling and pass (a stack value)
+struct CplCtx {
+    const TLayer &L;
+    const Cpl &c;
+    CplOff o;
+    double n;                        // pixels the batch moments are over: the GLOBAL minibatch when the ranks are synchronised
+    float *bn1, *bn2, *bb1, *bb2;    // the finalised BN scalars of the forward / backward pass (d_flt)
+};
+inline CplCtx cpl_ctx(const nf_trainer *t, const Geo &g, const TLayer &L)
+{
+    const Cpl &c = t->cpl[L.aux];
+    return CplCtx{L, c, cpl_off(L.off, L.width), (double)g.npix * t->sync_world,
+                  t->d_flt + c.f_bn1, t->d_flt + c.f_bn2, t->d_flt + c.f_bb1, t->d_flt + c.f_bb2};
+}
+
+// a coupling whose first forward stage / backward stage A rides in the last launch of its neighbour (CplPlan::above / below)
+struct Rider {
+    const TLayer *L = nullptr;
+    const float *A = nullptr;   // forward: the Conv2d1x1 between the two, folded into the rider's first stage
+    float *zin = nullptr;       // the rider's input tensor
+};
+
+// run-time value -> template argument: f gets a std::integral_constant
+template <class F>
+inline void with_bool(bool b, F f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+inline void with_nw(const nf_trainer *t, F f)   // wavefronts per patch of the patch-resident stages
+{
+    if ((t->pr & 3) == 2) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
+}
+template <class F>
+inline void with_nt(int HW, F f)                // threads per patch of the tiled stages
+{
+    if (HW <= 256) f(std::integral_constant<int, 256>{});
+    else if (HW <= 512) f(std::integral_constant<int, 512>{});
+    else f(std::integral_constant<int, 1024>{});
+}
+
 }  // namespace
 #include "nf_train_gemm.h"    // widths without stage kernels of their own: matrix-core GEMMs (nf_train_mm.h) + pixel kernels of run-time width
 namespace {
+
+TrainPath train_family(const nf_trainer *t, int w, int n_cpl)
+{
+    const bool gemm = t->all_gemm || gemm_width(w);
+    const int H = t->cfg.height, W = t->cfg.width;
+    // (the batch-statistics evaluator, a trimmed trainer otherwise on the GEMM path, takes the patch-resident forward stages too)
+    if (t->pr && t->wide_mfma != 0 && w == 32 && (!gemm || t->eval_only) && H == 32 && W == 32 && n_cpl > 0) return TP_PR;
+    if (gemm) return TP_GEMM;
+    if (w == 16 || w == 32) return TP_WIDE;
+    return t->tiled && H * W <= 1024 ? TP_TILED : TP_LAYER;
+}
+
+// pass: 1 backward, 2 forward (the bits of NF_TRAIN_TILED).  The tiled stages take one thread per pixel of a patch and one accumulator
+// slot per patch.  Measured on the shipped model (both passes tiled): 0.61 vs 0.77 ms per step at 138 patches, 0.77 vs 0.88 at 256,
+// break-even near 400 (one 1024-thread workgroup per CU: past one round over the 256 CUs the layer kernels' finer grain wins)
+inline TrainPath train_path(const nf_trainer *t, const Geo &g, int pass)
+{
+    if (t->family != TP_TILED) return t->family;
+    const int64_t npatch = g.npix / g.HW;
+    return (t->tiled & pass) && npatch <= g.nslot && npatch <= 384 ? TP_TILED : TP_LAYER;
+}
 
 // ---- width 32 on 32x32 patches: the patch-resident stages (nf_train_pr.h) ----
 template <int NW>
@@ -1726,7 +1850,12 @@ int pr_set_attributes_nw()
     }
     return NF_OK;
 }
-int pr_set_attributes(int mode) { return (mode & 3) == 2 ? pr_set_attributes_nw<4>() : pr_set_attributes_nw<8>(); }
+int pr_set_attributes(const nf_trainer *t)
+{
+    int rc = NF_OK;
+    with_nw(t, [&](auto NW) { rc = pr_set_attributes_nw<decltype(NW)::value>(); });
+    return rc;
+}
 
 void pr_pack_step(nf_trainer *t, hipStream_t st)
 {
@@ -1734,7 +1863,7 @@ void pr_pack_step(nf_trainer *t, hipStream_t st)
     int n = 0;
     for (int l = 0; l < t->tl.n; ++l)
         if (t->tl.l[l].type == NF_LAYER_COUPLING) {
-            offs.off[t->tl.l[l].aux] = t->tl.l[l].off;
+            offs.off[t->tl.l[l].aux] = cpl_off(t->tl.l[l].off, t->tl.l[l].width).w1;
             n = std::max(n, t->tl.l[l].aux + 1);
         }
     if (n) hipLaunchKernelGGL(k_pr_pack, dim3((unsigned)n, 13), dim3(256), 0, st, (const float *)t->d_params, offs, t->pr_img);
@@ -1750,90 +1879,95 @@ inline unsigned pr_grid(const nf_trainer *t, const Geo &g)
 // the slots a consumer adds up: the producer's grid — or the two slots the cross-rank totals come back in (sync_slots)
 inline int pr_nred(const nf_trainer *t, unsigned grid) { return (t->sync_fn && t->sync_world > 1) ? std::max<int>((int)grid, 2) : (int)grid; }
 
+// the operands every forward stage of a coupling shares, in the trainer and in the evaluator (stage 0 leaves its sums in `stats`)
+PrFwdArgs pr_fwd_args(nf_trainer *t, const CplCtx &x, unsigned grid)
+{
+    PrFwdArgs a{};
+    a.img = t->pr_img + (size_t)x.L.aux * PR_SIZE;
+    a.bn1 = x.bn1;
+    a.bn2 = x.bn2;
+    a.n = x.n;
+    a.nred = pr_nred(t, grid);
+    a.tail3 = t->d_params + x.o.tail3;
+    a.stats = t->acc(x.c.d_st1);
+    return a;
+}
+
+// f0_done: this coupling's stage 0 ran in the last launch of the coupling below; `nx`: the coupling above whose stage 0 rides in this
+// one's last launch.  Returns whether it did.
 template <int NW>
-void pr_coupling_forward(nf_trainer *t, const Geo &g, const TLayer &L, const float *zin, float *zout, Acc ldacc, const float *zpre,
-                         const float *A, hipStream_t st)
+bool pr_coupling_forward(nf_trainer *t, const Geo &g, const CplCtx &x, const float *zin, float *zout, Acc ldacc, const float *zpre,
+                         const float *A, hipStream_t st, bool f0_done, const Rider &nx)
 {
     constexpr int w = 32;
-    const Cpl &c = t->cpl[L.aux];
-    const int off_m1 = L.off + 19 * w, off_m2 = L.off + 22 * w + w * w, off_w3 = L.off + 24 * w + w * w;
+    const Cpl &c = x.c;
     const unsigned grid = pr_grid(t, g);
-    PrFwdArgs a{};
-    a.img = t->pr_img + (size_t)L.aux * PR_SIZE;
-    a.bn1 = t->d_flt + c.f_bn1;
-    a.bn2 = t->d_flt + c.f_bn2;
-    a.n = (double)g.npix * t->sync_world;   // the moments are over the GLOBAL minibatch when the ranks are synchronised
-    a.nred = pr_nred(t, grid);
-    a.tail3 = t->d_params + off_w3 + 36 * (w + 1);
-    a.stats = t->acc(c.d_st1);
-    if (t->pr_f0_done) {
+    const dim3 blk(64 * NW);
+    PrFwdArgs a = pr_fwd_args(t, x, grid);
+    if (f0_done) {
         // stage 0 ran in the last launch of the coupling below
     } else if (zpre) {
         a.zsrc = zpre;
         a.A = A;
         a.zmixed = const_cast<float *>(zin);
-        hipLaunchKernelGGL((k_pr_fwd<0, true, NW>), dim3(grid), dim3(64 * NW), pr_fwd_lds(0, NW), st, g, a);
+        hipLaunchKernelGGL((k_pr_fwd<0, true, NW>), dim3(grid), blk, pr_fwd_lds(0, NW), st, g, a);
     } else {
         a.zsrc = zin;
-        hipLaunchKernelGGL((k_pr_fwd<0, false, NW>), dim3(grid), dim3(64 * NW), pr_fwd_lds(0, NW), st, g, a);
+        hipLaunchKernelGGL((k_pr_fwd<0, false, NW>), dim3(grid), blk, pr_fwd_lds(0, NW), st, g, a);
     }
-    t->pr_f0_done = false;
     sync_slots(t, t->acc(c.d_st1), 2 * w, g.nslot, st);
     a.zsrc = zin;
     a.A = nullptr;
     a.zmixed = nullptr;
     a.stats_in = t->acc(c.d_st1);
-    a.run_mean = t->d_params + off_m1;
-    a.run_var = t->d_params + off_m1 + w;
+    a.run_mean = t->d_params + x.o.m1;
+    a.run_var = t->d_params + x.o.m1 + w;
     a.stats = t->acc(c.d_st2);
-    hipLaunchKernelGGL((k_pr_fwd<1, false, NW>), dim3(grid), dim3(64 * NW), pr_fwd_lds(1, NW), st, g, a);
+    hipLaunchKernelGGL((k_pr_fwd<1, false, NW>), dim3(grid), blk, pr_fwd_lds(1, NW), st, g, a);
     sync_slots(t, t->acc(c.d_st2), 2 * w, g.nslot, st);
     a.stats_in = t->acc(c.d_st2);
-    a.run_mean = t->d_params + off_m2;
-    a.run_var = t->d_params + off_m2 + w;
+    a.run_mean = t->d_params + x.o.m2;
+    a.run_var = t->d_params + x.o.m2 + w;
     a.zout = zout;
     a.u_out = c.u;
     a.ldacc = ldacc;
-    if (t->pr_next && (t->pr & 4) == 0) {
-        const Cpl &cn = t->cpl[t->pr_next->aux];
-        a.next_A = t->pr_next_A;
-        a.next_zmixed = t->pr_next_zin;
-        a.next_img = t->pr_img + (size_t)t->pr_next->aux * PR_SIZE;
-        a.next_stats = t->acc(cn.d_st1);
-        hipLaunchKernelGGL((k_pr_fwd<2, false, NW, true>), dim3(grid), dim3(64 * NW), pr_fwd_lds(2, NW), st, g, a);
-        t->pr_f0_done = true;
+    if (nx.L) {
+        a.next_A = nx.A;
+        a.next_zmixed = nx.zin;
+        a.next_img = t->pr_img + (size_t)nx.L->aux * PR_SIZE;
+        a.next_stats = t->acc(t->cpl[nx.L->aux].d_st1);
+        hipLaunchKernelGGL((k_pr_fwd<2, false, NW, true>), dim3(grid), blk, pr_fwd_lds(2, NW), st, g, a);
     } else {
-        hipLaunchKernelGGL((k_pr_fwd<2, false, NW>), dim3(grid), dim3(64 * NW), pr_fwd_lds(2, NW), st, g, a);
+        hipLaunchKernelGGL((k_pr_fwd<2, false, NW>), dim3(grid), blk, pr_fwd_lds(2, NW), st, g, a);
     }
+    return nx.L != nullptr;
 }
 
 // the operands every backward stage of a coupling shares (stage A reads dz / zlat and writes dz2, gu; B and C read gu)
-PrBwdArgs pr_bwd_args(nf_trainer *t, const Geo &g, const TLayer &L, const float *zin, float invB, const float *zlat, unsigned grid)
+PrBwdArgs pr_bwd_args(nf_trainer *t, const CplCtx &x, const float *zin, float invB, const float *zlat, unsigned grid)
 {
-    constexpr int w = 32;
-    const Cpl &c = t->cpl[L.aux];
     PrBwdArgs a{};
     a.zin = zin;
-    a.img = t->pr_img + (size_t)L.aux * PR_SIZE;
-    a.bn1 = t->d_flt + c.f_bn1;
-    a.bn2 = t->d_flt + c.f_bn2;
-    a.bb2 = t->d_flt + c.f_bb2;
-    a.bb1 = t->d_flt + c.f_bb1;
-    a.n = (double)g.npix * t->sync_world;
+    a.img = t->pr_img + (size_t)x.L.aux * PR_SIZE;
+    a.bn1 = x.bn1;
+    a.bn2 = x.bn2;
+    a.bb2 = x.bb2;
+    a.bb1 = x.bb1;
+    a.n = x.n;
     a.nred = pr_nred(t, grid);
-    a.off_w1 = L.off;
-    a.off_b1 = L.off + 18 * w;
-    a.off_w2 = L.off + 21 * w;
-    a.off_w3 = L.off + 24 * w + w * w;
-    a.tail3 = t->d_params + a.off_w3 + 36 * (w + 1);
-    a.u = c.u;
+    a.off_w1 = x.o.w1;
+    a.off_b1 = x.o.b1;
+    a.off_w2 = x.o.w2;
+    a.off_w3 = x.o.w3;
+    a.tail3 = t->d_params + x.o.tail3;
+    a.u = x.c.u;
     a.zlat = zlat;
     a.dz = t->dz;
     a.dz2 = t->dz2;
-    a.gu = t->gu[L.aux % 3];   // (by coupling index: the filter-gradient launches of a coupling may still read it on the side stream)
+    a.gu = t->gu[x.L.aux % 3];   // (by coupling index: the filter-gradient launches of a coupling may still read it on the side stream)
     a.invB = invB;
     a.G = t->acc(0);
-    a.bstats = t->acc(c.d_bs2);
+    a.bstats = t->acc(x.c.d_bs2);
     return a;
 }
 
@@ -1850,36 +1984,29 @@ inline bool pr_split(const nf_trainer *t, const Geo &g)
     return (t->pr & 16) == 0 && !t->serial && 4 * npatch <= 3 * (int64_t)t->n_cu && 4 * npatch >= t->n_cu;
 }
 
+// a_done: this coupling's stage A rode in the last launch of the coupling above; `nx`: the coupling below whose stage A rides in this
+// one's last launch (k_pr_bwd_CA).  Returns whether it did.
 template <int NW>
-void pr_coupling_backward(nf_trainer *t, const Geo &g, const TLayer &L, const float *zin, float invB, const float *zmix_in, const float *A,
-                          Acc dA, hipStream_t st, const float *zlat)
+bool pr_coupling_backward(nf_trainer *t, const Geo &g, const CplCtx &x, const float *zin, float invB, const float *zmix_in, const float *A,
+                          Acc dA, hipStream_t st, const float *zlat, bool a_done, const Rider &nx)
 {
     constexpr int w = 32;
-    const Cpl &c = t->cpl[L.aux];
+    const Cpl &c = x.c;
     const unsigned grid = pr_grid(t, g);
+    const dim3 blk(64 * NW);
     const bool split = pr_split(t, g);
-    const int par = L.aux % 3;
-    hipStream_t sd = t->serial ? st : t->side;
-    auto wait_side = [&](int p) {   // the side work of the coupling that used buffer set p last
-        if (t->done_pending[p]) {
-            (void)hipStreamWaitEvent(st, t->ev_done[p], 0);
-            t->done_pending[p] = false;
-        }
-    };
-    auto fork = [&] {               // the side stream picks up behind the main stream's last launch
-        (void)hipEventRecord(t->ev_fork[0], st);
-        (void)hipStreamWaitEvent(sd, t->ev_fork[0], 0);
-    };
-    PrBwdArgs a = pr_bwd_args(t, g, L, zin, invB, zlat, grid);
-    if (!t->pr_a_done) {   // (else: stage A rode in the last launch of the coupling above)
-        wait_side(par);
+    const int par = x.L.aux % 3;
+    hipStream_t sd = t->side_of(st);
+    PrBwdArgs a = pr_bwd_args(t, x, zin, invB, zlat, grid);
+    if (!a_done) {
+        t->wait_set(st, par);
 #ifdef NF_PR_TIMELINE
         a.dz_out = t->gu[(par + 1) % 3];   // the stamps of stage A (nf_train_pr.h, PR_TL)
 #endif
         if (split)
-            hipLaunchKernelGGL((k_pr_bwd<0, false, NW, 0>), dim3(grid), dim3(64 * NW), pr_bwd_lds(0, NW), st, g, a);
+            hipLaunchKernelGGL((k_pr_bwd<0, false, NW, 0>), dim3(grid), blk, pr_bwd_lds(0, NW), st, g, a);
         else
-            hipLaunchKernelGGL((k_pr_bwd<0, false, NW, 2>), dim3(grid), dim3(64 * NW), pr_bwd_lds(0, NW), st, g, a);
+            hipLaunchKernelGGL((k_pr_bwd<0, false, NW, 2>), dim3(grid), blk, pr_bwd_lds(0, NW), st, g, a);
 #ifdef NF_PR_TIMELINE
         {   // average phase lengths over the workgroups, printed for a few launches (100 MHz counter: 10 ns units)
             static int shown = 0;
@@ -1902,23 +2029,20 @@ void pr_coupling_backward(nf_trainer *t, const Geo &g, const TLayer &L, const fl
         }
 #endif
     }
-    const bool a_rode = t->pr_a_done;   // stage A ran in the launch of the coupling above: its product was launched behind that one
-    t->pr_a_done = false;
     // both products (stage C's and the next stage A's) leave the main launches while every side workgroup has ONE patch — at most half
     // of the CUs busy; beyond (138 patches: 118 side workgroups, 20 of them with two patches) the side launch outlasts the main one
     // (measured: 1.25 against 1.19 ms) and only d l_last/W goes.  NF_TRAIN_PR + 32: d l_last/W only, at every size
     const bool both_ok = (t->pr & 32) == 0 && (t->pr_both_max ? g.npix / g.HW <= t->pr_both_max : 2 * (g.npix / g.HW) <= (int64_t)t->n_cu);
     const unsigned side_grid = !split ? 0u : t->pr_side_full ? grid : std::max(1u, std::min(grid, (unsigned)t->n_cu - grid));
-    if (split && !(a_rode && both_ok)) {
-        fork();
-        hipLaunchKernelGGL((k_pr_bwd<0, false, NW, 1>), dim3(side_grid), dim3(64 * NW), pr_bwd_lds(0, NW), sd, g, a);
-        (void)hipEventRecord(t->ev_done[par], sd);
-        t->done_pending[par] = true;
+    if (split && !(a_done && both_ok)) {   // (a_done && both_ok: the product was launched behind the coupling above's last launch)
+        t->fork_side(st);
+        hipLaunchKernelGGL((k_pr_bwd<0, false, NW, 1>), dim3(side_grid), blk, pr_bwd_lds(0, NW), sd, g, a);
+        t->side_done(st, par);
     }
     sync_slots(t, t->acc(c.d_bs2), 2 * w, g.nslot, st);
     a.bstats_in = t->acc(c.d_bs2);
     a.bstats = t->acc(c.d_bs1);
-    hipLaunchKernelGGL((k_pr_bwd<1, false, NW, 2>), dim3(grid), dim3(64 * NW), pr_bwd_lds(1, NW), st, g, a);
+    hipLaunchKernelGGL((k_pr_bwd<1, false, NW, 2>), dim3(grid), blk, pr_bwd_lds(1, NW), st, g, a);
     sync_slots(t, t->acc(c.d_bs1), 2 * w, g.nslot, st);
     a.bstats_in = t->acc(c.d_bs1);
     a.dz_out = t->dz;
@@ -1927,70 +2051,62 @@ void pr_coupling_backward(nf_trainer *t, const Geo &g, const TLayer &L, const fl
     a.A = A;
     bool fused = false;
 #ifndef NF_PR_TIMELINE
-    if (t->pr_below && (t->pr & 8) == 0) {
-        // stage A of the coupling below in the same launch (nf_train_pr.h, k_pr_bwd_CA)
-        wait_side(t->pr_below->aux % 3);
-        const PrBwdArgs an = pr_bwd_args(t, g, *t->pr_below, t->pr_below_zin, invB, nullptr, grid);
+    if (nx.L) {
+        const int pb = nx.L->aux % 3;
+        t->wait_set(st, pb);
+        const PrBwdArgs an = pr_bwd_args(t, cpl_ctx(t, g, *nx.L), nx.zin, invB, nullptr, grid);
         const size_t lds = std::max(pr_bwd_lds(2, NW), pr_bwd_lds(0, NW));
         // split: both stages without their products — d l_1/W of this coupling and d l_last/W of the one below follow in ONE
         // launch on the side stream (NF_TRAIN_PR + 32: stage C keeps its product, stage A's is launched with the coupling below)
         const bool both = split && both_ok;
-        if (zmix_in && both) hipLaunchKernelGGL((k_pr_bwd_CA<true, NW, 0, 0>), dim3(grid), dim3(64 * NW), lds, st, g, a, an);
-        else if (zmix_in && split) hipLaunchKernelGGL((k_pr_bwd_CA<true, NW, 0, 2>), dim3(grid), dim3(64 * NW), lds, st, g, a, an);
-        else if (zmix_in) hipLaunchKernelGGL((k_pr_bwd_CA<true, NW, 2, 2>), dim3(grid), dim3(64 * NW), lds, st, g, a, an);
-        else if (both) hipLaunchKernelGGL((k_pr_bwd_CA<false, NW, 0, 0>), dim3(grid), dim3(64 * NW), lds, st, g, a, an);
-        else if (split) hipLaunchKernelGGL((k_pr_bwd_CA<false, NW, 0, 2>), dim3(grid), dim3(64 * NW), lds, st, g, a, an);
-        else hipLaunchKernelGGL((k_pr_bwd_CA<false, NW, 2, 2>), dim3(grid), dim3(64 * NW), lds, st, g, a, an);
+        with_bool(zmix_in != nullptr, [&](auto MIX) {
+            constexpr bool mix = decltype(MIX)::value;
+            if (both) hipLaunchKernelGGL((k_pr_bwd_CA<mix, NW, 0, 0>), dim3(grid), blk, lds, st, g, a, an);
+            else if (split) hipLaunchKernelGGL((k_pr_bwd_CA<mix, NW, 0, 2>), dim3(grid), blk, lds, st, g, a, an);
+            else hipLaunchKernelGGL((k_pr_bwd_CA<mix, NW, 2, 2>), dim3(grid), blk, lds, st, g, a, an);
+        });
         if (both) {
-            const int pb = t->pr_below->aux % 3;
-            fork();
-            hipLaunchKernelGGL((k_pr_bwd_grads<NW>), dim3(side_grid), dim3(64 * NW), lds, sd, g, a, an);
-            (void)hipEventRecord(t->ev_done[par], sd);
-            (void)hipEventRecord(t->ev_done[pb], sd);
-            t->done_pending[par] = t->done_pending[pb] = true;
+            t->fork_side(st);
+            hipLaunchKernelGGL((k_pr_bwd_grads<NW>), dim3(side_grid), blk, lds, sd, g, a, an);
+            t->side_done(st, par);
+            t->side_done(st, pb);
         }
-        t->pr_a_done = true;
         fused = true;
     }
 #endif
     if (!fused) {
-        if (zmix_in) hipLaunchKernelGGL((k_pr_bwd<2, true, NW, 2>), dim3(grid), dim3(64 * NW), pr_bwd_lds(2, NW), st, g, a);
-        else hipLaunchKernelGGL((k_pr_bwd<2, false, NW, 2>), dim3(grid), dim3(64 * NW), pr_bwd_lds(2, NW), st, g, a);
+        if (zmix_in) hipLaunchKernelGGL((k_pr_bwd<2, true, NW, 2>), dim3(grid), blk, pr_bwd_lds(2, NW), st, g, a);
+        else hipLaunchKernelGGL((k_pr_bwd<2, false, NW, 2>), dim3(grid), blk, pr_bwd_lds(2, NW), st, g, a);
     }
+    return fused;
 }
 
 // a coupling of the batch-statistics evaluator (nf_bs_wide_run) on the patch-resident forward stages: in place on z, the moments of
 // both normalisations left in mom [4][32], the per-patch log-det share added to t->eldp (NLL direction)
 template <int NW>
-void pr_coupling_eval(nf_trainer *t, const Geo &g, const TLayer &L, float *z, hipStream_t st, float *mom, bool inverse,
-                      const float *mixA = nullptr)   // mixA: the Conv2d1x1 in front of the coupling (NLL direction), applied by its first stage
+void pr_coupling_eval(nf_trainer *t, const Geo &g, const CplCtx &x, float *z, hipStream_t st, float *mom, bool inverse,
+                      const float *mixA)   // mixA: the Conv2d1x1 in front of the coupling (NLL direction), applied by its first stage
 {
     constexpr int w = 32;
-    const Cpl &c = t->cpl[L.aux];
+    const Cpl &c = x.c;
     const unsigned grid = pr_grid(t, g);
-    PrFwdArgs a{};
-    a.img = t->pr_img + (size_t)L.aux * PR_SIZE;
-    a.bn1 = t->d_flt + c.f_bn1;
-    a.bn2 = t->d_flt + c.f_bn2;
-    a.n = (double)g.npix * t->sync_world;
-    a.nred = pr_nred(t, grid);
-    a.tail3 = t->d_params + L.off + 24 * w + w * w + 36 * (w + 1);
+    const dim3 blk(64 * NW);
+    PrFwdArgs a = pr_fwd_args(t, x, grid);
     a.zsrc = z;
-    a.stats = t->acc(c.d_st1);
     if (mixA && !inverse) {   // in place: every lane reads its own pixels and writes them back mixed
         a.A = mixA;
         a.zmixed = z;
-        hipLaunchKernelGGL((k_pr_fwd<0, true, NW>), dim3(grid), dim3(64 * NW), pr_fwd_lds(0, NW), st, g, a);
+        hipLaunchKernelGGL((k_pr_fwd<0, true, NW>), dim3(grid), blk, pr_fwd_lds(0, NW), st, g, a);
         a.A = nullptr;
         a.zmixed = nullptr;
     } else {
-        hipLaunchKernelGGL((k_pr_fwd<0, false, NW>), dim3(grid), dim3(64 * NW), pr_fwd_lds(0, NW), st, g, a);
+        hipLaunchKernelGGL((k_pr_fwd<0, false, NW>), dim3(grid), blk, pr_fwd_lds(0, NW), st, g, a);
     }
     sync_slots(t, t->acc(c.d_st1), 2 * w, g.nslot, st);
     a.stats_in = t->acc(c.d_st1);
     a.stats = t->acc(c.d_st2);
     a.mom = mom;
-    hipLaunchKernelGGL((k_pr_fwd<1, false, NW>), dim3(grid), dim3(64 * NW), pr_fwd_lds(1, NW), st, g, a);
+    hipLaunchKernelGGL((k_pr_fwd<1, false, NW>), dim3(grid), blk, pr_fwd_lds(1, NW), st, g, a);
     sync_slots(t, t->acc(c.d_st2), 2 * w, g.nslot, st);
     a.stats_in = t->acc(c.d_st2);
     a.mom = mom ? mom + 2 * w : nullptr;
@@ -1998,101 +2114,85 @@ void pr_coupling_eval(nf_trainer *t, const Geo &g, const TLayer &L, float *z, hi
     a.ldp = t->eldp;
     if (inverse) a.A = mixA;   // (sampling direction: mixA is the INVERSE matrix of the Conv2d1x1, applied behind the coupling)
     if (inverse)
-        hipLaunchKernelGGL((k_pr_fwd<2, false, NW, false, 2>), dim3(grid), dim3(64 * NW), pr_fwd_lds(2, NW), st, g, a);
+        hipLaunchKernelGGL((k_pr_fwd<2, false, NW, false, 2>), dim3(grid), blk, pr_fwd_lds(2, NW), st, g, a);
     else
-        hipLaunchKernelGGL((k_pr_fwd<2, false, NW, false, 1>), dim3(grid), dim3(64 * NW), pr_fwd_lds(2, NW), st, g, a);
+        hipLaunchKernelGGL((k_pr_fwd<2, false, NW, false, 1>), dim3(grid), blk, pr_fwd_lds(2, NW), st, g, a);
 }
 
 template <int W>
-void coupling_forward(nf_trainer *t, const Geo &g, const TLayer &L, const float *zin, float *zout, Acc ldacc,
+void coupling_forward(nf_trainer *t, const Geo &g, const CplCtx &x, const float *zin, float *zout, Acc ldacc,
                       const float *zpre, const float *A, hipStream_t st)
 {
-    const Cpl &c = t->cpl[L.aux];
+    const Cpl &c = x.c;
     const unsigned nb = blocks_for(t, g.npix);
-    const int w = W, off_w1 = L.off, off_m1 = L.off + 19 * w, off_w2 = L.off + 21 * w, off_m2 = L.off + 22 * w + w * w,
-              off_w3 = L.off + 24 * w + w * w;
-    const double n = (double)g.npix * t->sync_world;   // the moments are over the GLOBAL minibatch when the ranks are synchronised
+    const int w = W, off_w1 = x.o.w1, off_m1 = x.o.m1, off_w2 = x.o.w2, off_m2 = x.o.m2, off_w3 = x.o.w3;
+    const double n = x.n;
     // zpre != null: the preceding Conv2d1x1 is folded into l_1 (which then also writes `zin`)
-    if (W == 32 && t->pr) {
-        if ((t->pr & 3) == 2) pr_coupling_forward<4>(t, g, L, zin, zout, ldacc, zpre, A, st);
-        else pr_coupling_forward<8>(t, g, L, zin, zout, ldacc, zpre, A, st);
-        return;
-    }
+    // (the per-stage fall-backs of the wide family stay here, each a marked exception: the operand tile in 60 KiB, the band in LDS)
     const size_t z_tile = ((size_t)(g.H + 2) * (g.W + 2) * 2 + g.HW) * sizeof(float);
     constexpr bool kWide = W == 16 || W == 32;   // widths with matrix-core stage kernels
     constexpr int WM = kWide ? W : 32;           // (only instantiated for the widths they exist for)
-    if (kWide && (t->wide_mfma & 256) && z_tile <= 60 * 1024) {
-        const int S = patch_split(g);
-        const unsigned ngrid = std::min<unsigned>((unsigned)(g.npix / g.HW) * S, (unsigned)g.nslot);
-        if (zpre)
-            hipLaunchKernelGGL((k_c1_fwd_mfma<WM, true>), dim3(ngrid), dim3(256), z_tile, st, g, zpre, A, const_cast<float *>(zin),
-                               (const float *)t->d_params, off_w1, c.h1, t->acc(c.d_st1), S);
-        else
-            hipLaunchKernelGGL((k_c1_fwd_mfma<WM, false>), dim3(ngrid), dim3(256), z_tile, st, g, zin, (const float *)nullptr, (float *)nullptr,
-                               (const float *)t->d_params, off_w1, c.h1, t->acc(c.d_st1), S);
-    } else if (zpre) {
-        hipLaunchKernelGGL((k_c1_fwd<W, true>), dim3(nb), dim3(TB), 0, st, g, zpre, A, const_cast<float *>(zin), t->d_params,
-                           off_w1, c.h1, t->acc(c.d_st1));
-    } else {
-        hipLaunchKernelGGL((k_c1_fwd<W, false>), dim3(nb), dim3(TB), 0, st, g, zin, (const float *)nullptr, (float *)nullptr,
-                           t->d_params, off_w1, c.h1, t->acc(c.d_st1));
-    }
+    const float *src = zpre ? zpre : zin;                            // (A is null without a fold)
+    float *zmixed = zpre ? const_cast<float *>(zin) : nullptr;
+    with_bool(zpre != nullptr, [&](auto MIX) {
+        constexpr bool mix = decltype(MIX)::value;
+        if (kWide && (t->wide_mfma & 256) && z_tile <= 60 * 1024) {
+            const int S = patch_split(g);
+            const unsigned ngrid = std::min<unsigned>((unsigned)(g.npix / g.HW) * S, (unsigned)g.nslot);
+            hipLaunchKernelGGL((k_c1_fwd_mfma<WM, mix>), dim3(ngrid), dim3(256), z_tile, st, g, src, A, zmixed, (const float *)t->d_params,
+                               off_w1, c.h1, t->acc(c.d_st1), S);
+        } else {
+            hipLaunchKernelGGL((k_c1_fwd<W, mix>), dim3(nb), dim3(TB), 0, st, g, src, A, zmixed, t->d_params, off_w1, c.h1, t->acc(c.d_st1));
+        }
+    });
     sync_slots(t, t->acc(c.d_st1), 2 * w, g.nslot, st);
     // wide couplings: the slot sums are added up once, by a finaliser kernel, not by every workgroup of the consumer
     const bool fin = W >= 16 && (t->wide_mfma & 8);
     if (fin)
         hipLaunchKernelGGL(k_bn_fin, dim3(w), dim3(64), 0, st, t->acc(c.d_st1), w, g.nslot, n, t->d_params, off_m1, off_m1 + w,
-                           t->d_flt + c.f_bn1);
+                           x.bn1);
     if (kWide && (t->wide_mfma & 2))
         hipLaunchKernelGGL(k_c2_fwd_mfma<WM>, dim3(nb), dim3(256), 0, st, g, (const float *)c.h1, t->acc(c.d_st1), n, t->d_params, off_m1,
-                           t->d_flt + c.f_bn1, off_w2, c.h2, t->acc(c.d_st2), (const float *)t->d_params, fin);
+                           x.bn1, off_w2, c.h2, t->acc(c.d_st2), (const float *)t->d_params, fin);
     else
         hipLaunchKernelGGL(k_c2_fwd<W>, dim3(nb), dim3(TB), 0, st, g, c.h1, t->acc(c.d_st1), n, t->d_params, off_m1,
-                           t->d_flt + c.f_bn1, off_w2, c.h2, t->acc(c.d_st2), (const float *)t->d_params, fin);
+                           x.bn1, off_w2, c.h2, t->acc(c.d_st2), (const float *)t->d_params, fin);
     sync_slots(t, t->acc(c.d_st2), 2 * w, g.nslot, st);
     if (fin)
         hipLaunchKernelGGL(k_bn_fin, dim3(w), dim3(64), 0, st, t->acc(c.d_st2), w, g.nslot, n, t->d_params, off_m2, off_m2 + w,
-                           t->d_flt + c.f_bn2);
+                           x.bn2);
     if (kWide && fin && (t->wide_mfma & 16) && 3 * g.W <= t->band_cap) {
         // bands of BR rows: (BR + 2) rows of 36 P values per pixel in LDS
         const int BR = std::max(1, std::min(g.H, t->band_cap / g.W - 2)), units = (int)(g.npix / g.HW) * ((g.H + BR - 1) / BR);
         const size_t lds = (size_t)(((BR + 2) * g.W + 31) / 32 * 32) * 36 * sizeof(float);
         hipLaunchKernelGGL(k_c3_fwd_mfma<WM>, dim3(std::min<unsigned>((unsigned)units, (unsigned)g.nslot)), dim3(256), lds, st, g, zin,
-                           (const float *)c.h2, (const float *)(t->d_flt + c.f_bn2), (const float *)t->d_params, off_w3, zout, ldacc,
+                           (const float *)c.h2, (const float *)(x.bn2), (const float *)t->d_params, off_w3, zout, ldacc,
                            c.u, BR);
     } else {
         hipLaunchKernelGGL(k_c3_fwd<W>, dim3(nb), dim3(TB), 0, st, g, zin, c.h2, t->acc(c.d_st2), n, t->d_params, off_m2,
-                           t->d_flt + c.f_bn2, off_w3, zout, ldacc, (const float *)t->d_params, fin, c.u);
+                           x.bn2, off_w3, zout, ldacc, (const float *)t->d_params, fin, c.u);
     }
 }
 
 template <int W>
-void coupling_backward(nf_trainer *t, const Geo &g, const TLayer &L, const float *zin, float invB, const float *zmix_in,
+void coupling_backward(nf_trainer *t, const Geo &g, const CplCtx &x, const float *zin, float invB, const float *zmix_in,
                        const float *A, Acc dA, hipStream_t st, const float *zlat)
 {
-    const Cpl &c = t->cpl[L.aux];
+    const Cpl &c = x.c;
     const unsigned nb = blocks_for(t, g.npix);
-    const int w = W, off_w1 = L.off, off_b1 = L.off + 18 * w, off_w2 = L.off + 21 * w, off_w3 = L.off + 24 * w + w * w;
-    const double n = (double)g.npix * t->sync_world;
-    const float *bn1 = t->d_flt + c.f_bn1, *bn2 = t->d_flt + c.f_bn2;
+    const int w = W, off_w1 = x.o.w1, off_b1 = x.o.b1, off_w2 = x.o.w2, off_w3 = x.o.w3;
+    const double n = x.n;
+    const float *bn1 = x.bn1, *bn2 = x.bn2;
     const Acc G = t->acc(0);
-    if (W == 32 && t->pr) {
-        if ((t->pr & 3) == 2) pr_coupling_backward<4>(t, g, L, zin, invB, zmix_in, A, dA, st, zlat);
-        else pr_coupling_backward<8>(t, g, L, zin, invB, zmix_in, A, dA, st, zlat);
-        return;
-    }
     const unsigned ng = std::min(nb, 96u);   // filter-gradient kernels: grid.y multiplies the workgroup count
     // The three filter-gradient kernels only feed the parameter gradient, not d loss / d z: they run
     // on the side stream, forked after their producer, while the main stream walks on.  The
     // temporaries they read are triple-buffered by coupling index; before a buffer set is reused
     // the main stream waits for the side work of the coupling that used it last.
-    const int par = L.aux % 3;
+    const int par = x.L.aux % 3;
     float *t1 = t->t1[par], *t2 = t->t2[par], *gu = t->gu[par];
-    hipStream_t sd = t->serial ? st : t->side;
-    if (t->done_pending[par]) {
-        (void)hipStreamWaitEvent(st, t->ev_done[par], 0);
-        t->done_pending[par] = false;
-    }
+    hipStream_t sd = t->side_of(st);
+    t->wait_set(st, par);
     const size_t gu_tile = ((size_t)(g.H + 2) * (g.W + 2) * 4 + g.HW) * sizeof(float);   // per-patch operand tile + pixel index
     constexpr bool kWide = W == 16 || W == 32;
     constexpr int WM = kWide ? W : 32;
@@ -2111,36 +2211,33 @@ void coupling_backward(nf_trainer *t, const Geo &g, const TLayer &L, const float
     const bool fuse_w3 = mfma_dh && fuse, fuse_w2 = kWide && (t->wide_mfma & 4) && fuse;
     const int S = patch_split(g);
     const unsigned npw = std::min<unsigned>((unsigned)(g.npix / g.HW) * S, (unsigned)g.nslot);   // grid of the per-patch kernels
-    if (mfma_dh && fuse_w3)
-        hipLaunchKernelGGL((k_c3_dh_mfma<WM, true>), dim3(npw), dim3(256), gu_tile, st, g,
-                           (const float *)c.h2, bn2, (const float *)t->d_params, off_w3, (const float *)gu, t1, t->acc(c.d_bs2), G, S, c3b);
-    else if (mfma_dh)
-        hipLaunchKernelGGL((k_c3_dh_mfma<WM, false>), dim3(npw), dim3(256), gu_tile, st, g,
-                           (const float *)c.h2, bn2, (const float *)t->d_params, off_w3, (const float *)gu, t1, t->acc(c.d_bs2), G, S, c3b);
+    if (mfma_dh)
+        with_bool(fuse_w3, [&](auto FUSE) {
+            hipLaunchKernelGGL((k_c3_dh_mfma<WM, decltype(FUSE)::value>), dim3(npw), dim3(256), gu_tile, st, g, (const float *)c.h2, bn2,
+                               (const float *)t->d_params, off_w3, (const float *)gu, t1, t->acc(c.d_bs2), G, S, c3b);
+        });
     else
         hipLaunchKernelGGL(k_c3_dh<W>, dim3(nb), dim3(TB), 0, st, g, c.h2, bn2, t->d_params, off_w3, gu, t1, t->acc(c.d_bs2));
     sync_slots(t, t->acc(c.d_bs2), 2 * w, g.nslot, st);
     const bool fin = W >= 16 && (t->wide_mfma & 8);
-    const float *pre2 = fin ? t->d_flt + c.f_bb2 : nullptr, *pre1 = fin ? t->d_flt + c.f_bb1 : nullptr;
-    if (fin) hipLaunchKernelGGL(k_bnb_fin, dim3(w), dim3(64), 0, st, t->acc(c.d_bs2), w, g.nslot, n, t->d_flt + c.f_bb2);
-    if (fuse_w2)
-        hipLaunchKernelGGL((k_c2_bwd_mfma<WM, true>), dim3(nb), dim3(256), 0, st, g, (const float *)c.h1, bn1, (const float *)c.h2, bn2,
-                           t->acc(c.d_bs2), n, (const float *)t->d_params, off_w2, t1, t2, t->acc(c.d_bs1), G, pre2);
-    else if (kWide && (t->wide_mfma & 4))
-        hipLaunchKernelGGL((k_c2_bwd_mfma<WM, false>), dim3(nb), dim3(256), 0, st, g, (const float *)c.h1, bn1, (const float *)c.h2, bn2,
-                           t->acc(c.d_bs2), n, (const float *)t->d_params, off_w2, t1, t2, t->acc(c.d_bs1), G, pre2);
+    const float *pre2 = fin ? x.bb2 : nullptr, *pre1 = fin ? x.bb1 : nullptr;
+    if (fin) hipLaunchKernelGGL(k_bnb_fin, dim3(w), dim3(64), 0, st, t->acc(c.d_bs2), w, g.nslot, n, x.bb2);
+    if (kWide && (t->wide_mfma & 4))
+        with_bool(fuse_w2, [&](auto FUSE) {
+            hipLaunchKernelGGL((k_c2_bwd_mfma<WM, decltype(FUSE)::value>), dim3(nb), dim3(256), 0, st, g, (const float *)c.h1, bn1,
+                               (const float *)c.h2, bn2, t->acc(c.d_bs2), n, (const float *)t->d_params, off_w2, t1, t2, t->acc(c.d_bs1), G, pre2);
+        });
     else
         hipLaunchKernelGGL(k_c2_bwd<W>, dim3(nb), dim3(TB), 0, st, g, c.h1, bn1, c.h2, bn2, t->acc(c.d_bs2), n, t->d_params, off_w2,
                            t1, t2, t->acc(c.d_bs1), G, pre2);
     sync_slots(t, t->acc(c.d_bs1), 2 * w, g.nslot, st);
-    if (fin) hipLaunchKernelGGL(k_bnb_fin, dim3(w), dim3(64), 0, st, t->acc(c.d_bs1), w, g.nslot, n, t->d_flt + c.f_bb1);
+    if (fin) hipLaunchKernelGGL(k_bnb_fin, dim3(w), dim3(64), 0, st, t->acc(c.d_bs1), w, g.nslot, n, x.bb1);
     if (fin && W % 4 == 0 && (256 % (W / 4)) == 0)
         hipLaunchKernelGGL(k_c1_bwd_flat<(W >= 16 ? W : 16)>, dim3(nb), dim3(256), 0, st, g, (const float *)c.h1, bn1, pre1, off_b1, t2, G);
     else
         hipLaunchKernelGGL(k_c1_bwd<W>, dim3(nb), dim3(TB), 0, st, g, c.h1, bn1, t->acc(c.d_bs1), n, off_b1, t2, G, pre1);
     // one fork per coupling (every event operation costs host time): all three producers are done
-    (void)hipEventRecord(t->ev_fork[0], st);
-    (void)hipStreamWaitEvent(sd, t->ev_fork[0], 0);
+    t->fork_side(st);
     // (the per-patch operand tiles of the matrix-core kernels sit in dynamic LDS: patches of up to ~3 000 pixels)
     if (kWide && (t->wide_mfma & 1) && ((size_t)(g.H + 2) * (g.W + 2) * 4 + g.HW) * sizeof(float) <= 60 * 1024) {
         const unsigned nw = std::min<unsigned>((unsigned)g.nslot, 512u);
@@ -2154,148 +2251,111 @@ void coupling_backward(nf_trainer *t, const Geo &g, const TLayer &L, const float
         hipLaunchKernelGGL(k_w2_grad<W>, dim3(ng, w), dim3(TB), 0, sd, g, c.h1, bn1, t1, off_w2, G);
         hipLaunchKernelGGL(k_w1_grad<W>, dim3(ng, 9), dim3(TB), 0, sd, g, zin, t2, off_w1, G);
     }
-    (void)hipEventRecord(t->ev_done[par], sd);
-    t->done_pending[par] = true;
-    // zmix_in != null: the backward of the preceding Conv2d1x1 is folded into this last stage
-    if (kWide && (t->wide_mfma & 64) && 3 * g.W <= t->band_cap) {
-        // (measured at 32x32, width 32: 46 us with 6-row bands = 8 tiles = two rounds of the 4 wavefronts, 55 us with 8-row bands;
-        // the l_last forward, twice the MFMA work per tile, is better off with the smaller halo share of 8-row bands)
-        const int cap = std::max(3 * g.W, std::min(t->band_cap, 256));
-        const int BR = std::max(1, std::min(g.H, cap / g.W - 2)), units = (int)(g.npix / g.HW) * ((g.H + BR - 1) / BR);
-        const size_t lds = (size_t)(((BR + 2) * g.W + 31) / 32 * 32) * 20 * sizeof(float);
-        const unsigned ngrid = std::min<unsigned>((unsigned)units, (unsigned)g.nslot);
-        if (zmix_in)
-            hipLaunchKernelGGL((k_c1_dz_mfma<WM, true>), dim3(ngrid), dim3(256), lds, st, g, (const float *)t2, (const float *)t->d_params,
-                               off_w1, t->dz, zmix_in, A, dA, BR, dz_src);
-        else
-            hipLaunchKernelGGL((k_c1_dz_mfma<WM, false>), dim3(ngrid), dim3(256), lds, st, g, (const float *)t2, (const float *)t->d_params,
-                               off_w1, t->dz, (const float *)nullptr, (const float *)nullptr, dA, BR, dz_src);
-    } else if (zmix_in) {
-        hipLaunchKernelGGL((k_c1_dz<W, true>), dim3(nb), dim3(TB), 0, st, g, t2, t->d_params, off_w1, t->dz, zmix_in, A, dA, dz_src);
-    } else {
-        hipLaunchKernelGGL((k_c1_dz<W, false>), dim3(nb), dim3(TB), 0, st, g, t2, t->d_params, off_w1, t->dz,
-                           (const float *)nullptr, (const float *)nullptr, dA, dz_src);
-    }
+    t->side_done(st, par);
+    // zmix_in != null: the backward of the preceding Conv2d1x1 is folded into this last stage (A is null without one)
+    with_bool(zmix_in != nullptr, [&](auto MIX) {
+        constexpr bool mix = decltype(MIX)::value;
+        if (kWide && (t->wide_mfma & 64) && 3 * g.W <= t->band_cap) {
+            // (measured at 32x32, width 32: 46 us with 6-row bands = 8 tiles = two rounds of the 4 wavefronts, 55 us with 8-row bands;
+            // the l_last forward, twice the MFMA work per tile, is better off with the smaller halo share of 8-row bands)
+            const int cap = std::max(3 * g.W, std::min(t->band_cap, 256));
+            const int BR = std::max(1, std::min(g.H, cap / g.W - 2)), units = (int)(g.npix / g.HW) * ((g.H + BR - 1) / BR);
+            const size_t lds = (size_t)(((BR + 2) * g.W + 31) / 32 * 32) * 20 * sizeof(float);
+            hipLaunchKernelGGL((k_c1_dz_mfma<WM, mix>), dim3(std::min<unsigned>((unsigned)units, (unsigned)g.nslot)), dim3(256), lds, st, g,
+                               (const float *)t2, (const float *)t->d_params, off_w1, t->dz, zmix_in, A, dA, BR, dz_src);
+        } else {
+            hipLaunchKernelGGL((k_c1_dz<W, mix>), dim3(nb), dim3(TB), 0, st, g, t2, t->d_params, off_w1, t->dz, zmix_in, A, dA, dz_src);
+        }
+    });
 }
 
 // The tiled form of coupling_forward (k_tiled_fwd): `f1_done` = this coupling's stage 1 already ran in the launch that
-// finished the coupling below it; `nxt` = the coupling above (index `ln`, behind a Conv2d1x1 when nxt_A != null) whose stage 1
-// shares this coupling's last launch.
+// finished the coupling below it; `nx` = the coupling above (behind a Conv2d1x1 when nx.A != null) whose stage 1
+// shares this coupling's last launch.  Returns whether one did.
 template <int W, int NT>
-void coupling_forward_tiled(nf_trainer *t, const Geo &g, const TLayer &L, const float *zin, float *zout, Acc ldacc,
-                            const float *zpre, const float *A, hipStream_t st, bool f1_done, const TLayer *nxt, const float *nxt_A,
-                            float *nxt_zin)
+bool coupling_forward_tiled(nf_trainer *t, const Geo &g, const CplCtx &x, const float *zin, float *zout, Acc ldacc,
+                            const float *zpre, const float *A, hipStream_t st, bool f1_done, const Rider &nx)
 {
-    const Cpl &c = t->cpl[L.aux];
+    const Cpl &c = x.c;
     const unsigned nb = blocks_for(t, g.npix), npatch = (unsigned)(g.npix / g.HW);
-    const int w = W, off_w1 = L.off, off_m1 = L.off + 19 * w, off_w2 = L.off + 21 * w, off_m2 = L.off + 22 * w + w * w,
-              off_w3 = L.off + 24 * w + w * w;
-    const double n = (double)g.npix * t->sync_world;
+    const int w = W;
+    const double n = x.n;
+    const float *P = t->d_params;
     const size_t smem = ((size_t)(g.H + 2) * (g.W + 2) * (W + 2) + (NT / 16) * (1 + 2 * W)) * sizeof(float);
     if (!f1_done) {
-        const TiledF1 f1{A, const_cast<float *>(zin), off_w1, c.h1, t->acc(c.d_st1)};
+        const TiledF1 f1{A, const_cast<float *>(zin), x.o.w1, c.h1, t->acc(c.d_st1)};
         if (zpre)
-            hipLaunchKernelGGL((k_tiled_fwd<W, NT, false, true, true>), dim3(npatch), dim3(NT), smem, st, g, TiledF3{}, f1, zpre, n, t->d_params, (const float *)t->d_params);
+            hipLaunchKernelGGL((k_tiled_fwd<W, NT, false, true, true>), dim3(npatch), dim3(NT), smem, st, g, TiledF3{}, f1, zpre, n, t->d_params, P);
         else
-            hipLaunchKernelGGL((k_tiled_fwd<W, NT, false, false, true>), dim3(npatch), dim3(NT), smem, st, g, TiledF3{}, f1, zin, n, t->d_params, (const float *)t->d_params);
+            hipLaunchKernelGGL((k_tiled_fwd<W, NT, false, false, true>), dim3(npatch), dim3(NT), smem, st, g, TiledF3{}, f1, zin, n, t->d_params, P);
     }
     sync_slots(t, t->acc(c.d_st1), 2 * w, g.nslot, st);
-    hipLaunchKernelGGL(k_c2_fwd<W>, dim3(nb), dim3(TB), 0, st, g, c.h1, t->acc(c.d_st1), n, t->d_params, off_m1,
-                       t->d_flt + c.f_bn1, off_w2, c.h2, t->acc(c.d_st2), (const float *)t->d_params, false);
+    hipLaunchKernelGGL(k_c2_fwd<W>, dim3(nb), dim3(TB), 0, st, g, c.h1, t->acc(c.d_st1), n, t->d_params, x.o.m1,
+                       x.bn1, x.o.w2, c.h2, t->acc(c.d_st2), P, false);
     sync_slots(t, t->acc(c.d_st2), 2 * w, g.nslot, st);
-    const TiledF3 f3{zin, c.h2, t->acc(c.d_st2), off_m2, off_w3, t->d_flt + c.f_bn2, zout, ldacc};
-    if (nxt) {
-        const Cpl &cn = t->cpl[nxt->aux];
-        const TiledF1 f1{nxt_A, nxt_zin, nxt->off, cn.h1, t->acc(cn.d_st1)};
-        if (nxt_A)
-            hipLaunchKernelGGL((k_tiled_fwd<W, NT, true, true, true>), dim3(npatch), dim3(NT), smem, st, g, f3, f1, (const float *)nullptr, n, t->d_params, (const float *)t->d_params);
+    const TiledF3 f3{zin, c.h2, t->acc(c.d_st2), x.o.m2, x.o.w3, x.bn2, zout, ldacc};
+    if (nx.L) {
+        const Cpl &cn = t->cpl[nx.L->aux];
+        const TiledF1 f1{nx.A, nx.zin, cpl_off(nx.L->off, w).w1, cn.h1, t->acc(cn.d_st1)};
+        if (nx.A)
+            hipLaunchKernelGGL((k_tiled_fwd<W, NT, true, true, true>), dim3(npatch), dim3(NT), smem, st, g, f3, f1, (const float *)nullptr, n, t->d_params, P);
         else
-            hipLaunchKernelGGL((k_tiled_fwd<W, NT, true, false, true>), dim3(npatch), dim3(NT), smem, st, g, f3, f1, (const float *)nullptr, n, t->d_params, (const float *)t->d_params);
+            hipLaunchKernelGGL((k_tiled_fwd<W, NT, true, false, true>), dim3(npatch), dim3(NT), smem, st, g, f3, f1, (const float *)nullptr, n, t->d_params, P);
     } else {
-        hipLaunchKernelGGL((k_tiled_fwd<W, NT, true, false, false>), dim3(npatch), dim3(NT), smem, st, g, f3, TiledF1{}, (const float *)nullptr, n, t->d_params, (const float *)t->d_params);
+        hipLaunchKernelGGL((k_tiled_fwd<W, NT, true, false, false>), dim3(npatch), dim3(NT), smem, st, g, f3, TiledF1{}, (const float *)nullptr, n, t->d_params, P);
     }
+    return nx.L != nullptr;
 }
 
-// The tiled form of coupling_backward (k_tiled_CA above): `a_done` = this coupling's stage A' already ran in the launch
-// that finished the coupling above it; `nxt` = the coupling below whose A' shares this coupling's last launch (or null).
+// The tiled form of coupling_backward (k_tiled_CA): `a_done` = this coupling's stage A' already ran in the launch
+// that finished the coupling above it; `nx` = the coupling below whose A' shares this coupling's last launch.  Returns whether one did.
 // The temporaries the side stream reads are triple-buffered by coupling index: A' of the coupling below is written while
 // the filter-gradient kernels of this one and of the one above may still be running.
 template <int W, int NT>
-void coupling_backward_tiled(nf_trainer *t, const Geo &g, const TLayer &L, const float *zin, float invB, const float *zmix_in,
-                             const float *A, Acc dA, hipStream_t st, const float *zlat, bool a_done, const TLayer *nxt,
-                             const float *nxt_zin)
+bool coupling_backward_tiled(nf_trainer *t, const Geo &g, const CplCtx &x, const float *zin, float invB, const float *zmix_in,
+                             const float *A, Acc dA, hipStream_t st, const float *zlat, bool a_done, const Rider &nx)
 {
-    const Cpl &c = t->cpl[L.aux];
+    const Cpl &c = x.c;
     const unsigned nb = blocks_for(t, g.npix), npatch = (unsigned)(g.npix / g.HW);
-    const int w = W, off_w1 = L.off, off_w2 = L.off + 21 * w, off_w3 = L.off + 24 * w + w * w;
-    const double n = (double)g.npix * t->sync_world;
-    const float *bn1 = t->d_flt + c.f_bn1, *bn2 = t->d_flt + c.f_bn2;
+    const int w = W;
+    const double n = x.n;
+    const float *bn1 = x.bn1, *bn2 = x.bn2, *P = t->d_params;
     const Acc G = t->acc(0);
     const unsigned ng = std::min(nb, 96u);
-    const int set = L.aux % 3;
+    const int set = x.L.aux % 3;
     float *t1 = t->t1[set], *t2 = t->t2[set], *gu = t->gu[set];
-    hipStream_t sd = t->serial ? st : t->side;
+    hipStream_t sd = t->side_of(st);
     const size_t smem = ((size_t)(g.H + 2) * (g.W + 2) * (W + 4) + (NT / 16) * (W + 16 + 2 * W + 9)) * sizeof(float);
-    auto wait_set = [&](int k) {
-        if (t->done_pending[k]) {
-            (void)hipStreamWaitEvent(st, t->ev_done[k], 0);
-            t->done_pending[k] = false;
-        }
-    };
-    const TiledA me{zin, c.h2, bn2, off_w3, gu, t1, t->acc(c.d_bs2)};
+    const TiledA me{zin, c.h2, bn2, x.o.w3, gu, t1, t->acc(c.d_bs2)};
     if (!a_done) {
-        wait_set(set);
-        hipLaunchKernelGGL((k_tiled_CA<W, NT, false, false, true>), dim3(npatch), dim3(NT), smem, st, g, TiledC{}, me, n,
-                           (const float *)t->d_params, invB, t->dz, zlat, G);
+        t->wait_set(st, set);
+        hipLaunchKernelGGL((k_tiled_CA<W, NT, false, false, true>), dim3(npatch), dim3(NT), smem, st, g, TiledC{}, me, n, P, invB, t->dz, zlat, G);
     }
     sync_slots(t, t->acc(c.d_bs2), 2 * w, g.nslot, st);
-    hipLaunchKernelGGL(k_c2_bwd<W>, dim3(nb), dim3(TB), 0, st, g, c.h1, bn1, c.h2, bn2, t->acc(c.d_bs2), n, t->d_params, off_w2,
+    hipLaunchKernelGGL(k_c2_bwd<W>, dim3(nb), dim3(TB), 0, st, g, c.h1, bn1, c.h2, bn2, t->acc(c.d_bs2), n, t->d_params, x.o.w2,
                        t1, t2, t->acc(c.d_bs1), G, (const float *)nullptr);
     sync_slots(t, t->acc(c.d_bs1), 2 * w, g.nslot, st);
-    const TiledC cc{zmix_in, A, c.h1, bn1, t2, off_w1, t->acc(c.d_bs1), dA};
+    const TiledC cc{zmix_in, A, c.h1, bn1, t2, x.o.w1, t->acc(c.d_bs1), dA};
     TiledA below{};
-    if (nxt) {
-        const Cpl &cn = t->cpl[nxt->aux];
-        const int ns = nxt->aux % 3;
-        wait_set(ns);
-        below = TiledA{nxt_zin, cn.h2, t->d_flt + cn.f_bn2, nxt->off + 24 * w + w * w, t->gu[ns], t->t1[ns], t->acc(cn.d_bs2)};
+    if (nx.L) {
+        const CplCtx xn = cpl_ctx(t, g, *nx.L);
+        const int ns = nx.L->aux % 3;
+        t->wait_set(st, ns);
+        below = TiledA{nx.zin, xn.c.h2, xn.bn2, xn.o.w3, t->gu[ns], t->t1[ns], t->acc(xn.c.d_bs2)};
     }
-#define NF_TILED(MIX, NEXT)                                                                                                        \
-    hipLaunchKernelGGL((k_tiled_CA<W, NT, true, MIX, NEXT>), dim3(npatch), dim3(NT), smem, st, g, cc, below, n,                    \
-                       (const float *)t->d_params, invB, t->dz, (const float *)nullptr, G)
-    if (zmix_in) {
-        if (nxt) NF_TILED(true, true); else NF_TILED(true, false);
-    } else {
-        if (nxt) NF_TILED(false, true); else NF_TILED(false, false);
-    }
-#undef NF_TILED
-    (void)hipEventRecord(t->ev_fork[0], st);
-    (void)hipStreamWaitEvent(sd, t->ev_fork[0], 0);
-    hipLaunchKernelGGL(k_w3_grad<W>, dim3(ng, 9), dim3(TB), 0, sd, g, c.h2, bn2, gu, off_w3, G);
-    hipLaunchKernelGGL(k_w2_grad<W>, dim3(ng, w), dim3(TB), 0, sd, g, c.h1, bn1, t1, off_w2, G);
-    hipLaunchKernelGGL(k_w1_grad<W>, dim3(ng, 9), dim3(TB), 0, sd, g, zin, t2, off_w1, G);
-    (void)hipEventRecord(t->ev_done[set], sd);
-    t->done_pending[set] = true;
+    with_bool(zmix_in != nullptr, [&](auto MIX) {
+        with_bool(nx.L != nullptr, [&](auto NEXT) {
+            hipLaunchKernelGGL((k_tiled_CA<W, NT, true, decltype(MIX)::value, decltype(NEXT)::value>), dim3(npatch), dim3(NT), smem, st, g, cc,
+                               below, n, P, invB, t->dz, (const float *)nullptr, G);
+        });
+    });
+    t->fork_side(st);
+    hipLaunchKernelGGL(k_w3_grad<W>, dim3(ng, 9), dim3(TB), 0, sd, g, c.h2, bn2, gu, x.o.w3, G);
+    hipLaunchKernelGGL(k_w2_grad<W>, dim3(ng, w), dim3(TB), 0, sd, g, c.h1, bn1, t1, x.o.w2, G);
+    hipLaunchKernelGGL(k_w1_grad<W>, dim3(ng, 9), dim3(TB), 0, sd, g, zin, t2, x.o.w1, G);
+    t->side_done(st, set);
+    return nx.L != nullptr;
 }
-
-// the tiled stages take one thread per pixel of a patch and one accumulator slot per patch
-bool tiled_ok(const nf_trainer *t, const Geo &g, int width, int pass /* 1 backward, 2 forward */)
-{
-    // measured on the shipped model (both passes tiled): 0.61 vs 0.77 ms per step at 138 patches, 0.77 vs 0.88 at 256, break-even
-    // near 400 (one 1024-thread workgroup per CU: past one round over the 256 CUs the layer kernels' finer grain wins)
-    const int64_t npatch = g.npix / g.HW;
-    // (NF_TRAIN_GEMM=1 sends widths 4 / 8 down the GEMM path: the create-time allocation and this dispatch share gemm_width())
-    return (t->tiled & pass) && !(t->all_gemm || gemm_width(width)) && (width == 4 || width == 8) && g.HW <= 1024 && npatch <= g.nslot && npatch <= 384;
-}
-
-#define NF_WIDTH_SWITCH(w, CALL)            \
-    switch (w) {                            \
-    case 4: CALL(4); break;                 \
-    case 8: CALL(8); break;                 \
-    case 16: CALL(16); break;               \
-    case 32: CALL(32); break;               \
-    default: break;                         \
-    }
 
 int cond_index(const nf_cond *cond, bool needed, bool needs_cam, CondIdx &ci)
 {
@@ -2324,6 +2384,10 @@ extern "C" {
 int nf_trainer_destroy(nf_trainer *t)
 {
     if (!t) return NF_OK;
+    if (t->owned.empty() && !t->side) {   // create failed before its first device call: nothing on the device, no HIP call here either
+        delete t;
+        return NF_OK;
+    }
     Guard guard;
     (void)guard.enter(t->device);
     if (t->side) {
@@ -2337,15 +2401,6 @@ int nf_trainer_destroy(nf_trainer *t)
     for (void *p : t->owned) (void)hipFree(p);
     delete t;
     return NF_OK;
-}
-
-static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params,
-                               int64_t max_batch, int32_t optimizer, bool eval_only, nf_trainer **out);
-
-int nf_trainer_create(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params,
-                      int64_t max_batch, int32_t optimizer, nf_trainer **out)
-{
-    return trainer_create_impl(cfg, layers, params, n_params, max_batch, optimizer, false, out);
 }
 
 static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params,
@@ -2364,6 +2419,12 @@ static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers
 
     nf_trainer *t = new (std::nothrow) nf_trainer();
     if (!t) return nf_fail(NF_ENOMEM, "out of host memory");
+    int rc;
+#define NF_TRY(x)                 \
+    if ((rc = (x)) != NF_OK) {    \
+        nf_trainer_destroy(t);    \
+        return rc;                \
+    }
     t->cfg = *cfg;
     t->eval_only = t->all_gemm = eval_only;
     if (const char *e = getenv("NF_TRAIN_TILED")) t->tiled = atoi(e);
@@ -2383,17 +2444,11 @@ static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers
     for (int i = 0; i < cfg->n_layers; ++i) {
         const nf_layer_desc &L = layers[i];
         const int64_t cnt = nf_layer_param_count(L.type, L.width);
-        if (cnt < 0 || L.param_offset < 0 || (uint64_t)L.param_offset + (uint64_t)cnt > n_params) {
-            delete t;
-            return nf_fail(NF_EINVAL, "layer %d: bad type / width / parameter range", i);
-        }
+        if (cnt < 0 || L.param_offset < 0 || (uint64_t)L.param_offset + (uint64_t)cnt > n_params) NF_TRY(nf_fail(NF_EINVAL, "layer %d: bad type / width / parameter range", i));
         // the slotted-sum storage is indexed by parameter position with the l_2/W bodies cut out (`holes`, `acc()`): that
         // bookkeeping — and the one-gradient-per-variable contract — needs the layers' parameter blocks in ascending order, disjoint
-        if (L.param_offset < prev_end) {
-            delete t;
-            return nf_fail(NF_EINVAL, "layer %d: parameter blocks must be ascending and must not overlap (offset %lld, previous block ends at %lld)",
-                           i, (long long)L.param_offset, (long long)prev_end);
-        }
+        if (L.param_offset < prev_end) NF_TRY(nf_fail(NF_EINVAL, "layer %d: parameter blocks must be ascending and must not overlap (offset %lld, previous block ends at %lld)",
+                           i, (long long)L.param_offset, (long long)prev_end));
         prev_end = L.param_offset + cnt;
         TLayer &T = t->tl.l[i];
         T.type = L.type;
@@ -2408,14 +2463,8 @@ static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers
             break;
         case NF_LAYER_COUPLING: {
             const int w = L.width;
-            if (w < 1 || w > 512) {
-                delete t;
-                return nf_fail(NF_EINVAL, "layer %d: the trainer takes the coupling widths 1 .. 512 (%d given)", i, w);
-            }
-            if (t->width && t->width != w) {
-                delete t;
-                return nf_fail(NF_EINVAL, "all coupling layers must share one width");
-            }
+            if (w < 1 || w > 512) NF_TRY(nf_fail(NF_EINVAL, "layer %d: the trainer takes the coupling widths 1 .. 512 (%d given)", i, w));
+            if (t->width && t->width != w) NF_TRY(nf_fail(NF_EINVAL, "all coupling layers must share one width"));
             t->width = w;
             T.aux = n_cpl++;
             for (int64_t k = 0; k < cnt; ++k) mk[k] = 1;
@@ -2475,32 +2524,45 @@ static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers
             t->needs_cond = true;
             break;
         default:
-            delete t;
-            return nf_fail(NF_EINVAL, "layer %d: unknown layer type %d", i, L.type);
+            NF_TRY(nf_fail(NF_EINVAL, "layer %d: unknown layer type %d", i, L.type));
         }
     }
 
+    // the step plan: each coupling's folded Conv2d1x1 and its fusable neighbours.  The layer list is fixed, so this is asked once, here.
+    for (int l = 0; l < t->tl.n; ++l) {
+        const TLayer *ls = t->tl.l;
+        CplPlan &p = t->plan[l];
+        p.fold = p.above = p.above_mix = p.below = -1;
+        if (ls[l].type != NF_LAYER_COUPLING) continue;
+        const auto same = [&](int k) { return k >= 0 && k < t->tl.n && ls[k].type == NF_LAYER_COUPLING && ls[k].width == ls[l].width; };
+        if (l > 0 && ls[l - 1].type == NF_LAYER_CONV1X1) p.fold = l - 1;
+        // above: directly, or behind ONE Conv2d1x1.  (Asymmetry: the patch-resident forward fuses only behind a Conv2d1x1 — stage 0 of
+        // k_pr_fwd<2, ..., true> always mixes —, the tiled forward in both cases: trainer_run asks above_mix.)
+        const bool mix_above = l + 1 < t->tl.n && ls[l + 1].type == NF_LAYER_CONV1X1;
+        if (same(l + 1 + mix_above)) {
+            p.above = l + 1 + mix_above;
+            p.above_mix = mix_above ? l + 1 : -1;
+        }
+        // below: both backward passes look through the FOLDED Conv2d1x1 only (it is this coupling's own last stage that applies it)
+        const int lb = p.fold >= 0 ? l - 2 : l - 1;
+        if (same(lb)) p.below = lb;
+    }
+
     hipError_t e;
-    if (cfg->device >= 0) {
-        t->device = cfg->device;
-    } else if ((e = hipGetDevice(&t->device)) != hipSuccess) {
-        delete t;
-        return nf_fail_hip(e, "hipGetDevice");
-    }
+    if (cfg->device >= 0) t->device = cfg->device;
+    else if ((e = hipGetDevice(&t->device)) != hipSuccess) NF_TRY(nf_fail_hip(e, "hipGetDevice"));
     Guard guard;
-    int rc = guard.enter(t->device);
-    if (rc != NF_OK) {
-        delete t;
-        return rc;
-    }
+    NF_TRY(guard.enter(t->device));
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess && cus > 0) t->n_cu = cus;
 
     const int w = t->width ? t->width : 4;
     const size_t act = (size_t)max_batch * cfg->height * cfg->width;   // pixels
     t->n_mix = n_mix;
-    const bool gemm_path = t->all_gemm || gemm_width(w);
-    // width 32 on 32x32 patches: the patch-resident stages (nf_train_pr.h) — no [pixel][32] tensor exists, none is allocated
-    // (the batch-statistics evaluator, a trimmed trainer otherwise on the GEMM path, takes its forward stages too)
-    t->pr = (t->pr && t->wide_mfma != 0 && w == 32 && (!gemm_path || eval_only) && cfg->height == 32 && cfg->width == 32 && n_cpl > 0) ? t->pr : 0;
+    // The family decides what exists: the patch-resident stages keep no [pixel][w] tensor (h1 / h2 / t1 / t2), the GEMM path keeps its
+    // operand windows and packed weights and ONE buffer set (no side work), every family but the two narrow ones keeps l_last's output u.
+    const TrainPath fam = t->family = train_family(t, w, n_cpl);
+    const bool gemm_ws = fam == TP_GEMM && n_cpl > 0, pixel_tensors = fam != TP_PR;
     // double workspace
     size_t nd = eval_only ? 0 : n_params;
     t->d_dA = (int)nd; nd += eval_only ? 0 : 16 * (size_t)n_mix;
@@ -2523,11 +2585,11 @@ static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers
     if (eval_only) nd = 4 * (size_t)w;
     t->d_ldc = (int)nd; nd += 1;   // last: the only value accumulated directly (k_prep), not through slots
     t->n_dbl = nd;
-    if (gemm_path && !eval_only)
+    if (fam == TP_GEMM && !eval_only)
         for (int l = 0; l < t->tl.n; ++l) {
             const TLayer &L = t->tl.l[l];
             if (L.type != NF_LAYER_COUPLING) continue;
-            t->holes.emplace_back(L.off + 21 * L.width, L.width * L.width);
+            t->holes.emplace_back(cpl_off(L.off, L.width).w2, L.width * L.width);
             t->hole_rows += (size_t)L.width * L.width;
         }
     // float scalars
@@ -2543,11 +2605,6 @@ static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers
     }
     t->n_flt = nf;
 
-#define NF_TRY(x)                 \
-    if ((rc = (x)) != NF_OK) {    \
-        nf_trainer_destroy(t);    \
-        return rc;                \
-    }
     NF_TRY(dev_alloc(t, (void **)&t->d_params, n_params * sizeof(float)));
     NF_TRY(dev_alloc(t, (void **)&t->d_dbl, nd * sizeof(double)));
     NF_TRY(dev_alloc(t, (void **)&t->d_part, t->part_floats() * sizeof(float)));
@@ -2557,13 +2614,7 @@ static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers
         NF_TRY(dev_alloc(t, (void **)&t->eldp, (size_t)max_batch * sizeof(double)));
         NF_TRY(dev_alloc(t, (void **)&t->emom, (size_t)std::max(n_cpl, 1) * 4 * w * sizeof(float)));
         NF_TRY(dev_alloc(t, (void **)&t->eAinv, (size_t)std::max(n_mix, 1) * 16 * sizeof(float)));
-        if (t->pr) {   // width 32 on 32x32 patches: the patch-resident forward stages need their packed weights and nothing else
-            NF_TRY(dev_alloc(t, (void **)&t->pr_img, (size_t)n_cpl * PR_SIZE * sizeof(float)));
-            if ((rc = pr_set_attributes(t->pr)) != NF_OK) {
-                nf_trainer_destroy(t);
-                return rc;
-            }
-        } else if (n_cpl > 0) {
+        if (gemm_ws) {   // ONE pair of hidden tensors, one coupling's windows and packed weights
             float *h1 = nullptr, *h2 = nullptr;
             NF_TRY(dev_alloc(t, (void **)&h1, act * w * sizeof(float)));
             NF_TRY(dev_alloc(t, (void **)&h2, act * w * sizeof(float)));
@@ -2575,104 +2626,77 @@ static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers
             NF_TRY(dev_alloc(t, (void **)&t->gp36, act * 36 * sizeof(float)));
             NF_TRY(dev_alloc(t, (void **)&t->gpack, gemm_pack_floats(w) * sizeof(float)));
         }
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess && cus > 0) t->n_cu = cus;
-        if ((e = hipMemcpy(t->d_params, params, n_params * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemset(t->d_part, 0, t->part_floats() * sizeof(float))) != hipSuccess) {
-            nf_trainer_destroy(t);
-            return nf_fail_hip(e, "evaluator initialisation");
+    } else {
+        NF_TRY(dev_alloc(t, (void **)&t->d_m, n_params * sizeof(float)));
+        NF_TRY(dev_alloc(t, (void **)&t->d_v, n_params * sizeof(float)));
+        NF_TRY(dev_alloc(t, (void **)&t->d_gradf, n_params * sizeof(float)));
+        NF_TRY(dev_alloc(t, (void **)&t->d_mask, n_params));
+        NF_TRY(dev_alloc(t, (void **)&t->d_patch, 2 * (size_t)max_batch * sizeof(float)));
+        NF_TRY(dev_alloc(t, (void **)&t->d_wpart, 2 * ((act + 63) / 64) * sizeof(float)));
+        t->zs.assign(cfg->n_layers + 1, nullptr);
+        for (int i = 1; i <= cfg->n_layers; ++i) NF_TRY(dev_alloc(t, (void **)&t->zs[i], act * 4 * sizeof(float)));
+        for (Cpl &c : t->cpl) {
+            if (pixel_tensors) {
+                NF_TRY(dev_alloc(t, (void **)&c.h1, act * w * sizeof(float)));
+                NF_TRY(dev_alloc(t, (void **)&c.h2, act * w * sizeof(float)));
+            }
+            if (fam != TP_LAYER && fam != TP_TILED) NF_TRY(dev_alloc(t, (void **)&c.u, act * 4 * sizeof(float)));
         }
-        *out = t;
-        return NF_OK;
-    }
-    NF_TRY(dev_alloc(t, (void **)&t->d_m, n_params * sizeof(float)));
-    NF_TRY(dev_alloc(t, (void **)&t->d_v, n_params * sizeof(float)));
-    NF_TRY(dev_alloc(t, (void **)&t->d_gradf, n_params * sizeof(float)));
-    NF_TRY(dev_alloc(t, (void **)&t->d_mask, n_params));
-    NF_TRY(dev_alloc(t, (void **)&t->d_patch, 2 * (size_t)max_batch * sizeof(float)));
-    NF_TRY(dev_alloc(t, (void **)&t->d_wpart, 2 * ((act + 63) / 64) * sizeof(float)));
-    t->zs.assign(cfg->n_layers + 1, nullptr);
-    for (int i = 1; i <= cfg->n_layers; ++i) NF_TRY(dev_alloc(t, (void **)&t->zs[i], act * 4 * sizeof(float)));
-    for (Cpl &c : t->cpl) {
-        if (!t->pr) {
-            NF_TRY(dev_alloc(t, (void **)&c.h1, act * w * sizeof(float)));
-            NF_TRY(dev_alloc(t, (void **)&c.h2, act * w * sizeof(float)));
+        if (gemm_ws) {   // nf_train_gemm.h
+            t->gz18_stride = act * kZ18;
+            NF_TRY(dev_alloc(t, (void **)&t->gz18, (size_t)n_cpl * t->gz18_stride * sizeof(float)));
+            NF_TRY(dev_alloc(t, (void **)&t->gp36, act * 36 * sizeof(float)));
+            NF_TRY(dev_alloc(t, (void **)&t->gq18, act * 18 * sizeof(float)));
+            NF_TRY(dev_alloc(t, (void **)&t->gpack, (size_t)n_cpl * gemm_pack_floats(w) * sizeof(float)));
+            NF_TRY(dev_alloc(t, (void **)&t->gdw, (size_t)n_cpl * 3 * gemm_part_floats(w) * sizeof(float)));
+            if (const char *ev = getenv("NF_TRAIN_GEMM_C1")) t->gemm_c1_fused = atoi(ev) != 0;
+            t->nb_floor = w <= 128 ? 512 : 0;   // measured at 138 patches: width 64 3.35 -> 3.21 ms, 128 5.37 -> 4.93; 256 / 512 + 1 % with it
+            if (const char *ev = getenv("NF_TRAIN_NB_FLOOR")) t->nb_floor = atoi(ev);   // A/B aid
         }
-        if (w >= 16 || gemm_path) NF_TRY(dev_alloc(t, (void **)&c.u, act * 4 * sizeof(float)));
-    }
-    if (gemm_path && n_cpl > 0) {   // nf_train_gemm.h
-        t->gz18_stride = act * kZ18;
-        NF_TRY(dev_alloc(t, (void **)&t->gz18, (size_t)n_cpl * t->gz18_stride * sizeof(float)));
-        NF_TRY(dev_alloc(t, (void **)&t->gp36, act * 36 * sizeof(float)));
-        NF_TRY(dev_alloc(t, (void **)&t->gq18, act * 18 * sizeof(float)));
-        NF_TRY(dev_alloc(t, (void **)&t->gpack, (size_t)n_cpl * gemm_pack_floats(w) * sizeof(float)));
-        NF_TRY(dev_alloc(t, (void **)&t->gdw, (size_t)n_cpl * 3 * gemm_part_floats(w) * sizeof(float)));
-        if (const char *ev = getenv("NF_TRAIN_GEMM_C1")) t->gemm_c1_fused = atoi(ev) != 0;
-        t->nb_floor = w <= 128 ? 512 : 0;   // measured at 138 patches: width 64 3.35 -> 3.21 ms, 128 5.37 -> 4.93; 256 / 512 + 1 % with it
-        if (const char *ev = getenv("NF_TRAIN_NB_FLOOR")) t->nb_floor = atoi(ev);   // A/B aid
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess && cus > 0) t->n_cu = cus;
-    }
-    for (int k = 0; k < (gemm_path ? 1 : 3); ++k) {
-        if (!t->pr) {
-            NF_TRY(dev_alloc(t, (void **)&t->t1[k], act * w * sizeof(float)));
-            NF_TRY(dev_alloc(t, (void **)&t->t2[k], act * w * sizeof(float)));
+        for (int k = 0; k < (fam == TP_GEMM ? 1 : 3); ++k) {
+            if (pixel_tensors) {
+                NF_TRY(dev_alloc(t, (void **)&t->t1[k], act * w * sizeof(float)));
+                NF_TRY(dev_alloc(t, (void **)&t->t2[k], act * w * sizeof(float)));
+            }
+            NF_TRY(dev_alloc(t, (void **)&t->gu[k], act * 4 * sizeof(float)));
         }
-        NF_TRY(dev_alloc(t, (void **)&t->gu[k], act * 4 * sizeof(float)));
+        NF_TRY(dev_alloc(t, (void **)&t->dz, act * 4 * sizeof(float)));
+        if (w >= 16) NF_TRY(dev_alloc(t, (void **)&t->dz2, act * 4 * sizeof(float)));
+        if (fam == TP_PR) {
+            if (const char *ev = getenv("NF_TRAIN_PR_GRID")) t->n_cu = std::max(1, atoi(ev));   // A/B aid: workgroups of the patch-resident stages
+            if (const char *ev = getenv("NF_TRAIN_PR_SIDE_FULL")) t->pr_side_full = atoi(ev);
+            if (const char *ev = getenv("NF_TRAIN_PR_BOTH_MAX")) t->pr_both_max = atoi(ev);
+        }
     }
-    NF_TRY(dev_alloc(t, (void **)&t->dz, act * 4 * sizeof(float)));
-    if (w >= 16) NF_TRY(dev_alloc(t, (void **)&t->dz2, act * 4 * sizeof(float)));
-    if (t->pr) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess && cus > 0) t->n_cu = cus;
-        if (const char *ev = getenv("NF_TRAIN_PR_GRID")) t->n_cu = std::max(1, atoi(ev));   // A/B aid: workgroups of the patch-resident stages
-        if (const char *ev = getenv("NF_TRAIN_PR_SIDE_FULL")) t->pr_side_full = atoi(ev);
-        if (const char *ev = getenv("NF_TRAIN_PR_BOTH_MAX")) t->pr_both_max = atoi(ev);
+    if (fam == TP_PR) {   // the packed weights of a step; the stages' dynamic LDS
         NF_TRY(dev_alloc(t, (void **)&t->pr_img, (size_t)n_cpl * PR_SIZE * sizeof(float)));
-        if ((rc = pr_set_attributes(t->pr)) != NF_OK) {
-            nf_trainer_destroy(t);
-            return rc;
+        NF_TRY(pr_set_attributes(t));
+    }
+    if ((e = hipMemcpy(t->d_params, params, n_params * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
+        // slots of values no kernel ever writes (constants, the gain parameters of other ISOs) stay zero
+        (e = hipMemset(t->d_part, 0, t->part_floats() * sizeof(float))) != hipSuccess)
+        NF_TRY(nf_fail_hip(e, eval_only ? "evaluator initialisation" : "trainer initialisation"));
+    if (!eval_only) {   // the optimizer state, the side stream and its events
+        if ((e = hipMemcpy(t->d_mask, mask.data(), n_params, hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemset(t->d_m, 0, n_params * sizeof(float))) != hipSuccess ||
+            (e = hipMemset(t->d_v, 0, n_params * sizeof(float))) != hipSuccess ||
+            (e = hipMemset(t->d_gradf, 0, n_params * sizeof(float))) != hipSuccess)
+            NF_TRY(nf_fail_hip(e, "trainer initialisation"));
+        if ((e = hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking)) != hipSuccess) NF_TRY(nf_fail_hip(e, "hipStreamCreate(trainer side stream)"));
+        for (int k = 0; k < 6; ++k) {
+            hipEvent_t *ev = k < 3 ? &t->ev_fork[k] : &t->ev_done[k - 3];
+            if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) NF_TRY(nf_fail_hip(e, "hipEventCreate(trainer)"));
         }
     }
 #undef NF_TRY
-    if ((e = hipMemcpy(t->d_params, params, n_params * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(t->d_mask, mask.data(), n_params, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemset(t->d_m, 0, n_params * sizeof(float))) != hipSuccess ||
-        (e = hipMemset(t->d_v, 0, n_params * sizeof(float))) != hipSuccess ||
-        (e = hipMemset(t->d_gradf, 0, n_params * sizeof(float))) != hipSuccess ||
-        // slots of values no kernel ever writes (constants, the gain parameters of other ISOs) stay zero
-        (e = hipMemset(t->d_part, 0, t->part_floats() * sizeof(float))) != hipSuccess) {
-        nf_trainer_destroy(t);
-        return nf_fail_hip(e, "trainer initialisation");
-    }
-    if ((e = hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking)) != hipSuccess) {
-        nf_trainer_destroy(t);
-        return nf_fail_hip(e, "hipStreamCreate(trainer side stream)");
-    }
-    for (int k = 0; k < 6; ++k) {
-        hipEvent_t *ev = k < 3 ? &t->ev_fork[k] : &t->ev_done[k - 3];
-        if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) {
-            nf_trainer_destroy(t);
-            return nf_fail_hip(e, "hipEventCreate(trainer)");
-        }
-    }
     *out = t;
     return NF_OK;
 }
 
-static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B, const nf_cond *cond, float *grads_out,
-                       float *loss_out, void *stream, bool backward);
-
-int nf_trainer_forward_backward(nf_trainer *t, const float *x, const float *y, int64_t B, const nf_cond *cond,
-                                float *grads_out, float *loss_out, void *stream)
+int nf_trainer_create(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params,
+                      int64_t max_batch, int32_t optimizer, nf_trainer **out)
 {
-    return trainer_run(t, x, y, B, cond, grads_out, loss_out, stream, true);
-}
-
-int nf_trainer_forward(nf_trainer *t, const float *x, const float *y, int64_t B, const nf_cond *cond, float *loss_out,
-                       void *stream)
-{
-    return trainer_run(t, x, y, B, cond, nullptr, loss_out, stream, false);
+    return trainer_create_impl(cfg, layers, params, n_params, max_batch, optimizer, false, out);
 }
 
 static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B, const nf_cond *cond, float *grads_out,
@@ -2689,21 +2713,12 @@ static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B,
     if ((rc = guard.enter(t->device)) != NF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
 
-    Geo g;
-    g.B = (int)B;
-    g.H = t->cfg.height;
-    g.W = t->cfg.width;
-    g.HW = g.H * g.W;
-    g.npix = B * (int64_t)g.HW;
-    g.nloop = (g.npix + 63) & ~(int64_t)63;
+    const Geo g = make_geo(t, B);
     const unsigned nb = blocks_for(t, g.npix);
-    g.nslot = (t->sync_fn && t->sync_world > 1) ? std::max((int)nb, 2) : (int)nb;   // the synchronised totals occupy slots 0 and 1
     t->sync_rc = 0;
     bool mm_failed = false;
-    if ((t->all_gemm || gemm_width(t->width ? t->width : 4)) && !t->cpl.empty()) gemm_pack_step(t, st);
-    if (t->pr) pr_pack_step(t, st);
-    t->pr_f0_done = t->pr_a_done = false;
-    t->pr_next = t->pr_below = nullptr;
+    if (t->family == TP_GEMM && !t->cpl.empty()) gemm_pack_step(t, st);
+    if (t->family == TP_PR) pr_pack_step(t, st);
     const float invB = 1.0f / (float)B;
     const int n = t->cfg.n_layers;
     hipError_t e;
@@ -2714,7 +2729,7 @@ static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B,
                        G + t->d_ldc, t->d_patch, 2 * (int)t->max_batch);
     // ---- forward ----
     t->zs[0] = const_cast<float *>(x);
-    bool f1_done = false;   // stage 1 of the next coupling already ran (tiled stages)
+    bool f_done = false;   // the first stage of this coupling already ran, in the last launch of the coupling below (tiled / patch-resident)
     for (int l = 0; l < n; ++l) {
         const TLayer &L = t->tl.l[l];
         const float *zin = t->zs[l];
@@ -2728,43 +2743,41 @@ static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B,
             hipLaunchKernelGGL(k_scale_fwd, dim3(nb), dim3(TB), 0, st, g, zin, t->d_flt + t->f_s + L.aux, zout);
             break;
         case NF_LAYER_CONV1X1:
-            if (l + 1 < n && t->tl.l[l + 1].type == NF_LAYER_COUPLING) break;   // folded into the coupling's l_1 kernel
-            hipLaunchKernelGGL(k_mix_fwd, dim3(nb), dim3(TB), 0, st, g, zin, t->d_flt + t->f_A + 16 * L.aux, zout);
+            if (l + 1 < n && t->plan[l + 1].fold == l) break;   // folded into the coupling's l_1 kernel
+            hipLaunchKernelGGL(k_mix_fwd, dim3(nb), dim3(TB), 0, st, g, zin, t->mixA(l), zout);
             break;
         case NF_LAYER_COUPLING: {
-            const bool fold = l > 0 && t->tl.l[l - 1].type == NF_LAYER_CONV1X1;
-            const float *zpre = fold ? t->zs[l - 1] : nullptr;
-            const float *Am = fold ? t->d_flt + t->f_A + 16 * t->tl.l[l - 1].aux : nullptr;
-            if (tiled_ok(t, g, L.width, 2)) {
-                // the coupling above: directly, or behind one Conv2d1x1 (then folded into its stage 1)
-                int ln = l + 1;
-                const bool mixn = ln < n && t->tl.l[ln].type == NF_LAYER_CONV1X1;
-                if (mixn) ++ln;
-                const TLayer *nxt = ln < n && t->tl.l[ln].type == NF_LAYER_COUPLING && t->tl.l[ln].width == L.width ? &t->tl.l[ln] : nullptr;
-                const float *An = nxt && mixn ? t->d_flt + t->f_A + 16 * t->tl.l[ln - 1].aux : nullptr;
-                float *nz = nxt ? t->zs[ln] : nullptr;
-#define NF_CALL(WW)                                                                                                                \
-    do {                                                                                                                           \
-        if (g.HW <= 256) coupling_forward_tiled<WW, 256>(t, g, L, zin, zout, t->acc(t->d_ld0 + l), zpre, Am, st, f1_done, nxt, An, nz);   \
-        else if (g.HW <= 512) coupling_forward_tiled<WW, 512>(t, g, L, zin, zout, t->acc(t->d_ld0 + l), zpre, Am, st, f1_done, nxt, An, nz); \
-        else coupling_forward_tiled<WW, 1024>(t, g, L, zin, zout, t->acc(t->d_ld0 + l), zpre, Am, st, f1_done, nxt, An, nz);       \
-    } while (0)
-                if (L.width == 4) NF_CALL(4); else NF_CALL(8);
-#undef NF_CALL
-                f1_done = nxt != nullptr;
-            } else if (t->all_gemm || gemm_width(L.width)) {
-                if (!coupling_forward_gemm(t, g, L, zin, zout, t->acc(t->d_ld0 + l), zpre, Am, st)) mm_failed = true;
-            } else {
-                t->pr_next = nullptr;
-                if (t->pr && l + 2 < n && t->tl.l[l + 1].type == NF_LAYER_CONV1X1 && t->tl.l[l + 2].type == NF_LAYER_COUPLING &&
-                    t->tl.l[l + 2].width == L.width) {
-                    t->pr_next = &t->tl.l[l + 2];
-                    t->pr_next_A = t->d_flt + t->f_A + 16 * t->tl.l[l + 1].aux;
-                    t->pr_next_zin = t->zs[l + 2];
+            const CplPlan &p = t->plan[l];
+            const CplCtx cx = cpl_ctx(t, g, L);
+            const float *zpre = p.fold >= 0 ? t->zs[p.fold] : nullptr;
+            const float *Am = p.fold >= 0 ? t->mixA(p.fold) : nullptr;
+            const Acc ld = t->acc(t->d_ld0 + l);
+            const TrainPath path = train_path(t, g, 2);
+            // the coupling above whose first stage rides in this one's last launch.  Asymmetry: the patch-resident stages fuse only behind
+            // a Conv2d1x1 (and not at all under NF_TRAIN_PR + 4), the tiled ones directly as well
+            const bool ride = p.above >= 0 && (path == TP_TILED || (path == TP_PR && p.above_mix >= 0 && (t->pr & 4) == 0));
+            const Rider nx = ride ? Rider{&t->tl.l[p.above], p.above_mix >= 0 ? t->mixA(p.above_mix) : nullptr, t->zs[p.above]} : Rider{};
+            switch (path) {
+            case TP_TILED:
+                with_nt(g.HW, [&](auto NT) {
+                    constexpr int nt = decltype(NT)::value;
+                    if (L.width == 4) f_done = coupling_forward_tiled<4, nt>(t, g, cx, zin, zout, ld, zpre, Am, st, f_done, nx);
+                    else f_done = coupling_forward_tiled<8, nt>(t, g, cx, zin, zout, ld, zpre, Am, st, f_done, nx);
+                });
+                break;
+            case TP_PR:
+                with_nw(t, [&](auto NW) { f_done = pr_coupling_forward<decltype(NW)::value>(t, g, cx, zin, zout, ld, zpre, Am, st, f_done, nx); });
+                break;
+            case TP_GEMM:
+                if (!coupling_forward_gemm(t, g, cx, zin, zout, ld, zpre, Am, st)) mm_failed = true;
+                break;
+            default:   // TP_LAYER, TP_WIDE: one driver per width
+                switch (L.width) {
+                case 4: coupling_forward<4>(t, g, cx, zin, zout, ld, zpre, Am, st); break;
+                case 8: coupling_forward<8>(t, g, cx, zin, zout, ld, zpre, Am, st); break;
+                case 16: coupling_forward<16>(t, g, cx, zin, zout, ld, zpre, Am, st); break;
+                case 32: coupling_forward<32>(t, g, cx, zin, zout, ld, zpre, Am, st); break;
                 }
-#define NF_CALL(WW) coupling_forward<WW>(t, g, L, zin, zout, t->acc(t->d_ld0 + l), zpre, Am, st)
-                NF_WIDTH_SWITCH(L.width, NF_CALL)
-#undef NF_CALL
             }
             break;
         }
@@ -2774,7 +2787,7 @@ static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B,
     // (joined with the filter-gradient work before the step ends) while the main stream starts walking back.
     hipStream_t ls = st;
     if (backward && loss_out) {
-        ls = t->serial ? st : t->side;
+        ls = t->side_of(st);
         (void)hipEventRecord(t->ev_fork[1], st);
         (void)hipStreamWaitEvent(ls, t->ev_fork[1], 0);
     }
@@ -2793,7 +2806,7 @@ static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B,
     // d loss / d latent = latent / B: formed inside the first stage when the stack ends in a coupling, else by its own kernel
     const bool dz_in_first = t->tl.l[n - 1].type == NF_LAYER_COUPLING;
     if (!dz_in_first) hipLaunchKernelGGL(k_dz_init, dim3(nb), dim3(TB), 0, st, g, t->zs[n], invB, t->dz);
-    bool a_done = false;   // stage A' of the next coupling already ran (tiled stages)
+    bool a_done = false;   // stage A of this coupling already ran, in the last launch of the coupling above (tiled / patch-resident)
     for (int l = n - 1; l >= 0; --l) {
         const TLayer &L = t->tl.l[l];
         switch (L.type) {
@@ -2807,55 +2820,53 @@ static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B,
                                t->acc(t->d_dg + L.aux));
             break;
         case NF_LAYER_CONV1X1:
-            hipLaunchKernelGGL(k_mix_bwd, dim3(nb), dim3(TB), 0, st, g, t->zs[l], t->d_flt + t->f_A + 16 * L.aux, t->dz,
-                               t->acc(t->d_dA + 16 * L.aux));
+            hipLaunchKernelGGL(k_mix_bwd, dim3(nb), dim3(TB), 0, st, g, t->zs[l], t->mixA(l), t->dz, t->acc(t->d_dA + 16 * L.aux));
             break;
         case NF_LAYER_COUPLING: {
-            const bool fold = l > 0 && t->tl.l[l - 1].type == NF_LAYER_CONV1X1;
-            const float *zmix_in = fold ? t->zs[l - 1] : nullptr;
-            const float *Am = fold ? t->d_flt + t->f_A + 16 * t->tl.l[l - 1].aux : nullptr;
-            const Acc dA = t->acc(fold ? t->d_dA + 16 * t->tl.l[l - 1].aux : 0);
+            const CplPlan &p = t->plan[l];
+            const CplCtx cx = cpl_ctx(t, g, L);
+            const float *zin = t->zs[l];
+            const float *zmix_in = p.fold >= 0 ? t->zs[p.fold] : nullptr;
+            const float *Am = p.fold >= 0 ? t->mixA(p.fold) : nullptr;
+            const Acc dA = t->acc(p.fold >= 0 ? t->d_dA + 16 * t->tl.l[p.fold].aux : 0);
             const float *zlat = (dz_in_first && l == n - 1) ? t->zs[n] : nullptr;
-            if (tiled_ok(t, g, L.width, 1)) {
-                const int lb = fold ? l - 2 : l - 1;   // the layer below this coupling (and its folded Conv2d1x1)
-                const TLayer *nxt = lb >= 0 && t->tl.l[lb].type == NF_LAYER_COUPLING && t->tl.l[lb].width == L.width ? &t->tl.l[lb] : nullptr;
-                const float *nz = nxt ? t->zs[lb] : nullptr;
-#define NF_CALL(WW)                                                                                                              \
-    do {                                                                                                                         \
-        if (g.HW <= 256) coupling_backward_tiled<WW, 256>(t, g, L, t->zs[l], invB, zmix_in, Am, dA, st, zlat, a_done, nxt, nz);  \
-        else if (g.HW <= 512) coupling_backward_tiled<WW, 512>(t, g, L, t->zs[l], invB, zmix_in, Am, dA, st, zlat, a_done, nxt, nz); \
-        else coupling_backward_tiled<WW, 1024>(t, g, L, t->zs[l], invB, zmix_in, Am, dA, st, zlat, a_done, nxt, nz);             \
-    } while (0)
-                if (L.width == 4) NF_CALL(4); else NF_CALL(8);
-#undef NF_CALL
-                a_done = nxt != nullptr;
-            } else if (t->all_gemm || gemm_width(L.width)) {
-                if (!coupling_backward_gemm(t, g, L, t->zs[l], invB, zmix_in, Am, dA, st, zlat)) mm_failed = true;
-            } else {
-                t->pr_below = nullptr;
-                {
-                    const int lb = fold ? l - 2 : l - 1;   // the layer below this coupling (and its folded Conv2d1x1)
-                    if (t->pr && lb >= 0 && t->tl.l[lb].type == NF_LAYER_COUPLING && t->tl.l[lb].width == L.width) {
-                        t->pr_below = &t->tl.l[lb];
-                        t->pr_below_zin = t->zs[lb];
-                    }
+            const TrainPath path = train_path(t, g, 1);
+            // the coupling below whose stage A rides in this one's last launch (NF_TRAIN_PR + 8: not on the patch-resident stages)
+            const bool ride = p.below >= 0 && (path == TP_TILED || (path == TP_PR && (t->pr & 8) == 0));
+            const Rider nx = ride ? Rider{&t->tl.l[p.below], nullptr, t->zs[p.below]} : Rider{};
+            switch (path) {
+            case TP_TILED:
+                with_nt(g.HW, [&](auto NT) {
+                    constexpr int nt = decltype(NT)::value;
+                    if (L.width == 4) a_done = coupling_backward_tiled<4, nt>(t, g, cx, zin, invB, zmix_in, Am, dA, st, zlat, a_done, nx);
+                    else a_done = coupling_backward_tiled<8, nt>(t, g, cx, zin, invB, zmix_in, Am, dA, st, zlat, a_done, nx);
+                });
+                break;
+            case TP_PR:
+                with_nw(t, [&](auto NW) {
+                    a_done = pr_coupling_backward<decltype(NW)::value>(t, g, cx, zin, invB, zmix_in, Am, dA, st, zlat, a_done, nx);
+                });
+                break;
+            case TP_GEMM:
+                if (!coupling_backward_gemm(t, g, cx, zin, invB, zmix_in, Am, dA, st, zlat)) mm_failed = true;
+                break;
+            default:   // TP_LAYER, TP_WIDE
+                switch (L.width) {
+                case 4: coupling_backward<4>(t, g, cx, zin, invB, zmix_in, Am, dA, st, zlat); break;
+                case 8: coupling_backward<8>(t, g, cx, zin, invB, zmix_in, Am, dA, st, zlat); break;
+                case 16: coupling_backward<16>(t, g, cx, zin, invB, zmix_in, Am, dA, st, zlat); break;
+                case 32: coupling_backward<32>(t, g, cx, zin, invB, zmix_in, Am, dA, st, zlat); break;
                 }
-#define NF_CALL(WW) coupling_backward<WW>(t, g, L, t->zs[l], invB, zmix_in, Am, dA, st, zlat)
-                NF_WIDTH_SWITCH(L.width, NF_CALL)
-#undef NF_CALL
             }
-            if (fold) --l;   // the Conv2d1x1 below was handled by the coupling's last stage
+            if (p.fold >= 0) --l;   // the Conv2d1x1 below was handled by the coupling's last stage
             break;
         }
         }
     }
     if (ls != st) (void)hipStreamWaitEvent(st, t->ev_fork[2], 0);
-    for (int par = 0; par < 3; ++par)   // join the side stream: its slots are read next
-        if (t->done_pending[par]) {
-            (void)hipStreamWaitEvent(st, t->ev_done[par], 0);
-            t->done_pending[par] = false;
-        }
-    if (t->all_gemm || gemm_width(t->width)) {
+    t->join_side(st);
+    // (a stack without couplings has no width: it has always taken the run-wise reduction below, over one run)
+    if (t->family == TP_GEMM || t->cpl.empty()) {
         // the filters of wide couplings get their gradients whole from the GEMMs: the slotted sums are added up for every other
         // value only (the runs between the filters), then the GEMM results are stored next to them
         int lo = 0;
@@ -2865,10 +2876,10 @@ static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B,
         for (int l = 0; l < n; ++l) {
             const TLayer &L = t->tl.l[l];
             if (L.type != NF_LAYER_COUPLING) continue;
-            const int w = L.width, off_w2 = L.off + 21 * w;
-            run(lo, L.off);                  // ... up to l_1/W
-            run(L.off + 18 * w, off_w2);     // l_1/b (and the BN statistics, masked out)
-            lo = off_w2 + w * w;             // behind l_2/W: l_2/b, BN, l_last/W (edge rows), b, logs, scale
+            const CplOff o = cpl_off(L.off, L.width);
+            run(lo, o.w1);       // ... up to l_1/W
+            run(o.b1, o.w2);     // l_1/b (and the BN statistics, masked out)
+            lo = o.b2;           // behind l_2/W: l_2/b, BN, l_last/W (edge rows), b, logs, scale
         }
         run(lo, t->d_ldc);
         reduce_runs_flush(st, runs, g.nslot, G);
@@ -2876,11 +2887,11 @@ static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B,
             const TLayer &L = t->tl.l[l];
             if (L.type != NF_LAYER_COUPLING) continue;
             const int w = L.width;
+            const CplOff o = cpl_off(L.off, w);
             const float *gdw = t->gdw + (size_t)(3 * L.aux) * gemm_part_floats(w);
-            store_grad(st, jobs, 18 * w, w, 0, gdw, t->gnp[3 * L.aux], G, L.off);
-            store_grad(st, jobs, w * w, w, 0, gdw + gemm_part_floats(w), t->gnp[3 * L.aux + 1], G, L.off + 21 * w);
-            store_grad(st, jobs, 36 * w, w, 1, gdw + 2 * gemm_part_floats(w), t->gnp[3 * L.aux + 2], G, L.off + 24 * w + w * w,
-                       t->gdual[L.aux] ? 2 * 36 * w : 0);
+            store_grad(st, jobs, 18 * w, w, 0, gdw, t->gnp[3 * L.aux], G, o.w1);
+            store_grad(st, jobs, w * w, w, 0, gdw + gemm_part_floats(w), t->gnp[3 * L.aux + 1], G, o.w2);
+            store_grad(st, jobs, 36 * w, w, 1, gdw + 2 * gemm_part_floats(w), t->gnp[3 * L.aux + 2], G, o.w3, t->gdual[L.aux] ? 2 * 36 * w : 0);
         }
         store_grads_flush(st, jobs, G);
     } else {
@@ -2894,6 +2905,18 @@ static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B,
     if (mm_failed) return nf_fail(NF_EHIP, "a matrix-core GEMM of the wide-coupling training step could not be launched");
     if (t->sync_rc) return nf_fail(NF_EINVAL, "the all-reduce callback of nf_trainer_set_sync failed (status %d)", t->sync_rc);
     return NF_OK;
+}
+
+int nf_trainer_forward_backward(nf_trainer *t, const float *x, const float *y, int64_t B, const nf_cond *cond,
+                                float *grads_out, float *loss_out, void *stream)
+{
+    return trainer_run(t, x, y, B, cond, grads_out, loss_out, stream, true);
+}
+
+int nf_trainer_forward(nf_trainer *t, const float *x, const float *y, int64_t B, const nf_cond *cond, float *loss_out,
+                       void *stream)
+{
+    return trainer_run(t, x, y, B, cond, nullptr, loss_out, stream, false);
 }
 
 int nf_trainer_set_sync(nf_trainer *t, nf_allreduce_fn fn, void *user, double *sync_buf, int32_t world_size)
@@ -2995,17 +3018,10 @@ int nf_bs_wide_run(nf_trainer *t, const nf_bs_wide_args &a, hipStream_t st)
     t->sync_world = a.sync_fn ? a.sync_world : 1;
     t->sync_rc = 0;
 
-    Geo g;
-    g.B = (int)a.B;
-    g.H = t->cfg.height;
-    g.W = t->cfg.width;
-    g.HW = g.H * g.W;
-    g.npix = a.B * (int64_t)g.HW;
-    g.nloop = (g.npix + 63) & ~(int64_t)63;
-    const unsigned nb = blocks_for(t, g.npix);
-    g.nslot = (t->sync_fn && t->sync_world > 1) ? std::max((int)nb, 2) : (int)nb;
+    const Geo g = make_geo(t, a.B);
+    const unsigned nb = blocks_for(t, g.npix), nB = (unsigned)a.B;
+    const bool pr = t->family == TP_PR, inverse = a.direction != 0;
     const int n = t->cfg.n_layers, w = t->width ? t->width : 4;
-    const unsigned nB = (unsigned)a.B;
     double *G = t->d_dbl;
     float *z = a.out ? a.out : t->ebuf;
     bool ok = true;
@@ -3015,69 +3031,48 @@ int nf_bs_wide_run(nf_trainer *t, const nf_bs_wide_args &a, hipStream_t st)
                        G + t->d_ldc, t->d_flt, 0);
     if ((e = hipMemsetAsync(t->eldp, 0, (size_t)a.B * sizeof(double), st)) != hipSuccess) return nf_fail_hip(e, "evaluator set-up");
     hipLaunchKernelGGL(k_e_input, dim3(nb), dim3(TB), 0, st, g, a.in, a.in_scale, a.seed, a.patch_base, z);
-    if (t->pr) pr_pack_step(t, st);
-    if (a.direction == 0) {
-        for (int l = 0; l < n; ++l) {
-            const TLayer &L = t->tl.l[l];
-            switch (L.type) {
-            case NF_LAYER_SDN5:
-            case NF_LAYER_SDN4:
-                hipLaunchKernelGGL(k_e_sdn<false>, dim3(nB), dim3(TB), 0, st, g.HW, z, a.y, t->d_flt + t->f_ab + 2 * L.aux, t->eldp);
-                break;
-            case NF_LAYER_GAIN4:
-                hipLaunchKernelGGL(k_scale_fwd, dim3(nb), dim3(TB), 0, st, g, (const float *)z, t->d_flt + t->f_s + L.aux, z);
-                break;
-            case NF_LAYER_CONV1X1:
-                if (t->pr && l + 1 < n && t->tl.l[l + 1].type == NF_LAYER_COUPLING) break;   // folded into the coupling's first stage
-                hipLaunchKernelGGL(k_mix_fwd, dim3(nb), dim3(TB), 0, st, g, (const float *)z, t->d_flt + t->f_A + 16 * L.aux, z);
-                break;
-            case NF_LAYER_COUPLING:
-                if (t->pr) {
-                    const float *Am = (l > 0 && t->tl.l[l - 1].type == NF_LAYER_CONV1X1) ? t->d_flt + t->f_A + 16 * t->tl.l[l - 1].aux : nullptr;
-                    if ((t->pr & 3) == 2) pr_coupling_eval<4>(t, g, L, z, st, t->emom + (size_t)L.aux * 4 * w, false, Am);
-                    else pr_coupling_eval<8>(t, g, L, z, st, t->emom + (size_t)L.aux * 4 * w, false, Am);
-                    break;
-                }
-                ok = coupling_cnn_gemm(t, g, L, z, st, t->emom + (size_t)L.aux * 4 * w) && ok;
-                hipLaunchKernelGGL(k_e_c3<false>, dim3(nB), dim3(TB), 0, st, g.H, g.W, L.width, z, (const float *)t->gp36, (const float *)t->d_params,
-                                   L.off + 24 * L.width + L.width * L.width, t->eldp);
+    if (pr) pr_pack_step(t, st);
+    if (inverse && t->n_mix > 0)
+        hipLaunchKernelGGL(k_e_inv4, dim3((unsigned)((t->n_mix + 63) / 64)), dim3(64), 0, st, t->n_mix, (const float *)(t->d_flt + t->f_A), t->eAinv);
+    // the matrix a Conv2d1x1 applies in this direction: its own (NLL) or its inverse (sampling)
+    const auto mix = [&](int l) { return inverse ? (const float *)(t->eAinv + 16 * t->tl.l[l].aux) : t->mixA(l); };
+    for (int i = 0; i < n; ++i) {
+        const int l = inverse ? n - 1 - i : i;
+        const TLayer &L = t->tl.l[l];
+        switch (L.type) {
+        case NF_LAYER_SDN5:
+        case NF_LAYER_SDN4:
+            if (inverse) hipLaunchKernelGGL(k_e_sdn<true>, dim3(nB), dim3(TB), 0, st, g.HW, z, a.y, t->d_flt + t->f_ab + 2 * L.aux, t->eldp);
+            else hipLaunchKernelGGL(k_e_sdn<false>, dim3(nB), dim3(TB), 0, st, g.HW, z, a.y, t->d_flt + t->f_ab + 2 * L.aux, t->eldp);
+            break;
+        case NF_LAYER_GAIN4:
+            if (inverse) hipLaunchKernelGGL(k_e_scale_mul, dim3(nb), dim3(TB), 0, st, g, z, (const float *)(t->d_flt + t->f_s + L.aux));
+            else hipLaunchKernelGGL(k_scale_fwd, dim3(nb), dim3(TB), 0, st, g, (const float *)z, t->d_flt + t->f_s + L.aux, z);
+            break;
+        case NF_LAYER_CONV1X1:
+            if (pr && l + 1 < n && t->plan[l + 1].fold == l) break;   // applied by the coupling above: its first stage (NLL), its last (sampling)
+            hipLaunchKernelGGL(k_mix_fwd, dim3(nb), dim3(TB), 0, st, g, (const float *)z, mix(l), z);
+            break;
+        case NF_LAYER_COUPLING: {
+            const CplCtx cx = cpl_ctx(t, g, L);
+            float *mom = t->emom + (size_t)L.aux * 4 * w;
+            if (pr) {
+                const float *Am = t->plan[l].fold >= 0 ? mix(t->plan[l].fold) : nullptr;
+                with_nw(t, [&](auto NW) { pr_coupling_eval<decltype(NW)::value>(t, g, cx, z, st, mom, inverse, Am); });
                 break;
             }
+            ok = coupling_cnn_gemm(t, g, cx, z, st, mom) && ok;
+            with_bool(inverse, [&](auto INV) {
+                hipLaunchKernelGGL(k_e_c3<decltype(INV)::value>, dim3(nB), dim3(TB), 0, st, g.H, g.W, L.width, z, (const float *)t->gp36,
+                                   (const float *)t->d_params, cx.o.w3, t->eldp);
+            });
+            break;
         }
-        if (a.nll_out || a.sd_out || a.ld_out || a.sums)
-            hipLaunchKernelGGL(k_e_finish, dim3(nB), dim3(TB), 0, st, g.HW, (const float *)z, (const double *)t->eldp, (const double *)(G + t->d_ldc),
-                               a.prior ? 1 : 0, a.nll_out, a.sd_out, a.ld_out, a.sums);
-    } else {
-        if (t->n_mix > 0)
-            hipLaunchKernelGGL(k_e_inv4, dim3((unsigned)((t->n_mix + 63) / 64)), dim3(64), 0, st, t->n_mix, (const float *)(t->d_flt + t->f_A), t->eAinv);
-        for (int l = n - 1; l >= 0; --l) {
-            const TLayer &L = t->tl.l[l];
-            switch (L.type) {
-            case NF_LAYER_SDN5:
-            case NF_LAYER_SDN4:
-                hipLaunchKernelGGL(k_e_sdn<true>, dim3(nB), dim3(TB), 0, st, g.HW, z, a.y, t->d_flt + t->f_ab + 2 * L.aux, t->eldp);
-                break;
-            case NF_LAYER_GAIN4:
-                hipLaunchKernelGGL(k_e_scale_mul, dim3(nb), dim3(TB), 0, st, g, z, (const float *)(t->d_flt + t->f_s + L.aux));
-                break;
-            case NF_LAYER_CONV1X1:
-                if (t->pr && l + 1 < n && t->tl.l[l + 1].type == NF_LAYER_COUPLING) break;   // applied by the coupling's last stage
-                hipLaunchKernelGGL(k_mix_fwd, dim3(nb), dim3(TB), 0, st, g, (const float *)z, (const float *)(t->eAinv + 16 * L.aux), z);
-                break;
-            case NF_LAYER_COUPLING:
-                if (t->pr) {
-                    const float *Ai = (l > 0 && t->tl.l[l - 1].type == NF_LAYER_CONV1X1) ? t->eAinv + 16 * t->tl.l[l - 1].aux : nullptr;
-                    if ((t->pr & 3) == 2) pr_coupling_eval<4>(t, g, L, z, st, t->emom + (size_t)L.aux * 4 * w, true, Ai);
-                    else pr_coupling_eval<8>(t, g, L, z, st, t->emom + (size_t)L.aux * 4 * w, true, Ai);
-                    break;
-                }
-                ok = coupling_cnn_gemm(t, g, L, z, st, t->emom + (size_t)L.aux * 4 * w) && ok;
-                hipLaunchKernelGGL(k_e_c3<true>, dim3(nB), dim3(TB), 0, st, g.H, g.W, L.width, z, (const float *)t->gp36, (const float *)t->d_params,
-                                   L.off + 24 * L.width + L.width * L.width, t->eldp);
-                break;
-            }
         }
     }
+    if (!inverse && (a.nll_out || a.sd_out || a.ld_out || a.sums))
+        hipLaunchKernelGGL(k_e_finish, dim3(nB), dim3(TB), 0, st, g.HW, (const float *)z, (const double *)t->eldp, (const double *)(G + t->d_ldc),
+                           a.prior ? 1 : 0, a.nll_out, a.sd_out, a.ld_out, a.sums);
     if ((e = hipGetLastError()) != hipSuccess) return nf_fail_hip(e, "evaluator launch");
     if (!ok) return nf_fail(NF_EHIP, "a matrix-core GEMM of the batch-statistics evaluation could not be launched");
     const size_t nmom = t->cpl.size() * 4 * (size_t)w;

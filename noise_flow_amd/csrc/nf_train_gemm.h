@@ -518,18 +518,18 @@ void gemm_pack_step(nf_trainer *t, hipStream_t st)
         const TLayer &L = t->tl.l[l];
         if (L.type != NF_LAYER_COUPLING) continue;
         if (n == mm::PackCpl::kMax) flush();
-        pc.off[n++] = L.off;   // couplings in layer order = aux order
+        pc.off[n++] = cpl_off(L.off, L.width).w1;   // couplings in layer order = aux order
     }
     flush();
 }
 
-bool coupling_cnn_gemm(nf_trainer *t, const Geo &g, const TLayer &L, const float *zin, hipStream_t st, float *mom)
+bool coupling_cnn_gemm(nf_trainer *t, const Geo &g, const CplCtx &x, const float *zin, hipStream_t st, float *mom)
 {
-    const Cpl &c = t->cpl[L.aux];
+    const TLayer &L = x.L;
+    const Cpl &c = x.c;
     const unsigned nb = blocks_for(t, g.npix), ns = gemm_grid(g);
-    const int w = L.width, off_w1 = L.off, off_b1 = L.off + 18 * w, off_m1 = L.off + 19 * w, off_w2 = L.off + 21 * w,
-              off_b2 = off_w2 + w * w, off_m2 = L.off + 22 * w + w * w;
-    const double n = (double)g.npix * t->sync_world;
+    const int w = L.width, off_w1 = x.o.w1, off_b1 = x.o.b1, off_m1 = x.o.m1, off_b2 = x.o.b2, off_m2 = x.o.m2;
+    const double n = x.n;
     const float *P = t->d_params;
     const bool v4 = w % 4 == 0;
     const mm::PackAll pl = mm::pack_layout(w);
@@ -547,10 +547,10 @@ bool coupling_cnn_gemm(nf_trainer *t, const Geo &g, const TLayer &L, const float
     mm::PixArgs a{};
     a.P = g.npix;
     a.nslot = g.nslot;
-    auto bn_fin = [&](int d_st, int off_m, int f_bn, float *mo) {
+    auto bn_fin = [&](int d_st, int off_m, float *bn, float *mo) {
         sync_slots(t, t->acc(d_st), 2 * w, g.nslot, st);
-        if (mom) hipLaunchKernelGGL(k_bn_fin_eval, dim3(w), dim3(64), 0, st, t->acc(d_st), w, g.nslot, n, t->d_flt + f_bn, mo);
-        else hipLaunchKernelGGL(k_bn_fin, dim3(w), dim3(64), 0, st, t->acc(d_st), w, g.nslot, n, t->d_params, off_m, off_m + w, t->d_flt + f_bn);
+        if (mom) hipLaunchKernelGGL(k_bn_fin_eval, dim3(w), dim3(64), 0, st, t->acc(d_st), w, g.nslot, n, bn, mo);
+        else hipLaunchKernelGGL(k_bn_fin, dim3(w), dim3(64), 0, st, t->acc(d_st), w, g.nslot, n, t->d_params, off_m, off_m + w, bn);
     };
     // ---- l_1: h1 = Z18 . W1 and the batch sums of h1 + b1 ----
     if (v4 && t->gemm_c1_fused) {
@@ -563,49 +563,46 @@ bool coupling_cnn_gemm(nf_trainer *t, const Geo &g, const TLayer &L, const float
         a.ebias = P + off_b1; a.stats = t->acc(c.d_st1).p;
         ok = mm::mm_pix<0, 1, 4>(cx, st, a) && ok;
     }
-    bn_fin(c.d_st1, off_m1, c.f_bn1, mom);
+    bn_fin(c.d_st1, off_m1, x.bn1, mom);
     // ---- l_2: h2 = relu(bn1(h1 + b1)) . W2 and the batch sums of h2 + b2 ----
     a.N = w; a.K = w;
     a.A = c.h1; a.lda = w;
     a.Bt = pk + pl.o_w2t; a.ldb = pl.w4;
     a.C = c.h2; a.ldc = w;
-    a.abias = P + off_b1; a.abn = t->d_flt + c.f_bn1;
+    a.abias = P + off_b1; a.abn = x.bn1;
     a.ebias = P + off_b2; a.stats = t->acc(c.d_st2).p;
     ok = (v4 ? mm::mm_pix<1, 1, 4>(cx, st, a) : mm::mm_pix<1, 1, 1>(cx, st, a)) && ok;
-    bn_fin(c.d_st2, off_m2, c.f_bn2, mom ? mom + 2 * w : nullptr);
+    bn_fin(c.d_st2, off_m2, x.bn2, mom ? mom + 2 * w : nullptr);
     // ---- l_last, transposed: P36 = relu(bn2(h2 + b2)) . W3r ----
     a.N = 36; a.K = w;
     a.A = c.h2; a.lda = w;
     a.Bt = pk + pl.o_w3a; a.ldb = pl.w4;
     a.C = t->gp36; a.ldc = 36;
-    a.abias = P + off_b2; a.abn = t->d_flt + c.f_bn2;
+    a.abias = P + off_b2; a.abn = x.bn2;
     a.ebias = nullptr; a.stats = nullptr;
     ok = (v4 ? mm::mm_pix<1, 0, 4>(cx, st, a) : mm::mm_pix<1, 0, 1>(cx, st, a)) && ok;
     return ok;
 }
 
-bool coupling_forward_gemm(nf_trainer *t, const Geo &g, const TLayer &L, const float *zin, float *zout, Acc ldacc, const float *zpre,
+bool coupling_forward_gemm(nf_trainer *t, const Geo &g, const CplCtx &x, const float *zin, float *zout, Acc ldacc, const float *zpre,
                            const float *A, hipStream_t st)
 {
-    const Cpl &c = t->cpl[L.aux];
     const unsigned nb = blocks_for(t, g.npix);
-    const int w = L.width, off_w3 = L.off + 24 * w + w * w;
     if (zpre) hipLaunchKernelGGL(k_mix_fwd, dim3(nb), dim3(TB), 0, st, g, zpre, A, const_cast<float *>(zin));
-    const bool ok = coupling_cnn_gemm(t, g, L, zin, st, nullptr);
-    hipLaunchKernelGGL(k_g_c3_fwd, dim3(nb), dim3(TB), 0, st, g, w, zin, (const float *)t->gp36, t->d_params, off_w3, zout, ldacc, c.u);
+    const bool ok = coupling_cnn_gemm(t, g, x, zin, st, nullptr);
+    hipLaunchKernelGGL(k_g_c3_fwd, dim3(nb), dim3(TB), 0, st, g, x.L.width, zin, (const float *)t->gp36, t->d_params, x.o.w3, zout, ldacc, x.c.u);
     return ok;
 }
 
-bool coupling_backward_gemm(nf_trainer *t, const Geo &g, const TLayer &L, const float *zin, float invB, const float *zmix_in,
+bool coupling_backward_gemm(nf_trainer *t, const Geo &g, const CplCtx &x, const float *zin, float invB, const float *zmix_in,
                             const float *A, Acc dA, hipStream_t st, const float *zlat)
 {
-    const Cpl &c = t->cpl[L.aux];
+    const TLayer &L = x.L;
+    const Cpl &c = x.c;
     const unsigned nb = blocks_for(t, g.npix);
-    const int w = L.width, off_w1 = L.off, off_b1 = L.off + 18 * w, off_w2 = L.off + 21 * w, off_b2 = off_w2 + w * w,
-              off_w3 = L.off + 24 * w + w * w;
-    (void)off_w1; (void)off_w2;
-    const double n = (double)g.npix * t->sync_world;
-    const float *P = t->d_params, *bn1 = t->d_flt + c.f_bn1, *bn2 = t->d_flt + c.f_bn2, *bb1 = t->d_flt + c.f_bb1, *bb2 = t->d_flt + c.f_bb2;
+    const int w = L.width, off_b1 = x.o.b1, off_b2 = x.o.b2, off_w3 = x.o.w3;
+    const double n = x.n;
+    const float *P = t->d_params, *bn1 = x.bn1, *bn2 = x.bn2, *bb1 = x.bb1, *bb2 = x.bb2;
     // in-kernel offsets from G are all behind this coupling's l_2/W (the rows before it are shifted by the holes: nf_trainer::acc)
     const Acc G = Acc{t->acc(off_w3).p - (size_t)off_w3 * NSLOT};
     float *t1 = t->t1[0], *t2 = t->t2[0], *gu = t->gu[0];
