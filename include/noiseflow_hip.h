@@ -135,6 +135,9 @@ typedef struct nf_config {
                               (v_mfma_f32_32x32x16_f16); widths 33 .. 512: any patch up to 64x64. */
 #define NF_CFG_EXACT_FP32 2 /* width 4, full 32x32 patches: keep the exact-fp32 kernel (every conv on
                               v_mfma_f32_4x4x1) instead of the default split-bf16 one (NF_PATH_SPLIT_BF16) */
+#define NF_CFG_GRAD_MFMA 4  /* nf_nll_grad at coupling widths 17 .. 32: the matrix-core gradient kernel
+                              (csrc/nf_grad_wide.hip, patches up to 32x32) and its weight image, uploaded by
+                              nf_create.  No effect on any other call, nor on widths up to 16. */
 
 /* Per-call conditioning: ONE value per call, not per patch — the reference
  * feeds length-1 lists (MiniBatchSampler.py:61-64, NoiseFlowWrapper.py:85-86).
@@ -261,7 +264,12 @@ int nf_sample_percond(nf_handle *h, const float *y, const float *eps, uint64_t s
  * every layer's input from its output (the flow is invertible), so no activation is stored and HBM traffic is x, y in and
  * gx, gy out.  Supported set (nf_grad_supported decides, everything else is NF_EINVAL): fp32 handles (NF_CFG_FP16_CNN is
  * refused, NF_CFG_EXACT_FP32 is ignored), the whole layer vocabulary, patches up to 64x64, coupling widths up to 32 as far
- * as one workgroup's LDS (160 KiB) holds the patch: width 4 up to 64x64, widths 8 and 16 at least up to 32x32.
+ * as one workgroup's LDS (160 KiB) holds the patch: width 4 up to 64x64, widths 8 and 16 at least up to 32x32; widths
+ * 17 .. 32 (zero-padded to 32) keep relu(h2) of the whole patch in LDS and stop near 29x29 with 3 couplings, 24x24 with 8.
+ * With NF_CFG_GRAD_MFMA, widths 17 .. 32 run the same contract on v_mfma_f32_32x32x2_f32 (csrc/nf_grad_wide.hip): every
+ * H, W <= 32, up to 12 couplings on a 32x32 patch (the gate record, 8 KiB per coupling there, must fit the LDS beside the
+ * tiles); a shape beyond 32x32 stays with the scalar kernel where that kernel holds it (the flag only adds), and is refused
+ * otherwise.  nf_grad_path reports which kernel a handle launches.
  * Not covered: images beyond 64x64 (tiled evaluation), widths beyond 32 (the GEMM families), batch-statistics mode, and
  * host-fed variants. */
 int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond,
@@ -270,6 +278,20 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
 /* Host-only (no device, same argument style as nf_fold_params): 0 when nf_nll_grad supports this model and patch
  * size, NF_EINVAL otherwise, with nf_last_error() naming the limit that was hit. */
 int nf_grad_supported(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params);
+
+/* Which kernel nf_nll_grad launches for this handle, or NF_EINVAL when the handle has no gradient block (nf_grad_supported).
+ * With NF_CFG_GRAD_MFMA and a padded coupling width of 32 every supported shape is NF_GRAD_PATH_WIDE32; the environment
+ * variable NF_GRAD=scalar, read at nf_create, sends such a handle to the scalar kernel wherever that kernel holds the shape
+ * (A/B aid, like NF_KERNEL=valu). */
+#define NF_GRAD_PATH_SCALAR 0   /* nf_grad_kernel (csrc/nf_grad.hip) */
+#define NF_GRAD_PATH_WIDE32 1   /* nf_grad_wide_kernel (csrc/nf_grad_wide.hip), v_mfma_f32_32x32x2_f32 */
+int nf_grad_path(const nf_handle *h);
+
+/* Host-only: the program and parameter block nf_nll_grad would run for this model ("gradient block": A^-1 beside every 1x1
+ * matrix, 1/s beside every scale; couplings in the generic layout or, *path == NF_GRAD_PATH_WIDE32, in the fetch-order layout of
+ * csrc/nf_device.h, NFGW_*).  Argument style and sizing protocol of nf_fold_layout. */
+int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params, int32_t *path,
+                 int32_t *ops_out, int32_t ops_cap, int32_t *n_ops, float *folded, size_t folded_cap, size_t *n_folded);
 
 /* The tile plan of one image axis (see "Patch sizes"): `size` pixels, tiles of `tile` = min(size, 64) pixels, `halo` =
  * 2 x the number of coupling layers.  Returns the number of tiles n (or a negative NF_E* code) and, for i < min(n, cap),

@@ -32,7 +32,7 @@ from .noise_flow_model import NoiseFlow
 
 class NoiseFlowWrapper:
     def __init__(self, path, sampling_temperature=0.6, binding="loss_first", device=None, seed=None,
-                 bn_mode="running", compat=None, patch_shape=None):
+                 bn_mode="running", compat=None, patch_shape=None, grad_kernel=None):
         if compat not in (None, "reference"):
             raise ValueError("compat must be None or 'reference'")
         if compat == "reference":
@@ -53,6 +53,7 @@ class NoiseFlowWrapper:
         self.patch_shape = (32, 32) if patch_shape is None else (int(patch_shape[0]), int(patch_shape[1]))
         self.binding = binding
         self.device = device
+        self.grad_kernel = grad_kernel   # 'scalar' | 'mfma' (NoiseFlow); None: hps.grad_kernel, else 'scalar'
         self.hps = self.hps_loader(os.path.join(self.nf_path, "hps.txt"))
         if seed is not None:
             self.hps.seed = seed
@@ -65,7 +66,8 @@ class NoiseFlowWrapper:
         if not hasattr(self.hps, "x_shape") or isinstance(self.hps.x_shape, str):
             setattr(self.hps, "x_shape", self.x_shape)
         self.logger.info("Building Noise Flow")
-        self.nf_model = NoiseFlow(self.x_shape[1:], self.bn_mode == "batch", self.hps, binding=self.binding, device=self.device)
+        self.nf_model = NoiseFlow(self.x_shape[1:], self.bn_mode == "batch", self.hps, binding=self.binding, device=self.device,
+                                  grad_kernel=self.grad_kernel)
         self.logger.info("Restoring best model")
         self.nf_model.restore(self.model_checkpoint_path)
 

@@ -434,6 +434,51 @@ __host__ __device__ constexpr size_t nf_grad_lds_floats(int H, int W, int width,
            (size_t)nf_grad_gate_words(n_cpl, width) * (size_t)(nf_grad_threads(H * W, width) * nf_grad_px(H * W, width)) + 32;
 }
 
+// ---- input gradients at coupling width 32 on the f32 matrix cores (nf_grad_wide.hip, NF_CFG_GRAD_MFMA) --------------------
+// Same launch record (NfGradLaunch), same op list; the gradient block carries per coupling, instead of the generic block, every
+// weight in the fetch order of v_mfma_f32_32x32x2_f32 (tile / lane / register conventions of NF4_*), for the forward chain and
+// for the three transposed products.  Nothing is pre-scaled: tanh / exp are nf_tanh / nf_exp as in nf_grad.hip.
+//   MIX, SCALE  as the scalar gradient block
+//   COUPLING  E [16][4] @0 (generic values), S [4] @64 (rescaling_scale, 0, 0, 0),
+//             FWD @68: the NF4_IMG_* image without the 2 log2(e) factor (A1, B1, A2, B2, A3, A3C)
+//             BWD @68 + NF4_IMG_SIZE:
+//               A3T [5][64][4]  l_last^T, K = 9 taps x 4 = 36 in 18 steps (20 stored): step s, lane l:
+//                               W3[tap = s>>1][c = l&31][j = 2 (s&1) + (l>>5)]; the B operand is d(shift, raw)[j] at pixel - (tap - centre)
+//               A2T [4][64][4]  l_2^T: step s, lane l: W2[in = l&31][out = c(s, l>>5)]
+//               A1T [4][64][4]  l_1^T as P = W1 d h1 with the P rows of NF4_IMG_A3 (j < 2 used): the row at shift-add position tap'
+//                               holds W1[tap = 8 - tap'][ch = j][in = c(s, l>>5)] — the transposed convolution is the forward
+//                               shift-add over the flipped taps
+//               A1TC[4][8][4]   its centre tap on v_mfma_f32_4x4x1: step s, (g, j): W1[centre][j][c(s, g)]
+// One workgroup per patch, H, W <= 32, a wavefront owning a strip of TPW = 2 / 4 / 8 rows (H <= 8 / <= 16 / else: short patches
+// spread over as many wavefronts as tall ones): four wavefronts, except two at H <= 4 and one at H <= 2.  LDS: two tiles at a fixed pitch of 34 pixels (z0:
+// 2 planes, d(shift, raw): 4 planes; lanes beyond W read zeros), one coupling's block, the strip-boundary exchange, the gate
+// record — ONE word per lane, tile and coupling (bits 0-15: the lane's 16 D registers of h1, 16-31: of h2), [coupling][tile][lane] —
+// and the reduction scratch.
+#define NFGW_PITCH 34
+#define NFGW_CPL_E 0
+#define NFGW_CPL_S 64
+#define NFGW_CPL_FWD 68
+#define NFGW_CPL_BWD (68 + NF4_IMG_SIZE)
+#define NFGW_BWD_A3T 0
+#define NFGW_BWD_A2T 1280
+#define NFGW_BWD_A1T 2304
+#define NFGW_BWD_A1TC 3328
+#define NFGW_BWD_SIZE 3456
+#define NFGW_CPL_SIZE (NFGW_CPL_BWD + NFGW_BWD_SIZE)
+__host__ __device__ constexpr int nfgw_tpw(int H) { return H <= 8 ? 2 : H <= 16 ? 4 : 8; }
+__host__ __device__ constexpr int nfgw_waves(int H) { return H <= nfgw_tpw(H) ? 1 : H <= 2 * nfgw_tpw(H) ? 2 : 4; }
+__host__ __device__ constexpr int nfgw_plane(int H) { return ((H + 2) * NFGW_PITCH + 3) & ~3; }
+__host__ __device__ constexpr size_t nfgw_lds_floats(int H, int n_cpl)
+{
+    return 6 * (size_t)nfgw_plane(H) + NFGW_CPL_SIZE + (size_t)nfgw_waves(H) * 256 + (size_t)n_cpl * nfgw_tpw(H) * 64 * nfgw_waves(H) + 8;
+}
+// the most couplings whose gate record fits the CU's 160 KiB beside the rest, at patch height H
+__host__ __device__ constexpr int nfgw_max_couplings(int H)
+{
+    return (int)((160 * 256 - (6 * (size_t)nfgw_plane(H) + NFGW_CPL_SIZE + (size_t)nfgw_waves(H) * 256 + 8)) /
+                 ((size_t)nfgw_tpw(H) * 64 * nfgw_waves(H)));
+}
+
 #define NF_STATS_SLOTS 64   // power of two
 
 // Philox stream ids (4th counter word)

@@ -48,6 +48,7 @@ hipError_t nf_launch_tile_combine(const float *part, const NfTileParts &tp, int6
                                   float *nll_out, float *sd_out, float *ld_out, double *sums, hipStream_t stream);
 hipError_t nf_launch_gather(float *dst, const float *src, const int32_t *pairs, int n, hipStream_t stream);
 hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
+hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 
 namespace {
 
@@ -958,7 +959,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     out.tile_w = tw;
     out.segs.clear();
     if (cfg->n_layers < 1) return fail(NF_EINVAL, "n_layers must be >= 1");
-    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
+    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
     const double HW = (double)cfg->height * cfg->width;
 
     // intermediate list in NLL order
@@ -1211,10 +1212,22 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     return NF_OK;
 }
 
-// ---- input gradients (nf_nll_grad, nf_grad.hip) ---------------------------------------------------
-// THE place that decides what nf_nll_grad supports: `fwd` = the NLL-direction program of the model.
-int grad_support(const nf_config *cfg, const Built &fwd)
+// ---- input gradients (nf_nll_grad, nf_grad.hip, nf_grad_wide.hip) -----------------------------------
+// NF_GRAD=scalar sends a handle with NF_CFG_GRAD_MFMA to the scalar-weight gradient kernel wherever that kernel holds the shape (A/B aid)
+bool grad_force_scalar()
 {
+    static const bool fs = [] {
+        const char *e = getenv("NF_GRAD");
+        return e && strcmp(e, "scalar") == 0;
+    }();
+    return fs;
+}
+
+// THE place that decides what nf_nll_grad supports and which kernel runs it (`path`: NF_GRAD_PATH_*): `fwd` = the NLL-direction
+// program of the model.
+int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr)
+{
+    if (path) *path = NF_GRAD_PATH_SCALAR;
     if (cfg->flags & NF_CFG_FP16_CNN) return fail(NF_EINVAL, "nf_nll_grad: fp32 handles only (NF_CFG_FP16_CNN is set)");
     if (cfg->height > 64 || cfg->width > 64)
         return fail(NF_EINVAL, "nf_nll_grad: patches of up to 64x64 (%dx%d given; no tiled evaluation)", cfg->height, cfg->width);
@@ -1223,23 +1236,78 @@ int grad_support(const nf_config *cfg, const Built &fwd)
     if (w > 32) return fail(NF_EINVAL, "nf_nll_grad: coupling widths up to 32 (%d given; the GEMM families have no gradient kernel)", fwd.raw_width);
     int n_cpl = 0;
     for (int i = 0; i < prog.n_ops; ++i) n_cpl += prog.ops[i].type == NF_OP_COUPLING_FWD ? 1 : 0;
+    const size_t lds = sizeof(float) * nf_grad_lds_floats(cfg->height, cfg->width, w, n_cpl);
+    const bool scalar_holds = !(hw > 1024 && w > 8) && lds <= 160 * 1024;
+    if ((cfg->flags & NF_CFG_GRAD_MFMA) && w == 32) {
+        // The flag only adds: the matrix-core kernel (nf_grad_wide.hip) takes every shape up to 32x32 — unless NF_GRAD=scalar asks for
+        // the other arm where that one holds the shape — and a shape beyond it (16x48, 8x64) stays with the scalar kernel as far as
+        // that kernel holds it
+        const bool wide_shape = cfg->height <= 32 && cfg->width <= 32;
+        if (scalar_holds && (!wide_shape || grad_force_scalar())) return NF_OK;
+        if (!wide_shape)
+            return fail(NF_EINVAL, "nf_nll_grad: coupling width %d covers patches of up to 32x32 on the matrix-core gradient kernel, and the "
+                                   "scalar kernel does not hold a %dx%d patch of it either (registers beyond 1024 pixels, LDS)",
+                        fwd.raw_width, cfg->height, cfg->width);
+        if (n_cpl > nfgw_max_couplings(cfg->height))
+            return fail(NF_EINVAL, "nf_nll_grad: at most %d couplings at coupling width %d on a %dx%d patch (%d given): the gate record must fit 160 KiB of LDS",
+                        nfgw_max_couplings(cfg->height), fwd.raw_width, cfg->height, cfg->width, n_cpl);
+        if (path) *path = NF_GRAD_PATH_WIDE32;
+        return NF_OK;
+    }
     // registers: beyond 32x32 a lane of the 1 024-thread workgroup holds 4 pixels inside 128 VGPRs.  No width fits that without
     // scratch (width 4 spills 167 VGPRs, width 8 269: both run, slower); widths 16 and 32 would keep most of their hidden
     // vectors in scratch and are refused.  Width 32 keeps one pixel per lane (12 spilled VGPRs at 1 024 threads)
     if (hw > 1024 && w > 8)
         return fail(NF_EINVAL, "nf_nll_grad: coupling width %d covers patches of up to 1024 pixels (%dx%d given): registers", fwd.raw_width,
                     cfg->height, cfg->width);
-    const size_t lds = sizeof(float) * nf_grad_lds_floats(cfg->height, cfg->width, w, n_cpl);
     if (lds > 160 * 1024)
         return fail(NF_EINVAL, "nf_nll_grad: a %dx%d patch with coupling width %d and %d couplings needs %zu KiB of LDS (> 160)", cfg->height,
                     cfg->width, w, n_cpl, (lds + 1023) / 1024);
     return NF_OK;
 }
 
+// One coupling of the wide gradient block (nf_device.h, NFGW_*) from its generic block at width 32: the NF4_IMG_* image of the
+// forward chain without the 2 log2(e) factor, and the fetch-order images of the three transposed products.
+void relayout_coupling_grad_wide(const float *v1, float *out)
+{
+    const int w = 32;
+    memcpy(out + NFGW_CPL_E, v1 + nf_cpl_off_E(w), 64 * sizeof(float));
+    out[NFGW_CPL_S] = v1[nf_cpl_off_S(w)];
+    out[NFGW_CPL_S + 1] = out[NFGW_CPL_S + 2] = out[NFGW_CPL_S + 3] = 0.0f;
+    const float *W1 = v1 + nf_cpl_off_W1(w), *B1 = v1 + nf_cpl_off_B1(w), *W2 = v1 + nf_cpl_off_W2(w);
+    const float *B2 = v1 + nf_cpl_off_B2(w), *W3 = v1 + nf_cpl_off_W3(w);
+    // taps (di,dj) of the 8 off-centre row groups of a shift-add product P, by (a, g') (as relayout_coupling_wide32)
+    static const int tap_of[4][2] = {{0 * 3 + 0, 2 * 3 + 0}, {0 * 3 + 2, 2 * 3 + 2}, {0 * 3 + 1, 2 * 3 + 1}, {1 * 3 + 0, 1 * 3 + 2}};
+    float *img = out + NFGW_CPL_FWD;
+    for (int step = 0; step < 12; ++step)
+        for (int l = 0; l < 64; ++l)
+            img[NF4_IMG_A1 + ((step >> 2) * 64 + l) * 4 + (step & 3)] = step < 9 ? W1[(step * 2 + (l >> 5)) * w + (l & 31)] : 0.0f;
+    bias_tables32(B1, B2, 0, w, img + NF4_IMG_B1, img + NF4_IMG_B2);
+    float *bwd = out + NFGW_CPL_BWD;
+    for (int s = 0; s < 20; ++s)   // l_last^T: K step s = (tap s >> 1, elements j = 2 (s & 1) + K slice)
+        for (int l = 0; l < 64; ++l)
+            bwd[NFGW_BWD_A3T + ((s >> 2) * 64 + l) * 4 + (s & 3)] = s < 18 ? W3[((s >> 1) * w + (l & 31)) * 4 + 2 * (s & 1) + (l >> 5)] : 0.0f;
+    for (int s = 0; s < 16; ++s)
+        for (int l = 0; l < 64; ++l) {
+            const int cin = nf4_chan(s, l >> 5), i = l & 31;
+            const int a = i >> 3, gp = (i >> 2) & 1, j = i & 3;
+            img[NF4_IMG_A2 + ((s >> 2) * 64 + l) * 4 + (s & 3)] = W2[cin * w + i];
+            img[NF4_IMG_A3 + ((s >> 2) * 64 + l) * 4 + (s & 3)] = W3[(tap_of[a][gp] * w + cin) * 4 + j];
+            bwd[NFGW_BWD_A2T + ((s >> 2) * 64 + l) * 4 + (s & 3)] = W2[i * w + cin];
+            bwd[NFGW_BWD_A1T + ((s >> 2) * 64 + l) * 4 + (s & 3)] = j < 2 ? W1[((8 - tap_of[a][gp]) * 2 + j) * w + cin] : 0.0f;
+        }
+    for (int s = 0; s < 16; ++s)
+        for (int g = 0; g < 2; ++g)
+            for (int j = 0; j < 4; ++j) {
+                img[NF4_IMG_A3C + ((s >> 2) * 8 + g * 4 + j) * 4 + (s & 3)] = W3[(4 * w + nf4_chan(s, g)) * 4 + j];   // centre tap (1,1)
+                bwd[NFGW_BWD_A1TC + ((s >> 2) * 8 + g * 4 + j) * 4 + (s & 3)] = j < 2 ? W1[(4 * 2 + j) * w + nf4_chan(s, g)] : 0.0f;
+            }
+}
+
 // The gradient block (nf_device.h, NfGradLaunch): the NLL-order generic block with A^-1 beside every 1x1 matrix — op i of
 // the NLL program is op n - 1 - i of the sampling program, whose block holds the inverse — and 1/s beside every scale.
-// (`fwd`, `rev` = the generic layouts of the two directions)
-void build_grad_block(const Layout &fwd, const Layout &rev, NfProgram &gp, std::vector<float> &blk, int &n_cpl, int &first_cpl)
+// (`fwd`, `rev` = the generic layouts of the two directions).  `wide`: couplings in the NFGW_* layout (nf_grad_wide.hip).
+void build_grad_block(const Layout &fwd, const Layout &rev, bool wide, NfProgram &gp, std::vector<float> &blk, int &n_cpl, int &first_cpl)
 {
     memset(&gp, 0, sizeof(gp));
     gp.width = fwd.prog.width;
@@ -1257,7 +1325,12 @@ void build_grad_block(const Layout &fwd, const Layout &rev, NfProgram &gp, std::
             blk.insert(blk.end(), v, v + 16);
             blk.insert(blk.end(), rev.block.data() + inv.off, rev.block.data() + inv.off + 16);
         } else if (src.type == NF_OP_COUPLING_FWD) {
-            blk.insert(blk.end(), v, v + nf_cpl_size(gp.width));
+            if (wide) {
+                blk.resize(blk.size() + NFGW_CPL_SIZE);
+                relayout_coupling_grad_wide(v, blk.data() + gp.ops[i].off);
+            } else {
+                blk.insert(blk.end(), v, v + nf_cpl_size(gp.width));
+            }
             if (n_cpl == 0) first_cpl = i;
             ++n_cpl;
         } else if (src.type == NF_OP_SCALE) {
@@ -1350,6 +1423,7 @@ struct nf_handle {
     float *d_grad = nullptr;
     int grad_n_cpl = 0, grad_first_cpl = 0;
     int grad_rc = NF_EINVAL;
+    int grad_path = NF_GRAD_PATH_SCALAR;   // NF_GRAD_PATH_*: which kernel nf_nll_grad launches (grad_support)
     std::string grad_why;
     // scratch of the tiled calls (images beyond 64x64): the per-tile sums and the tensors between two segments.  A small set of
     // device buffers owned by the handle, one per call in flight; a call takes a free one (waiting, on ITS stream, for the work
@@ -1520,12 +1594,13 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
         }
     {   // the gradient kernel's block, where nf_nll_grad supports the model (otherwise the call reports grad_why)
         const std::string keep = g_last_error;
-        h->grad_rc = grad_support(cfg, h->fwd);
+        h->grad_rc = grad_support(cfg, h->fwd, &h->grad_path);
         h->grad_why = g_last_error;
         g_last_error = keep;
         if (h->grad_rc == NF_OK) {
             std::vector<float> gb;
-            build_grad_block(h->fwd.lay[NF_PATH_SCALAR], h->rev.lay[NF_PATH_SCALAR], h->gprog, gb, h->grad_n_cpl, h->grad_first_cpl);
+            build_grad_block(h->fwd.lay[NF_PATH_SCALAR], h->rev.lay[NF_PATH_SCALAR], h->grad_path == NF_GRAD_PATH_WIDE32, h->gprog, gb,
+                             h->grad_n_cpl, h->grad_first_cpl);
             if ((e = hipMalloc((void **)&h->d_grad, gb.size() * sizeof(float))) != hipSuccess ||
                 (e = hipMemcpy(h->d_grad, gb.data(), gb.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) {
                 nf_destroy(h);
@@ -2012,6 +2087,29 @@ int nf_grad_supported(const nf_config *cfg, const nf_layer_desc *layers, const f
     return grad_support(cfg, b);
 }
 
+int nf_grad_path(const nf_handle *h)
+{
+    if (!h) return fail(NF_EINVAL, "handle is NULL");
+    if (h->grad_rc != NF_OK) return fail(h->grad_rc, "%s", h->grad_why.c_str());
+    return h->grad_path;
+}
+
+int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params, int32_t *path, int32_t *ops_out,
+                 int32_t ops_cap, int32_t *n_ops, float *folded, size_t folded_cap, size_t *n_folded)
+{
+    Built f, r;
+    int rc = build_program(cfg, layers, params, n_params, 0, f);
+    if (rc == NF_OK) rc = build_program(cfg, layers, params, n_params, 1, r);
+    if (rc != NF_OK) return rc;
+    int gpath = NF_GRAD_PATH_SCALAR;
+    if ((rc = grad_support(cfg, f, &gpath)) != NF_OK) return rc;
+    Layout l;
+    int n_cpl = 0, first_cpl = 0;
+    build_grad_block(f.lay[NF_PATH_SCALAR], r.lay[NF_PATH_SCALAR], gpath == NF_GRAD_PATH_WIDE32, l.prog, l.block, n_cpl, first_cpl);
+    if (path) *path = gpath;
+    return export_layout(l, ops_out, ops_cap, n_ops, folded, folded_cap, n_folded);
+}
+
 int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond, const nf_cond_row *rows, float *nll_out,
                 float *gx_out, float *gy_out, void *stream)
 {
@@ -2050,11 +2148,13 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
     a.H = h->cfg.height;
     a.W = h->cfg.width;
     a.first_cpl = h->grad_first_cpl;
-    a.gate_words = nf_grad_gate_words(h->grad_n_cpl, h->gprog.width);
+    const bool wide = h->grad_path == NF_GRAD_PATH_WIDE32;
+    a.gate_words = wide ? nfgw_tpw(h->cfg.height) * h->grad_n_cpl : nf_grad_gate_words(h->grad_n_cpl, h->gprog.width);
     DeviceGuard guard;
     int rc = guard.enter(h->device);
     if (rc != NF_OK) return rc;
-    hipError_t e = nf_launch_grad(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream);
+    hipError_t e = wide ? nf_launch_grad_wide(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream)
+                        : nf_launch_grad(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "nf_nll_grad launch");
     return NF_OK;
 }

@@ -184,7 +184,7 @@ class FlowHandle:
 
     def __init__(self, arch, variables: Dict[str, np.ndarray], x_shape, width: int,
                  binding: str = "loss_first", device: Optional[int] = None, layers=None, tmpl=None,
-                 cnn_dtype: str = "fp32", flow_permutation: int = 1, decomp: str = "LU"):
+                 cnn_dtype: str = "fp32", flow_permutation: int = 1, decomp: str = "LU", grad_kernel: str = "scalar"):
         self.lib = _lib.load()
         if layers is None:
             self.layers, descs, flat = _params.pack(arch, variables, width, binding, flow_permutation, decomp)
@@ -194,7 +194,12 @@ class FlowHandle:
         self.x_shape = (H, W, Cc)
         if cnn_dtype not in ("fp32", "fp16", "fp32_exact"):
             raise ValueError("cnn_dtype must be 'fp32', 'fp16' or 'fp32_exact'")
+        if grad_kernel not in ("scalar", "mfma"):
+            raise ValueError("grad_kernel must be 'scalar' or 'mfma'")
+        if grad_kernel == "mfma" and cnn_dtype == "fp16":
+            raise ValueError("grad_kernel='mfma' needs an fp32 handle (cnn_dtype='fp16' has no gradient kernel)")
         flags = {"fp32": 0, "fp16": _lib.NF_CFG_FP16_CNN, "fp32_exact": _lib.NF_CFG_EXACT_FP32}[cnn_dtype]
+        flags |= _lib.NF_CFG_GRAD_MFMA if grad_kernel == "mfma" else 0
         cfg = _lib.nf_config(H, W, Cc, len(self.layers), -1 if device is None else int(device), flags)
         self._model_args = (cfg, descs, flat)   # what nf_cond_rows takes (kept alive with the handle)
         h = C.c_void_p()
@@ -254,11 +259,14 @@ class NoiseFlow(object):
           names; default = fresh initialisation with the reference initialisers.
     cnn_dtype : 'fp32' (default) | 'fp16' — precision of the coupling-CNN convolutions; 'fp32_exact' keeps every conv of the
           width-4 model on the fp32 matrix instruction where 'fp32' would use the fp32-accurate split-bf16 kernel (32x32 patches).
+    grad_kernel : 'scalar' (default) | 'mfma' — which kernel ``nll_and_grad`` / ``nll_torch`` run at coupling widths 17 .. 32:
+          'mfma' is the matrix-core gradient kernel (patches up to 32x32, ``NF_CFG_GRAD_MFMA``); no effect on narrower models.
+          Also selectable as ``hps.grad_kernel``; not with cnn_dtype='fp16'.
     binding : 'loss_first' | 'sample_first' — template→layer binding (quirk Q1).
     """
 
     def __init__(self, x_shape, is_training=False, hps=None, variables=None, binding="loss_first", device=None,
-                 cnn_dtype=None):
+                 cnn_dtype=None, grad_kernel=None):
         if hps is None:
             raise ValueError("hps is required (arch, width, ...)")
         self.x_shape = [int(v) for v in x_shape]
@@ -288,8 +296,10 @@ class NoiseFlow(object):
         # 'fp16': coupling-CNN convs in half precision on the matrix cores, everything else fp32
         # (BASELINE configs[4]); also selectable as hps.cnn_dtype.  Default: all fp32.
         self.cnn_dtype = cnn_dtype or str(getattr(hps, "cnn_dtype", "fp32"))
+        self.grad_kernel = grad_kernel or str(getattr(hps, "grad_kernel", "scalar"))
         self._flow = FlowHandle(self.arch, self._variables, self.x_shape, self.width, binding, self._dev.device.index,
-                                cnn_dtype=self.cnn_dtype, flow_permutation=self.flow_permutation, decomp=self.decomp)
+                                cnn_dtype=self.cnn_dtype, flow_permutation=self.flow_permutation, decomp=self.decomp,
+                                grad_kernel=self.grad_kernel)
 
     # ------------------------------------------------------------------ variables
     @property
@@ -307,7 +317,7 @@ class NoiseFlow(object):
         old = self._flow
         self._flow = FlowHandle(self.arch, self._variables, self.x_shape, self.width, self.binding,
                                 self._dev.device.index, cnn_dtype=self.cnn_dtype, flow_permutation=self.flow_permutation,
-                                decomp=self.decomp)
+                                decomp=self.decomp, grad_kernel=self.grad_kernel)
         old.close()
         if getattr(self, "_sync", None) is not None:
             self._install_sync()

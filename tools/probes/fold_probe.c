@@ -5,8 +5,9 @@
  * The Makefile target compiles nf_host.hip with -fsanitize=address,undefined on the host side and links it with the library's
  * other (unsanitised) objects into this stand-alone program.  Over a fixed list of (coupling width, H, W, flags) that reaches all
  * nine kernel paths in both directions it calls nf_fold_params, nf_fold_layout (size query, then an exactly-sized malloc buffer,
- * so that one float too many is a heap overflow the sanitizer reports), nf_cond_rows and nf_tile_segments.  Exit status 0 and the
- * last line "fold_probe ok" = nothing reported and every path seen with a block in both directions. */
+ * so that one float too many is a heap overflow the sanitizer reports), nf_cond_rows and nf_tile_segments, and — the gradient
+ * blocks of nf_nll_grad, with and without NF_CFG_GRAD_MFMA — nf_grad_fold.  Exit status 0 and the last line "fold_probe ok" =
+ * nothing reported, every path seen with a block in both directions and both gradient blocks seen. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -132,6 +133,34 @@ int main(void)
         }
         free(params);
     }
+    /* the gradient blocks (nf_grad_fold): scalar layout, and the fetch-order layout of the matrix-core gradient kernel */
+    static const int gcases[][4] = {{4, 32, 32, 0}, {8, 16, 16, NF_CFG_GRAD_MFMA}, {32, 16, 16, 0}, {32, 32, 32, NF_CFG_GRAD_MFMA},
+                                    {24, 9, 13, NF_CFG_GRAD_MFMA}, {17, 1, 1, NF_CFG_GRAD_MFMA}};
+    int gseen[2] = {0, 0};
+    for (size_t k = 0; k < sizeof(gcases) / sizeof(gcases[0]); ++k) {
+        nf_layer_desc layers[N_LAYERS];
+        size_t n_params = 0, n_folded = 0;
+        float *params = make_model(gcases[k][0], layers, &n_params);
+        if (!params) return 1;
+        nf_config cfg = {gcases[k][1], gcases[k][2], 4, N_LAYERS, -1, gcases[k][3]};
+        int32_t n_ops = 0, gpath = -1;
+        int rc = nf_grad_fold(&cfg, layers, params, n_params, &gpath, NULL, 0, &n_ops, NULL, 0, &n_folded);
+        if (rc == NF_OK) {
+            int32_t *ops = (int32_t *)malloc(2 * (size_t)n_ops * sizeof(int32_t));
+            float *blk = (float *)malloc(n_folded * sizeof(float));
+            rc = nf_grad_fold(&cfg, layers, params, n_params, &gpath, ops, n_ops, &n_ops, blk, n_folded, &n_folded);
+            free(blk);
+            free(ops);
+        }
+        if (rc != NF_OK || gpath < 0 || gpath > 1) {
+            fprintf(stderr, "gradient case %zu: nf_grad_fold: %s\n", k, nf_last_error());
+            return 1;
+        }
+        gseen[gpath]++;
+        free(params);
+    }
+    printf("gradient blocks: %d scalar, %d matrix-core\n", gseen[0], gseen[1]);
+    if (!gseen[0] || !gseen[1]) return 1;
     for (int d = 0; d < 2; ++d)
         for (int p = 0; p < N_PATHS; ++p) {
             printf("direction %d path %d: %d blocks\n", d, p, seen[d][p]);

@@ -1,10 +1,19 @@
-"""nf_nll_grad next to nf_nll: the shipped model at 32x32 and 64x64, B = 1 024, same box, same process.
+"""nf_nll_grad next to nf_nll: the shipped model at 32x32 and 64x64, and the paper-scale model (width 32, 8 couplings) on the
+matrix-core gradient kernel, B = 1 024, same box, same process.
 
-    python tools/time_nll_grad.py [--launches 200] [--out FILE.json]
+    python tools/time_nll_grad.py [--launches 200] [--legs shipped,wide] [--out FILE.json]
 
 Every figure is the mean over a window of `--launches` (at least 200) back-to-back launches between two device events, after
 a warm-up of a quarter of that; three windows per entry, their median is reported.  The yardstick is nf_nll (the forward
 kernel, which the gradient kernel does not touch): ms per launch, patches/s and the ratio grad / nll.
+
+Legs `wide` (the full architecture at width 32; variables: paper_like_variables below, the model of the deep GPU tests):
+  A/B at 24x24, the largest 8-coupling shape both gradient kernels hold: a handle with grad_kernel="mfma" (csrc/nf_grad_wide.hip)
+      against one without (the scalar kernel, csrc/nf_grad.hip), the arms alternated `--reps` (at least 4) times in one process.
+      Reported per arm: the median of its repetitions and its spread (max - min); the matrix-core kernel counts as faster when the
+      difference of the medians exceeds twice the larger spread.
+      `--ab-sides 8,16,24` adds other shapes both kernels hold.
+  32x32: the matrix-core gradient kernel next to nf_nll of the same model (NF_PATH_WIDE32), as for the shipped model.
 """
 import argparse
 import ctypes as C
@@ -19,8 +28,14 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--legs", default="shipped,wide")
+    ap.add_argument("--reps", type=int, default=4)
+    ap.add_argument("--ab-sides", default="24", help="patch sides of the A/B legs (both gradient kernels must hold them)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    legs = a.legs.split(",")
+    if a.reps < 4:
+        raise SystemExit("--reps must be at least 4")
     if a.launches < 200:
         raise SystemExit("--launches must be at least 200")
     import numpy as np
@@ -45,7 +60,7 @@ def main():
         return sorted(window(a.launches) for _ in range(3))[1]
 
     res = {"B": B, "launches_per_window": a.launches, "shapes": {}}
-    for side in (32, 64):
+    for side in (32, 64) if "shipped" in legs else ():
         m = NoiseFlow([side, side, 4], False, default_hps(), variables=v, device=0)
         rng = np.random.RandomState(0)
         y = torch.as_tensor(rng.rand(B, side, side, 4).astype(np.float32)).cuda()
@@ -62,12 +77,103 @@ def main():
         res["shapes"]["%dx%d" % (side, side)] = r
         print("%dx%d  nf_nll %.4f ms (%.3e patches/s)   nf_nll_grad %.4f ms (%.3e patches/s)   ratio %.2f"
               % (side, side, t_nll, r["nll_patches_per_s"], t_grad, r["grad_patches_per_s"], r["grad_over_nll"]), flush=True)
+    if "wide" in legs:
+        res["wide32"] = wide_legs(a, timed, B)
     print("RESULT " + json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
     return 0
+
+
+FULL_ARCH = "sdn5|unc|unc|unc|unc|gain4|unc|unc|unc|unc"
+
+
+def paper_like_variables(arch, width, seed=0):
+    """Fresh variables perturbed so that every term of the stack is exercised, the per-layer gain held independent of the width
+    (l_2 by sqrt(4 / w), l_last by sqrt(5 / (w + 1))) — the same construction, value for value, as the model of
+    tests/test_gpu_nll_grad_wide.py, restated here so that the tool stands without the test modules."""
+    import numpy as np
+    from noise_flow_amd import params
+    rng = np.random.RandomState(seed + 1000)
+    v = params.init_variables(arch, width, 4, seed)
+    for k in list(v):
+        a = v[k]
+        if k.endswith("l_1/W"):
+            v[k] = (rng.randn(*a.shape) * 0.4).astype(np.float32)
+        elif k.endswith("l_2/W"):
+            v[k] = ((rng.randn(*a.shape) * 0.4).astype(np.float32) * np.sqrt(4.0 / width)).astype(np.float32)
+        elif k.endswith("l_last/W"):
+            v[k] = ((rng.randn(*a.shape) * 0.15).astype(np.float32) * np.sqrt(5.0 / (width + 1))).astype(np.float32)
+        elif k.endswith("/b") or k.endswith("l_last/logs"):
+            v[k] = (rng.randn(*a.shape) * 0.1).astype(np.float32)
+        elif k.endswith("/mean"):
+            v[k] = (rng.randn(*a.shape) * 0.2).astype(np.float32)
+        elif k.endswith("/var"):
+            v[k] = (0.5 + rng.rand(*a.shape)).astype(np.float32)
+        elif "rescaling_scale" in k:
+            v[k] = np.float32(0.3 + 0.6 * rng.rand())
+        elif "log_S" in k or "L_vec" in k or "U_vec" in k:
+            v[k] = (a + rng.randn(*a.shape).astype(np.float32) * 0.1).astype(np.float32)
+        elif k.endswith("gain_val"):
+            v[k] = np.asarray([1.3], np.float32)
+    return v
+
+
+def wide_legs(a, timed, B):
+    import numpy as np
+    import torch
+    from noise_flow_amd import NoiseFlow, _lib, default_hps
+    v = paper_like_variables(FULL_ARCH, 32)
+    cond = _lib.nf_cond(800.0, 2.0, 0.0, 0.0)
+    out = {}
+
+    def setup(side, grad_kernel):
+        m = NoiseFlow([side, side, 4], False, default_hps(arch=FULL_ARCH, width=32), variables=v, device=0, grad_kernel=grad_kernel)
+        rng = np.random.RandomState(0)
+        y = torch.as_tensor(rng.rand(B, side, side, 4).astype(np.float32)).cuda()
+        x = torch.as_tensor((rng.randn(B, side, side, 4) * 0.02).astype(np.float32)).cuda()
+        bufs = (x, y, torch.empty((B,), device="cuda"), torch.empty_like(x), torch.empty_like(y))
+        lib, h, st = m._flow.lib, m._flow.ptr, m._dev.stream_ptr()
+        grad = lambda: _lib.check(lib.nf_nll_grad(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), None, bufs[2].data_ptr(),   # noqa: E731
+                                                  bufs[3].data_ptr(), bufs[4].data_ptr(), st))
+        return m, bufs, grad
+
+    # A/B at 24x24 (and any other side asked for)
+    med = lambda t: float(np.median(t))   # noqa: E731
+    for side in [int(v) for v in a.ab_sides.split(",") if v]:
+        ma, ba, ga = setup(side, "mfma")
+        mb, bb, gb = setup(side, "scalar")
+        assert ma._flow.lib.nf_grad_path(ma._flow.ptr) == _lib.NF_GRAD_PATH_WIDE32
+        assert mb._flow.lib.nf_grad_path(mb._flow.ptr) == _lib.NF_GRAD_PATH_SCALAR
+        ta, tb = [], []
+        for rep in range(a.reps):
+            ta.append(timed(ga))
+            tb.append(timed(gb))
+            print("%dx%d rep %d  matrix-core %.4f ms   scalar %.4f ms" % (side, side, rep, ta[-1], tb[-1]), flush=True)
+        spread = max(max(ta) - min(ta), max(tb) - min(tb))
+        r = {"mfma_ms": ta, "scalar_ms": tb, "mfma_median_ms": med(ta), "scalar_median_ms": med(tb), "larger_spread_ms": spread,
+             "scalar_over_mfma": med(tb) / med(ta), "faster_by_the_rule": bool(med(tb) - med(ta) > 2.0 * spread)}
+        out["%dx%d" % (side, side)] = r
+        print("%dx%d  matrix-core %.4f ms (%.3e patches/s)   scalar %.4f ms (%.3e patches/s)   scalar / matrix-core %.2f   "
+              "difference %.4f ms vs 2 x larger in-arm spread %.4f ms: %s"
+              % (side, side, med(ta), B / med(ta) * 1e3, med(tb), B / med(tb) * 1e3, med(tb) / med(ta), med(tb) - med(ta), 2.0 * spread,
+                 "faster" if r["faster_by_the_rule"] else "NOT faster by the rule"), flush=True)
+        del ma, mb, ba, bb
+    # 32x32 next to nf_nll
+    m, (x, y, nll, gx, gy), grad = setup(32, "mfma")
+    sd, ld = torch.empty((B,), device="cuda"), torch.empty((B,), device="cuda")
+    lib, h, st = m._flow.lib, m._flow.ptr, m._dev.stream_ptr()
+    assert lib.nf_grad_path(h) == _lib.NF_GRAD_PATH_WIDE32 and lib.nf_kernel_path(h, 0) == _lib.NF_PATH_WIDE32
+    t_nll = timed(lambda: _lib.check(lib.nf_nll(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), nll.data_ptr(), sd.data_ptr(),
+                                                ld.data_ptr(), None, None, 0, st)))
+    t_grad = timed(grad)
+    out["32x32"] = {"nll_ms": t_nll, "grad_ms": t_grad, "nll_patches_per_s": B / t_nll * 1e3, "grad_patches_per_s": B / t_grad * 1e3,
+                    "grad_over_nll": t_grad / t_nll}
+    print("width 32, 32x32  nf_nll %.4f ms (%.3e patches/s)   nf_nll_grad (matrix-core) %.4f ms (%.3e patches/s)   ratio %.2f"
+          % (t_nll, B / t_nll * 1e3, t_grad, B / t_grad * 1e3, t_grad / t_nll), flush=True)
+    return out
 
 
 if __name__ == "__main__":
