@@ -1166,6 +1166,8 @@ __global__ void k_mm_pack(int mode, int rows, int cols, int ld, int w, const flo
 // ---- launches (host) ----------------------------------------------------------------------------------------------------------
 struct Ctx {
     int n_cu, device;
+    int mode = -1;   // >= 0: what pix_mode() returns, whatever NF_MM_MODE and the pixel count say (tools/probes/mm_check.hip: the tests
+                     // launch every mode in one process; the trainer leaves it at -1)
 };
 
 // floats of partial products one filter gradient may leave (k_mm_kpix: S x M x N)
@@ -1211,9 +1213,10 @@ inline bool mm_pix_launch(const Ctx &cx, hipStream_t st, PixArgs a)
 
 // How the 128-column products (widths beyond 64: the l_2 products) run.  0: fp32, 4 wavefronts on 128 x 128 (two workgroups per CU);
 // 1: fp32, 8 wavefronts on 256 x 128; 2: bf16 x 6 (k_mm_pix, PREC 1), 8 wavefronts on 256 x 128; 3: bf16 x 6, 4 wavefronts on 128 x 128, one
-// operand buffer.  NF_MM_MODE overrides (A/B aid, read once).
-inline int pix_mode(int64_t P, int n_cu)
+// operand buffer.  NF_MM_MODE overrides (A/B aid, read once); `ctx_mode` >= 0 (Ctx::mode) overrides both.
+inline int pix_mode(int64_t P, int n_cu, int ctx_mode)
 {
+    if (ctx_mode >= 0) return ctx_mode;
     static const int forced = [] { const char *e = getenv("NF_MM_MODE"); return e ? atoi(e) : -1; }();
     if (forced >= 0) return forced;                                       // (every size: the probe checks small products this way)
     if (MM_DEFAULT_MODE == 1 || MM_DEFAULT_MODE == 2) return P >= (int64_t)pix_bm(8) * n_cu / 2 ? MM_DEFAULT_MODE : 0;   // 256-pixel tiles want enough of them to fill the chip
@@ -1224,7 +1227,7 @@ template <int APRO, int EPI, int AV, int CV>
 inline bool mm_pix_cv(const Ctx &cx, hipStream_t st, const PixArgs &a)
 {
     if (a.N > 64) {
-        const int mode = pix_mode(a.P, cx.n_cu);
+        const int mode = pix_mode(a.P, cx.n_cu, cx.mode);
         if (mode == 3) return mm_pix_launch<2, 2, APRO, EPI, AV, CV, 4, 1>(cx, st, a);
         if (mode == 2) return mm_pix_launch<2, 2, APRO, EPI, AV, CV, 8, 1>(cx, st, a);
         if (mode == 1) return mm_pix_launch<2, 2, APRO, EPI, AV, CV, 8, 0>(cx, st, a);
@@ -1269,7 +1272,7 @@ inline int mm_kpix_launch(const Ctx &cx, hipStream_t st, KpixArgs a)
     a.chunk = ((a.npix + S - 1) / S + kBK - 1) / kBK * kBK;
     a.S = (int)((a.npix + a.chunk - 1) / a.chunk);
     if constexpr (WMv == 2 && TM == 2 && TN == 2 && APRO <= 1 && AV == 4 && BV == 4 && BPRO == 0) {
-        if (pix_mode(a.npix, cx.n_cu) >= 2 && a.M % 4 == 0 && a.N % 4 == 0) {   // the bf16 x 6 twin (same tiles, same chunks)
+        if (pix_mode(a.npix, cx.n_cu, cx.mode) >= 2 && a.M % 4 == 0 && a.N % 4 == 0) {   // the bf16 x 6 twin (same tiles, same chunks)
             const unsigned grid6 = (unsigned)((a.S + 7) / 8 * 8 * tiles);
             hipLaunchKernelGGL(k_mm_kpix6<APRO>, dim3(grid6), dim3(kT), kpix6_lds_bytes(), st, a);
             return a.S;

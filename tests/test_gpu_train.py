@@ -878,3 +878,120 @@ def test_gradients_at_coupling_widths_beyond_32(arch, width, hw, B, iso, cam):
         a, b = np.asarray(after[k], np.float64).reshape(-1), np.asarray(want[k], np.float64).reshape(-1)
         moved = np.abs(b - np.asarray(v[k], np.float64).reshape(-1)) > 0
         assert (np.abs(a - b)[moved] <= 2.5e-3).all(), k       # a step is +-lr wherever the gradient is resolved; sign flips only at its noise floor
+
+
+# ---- the bf16 x 6 products of the widths beyond 64 in a whole step (csrc/nf_train_mm.h; the single products at fp32 resolution:
+#      tests/test_gpu_train_mm.py) ------------------------------------------------------------------------------------------------
+MM_MODE = "NF_MM_MODE"      # read once per process (mm::pix_mode): a step under it runs in a fresh child
+
+
+def _wide_variables(arch, width):
+    v = trained_like_variables(arch, width, seed=width)
+    for k in v:     # activations of O(1) at every width, as test_gradients_at_coupling_widths_beyond_32
+        if k.endswith("l_2/W") or k.endswith("l_last/W"):
+            v[k] = (v[k] * np.float32((4.0 / width) ** 0.5)).astype(np.float32)
+    return v
+
+
+def _check_running_statistics(tr, new_running):
+    got = tr.variables
+    for k, want in new_running.items():
+        assert np.abs(np.asarray(got[k], np.float64).reshape(want.shape) - want).max() <= 1e-5 * max(np.abs(want).max(), 1e-3), k
+
+
+def _child(mode, *args):
+    """python test_gpu_train.py <args> in a fresh process with NF_MM_MODE = mode."""
+    import subprocess
+    import sys
+    assert MM_MODE not in os.environ, "the parent must take the default dispatch"
+    env = dict(os.environ)
+    env[MM_MODE] = str(mode)
+    subprocess.run([sys.executable, os.path.abspath(__file__)] + [str(a) for a in args], check=True, env=env, timeout=300)
+
+
+def _child_oracle_check(arch, width, H, W, B, iso, cam, out):
+    """(child) the step under the NF_MM_MODE of this process against the fp64 oracle, exactly as
+    test_gradients_at_coupling_widths_beyond_32 holds the default dispatch; leaves the raw gradient in `out`."""
+    v = _wide_variables(arch, width)
+    x, y = make_inputs(B, H, W, seed=19)
+    tr = _trainer(arch, v, (H, W, 4), width)
+    _oracle_check_next_to_kinks(tr, arch, v, x, y, iso, cam, width, rtol=1e-3)
+    _check_running_statistics(tr, _grad_oracle(arch, v).loss_and_grads(x, y, iso, cam)[3])
+    tr.close()
+    g, _ = _trainer(arch, v, (H, W, 4), width).forward_backward(x, y, [0.0], [0.0], [iso], [cam])      # a fresh trainer's first step, as the parent's
+    np.save(out, g.cpu().numpy())
+
+
+@pytest.mark.parametrize("mode", [2, 3])
+@pytest.mark.parametrize("arch,width,hw,B,iso,cam", [("sdn5|unc|gain4", 132, (7, 5), 3, 1600, 3), ("unc|unc", 96, (32, 32), 6, 800, 2)])
+def test_forced_bf16x6_modes_against_the_oracle(arch, width, hw, B, iso, cam, mode, tmp_path):
+    """NF_MM_MODE = 2 (8 wavefronts) and 3 (4 wavefronts, one operand buffer) at sizes the default dispatch leaves to the fp32 twin
+    and the kink rule handles: loss, sd_z, every gradient tensor and the BN running statistics against the fp64 oracle, in a fresh
+    child process.  That the switch was taken: the child's raw gradient is not, bit for bit, the default dispatch's."""
+    out = os.path.join(str(tmp_path), "grad.npy")
+    _child(mode, "oracle", arch, width, hw[0], hw[1], B, iso, cam, out)
+    x, y = make_inputs(B, hw[0], hw[1], seed=19)
+    tr = _trainer(arch, _wide_variables(arch, width), (hw[0], hw[1], 4), width)
+    g, _ = tr.forward_backward(x, y, [0.0], [0.0], [iso], [cam])
+    g = g.cpu().numpy()
+    forced = np.load(out)
+    assert forced.shape == g.shape and not np.array_equal(forced.view(np.uint32), g.view(np.uint32))
+
+
+def _child_grads(arch, width, H, W, out, *batches):
+    """(child) the raw gradient of one step per batch size, under the NF_MM_MODE of this process."""
+    v = _wide_variables(arch, width)
+    res = {}
+    for B in batches:
+        x, y = make_inputs(B, H, W, seed=19)
+        tr = _trainer(arch, v, (H, W, 4), width, max_batch=B)
+        g, _ = tr.forward_backward(x, y, [0.0], [0.0], [800], [2])
+        res["g%d" % B] = g.cpu().numpy()
+        tr.close()
+    np.savez(out, **res)
+
+
+def test_default_dispatch_switches_to_bf16x6_at_half_a_tile_per_cu(tmp_path):
+    """mm::pix_mode() takes the bf16 x 6 kernels from 128 x multi_processor_count pixels up: B = that many / 1 024 patches of
+    32x32 (32 on an MI355X) at width 68 run them, B - 1 patches the fp32 twin.  With B patches the raw gradient is, bit for bit,
+    that of a child under NF_MM_MODE=2 and differs from a child's under NF_MM_MODE=0; with B - 1 it is the mode-0 child's.
+    Loss, sd_z (1e-5) and the BN running statistics (1e-5 of their scale) against the fp64 oracle — all three continuous across
+    ReLU kinks.  No gradient-against-oracle comparison at this size: 4.5 million ReLU inputs put on the order of a hundred
+    activations within 32 ulps of their kink, more than the kink rule solves for (max_kinks = 64); the products themselves are held
+    to fp32 resolution by tests/test_gpu_train_mm.py.  (The oracle takes 1.6 s of CPU time for the 32 patches.)"""
+    import torch
+    arch, width, hw = "unc", 68, (32, 32)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = -(-128 * cus // 1024)
+    assert (B - 1) * 1024 < 128 * cus <= B * 1024
+    v = _wide_variables(arch, width)
+    got = {}
+    for n in (B, B - 1):
+        x, y = make_inputs(n, hw[0], hw[1], seed=19)
+        tr = _trainer(arch, v, (hw[0], hw[1], 4), width, max_batch=n)
+        g, loss = tr.forward_backward(x, y, [0.0], [0.0], [800], [2])
+        got[n] = g.cpu().numpy().copy()
+        if n == B:
+            lv = loss.cpu().numpy()
+            ref_loss, ref_sd, _, new_running = _grad_oracle(arch, v).loss_and_grads(x, y, 800, 2)
+            assert abs(lv[0] - ref_loss) <= 1e-5 * abs(ref_loss)
+            assert abs(lv[1] - ref_sd) <= 1e-5 * ref_sd
+            _check_running_statistics(tr, new_running)
+        tr.close()
+    out2, out0 = os.path.join(str(tmp_path), "m2.npz"), os.path.join(str(tmp_path), "m0.npz")
+    _child(2, "grads", arch, width, hw[0], hw[1], out2, B)
+    _child(0, "grads", arch, width, hw[0], hw[1], out0, B, B - 1)
+    bits = lambda a: a.view(np.uint32)      # noqa: E731
+    with np.load(out2) as m2, np.load(out0) as m0:
+        assert np.array_equal(bits(got[B]), bits(m2["g%d" % B]))
+        assert not np.array_equal(bits(got[B]), bits(m0["g%d" % B]))
+        assert np.array_equal(bits(got[B - 1]), bits(m0["g%d" % (B - 1)]))
+
+
+if __name__ == "__main__":      # the children of the NF_MM_MODE tests: python test_gpu_train.py oracle|grads <arguments>
+    import sys
+    a = sys.argv[2:]
+    if sys.argv[1] == "oracle":
+        _child_oracle_check(a[0], int(a[1]), int(a[2]), int(a[3]), int(a[4]), float(a[5]), float(a[6]), a[7])
+    else:
+        _child_grads(a[0], int(a[1]), int(a[2]), int(a[3]), a[4], *[int(b) for b in a[5:]])
