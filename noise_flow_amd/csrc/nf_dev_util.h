@@ -1,5 +1,7 @@
-// Device helpers shared by the fused flow kernels (nf_kernels.hip, nf_wide.hip): Philox4x32-10 /
-// Box-Muller, the hardware-transcendental exp / tanh, one-instruction ReLU, wavefront reductions.
+// Device helpers shared by every kernel of the library (the fused flow kernels nf_kernels.hip, nf_wide.hip, nf_wide16.hip, nf_gemm.hip,
+// nf_gemm16.hip, the gradient kernels nf_grad.hip, nf_grad_wide.hip and the trainer nf_train.hip): Philox4x32-10 / Box-Muller, the
+// hardware-transcendental exp / tanh, one-instruction ReLU, the bf16 split, wavefront reductions and lane shifts, and the accessors of
+// per-patch conditioning.  What the flow kernels beyond width 4 share around their coupling CNN is in nf_flow_common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,8 +19,9 @@ typedef const float __attribute__((address_space(4))) *cfloat_p;
 // PC is a template flag of every fused kernel body: the per-call kernels (PC = false) compile to the code they were before the
 // rows existed — these kernels sit at their scalar-register limit, and a run-time choice between the two sources moved their
 // register allocation — and each has a twin with PC = true that the launchers pick when cond_rows is set (nf_kernels.hip,
-// nf_wide.hip: `..._pc_kernel` wrappers of the shared body; the GEMM and width-16 kernels carry the flag themselves, because
-// moving their code into a body behind a wrapper changed their spills).
+// nf_wide.hip: `..._pc_kernel` wrappers of the shared body; the GEMM and width-16 kernels carry the flag as a template parameter
+// of the __global__ function itself, because moving their code into a body behind a wrapper changed their spills — their shared
+// pieces are force-inlined helpers, nf_flow_common.h and nf_gemm_common.h).
 typedef const nf_cond_row __attribute__((address_space(4))) *nf_crow_p;
 template <bool PC>
 __device__ __forceinline__ nf_crow_p nf_cond_row_of(const NfLaunch &a, int64_t patch)
@@ -163,6 +166,26 @@ __device__ __forceinline__ float wave_sum(float v)
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
     const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
     return (r0 + r1) + (r2 + r3);
+}
+
+// Value of the lane one pixel to the left / right of a wavefront-wide row of pixels (nf_wide.hip, nf_grad_wide.hip): DPP wave_shr:1 /
+// wave_shl:1 — a VALU operand modifier, no LDS traffic and no address register.  Callers multiply the tile ends away: lane 32
+// receives lane 31's value and vice versa.
+__device__ __forceinline__ float from_prev(float x)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x138, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float from_next(float x)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x130, 0xf, 0xf, true));
+}
+// a(lanes 0-31) + a(lanes 32-63) in the low half, b(lanes 0-31) + b(lanes 32-63) in the high half: the two lane
+// halves hold partial sums of the same pixels; the low half finishes tile `a`, the high half tile `b` — one
+// v_permlane32_swap + one add for two tiles
+__device__ __forceinline__ float half_sums(float a, float b)
+{
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
 // every lane of a 16-lane DPP row gets its row's sum (the first four issues of wave_sum)

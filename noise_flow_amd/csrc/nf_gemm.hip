@@ -90,9 +90,9 @@ __global__ __launch_bounds__(GT) void nf_gemm_kernel(const NfProgram prog, const
     double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const GemmTile T = gemm_tile<PC>(a, b, H, W);
+        const FlowTile T = flow_tile<PC>(a, b, H, W);
         float z[OWN][4];
-        gemm_input<OWN, PHILOX>(a, T, GemmPixTable<OWN>{pr, pc, act}, z);
+        flow_input<OWN, PHILOX>(a, T, GemmPixTable<OWN>{pr, pc, act}, z);
 
         float ld = 0.0f, ld2 = 0.0f;   // natural-log / log2 parts of this thread's log-det share
 
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(GT) void nf_gemm_kernel(const NfProgram prog, const
             const cfloat_p P = (cfloat_p)(a.params + prog.ops[op].off);   // wave-uniform, scalar loads
 
             if (type == NF_OP_MIX) {
-                gemm_mix<OWN>(P, z);
+                flow_mix<OWN>(P, z);
             } else if (type == NF_OP_COUPLING_FWD || type == NF_OP_COUPLING_REV) {
                 const float *const img = a.params + prog.ops[op].off + NF7_CPL_IMG;
                 // ---- publish the pass-through half ----
@@ -292,17 +292,17 @@ __global__ __launch_bounds__(GT) void nf_gemm_kernel(const NfProgram prog, const
                 }
 
                 // ---- finish the coupling on the owned pixels ----
-                gemm_finish_coupling<OWN, false>(type, a.params + prog.ops[op].off + NF7_CPL_E, P[NF7_CPL_S + 1], P[NF7_CPL_S + 2], T, GemmPixTable<OWN>{pr, pc, act}, o, z, ld2);
+                flow_finish_coupling<OWN, false>(type, a.params + prog.ops[op].off + NF7_CPL_E, P[NF7_CPL_S + 1], P[NF7_CPL_S + 2], T, GemmPixTable<OWN>{pr, pc, act}, o, z, ld2);
             } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
-                gemm_sdn<OWN, PC>(type, prog.ops[op].off, a, T, GemmPixTable<OWN>{pr, pc, act}, z, ld);
+                flow_sdn<OWN, PC>(type, prog.ops[op].off, a, T, GemmPixTable<OWN>{pr, pc, act}, z, ld);
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off), z);
+                flow_scale<OWN>(type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off), z);
             }
         }
 
-        gemm_epilogue<OWN, PC>(a, T, b, HW, GemmPixTable<OWN>{pr, pc, act}, z, ld, ld2, red, acc_nll, acc_sd);
+        flow_epilogue<OWN, PC, GW>(a, T, b, HW, GemmPixTable<OWN>{pr, pc, act}, z, ld, ld2, red, acc_nll, acc_sd);
     }
-    gemm_flush_sums(a, acc_nll, acc_sd);
+    flow_flush_sums(a, acc_nll, acc_sd);
 }
 
 
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(GT) void nf_gemmb_kernel(const NfProgram prog, cons
     for (int i = t; i < 2 * PL; i += GT) z0s[i] = 0.0f;
     __syncthreads();
 
-    gemm_frame<OWN, PHILOX, PC>(prog, a, red, [&](int type, int off, cfloat_p P, const GemmTile &T, const GemmPix<OWN> &pix, float (&z)[OWN][4],
+    gemm_frame<OWN, PHILOX, PC>(prog, a, red, [&](int type, int off, cfloat_p P, const FlowTile &T, const GemmPix<OWN> &pix, float (&z)[OWN][4],
                                                   float (&o)[OWN][4], float &ld2) __attribute__((always_inline)) {
         const float *const img = a.params + off + NF7_CPL_IMG;
         // publish the pass-through half, stage this coupling's slabs
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(GT) void nf_gemmb_kernel(const NfProgram prog, cons
             __syncthreads();   // the next round overwrites the records
         }
 
-        gemm_finish_coupling<OWN, false>(type, a.params + off + NF7_CPL_E, P[NF7_CPL_S + 1], P[NF7_CPL_S + 2], T, pix, o, z, ld2);
+        flow_finish_coupling<OWN, false>(type, a.params + off + NF7_CPL_E, P[NF7_CPL_S + 1], P[NF7_CPL_S + 2], T, pix, o, z, ld2);
     });
 }
 
@@ -451,7 +451,7 @@ struct GemmA {
 // variant B: programs in the NF10 layout (widths <= 128)
 bool nf_gemmb_shape_ok(int wp, int H, int W)
 {
-    return wp <= 128 && H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemmb_lds_bytes(wp, H, W) <= GEMM_LDS_MAX;
+    return wp <= 128 && H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemmb_lds_bytes(wp, H, W) <= FLOW_LDS_MAX;
 }
 hipError_t nf_launch_gemmb(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
 {
@@ -464,7 +464,7 @@ hipError_t nf_launch_gemmb(const NfProgram &prog, const NfLaunch &a, int n_cu, i
 // whether a patch shape fits the GEMM kernel (nf_create asks before accepting a width > 32)
 bool nf_gemm_shape_ok(int H, int W)
 {
-    return H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemm_lds_bytes(H, W, false) <= GEMM_LDS_MAX;
+    return H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemm_lds_bytes(H, W, false) <= FLOW_LDS_MAX;
 }
 
 // entry point used by nf_host.hip: programs in the NF7 layout (coupling width padded to 64 / 128 / 256 / 512)
@@ -475,7 +475,7 @@ hipError_t nf_launch_gemm(const NfProgram &prog, const NfLaunch &a, int n_cu, in
         constexpr int WP = decltype(wp)::value;
         constexpr bool PHILOX = decltype(philox)::value;
         // 8 pixels per thread (beyond 2048 pixels, up to 64x64): the bordered tile of the largest shapes does not fit beside the band
-        if (a.H * a.W > 4 * GT && gemm_lds_bytes(a.H, a.W, true) > GEMM_LDS_MAX)
+        if (a.H * a.W > 4 * GT && gemm_lds_bytes(a.H, a.W, true) > FLOW_LDS_MAX)
             return gemm_launch_own<GemmA<WP, PHILOX, false>, 8>(gemm_lds_bytes(a.H, a.W, false), prog, a, n_cu, device, stream);
         return gemm_launch<GemmA<WP, PHILOX, true>>(gemm_lds_bytes(a.H, a.W, true), prog, a, n_cu, device, stream);
     });

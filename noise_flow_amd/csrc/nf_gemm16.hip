@@ -74,7 +74,7 @@ __global__ __launch_bounds__(GT) void nf_gemm16_kernel(const NfProgram prog, con
     for (int i = t; i < PL; i += GT) z0h[i] = 0u;
     __syncthreads();
 
-    gemm_frame<OWN, PHILOX, PC>(prog, a, red, [&](int type, int off, cfloat_p P, const GemmTile &T, const GemmPix<OWN> &pix, float (&z)[OWN][4],
+    gemm_frame<OWN, PHILOX, PC>(prog, a, red, [&](int type, int off, cfloat_p P, const FlowTile &T, const GemmPix<OWN> &pix, float (&z)[OWN][4],
                                                   float (&o)[OWN][4], float &ld2) __attribute__((always_inline)) {
         const float *const img = a.params + off + NF8_CPL_IMG;
         gemm_publish_half<OWN>(z0h, Wp, pix, z);   // rounded to half: a CNN input
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(GT) void nf_gemm16_kernel(const NfProgram prog, con
             __syncthreads();   // the next band's l_1 overwrites the region
         }
 
-        gemm_finish_coupling<OWN, true>(type, a.params + off + NF8_CPL_E, P[NF8_CPL_S + 1], P[NF8_CPL_S + 2], T, pix, o, z, ld2);
+        flow_finish_coupling<OWN, true>(type, a.params + off + NF8_CPL_E, P[NF8_CPL_S + 1], P[NF8_CPL_S + 2], T, pix, o, z, ld2);
     });
 }
 
@@ -249,9 +249,9 @@ __global__ __launch_bounds__(GT) void nf_gemm16b_kernel(const NfProgram prog, co
     double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const GemmTile T = gemm_tile<PC>(a, b, H, W);
+        const FlowTile T = flow_tile<PC>(a, b, H, W);
         float z[OWN][4];
-        gemm_input<OWN, PHILOX>(a, T, GemmPixTable<OWN>{pr, pc, act}, z);
+        flow_input<OWN, PHILOX>(a, T, GemmPixTable<OWN>{pr, pc, act}, z);
 
         float ld = 0.0f, ld2 = 0.0f;   // natural-log / log2 parts of this thread's log-det share
 
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(GT) void nf_gemm16b_kernel(const NfProgram prog, co
             const cfloat_p P = (cfloat_p)(a.params + prog.ops[op].off);   // wave-uniform, scalar loads
 
             if (type == NF_OP_MIX) {
-                gemm_mix<OWN>(P, z);
+                flow_mix<OWN>(P, z);
             } else if (type == NF_OP_COUPLING_FWD || type == NF_OP_COUPLING_REV) {
                 const float *const img = a.params + prog.ops[op].off + NF8_CPL_IMG;
                 const float *const slabs = img + nf9_img_SLAB(WP);
@@ -400,17 +400,17 @@ __global__ __launch_bounds__(GT) void nf_gemm16b_kernel(const NfProgram prog, co
                 }
 
                 // ---- finish the coupling on the owned pixels ----
-                gemm_finish_coupling<OWN, true>(type, a.params + prog.ops[op].off + NF8_CPL_E, P[NF8_CPL_S + 1], P[NF8_CPL_S + 2], T, GemmPixTable<OWN>{pr, pc, act}, o, z, ld2);
+                flow_finish_coupling<OWN, true>(type, a.params + prog.ops[op].off + NF8_CPL_E, P[NF8_CPL_S + 1], P[NF8_CPL_S + 2], T, GemmPixTable<OWN>{pr, pc, act}, o, z, ld2);
             } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
-                gemm_sdn<OWN, PC>(type, prog.ops[op].off, a, T, GemmPixTable<OWN>{pr, pc, act}, z, ld);
+                flow_sdn<OWN, PC>(type, prog.ops[op].off, a, T, GemmPixTable<OWN>{pr, pc, act}, z, ld);
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                gemm_scale<OWN>(type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off), z);
+                flow_scale<OWN>(type == NF_OP_SCALE ? P[0] : nf_cond_a<PC>(a, T.crow, prog.ops[op].off), z);
             }
         }
 
-        gemm_epilogue<OWN, PC>(a, T, b, HW, GemmPixTable<OWN>{pr, pc, act}, z, ld, ld2, red, acc_nll, acc_sd);
+        flow_epilogue<OWN, PC, GW>(a, T, b, HW, GemmPixTable<OWN>{pr, pc, act}, z, ld, ld2, red, acc_nll, acc_sd);
     }
-    gemm_flush_sums(a, acc_nll, acc_sd);
+    flow_flush_sums(a, acc_nll, acc_sd);
 }
 
 // ---- launching ---------------------------------------------------------------------------------------------------------------------
@@ -438,7 +438,7 @@ struct Gemm16A {
 // whether a patch shape fits the band kernel (asked by its entry point only: nf_create accepts shapes by nf_gemm_shape_ok)
 bool nf_gemm16_shape_ok(int H, int W)
 {
-    return H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemm16_lds_bytes(H, W) <= GEMM_LDS_MAX;
+    return H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemm16_lds_bytes(H, W) <= FLOW_LDS_MAX;
 }
 
 }  // namespace
@@ -446,7 +446,7 @@ bool nf_gemm16_shape_ok(int H, int W)
 // variant B: programs in the NF9 layout (widths <= 128); nf_create asks before it lays a program out for it
 bool nf_gemm16b_shape_ok(int wp, int H, int W)
 {
-    return wp <= 128 && H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemm16b_lds_bytes(wp, H, W) <= GEMM_LDS_MAX;
+    return wp <= 128 && H >= 1 && W >= 1 && H * W <= NF7_MAX_PIXELS && gemm16b_lds_bytes(wp, H, W) <= FLOW_LDS_MAX;
 }
 hipError_t nf_launch_gemm16b(const NfProgram &prog, const NfLaunch &a, int n_cu, int device, hipStream_t stream)
 {

@@ -20,6 +20,7 @@
 #include "nf_device.h"
 #include "nf_dev_util.h"
 #include "nf_internal.h"
+#include "nf_flow_common.h"   // flow_launch: the persistent-grid launcher
 
 namespace {
 
@@ -505,34 +506,9 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
 template <int WIDTH, int THREADS, int PX>
 hipError_t launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
 {
-    void (*const kern)(const NfProgram, const NfGradLaunch) = &nf_grad_kernel<WIDTH, THREADS, PX>;
-    const void *fn = reinterpret_cast<const void *>(kern);
-    // (device << 40 | lds bytes << 8 | resident workgroups per CU) of the last query, as launch_flow_p keeps it
     int dev = 0;
     (void)hipGetDevice(&dev);
-    static std::atomic<uint64_t> cache{0};
-    const uint64_t key = ((uint64_t)(dev & 0xff) << 40) | ((uint64_t)lds << 8);
-    const uint64_t c = cache.load(std::memory_order_relaxed);
-    int occ;
-    if ((c & ~(uint64_t)0xff) == key && (c & 0xff) != 0) {
-        occ = (int)(c & 0xff);
-    } else {
-        if (lds > 64 * 1024) {   // always the CU's whole 160 KiB: concurrent callers with other patch sizes never lower it under a launch
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-        occ = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, THREADS, lds);
-        if (e != hipSuccess) return e;
-        if (occ < 1) occ = 1;
-        if (occ > 32) occ = 32;
-        cache.store(key | (uint64_t)occ, std::memory_order_relaxed);
-    }
-    int64_t groups = (int64_t)n_cu * occ;
-    if (a.B < groups) groups = a.B;
-    if (groups < 1) groups = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(THREADS), lds, stream, prog, a);
-    return hipGetLastError();
+    return flow_launch<&nf_grad_kernel<WIDTH, THREADS, PX>>(THREADS, lds, prog, a, n_cu, dev, stream);
 }
 
 template <int WIDTH>

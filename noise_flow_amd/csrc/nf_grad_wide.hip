@@ -23,26 +23,12 @@
 #include "nf_device.h"
 #include "nf_dev_util.h"
 #include "nf_internal.h"
+#include "nf_flow_common.h"   // flow_launch: the persistent-grid launcher
 
 namespace {
 
 typedef float v16f __attribute__((ext_vector_type(16)));
 
-// value of the lane one pixel to the left / right (DPP wave_shr:1 / wave_shl:1; callers multiply the tile ends away)
-__device__ __forceinline__ float gw_from_prev(float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float gw_from_next(float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x130, 0xf, 0xf, true));
-}
-// a(lanes 0-31) + a(lanes 32-63) in the low half, b(lanes 0-31) + b(lanes 32-63) in the high half (nf_wide.hip)
-__device__ __forceinline__ float gw_half_sums(float a, float b)
-{
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 __device__ __forceinline__ float gw_gate(uint32_t word, int bit, float x) { return ((word >> bit) & 1u) ? x : 0.0f; }
 
 //   NW   wavefronts (strips) of the workgroup
@@ -101,8 +87,8 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
         float rm[4];   // g'=0: row di=0 (goes one row down), g'=1: row di=2 (goes one row up)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            rm[j] = fmaf(gw_from_next(p[4 + j]), mr, fmaf(gw_from_prev(p[j]), ml, p[8 + j]));
-            cp[k][j] += fmaf(gw_from_next(p[12 + j]), mr1, fmaf(gw_from_prev(p[12 + j]), ml0, pc[j]));
+            rm[j] = fmaf(from_next(p[4 + j]), mr, fmaf(from_prev(p[j]), ml, p[8 + j]));
+            cp[k][j] += fmaf(from_next(p[12 + j]), mr1, fmaf(from_prev(p[12 + j]), ml0, pc[j]));
         }
         if (k + 1 < TPW) {
 #pragma unroll
@@ -134,7 +120,7 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
 #pragma unroll
         for (int m = 0; m < OWN; ++m)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[m][j] = gw_half_sums(cp[2 * m][j], cp[2 * m + 1][j]);
+            for (int j = 0; j < 4; ++j) o[m][j] = half_sums(cp[2 * m][j], cp[2 * m + 1][j]);
     };
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
@@ -563,34 +549,9 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
 template <int NW, int TPW>
 hipError_t launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
 {
-    void (*const kern)(const NfProgram, const NfGradLaunch) = &nf_grad_wide_kernel<NW, TPW>;
-    const void *fn = reinterpret_cast<const void *>(kern);
-    // (device << 40 | lds bytes << 8 | resident workgroups per CU) of the last query, as launch_grad keeps it
     int dev = 0;
     (void)hipGetDevice(&dev);
-    static std::atomic<uint64_t> cache{0};
-    const uint64_t key = ((uint64_t)(dev & 0xff) << 40) | ((uint64_t)lds << 8);
-    const uint64_t cv = cache.load(std::memory_order_relaxed);
-    int occ;
-    if ((cv & ~(uint64_t)0xff) == key && (cv & 0xff) != 0) {
-        occ = (int)(cv & 0xff);
-    } else {
-        if (lds > 64 * 1024) {   // always the CU's whole 160 KiB: concurrent callers with other models never lower it under a launch
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-        occ = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64 * NW, lds);
-        if (e != hipSuccess) return e;
-        if (occ < 1) occ = 1;
-        if (occ > 32) occ = 32;
-        cache.store(key | (uint64_t)occ, std::memory_order_relaxed);
-    }
-    int64_t groups = (int64_t)n_cu * occ;
-    if (a.B < groups) groups = a.B;
-    if (groups < 1) groups = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(64 * NW), lds, stream, prog, a);
-    return hipGetLastError();
+    return flow_launch<&nf_grad_wide_kernel<NW, TPW>>(64 * NW, lds, prog, a, n_cu, dev, stream);
 }
 
 }  // namespace

@@ -24,6 +24,7 @@
 #include "../../include/noiseflow_hip.h"   // NF_SUMS_SLOTS / NF_SUMS_STRIDE
 #include "nf_device.h"
 #include "nf_dev_util.h"
+#include "nf_flow_common.h"   // flow_launch: the persistent-grid launcher
 
 // s_setprio level of a wave while it streams MFMAs (0 = off): keeps bursts of matrix
 // instructions contiguous on a SIMD that other waves share (+5 % at 512-thread geometry)
@@ -1966,8 +1967,7 @@ hipError_t launch_flow_p(const NfProgram &prog, const NfLaunch &a, int n_cu, hip
     if (MFMA) lds_f += (size_t)((a.n_params + 3) & ~3) + 16;   // + the identity block
     if (BS) lds_f += (size_t)(THREADS / 64) * 8 + 16;
     const size_t lds = sizeof(float) * lds_f;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    void (*const kern)(const NfProgram, const NfLaunch) = [] {
+    constexpr auto kern = [] {
         if constexpr (PC && TF) return &nf_flow_tile64_pc_kernel<PHILOX, PREC>;
         else if constexpr (PC && PREC == 3) return &nf_flow_split_pc_kernel<PHILOX>;
         else if constexpr (PC) return &nf_flow_pc_kernel<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, PREC>;
@@ -1975,35 +1975,9 @@ hipError_t launch_flow_p(const NfProgram &prog, const NfLaunch &a, int n_cu, hip
         else if constexpr (PREC == 3) return &nf_flow_split_kernel<PHILOX>;
         else return &nf_flow_kernel<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, PREC, BS>;
     }();
-    const void *fn = reinterpret_cast<const void *>(kern);
-    // (device << 40 | lds bytes << 8 | resident workgroups per CU) of the last query; racy but idempotent.  The
-    // >64 KiB opt-in is a per-device function attribute, so the device is part of the key.
     int dev = 0;
     (void)hipGetDevice(&dev);
-    static std::atomic<uint64_t> cache{0};
-    const uint64_t key = ((uint64_t)(dev & 0xff) << 40) | ((uint64_t)lds << 8);
-    uint64_t c = cache.load(std::memory_order_relaxed);
-    int occ;
-    if ((c & ~(uint64_t)0xff) == key && (c & 0xff) != 0) {
-        occ = (int)(c & 0xff);
-    } else {
-        if (lds > 64 * 1024) {   // opt in to exactly what this launch needs
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        occ = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, THREADS, lds);
-        if (e != hipSuccess) return e;
-        if (occ < 1) occ = 1;
-        if (occ > 32) occ = 32;
-        cache.store(key | (uint64_t)occ, std::memory_order_relaxed);
-    }
-    // persistent grid: exactly the resident capacity, each workgroup strides over patches
-    int64_t groups = (int64_t)n_cu * occ;
-    if (a.B < groups) groups = a.B;
-    if (groups < 1) groups = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(THREADS), lds, stream, prog, a);
-    return hipGetLastError();
+    return flow_launch<kern>(THREADS, lds, prog, a, n_cu, dev, stream);   // persistent grid: the resident capacity (nf_flow_common.h)
 }
 
 template <int WIDTH, int THREADS, int PX, bool PHILOX, bool MFMA, bool FULL>

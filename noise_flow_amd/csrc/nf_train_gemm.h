@@ -850,7 +850,7 @@ __global__ __launch_bounds__(TB) void k_e_c3(int H, int W, int w, float *__restr
     }
 }
 
-// per-patch outputs of the NLL direction (noise_flow_model.py:394-428, 477-478, 537-539, as gemm_epilogue of the fused kernels):
+// per-patch outputs of the NLL direction (noise_flow_model.py:394-428, 477-478, 537-539, as flow_epilogue of the fused kernels):
 // log-det = data part + constant, nll = -log-det (+ prior), sd_z; the call's sums (sum nll, sum sd, B).  One workgroup per patch.
 __global__ __launch_bounds__(TB) void k_e_finish(int HW, const float *__restrict__ z, const double *__restrict__ ldp, const double *__restrict__ ldc,
                                                   int prior, float *__restrict__ nll_out, float *__restrict__ sd_out, float *__restrict__ ld_out,

@@ -24,20 +24,10 @@
 // :555-613, :651-674 (conv2d / add_edge_padding / conv2d_zeros) at hps.width = 32 (job_noise_flow.sh:19).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <atomic>
 #include "../../include/noiseflow_hip.h"   // NF_SUMS_SLOTS / NF_SUMS_STRIDE
 #include "nf_device.h"
 #include "nf_dev_util.h"
-
-// Instrumented build (-DNF_TIMELINE, tools/timeline_wide.py only): thread 0 of every workgroup stamps the 100 MHz s_memrealtime
-// counter at the phase boundaries of its MIDDLE patch into NfLaunch::sd_out, reinterpreted as int64[grid][64] (sd_z is not written
-// in this build): 0 patch start, 1 inputs in registers, per coupling c: 2+4c weights staged (after the barrier of phase A), +1 phase B
-// done (this wavefront), +2 every wavefront's phase B done (barrier), +3 phase C done; 40 outputs written, 41 patch done.
-#ifdef NF_TIMELINE
-#define NF_WSTAMP(i) do { if (t == 0 && stamp_on) reinterpret_cast<long long *>(a.sd_out)[(size_t)blockIdx.x * 64 + (i)] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define NF_WSTAMP(i) do { } while (0)
-#endif
+#include "nf_flow_common.h"   // flow_launch: the persistent-grid launcher
 
 namespace {
 
@@ -72,37 +62,6 @@ constexpr int TPW = 8;   // tiles (= rows of a strip) per wavefront
 #ifndef NF_WIDE_HOIST16
 #define NF_WIDE_HOIST16 0
 #endif
-
-// value of the lane one pixel to the left / right (callers multiply the tile ends away: lane 32 receives lane 31's
-// value and vice versa).  NF_WIDE_DPP=1: DPP wave_shr:1 / wave_shl:1 — a VALU operand modifier, no LDS traffic and no
-// address register; 0: ds_bpermute.
-#ifndef NF_WIDE_DPP
-#define NF_WIDE_DPP 1
-#endif
-__device__ __forceinline__ float from_prev(float x, int lane)
-{
-#if NF_WIDE_DPP
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x138, 0xf, 0xf, true));
-#else
-    return __int_as_float(__builtin_amdgcn_ds_bpermute((lane - 1) << 2, __float_as_int(x)));
-#endif
-}
-__device__ __forceinline__ float from_next(float x, int lane)
-{
-#if NF_WIDE_DPP
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x130, 0xf, 0xf, true));
-#else
-    return __int_as_float(__builtin_amdgcn_ds_bpermute((lane + 1) << 2, __float_as_int(x)));
-#endif
-}
-// a(lanes 0-31) + a(lanes 32-63) in the low half, b(lanes 0-31) + b(lanes 32-63) in the high half: the two lane
-// halves hold partial sums of the same pixels; the low half finishes tile `a`, the high half tile `b` — one
-// v_permlane32_swap + one add for two tiles
-__device__ __forceinline__ float half_sums(float a, float b)
-{
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 
 //   THREADS  64 x number of strips: (rows / 8) x TPR
 //   PHILOX   input = in-kernel Philox/Box-Muller draw
@@ -169,14 +128,10 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
     if (first_cpl >= 0 && (int64_t)blockIdx.x < a.B) stage(prog.ops[first_cpl].off, 0);
     double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
 
-    [[maybe_unused]] bool stamp_on = false;
-    [[maybe_unused]] int64_t stamp_it = 0;
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-#ifdef NF_TIMELINE
-        stamp_on = stamp_it++ == (a.B / gridDim.x) / 2;
-        int n_cpl = 0;
-        NF_WSTAMP(0);
-#endif
+        // Tile geometry, input, per-pixel layers, affine finish and epilogue below restate the helpers of nf_flow_common.h inline: on the
+        // helpers the fp16 instantiation keeps every bit and loses 5.6 - 8.7 % at 32x32 — more spills inside its tile loop at the
+        // 168-VGPR cap (profiles/r15_wide_common_ab.txt, table 2; fp32 is level)
         // Where this "patch" sits: on its own ([B,H,W,4] tensors), or — NF_K_TILED (nf_device.h, "overlapping tiles") — as
         // tile b % tiles of image b / tiles: pixel (r, c) of the tile is pixel (oy + r, ox + c) of an IH x IW image, border
         // masks follow the image border, and results are reported for the core window [cy0, cy1) x [cx0, cx1) only.
@@ -226,10 +181,6 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
         }
 
         float ld = 0.0f, ld2 = 0.0f;   // natural-log / log2 parts of this lane's log-det share
-#ifdef NF_TIMELINE
-        asm volatile("" ::"v"(z[0][0]));
-        NF_WSTAMP(1);
-#endif
 
         for (int op = 0; op < n_ops; ++op) {
             const int type = prog.ops[op].type;
@@ -281,9 +232,6 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
                     if (nx >= 0) stage(prog.ops[nx].off, cur ^ 1);
                 }
                 cur ^= 1;
-#ifdef NF_TIMELINE
-                if (n_cpl < 8) NF_WSTAMP(2 + 4 * n_cpl);
-#endif
 
                 // ---- phase B: the CNN on the matrix cores, strip-local shift-add ----
                 const float4 *const wb4 = reinterpret_cast<const float4 *>(wbuf);
@@ -430,8 +378,8 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
                     float rm[4];   // g'=0: R[.][di=0] (goes one row down), g'=1: R[.][di=2] (goes one row up)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        rm[j] = fmaf(from_next(p[4 + j], lane), mr, fmaf(from_prev(p[j], lane), ml, p[8 + j]));
-                        cp[k][j] += fmaf(from_next(p[12 + j], lane), mr1, fmaf(from_prev(p[12 + j], lane), ml0, pc[j]));
+                        rm[j] = fmaf(from_next(p[4 + j]), mr, fmaf(from_prev(p[j]), ml, p[8 + j]));
+                        cp[k][j] += fmaf(from_next(p[12 + j]), mr1, fmaf(from_prev(p[12 + j]), ml0, pc[j]));
                     }
                     if (k + 1 < TPW) {
 #pragma unroll
@@ -466,14 +414,7 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
                         }
                     }
                 }
-#ifdef NF_TIMELINE
-                asm volatile("" ::"v"(cp[0][0]), "v"(cp[TPW - 1][3]));
-                if (n_cpl < 8) NF_WSTAMP(3 + 4 * n_cpl);
-#endif
                 __syncthreads();
-#ifdef NF_TIMELINE
-                if (n_cpl < 8) NF_WSTAMP(4 + 4 * n_cpl);
-#endif
 
                 // ---- phase C: strip-boundary rows, column seam, then each lane half finishes the rows it owns ----
                 if (row0 > 0 && g == 0) {
@@ -525,11 +466,6 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
                         z[m][3] = (z[m][3] - o[1]) * __builtin_amdgcn_exp2f(-l1);
                     }
                 }
-#ifdef NF_TIMELINE
-                asm volatile("" ::"v"(z[0][2]));
-                if (n_cpl < 8) NF_WSTAMP(5 + 4 * n_cpl);
-                ++n_cpl;
-#endif
             } else if (type == NF_OP_SDN_DIV || type == NF_OP_SDN_MUL) {
                 // AffineCouplingSdnEx5: scale = sqrt(beta1*y/gain + beta2)  (cond_utils.py:238)
                 const float4 *y4 = reinterpret_cast<const float4 *>(a.y + patch_off);
@@ -572,7 +508,6 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
                 if (r < H && col_own && R >= cy0 && R < cy1) out4[R * IW + C] = make_float4(z[m][0], z[m][1], z[m][2], z[m][3]);
             }
         }
-        NF_WSTAMP(40);
         if (a.nll_out || a.sd_out || a.ld_out || a.sums || (tiled && a.tile_part)) {
             float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -613,16 +548,13 @@ __device__ __forceinline__ void nf_wide32_body(const NfProgram &prog, const NfLa
                 var = var > 0.0 ? var : 0.0;
                 const double sd = sqrt(var);
                 if (a.nll_out) a.nll_out[b] = (float)nll;
-#ifndef NF_TIMELINE
                 if (a.sd_out) a.sd_out[b] = (float)sd;
-#endif
                 if (a.ld_out) a.ld_out[b] = (float)logdet;
                 acc_nll += (double)(float)nll;
                 acc_sd += (double)(float)sd;
             }
             __syncthreads();   // scratch is reused by the next patch
         }
-        NF_WSTAMP(41);
     }
 
     if (a.sums && t == 0 && !TILED) {
@@ -674,36 +606,13 @@ hipError_t launch_wide_p(const NfProgram &prog, const NfLaunch &a, int n_cu, int
         if (a.cond_rows) return launch_wide_p<THREADS, PHILOX, TPR, PREC, true>(prog, a, n_cu, device, stream);
     }
     const size_t lds = wide_lds_bytes(a.H, a.W, THREADS, TPR, PREC);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const bool tiled = (a.flags & NF_K_TILED) != 0;
-    void (*const kern)(const NfProgram, const NfLaunch) =
-        PC ? (tiled ? &nf_wide32_tiled_pc_kernel<THREADS, PHILOX, TPR, PREC> : &nf_wide32_pc_kernel<THREADS, PHILOX, TPR, PREC>)
-           : (tiled ? &nf_wide32_tiled_kernel<THREADS, PHILOX, TPR, PREC> : &nf_wide32_kernel<THREADS, PHILOX, TPR, PREC>);
-    const void *fn = reinterpret_cast<const void *>(kern);
-    // (tiled << 48 | device << 40 | lds bytes << 8 | resident workgroups per CU) of the last query; racy but idempotent
-    static std::atomic<uint64_t> cache{0};
-    const uint64_t key = ((uint64_t)(tiled ? 1 : 0) << 48) | ((uint64_t)(device & 0xff) << 40) | ((uint64_t)lds << 8);
-    uint64_t cv = cache.load(std::memory_order_relaxed);
-    int occ;
-    if ((cv & ~(uint64_t)0xff) == key && (cv & 0xff) != 0) {
-        occ = (int)(cv & 0xff);
-    } else {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        occ = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, THREADS, lds);
-        if (e != hipSuccess) return e;
-        if (occ < 1) occ = 1;
-        if (occ > 32) occ = 32;
-        cache.store(key | (uint64_t)occ, std::memory_order_relaxed);
+    // one kernel symbol (and so one launcher cache) per answer to "tiled" and "per-patch conditioning"
+    if (a.flags & NF_K_TILED) {
+        if constexpr (PC) return flow_launch<&nf_wide32_tiled_pc_kernel<THREADS, PHILOX, TPR, PREC>>(THREADS, lds, prog, a, n_cu, device, stream);
+        else return flow_launch<&nf_wide32_tiled_kernel<THREADS, PHILOX, TPR, PREC>>(THREADS, lds, prog, a, n_cu, device, stream);
     }
-    int64_t groups = (int64_t)n_cu * occ;
-    if (a.B < groups) groups = a.B;
-    if (groups < 1) groups = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(THREADS), lds, stream, prog, a);
-    return hipGetLastError();
+    if constexpr (PC) return flow_launch<&nf_wide32_pc_kernel<THREADS, PHILOX, TPR, PREC>>(THREADS, lds, prog, a, n_cu, device, stream);
+    else return flow_launch<&nf_wide32_kernel<THREADS, PHILOX, TPR, PREC>>(THREADS, lds, prog, a, n_cu, device, stream);
 }
 
 template <int THREADS, bool PHILOX, int TPR>

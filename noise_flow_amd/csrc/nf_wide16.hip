@@ -17,11 +17,10 @@
 // Replaces (reference): layers.py:251-375, 452-498, 555-613, 651-674 at hps.width = 16.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <atomic>
 #include "../../include/noiseflow_hip.h"   // NF_SUMS_SLOTS / NF_SUMS_STRIDE
 #include "nf_device.h"
 #include "nf_dev_util.h"
-#include "nf_gemm_common.h"   // GemmTile: where a patch or, NF_K_TILED, a tile of an image sits
+#include "nf_flow_common.h"   // FlowTile: where a patch or, NF_K_TILED, a tile of an image sits; flow_launch: the persistent-grid launcher
 
 namespace {
 
@@ -112,9 +111,12 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
     double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const GemmTile T = gemm_tile<PC>(a, b, H, W);      // the patch on its own, or (NF_K_TILED) a tile of an image: nf_gemm_common.h
+        const FlowTile T = flow_tile<PC>(a, b, H, W);      // the patch on its own, or (NF_K_TILED) a tile of an image: nf_flow_common.h
         const size_t patch_off = T.patch_off;
 
+        // Input, per-pixel layers, affine finish and epilogue below restate the helpers of nf_flow_common.h inline: on the helpers this
+        // kernel keeps every bit and loses 1.5 % (32x32) to 12 % (64x64) — its register allocation at the 128-VGPR cap moves
+        // (profiles/r15_wide_common_ab.txt, table 2)
         float z[OWN][4];
 #pragma unroll
         for (int m = 0; m < OWN; ++m) {
@@ -328,7 +330,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS
             }
         }
 
-        // ---- epilogue (as nf_flow_kernel) ----
+        // ---- epilogue: flow_epilogue (nf_flow_common.h) restated, with sd_z through the hardware fp32 square root ----
         if (a.out) {
             float4 *out4 = reinterpret_cast<float4 *>(a.out + patch_off);
 #pragma unroll
@@ -409,33 +411,7 @@ hipError_t launch_wide16(const NfProgram &prog, const NfLaunch &a, int n_cu, int
     if constexpr (!PC) {
         if (a.cond_rows) return launch_wide16<THREADS, TPW, PHILOX, true>(prog, a, n_cu, device, stream);
     }
-    void (*const kern)(const NfProgram, const NfLaunch) = &nf_wide16_kernel<THREADS, TPW, PHILOX, PC>;
-    const size_t lds = wide16_lds_bytes(a.H, a.W, THREADS);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const void *fn = reinterpret_cast<const void *>(kern);
-    static std::atomic<uint64_t> cache{0};   // (device << 40 | lds bytes << 8 | resident workgroups per CU) of the last query
-    const uint64_t key = ((uint64_t)(device & 0xff) << 40) | ((uint64_t)lds << 8);
-    uint64_t cv = cache.load(std::memory_order_relaxed);
-    int occ;
-    if ((cv & ~(uint64_t)0xff) == key && (cv & 0xff) != 0) {
-        occ = (int)(cv & 0xff);
-    } else {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        occ = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, THREADS, lds);
-        if (e != hipSuccess) return e;
-        if (occ < 1) occ = 1;
-        if (occ > 32) occ = 32;
-        cache.store(key | (uint64_t)occ, std::memory_order_relaxed);
-    }
-    int64_t groups = (int64_t)n_cu * occ;
-    if (a.B < groups) groups = a.B;
-    if (groups < 1) groups = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(THREADS), lds, stream, prog, a);
-    return hipGetLastError();
+    return flow_launch<&nf_wide16_kernel<THREADS, TPW, PHILOX, PC>>(THREADS, wide16_lds_bytes(a.H, a.W, THREADS), prog, a, n_cu, device, stream);
 }
 
 template <bool PHILOX>

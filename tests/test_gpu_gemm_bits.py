@@ -1,7 +1,8 @@
 """The four GEMM coupling kernels (csrc/nf_gemm.hip: nf_gemm_kernel, nf_gemmb_kernel; csrc/nf_gemm16.hip: nf_gemm16_kernel,
 nf_gemm16b_kernel) share code through csrc/nf_gemm_common.h: nf_gemmb_kernel and nf_gemm16_kernel their frame (patch loop, op
 interpreter, epilogue), the 9-tap gather of the P records, the P-record store, the bias fill and the publication of the pass-through
-half; all four the per-pixel helpers and the launcher.  Moving those from four copies into one
+half; all four the per-pixel helpers (since then in csrc/nf_flow_common.h, which the width-16 / 32 kernels use too:
+tests/test_gpu_wide_bits.py) and the launcher.  Moving those from four copies into one
 changed no product, no addition order and no rounding point, so every per-patch output is bit for bit what the four stand-alone
 kernels gave: tests/golden/gemm_family_bits.npz was recorded with tools/make_golden_gemm_bits.py on an MI355X from the build of
 commit 55960a5, the last one with the four copies.  array_equal on the uint32 views; a differing bit is an expression that was
@@ -16,7 +17,7 @@ per-thread count (OWN 2 / 4 / 8), the bordered and the bare pass-through tile of
 P stage (two bands of 128 pixels at width 512), the band kernels at width 64 under NF_GEMM=a / NF_GEMM16=a (nf_kernel_path does
 not tell the variants apart, so these cases also run the model without the switch: in fp16 the latents agree but not bit for bit,
 which shows that the switch was read; in fp32 at width 64 the two variants give the same bits), and per kernel one
-case each of per-patch conditioning (the PC = true instantiation), an 80x100 image (NF_K_TILED through gemm_tile and the epilogue's
+case each of per-patch conditioning (the PC = true instantiation), an 80x100 image (NF_K_TILED through flow_tile and the epilogue's
 tile share) and a batch larger than the CU count at 7x5 (the persistent loop takes a second patch through the frame; the NLL of
 the first, a middle and the last patch is kept).
 

@@ -12,14 +12,18 @@ OBJ=${OBJ:-nf_kernels}
 mkdir -p $R/build/variants
 for ob in $OBJ; do
   EXTRA=""
-  case $ob in nf_kernels|nf_host|nf_hostfed) ;; *) EXTRA="-mllvm -amdgpu-mfma-vgpr-form";; esac
+  case $ob in    # the flags of the object's rule in csrc/Makefile
+    nf_kernels|nf_grad|nf_host|nf_hostfed) ;;
+    *) EXTRA="-mllvm -amdgpu-mfma-vgpr-form";;
+  esac
   S=$C/$ob.hip
   [ -n "$SRC" ] && [ "$OBJ" = "$ob" ] && S=$SRC
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics -Wall -Wno-unused-function $EXTRA -I$C "$@" -c $S -o $R/build/variants/${ob}_$NAME.o &
 done
 wait
 OBJS=""
-for o in nf_kernels nf_wide nf_wide16 nf_gemm nf_gemm16 nf_host nf_hostfed nf_train; do
+# every object of the library: SRCS of csrc/Makefile
+for o in $(sed -n 's/^SRCS *= *//p' $C/Makefile | sed 's/\.hip//g'); do
   if [[ " $OBJ " == *" $o "* ]]; then OBJS="$OBJS $R/build/variants/${o}_$NAME.o"; else OBJS="$OBJS $C/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS -lpthread -o $R/build/variants/lib_$NAME.so
