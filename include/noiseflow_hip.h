@@ -509,6 +509,19 @@ int nf_split_run_info(const int32_t *ops, int32_t n_ops, const float *block, siz
  * NF_GEMM16=a (read at nf_create) force the band variant everywhere — an A/B aid, like NF_KERNEL=valu. */
 int nf_kernel_path(const nf_handle *h, int32_t direction);
 
+/* How nf_nll_batchstats / nf_sample_batchstats of this handle run, decided where the calls decide it:
+ *   NF_BS_ROUTE_MFMA4    width 4: every launch on the matrix-core kernel, the re-fold fused into the next launch (any size)
+ *   NF_BS_ROUTE_SCALAR   widths up to 32 where both LDS tiles of a patch fit one CU: the scalar-weight kernel + a finaliser kernel
+ *   NF_BS_ROUTE_TRAINER  everything else (and width 32 on 32x32): layer by layer on the trainer's kernels (csrc/nf_train.hip)
+ * The environment variables NF_BS_WIDE (non-zero: NF_BS_ROUTE_TRAINER everywhere) and NF_TRAIN_PR (0: width 32 on 32x32 stays
+ * on NF_BS_ROUTE_SCALAR) are read at the time of the call, here as in the entry points.  A handle the calls refuse
+ * (NF_CFG_FP16_CNN: "batch-statistics mode is fp32 only") gives the same NF_EINVAL and message here.  No reference counterpart
+ * (diagnostic, like nf_kernel_path). */
+#define NF_BS_ROUTE_MFMA4 0
+#define NF_BS_ROUTE_SCALAR 1
+#define NF_BS_ROUTE_TRAINER 2
+int nf_batchstats_route(const nf_handle *h);
+
 /* Device scratch of calls on images beyond 64x64 (evaluated as overlapping tiles: the per-tile sums and the tensors between two
  * segments of the program).  The handle owns a small set of buffers, one per call in flight; nf_nll / nf_sample allocate only
  * when a call needs more than any earlier call did or when more calls are in flight than ever before.  nf_workspace_bytes says

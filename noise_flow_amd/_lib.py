@@ -158,6 +158,9 @@ def load() -> C.CDLL:
     lib.nf_split_run_info.argtypes = [C.POINTER(i32), i32, C.POINTER(C.c_float), C.c_size_t, C.POINTER(i32)]
     lib.nf_kernel_path.restype = C.c_int
     lib.nf_kernel_path.argtypes = [vp, i32]
+    if hasattr(lib, "nf_batchstats_route"):   # (tools/ record fixtures from builds of earlier commits through NF_TOOL_LIB; build() checks EXPORTED_SYMBOLS)
+        lib.nf_batchstats_route.restype = C.c_int
+        lib.nf_batchstats_route.argtypes = [vp]
     lib.nf_workspace_bytes.restype = i64
     lib.nf_workspace_bytes.argtypes = [vp, i32, i64]
     lib.nf_reserve_workspace.restype = C.c_int
@@ -195,7 +198,7 @@ def check(rc: int) -> None:
 EXPORTED_SYMBOLS = (
     "nf_abi_version", "nf_last_error", "nf_layer_param_count", "nf_create", "nf_destroy", "nf_nll",
     "nf_sample", "nf_set_sync", "nf_sample_eps", "nf_tile_plan", "nf_tile_segments", "nf_nll_host", "nf_sample_host", "nf_synth_patches", "nf_fold_params", "nf_fold_layout", "nf_split_run_info", "nf_sdn5_scalars",
-    "nf_nll_batchstats", "nf_sample_batchstats", "nf_sums_reduce", "nf_kernel_path", "nf_workspace_bytes", "nf_reserve_workspace",
+    "nf_nll_batchstats", "nf_sample_batchstats", "nf_sums_reduce", "nf_kernel_path", "nf_batchstats_route", "nf_workspace_bytes", "nf_reserve_workspace",
     "nf_trainer_create", "nf_trainer_destroy", "nf_trainer_forward_backward", "nf_trainer_forward", "nf_trainer_apply", "nf_trainer_step",
     "nf_trainer_get_params", "nf_trainer_set_params", "nf_trainer_steps", "nf_trainer_set_sync",
     "nf_cond_rows", "nf_nll_percond", "nf_sample_percond",
@@ -204,6 +207,7 @@ EXPORTED_SYMBOLS = (
 NF_GRAD_PATH_SCALAR, NF_GRAD_PATH_WIDE32 = 0, 1
 NF_PATH_SCALAR, NF_PATH_MFMA4, NF_PATH_FP16, NF_PATH_WIDE32, NF_PATH_WIDE16, NF_PATH_WIDE32_FP16, NF_PATH_GEMM, NF_PATH_GEMM_FP16 = 0, 1, 2, 3, 4, 5, 6, 7
 NF_PATH_SPLIT_BF16 = 8
+NF_BS_ROUTE_MFMA4, NF_BS_ROUTE_SCALAR, NF_BS_ROUTE_TRAINER = 0, 1, 2
 NF_HOST_F32, NF_HOST_F64 = 0, 1
 NF_OPT_ADAM = 0
 NF_OPT_MOMENTUM = 1

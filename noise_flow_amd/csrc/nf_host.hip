@@ -46,7 +46,6 @@ hipError_t nf_launch_bs_finalize(double *stats, int w, double n, float *Wm, int 
 hipError_t nf_launch_tile_combine(const float *part, const NfTileParts &tp, int64_t B, double n, double ld_const, const nf_cond_row *cond_rows,
                                   uint32_t flags,
                                   float *nll_out, float *sd_out, float *ld_out, double *sums, hipStream_t stream);
-hipError_t nf_launch_gather(float *dst, const float *src, const int32_t *pairs, int n, hipStream_t stream);
 hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 
@@ -1394,6 +1393,33 @@ struct DeviceGuard {
     }
 };
 
+// A device buffer that grows: reserve(n) frees and reallocates only when it is too small; empty after a failed allocation.
+template <class T>
+struct DevBuf {
+    T *ptr = nullptr;
+    size_t cap = 0;   // elements
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : ptr(o.ptr), cap(o.cap) { o.ptr = nullptr, o.cap = 0; }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release()
+    {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        cap = 0;
+    }
+    hipError_t reserve(size_t n)
+    {
+        if (cap >= n) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc((void **)&ptr, n * sizeof(T));
+        if (e != hipSuccess) ptr = nullptr;
+        else cap = n;
+        return e;
+    }
+};
+
 }  // namespace
 
 int nf_fail(int code, const char *fmt, ...)
@@ -2000,6 +2026,36 @@ int nf_kernel_path(const nf_handle *h, int32_t direction)
     return select_path(h, direction);
 }
 
+// THE place that decides how a batch-statistics call of a handle runs (nf_batchstats_route reports it, run_batchstats switches
+// on it and nothing else re-derives a part of it).  The width-4 schedule on the matrix-core kernel takes every size (images beyond
+// 64x64 as overlapping tiles); the generic schedule runs on the scalar-weight kernel: both LDS tiles of a patch on one CU, one
+// pixel per lane at width 32; everything else — coupling widths beyond 32, patches the scalar-weight kernel cannot hold — is a
+// layer-by-layer walk on the trainer's kernels (run_batchstats_wide).  Both switches are read per call on purpose (the tests
+// flip them inside one process).
+static int bs_route(const nf_handle *h)
+{
+    const int pw = h->fwd.lay[NF_PATH_SCALAR].prog.width, H = h->cfg.height, W = h->cfg.width;
+    const size_t tile_px = ((size_t)(H + 2) * (W + 2) + 1) & ~(size_t)1;
+    const bool scalar_fits = sizeof(float) * (tile_px * (2 + (size_t)pw) + 64) <= 160 * 1024 && !(pw >= 32 && H * W > 1024) && h->scalar_ok && !h->fwd.tiled;
+    const bool mc4 = pw == 4 && !h->fwd.lay[NF_PATH_MFMA4].block.empty() && use_matrix_core();
+    const char *bw = getenv("NF_BS_WIDE");   // A/B aid: non-zero sends every call to the trainer's kernels
+    // width 32 on 32x32 patches (the paper's coupling CNN on the training patch size): the evaluator runs the trainer's patch-resident
+    // forward stages on the matrix cores (csrc/nf_train_pr.h) — 3 launches per coupling instead of the scalar-weight schedule
+    // (1 024 patches: 3.7 -> 1.1 ms, 138: 1.24 -> 0.48).  NF_TRAIN_PR=0 keeps the scalar schedule.
+    const char *pe = getenv("NF_TRAIN_PR");
+    const bool pr_off = pe && atoi(pe) == 0;
+    const bool pr32 = h->fwd.raw_width == 32 && H == 32 && W == 32 && !h->fwd.tiled && !pr_off;
+    if (pw > 32 || pr32 || (!mc4 && !scalar_fits) || (bw && atoi(bw) != 0)) return NF_BS_ROUTE_TRAINER;
+    return mc4 ? NF_BS_ROUTE_MFMA4 : NF_BS_ROUTE_SCALAR;
+}
+
+int nf_batchstats_route(const nf_handle *h)
+{
+    if (!h) return fail(NF_EINVAL, "handle is NULL");
+    if (h->cfg.flags & NF_CFG_FP16_CNN) return fail(NF_EINVAL, "batch-statistics mode is fp32 only");
+    return bs_route(h);
+}
+
 // nf_nll (one `cond` for the call) and nf_nll_percond (`with_rows`: device `rows`, one per patch)
 static int nll_call(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond, bool with_rows, const nf_cond_row *rows,
                     float *nll_out, float *sd_out, float *logdet_out, float *z_out, double *sums_out, uint32_t flags, void *stream,
@@ -2172,52 +2228,42 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
 // earlier segment already ran in its final form in the launch that stored the tensor behind it, and the log-det it
 // contributed travels with that tensor (NfLaunch::ld_carry, one float per thread of the patch's workgroup).  2 short launches per coupling instead of
 // re-running the whole prefix, no host round trip until the moments are copied out at the end.
+//
+// Two routes run this schedule (bs_route; the third, NF_BS_ROUTE_TRAINER, is run_batchstats_wide): ONE walker, bs_walk, holds the
+// loops, the input choice, the resident-tensor ping-pong, the log-det carry and the moments; a route description (BsScalarRoute /
+// BsMfma4Route) says which layout's programs and parameter block a launch reads, where a pass puts its sums, and what becomes of
+// them — a finaliser kernel on the scalar-weight route, the "pending fix" in the prologue of the next launch on the width-4 one.
+
+// The launches of the schedule over ONE kernel layout (lay[NF_PATH_SCALAR] or lay[NF_PATH_MFMA4] of the identity-normalised model)
+struct BsProgs {
+    std::vector<NfProgram> A, B;      // per coupling: the two statistics launches
+    NfProgram F;                      // the final launch: the last segment + everything behind it (the whole program with < 2 couplings)
+};
+
 struct BsPlan {
     bool ready = false;
     Built ident;                      // the model folded with an identity normalisation in every coupling CNN
-    float *d_ident = nullptr;         // ... on the device, scalar layout
-    float *d_ident2 = nullptr;        // ... matrix-core layout (null when unavailable)
-    std::vector<int> cpl_ops;         // op index of every coupling in ident.prog, execution order
+    DevBuf<float> d_ident[2];         // ... on the device, [NF_PATH_SCALAR] / [NF_PATH_MFMA4] (empty where the model has no such layout)
+    BsProgs progs[2];                 // same index
+    std::vector<int> cpl_ops;         // op index of every coupling in ident's programs, execution order
     std::vector<int> cpl_row;         // its row in moments_out (NLL layer order)
     std::vector<float> shift;         // [coupling in NLL layer order][2][width]: the running means the statistics are taken around
-    std::vector<NfProgram> progA, progB;
-    std::vector<NfProgram> progA2, progB2;   // the same segments over the matrix-core layout (width 4)
-    NfProgram progF, progF2;          // the last segment + everything behind it (the final launch when there are >= 2 couplings)
-    int32_t *d_pairs = nullptr;       // (dst in matrix-core block, src in scalar block) of the BN-dependent entries
-    int n_pairs = 0;
 };
+static_assert(NF_PATH_SCALAR == 0 && NF_PATH_MFMA4 == 1, "BsPlan indexes its two layouts by path");
 
 struct nf_bs_state {
     BsPlan plan[2];
-    float *d_work = nullptr, *d_work2 = nullptr;   // working copies of the parameter block (scalar / matrix-core layout)
-    float *d_work2b = nullptr;                      // matrix-core path: the launches ping-pong between two copies
-    size_t work_cap = 0, work2_cap = 0, work2b_cap = 0;
-    double *d_stats_mc = nullptr;                   // matrix-core path: one [NF_STATS_SLOTS][8] block per statistics pass
-    size_t stats_mc_passes = 0;
-    double *d_stats = nullptr;
-    float *d_mom = nullptr;            // [couplings][4][w]
-    float *d_T[2] = {nullptr, nullptr};
-    size_t T_cap = 0;                  // floats per scratch tensor
-    float *d_carry = nullptr;          // [B][1024] per-thread log-det of the segments behind the resident tensor
-    size_t carry_cap = 0;
+    DevBuf<float> work;                // scalar-weight route: the working copy of the parameter block, re-folded in place
+    DevBuf<double> stats;              // ... its one [NF_STATS_SLOTS][2 w] block of sums (the finaliser zeroes it again)
+    DevBuf<float> work_mc[2];          // width-4 route: the launches ping-pong between two working copies (matrix-core layout)
+    DevBuf<double> stats_mc;           // ... one [NF_STATS_SLOTS][8] block per statistics pass
+    DevBuf<float> mom;                 // [couplings][4][w]
+    DevBuf<float> T[2];                // the resident tensors
+    DevBuf<float> carry;               // [B][1024] per-thread log-det of the segments behind the resident tensor
     nf_trainer *wide = nullptr;        // the layer-by-layer evaluator on the trainer's GEMM path (nf_bs_wide_*), where the passes above do not reach
     ~nf_bs_state()
     {
         if (wide) (void)nf_trainer_destroy(wide);
-        for (int d = 0; d < 2; ++d) {
-            if (plan[d].d_ident) (void)hipFree(plan[d].d_ident);
-            if (plan[d].d_ident2) (void)hipFree(plan[d].d_ident2);
-            if (plan[d].d_pairs) (void)hipFree(plan[d].d_pairs);
-        }
-        if (d_work) (void)hipFree(d_work);
-        if (d_work2) (void)hipFree(d_work2);
-        if (d_work2b) (void)hipFree(d_work2b);
-        if (d_stats_mc) (void)hipFree(d_stats_mc);
-        if (d_stats) (void)hipFree(d_stats);
-        if (d_mom) (void)hipFree(d_mom);
-        if (d_T[0]) (void)hipFree(d_T[0]);
-        if (d_T[1]) (void)hipFree(d_T[1]);
-        if (d_carry) (void)hipFree(d_carry);
     }
 };
 
@@ -2253,88 +2299,53 @@ static int bs_build_plan(nf_handle *h, int direction, BsPlan &P)
     if ((int)P.cpl_ops.size() != n_cpl) return fail(NF_EINVAL, "internal: batch-statistics plan mismatch");
     P.cpl_row.resize(n_cpl);
     for (int c = 0; c < n_cpl; ++c) P.cpl_row[c] = direction == 0 ? c : n_cpl - 1 - c;
-    P.progA.assign(n_cpl, NfProgram());
-    P.progB.assign(n_cpl, NfProgram());
+    // A launch = a list of op indices into the full program (every layout has the same op sequence: build_layout) and kStore for
+    // the NF_OP_STORE behind a re-run segment; built once, then materialised against each layout's program, whose offsets it takes.
+    const int kStore = -1;
+    typedef std::vector<int> Seg;
+    auto append = [](Seg &s, int first, int last) {
+        for (int i = first; i <= last; ++i) s.push_back(i);
+    };
+    auto seg_first = [&](int c) { return c <= 0 ? 0 : P.cpl_ops[c - 1] + 1; };   // segment c = the layers after coupling c-1 up to and including coupling c
+    std::vector<Seg> segA(n_cpl), segB(n_cpl);
+    Seg segF;
     for (int c = 0; c < n_cpl; ++c) {
-        NfProgram &A = P.progA[c], &B = P.progB[c];
-        memset(&A, 0, sizeof(A));
-        memset(&B, 0, sizeof(B));
-        A.width = B.width = prog.width;
-        const int first = c == 0 ? 0 : P.cpl_ops[c - 1] + 1;
-        if (c > 0) {   // segment c-1 (the layers after coupling c-2 up to and including coupling c-1), now with its moments
-            const int prev_first = c == 1 ? 0 : P.cpl_ops[c - 2] + 1;
-            if (P.cpl_ops[c - 1] - prev_first + 2 > NF_MAX_OPS) return fail(NF_EINVAL, "too many layers for the batch-statistics plan");
-            for (int i = prev_first; i <= P.cpl_ops[c - 1]; ++i) A.ops[A.n_ops++] = prog.ops[i];
-            A.ops[A.n_ops].type = NF_OP_STORE;
-            A.ops[A.n_ops++].off = 0;
+        if (c > 0) {   // segment c-1, now with its moments
+            append(segA[c], seg_first(c - 1), P.cpl_ops[c - 1]);
+            segA[c].push_back(kStore);
         }
-        if (A.n_ops + (P.cpl_ops[c] - first + 1) > NF_MAX_OPS) return fail(NF_EINVAL, "too many layers for the batch-statistics plan");
-        for (int i = first; i <= P.cpl_ops[c]; ++i) {
-            A.ops[A.n_ops++] = prog.ops[i];
-            B.ops[B.n_ops++] = prog.ops[i];
-        }
+        append(segA[c], seg_first(c), P.cpl_ops[c]);
+        append(segB[c], seg_first(c), P.cpl_ops[c]);
+        if ((int)segA[c].size() > NF_MAX_OPS) return fail(NF_EINVAL, "too many layers for the batch-statistics plan");
     }
-    memset(&P.progF, 0, sizeof(P.progF));
-    P.progF.width = prog.width;
-    if (n_cpl > 1) {
-        const int first = P.cpl_ops[n_cpl - 2] + 1;
-        if (prog.n_ops - first > NF_MAX_OPS) return fail(NF_EINVAL, "too many layers for the batch-statistics plan");
-        for (int i = first; i < prog.n_ops; ++i) P.progF.ops[P.progF.n_ops++] = prog.ops[i];
-    }
-    if (!P.ident.lay[NF_PATH_MFMA4].block.empty()) {   // same op sequences, offsets of the matrix-core layout
-        auto to_mc = [&](const NfProgram &src) {
-            NfProgram dst = src;
-            for (int i = 0; i < src.n_ops; ++i) {
-                if (src.ops[i].type == NF_OP_STORE) continue;
-                for (int k = 0; k < prog.n_ops; ++k)   // identify the op in the full program by (type, offset)
-                    if (prog.ops[k].type == src.ops[i].type && prog.ops[k].off == src.ops[i].off) {
-                        dst.ops[i].off = P.ident.lay[NF_PATH_MFMA4].prog.ops[k].off;
-                        break;
-                    }
+    append(segF, seg_first(n_cpl - 1), prog.n_ops - 1);
+    if ((int)segF.size() > NF_MAX_OPS) return fail(NF_EINVAL, "too many layers for the batch-statistics plan");
+    for (int path : {NF_PATH_SCALAR, NF_PATH_MFMA4}) {
+        const Layout &lay = P.ident.lay[path];
+        if (lay.block.empty()) continue;
+        auto materialise = [&](const Seg &s) {
+            NfProgram out;
+            memset(&out, 0, sizeof(out));
+            out.width = lay.prog.width;
+            for (int i : s) {
+                if (i == kStore) out.ops[out.n_ops].type = NF_OP_STORE;
+                else out.ops[out.n_ops] = lay.prog.ops[i];
+                ++out.n_ops;
             }
-            return dst;
+            return out;
         };
-        P.progA2.resize(n_cpl);
-        P.progB2.resize(n_cpl);
+        BsProgs &G = P.progs[path];
+        G.A.clear();
+        G.B.clear();
         for (int c = 0; c < n_cpl; ++c) {
-            P.progA2[c] = to_mc(P.progA[c]);
-            P.progB2[c] = to_mc(P.progB[c]);
+            G.A.push_back(materialise(segA[c]));
+            G.B.push_back(materialise(segB[c]));
         }
-        P.progF2 = to_mc(P.progF);
-    }
-    hipError_t e;
-    const size_t nb = P.ident.lay[NF_PATH_SCALAR].block.size() * sizeof(float);
-    if ((e = hipMalloc((void **)&P.d_ident, nb)) != hipSuccess ||
-        (e = hipMemcpy(P.d_ident, P.ident.lay[NF_PATH_SCALAR].block.data(), nb, hipMemcpyHostToDevice)) != hipSuccess)
-        return fail_hip(e, "batch-statistics plan upload");
-    if (!P.ident.lay[NF_PATH_MFMA4].block.empty()) {
-        // the normalisation-dependent entries of the matrix-core layout are plain copies of scalar-layout entries
-        std::vector<int32_t> pairs;
-        const int w = 4;
-        for (int i = 0; i < prog.n_ops; ++i) {
-            if (prog.ops[i].type != NF_OP_COUPLING_FWD && prog.ops[i].type != NF_OP_COUPLING_REV) continue;
-            const int o1 = prog.ops[i].off, o2 = P.ident.lay[NF_PATH_MFMA4].prog.ops[i].off;
-            for (int j = 0; j < 4; ++j) {
-                pairs.push_back(o2 + NF2_CPL_B1 + j); pairs.push_back(o1 + nf_cpl_off_B1(w) + j);
-                pairs.push_back(o2 + NF2_CPL_B2 + j); pairs.push_back(o1 + nf_cpl_off_B2(w) + j);
-                for (int di = 0; di < 3; ++di)
-                    for (int q = 0; q < 6; ++q) {
-                        pairs.push_back(o2 + NF2_CPL_W1T + 24 * j + 8 * di + q);
-                        pairs.push_back(o1 + nf_cpl_off_W1(w) + (di * 6 + q) * 4 + j);
-                    }
-                for (int i2 = 0; i2 < 4; ++i2) {
-                    pairs.push_back(o2 + NF2_CPL_W2T + 4 * j + i2);
-                    pairs.push_back(o1 + nf_cpl_off_W2(w) + i2 * 4 + j);
-                }
-            }
-        }
-        P.n_pairs = (int)(pairs.size() / 2);
-        const size_t nb2 = P.ident.lay[NF_PATH_MFMA4].block.size() * sizeof(float);
-        if ((e = hipMalloc((void **)&P.d_ident2, nb2)) != hipSuccess ||
-            (e = hipMemcpy(P.d_ident2, P.ident.lay[NF_PATH_MFMA4].block.data(), nb2, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMalloc((void **)&P.d_pairs, pairs.size() * sizeof(int32_t))) != hipSuccess ||
-            (e = hipMemcpy(P.d_pairs, pairs.data(), pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess)
-            return fail_hip(e, "batch-statistics plan upload (matrix-core layout)");
+        G.F = materialise(segF);
+        hipError_t e;
+        if ((e = P.d_ident[path].reserve(lay.block.size())) != hipSuccess ||
+            (e = hipMemcpy(P.d_ident[path].ptr, lay.block.data(), lay.block.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
+            return fail_hip(e, "batch-statistics plan upload");
     }
     P.ready = true;
     return NF_OK;
@@ -2402,303 +2413,247 @@ static int run_batchstats_wide(nf_handle *h, int direction, const NfLaunch &a, c
     return nf_bs_wide_run(S.wide, w, st);
 }
 
-static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moments_out, hipStream_t st, const nf_cond *cond)
-{
-    if (h->cfg.flags & NF_CFG_FP16_CNN) return fail(NF_EINVAL, "batch-statistics mode is fp32 only");
+// ---- what bs_walk asks of a route ----
+// A further route adds such a struct, its case in run_batchstats and its condition in bs_route; bs_walk stays as it is.
+// (Virtual calls, one per launch: no allocation, and nothing next to the launch itself.)
+struct BsRoute {
+    nf_handle *h;
+    nf_bs_state &S;
+    const BsPlan &P;
+    hipStream_t st;
+    const int path;    // the kernel layout: which BsProgs / d_ident of the plan the launches read
+    const int w;       // its coupling width
+    const double n;    // values per channel and pass
+    int nt = 1;        // workgroups a patch is cut into
+    BsRoute(nf_handle *h_, nf_bs_state &S_, const BsPlan &P_, hipStream_t st_, int path_, double n_)
+        : h(h_), S(S_), P(P_), st(st_), path(path_), w(P_.ident.lay[path_].prog.width), n(n_)
     {
-        // the generic schedule below runs on the scalar-weight kernel: both LDS tiles of a patch on one CU, one pixel per lane at
-        // width 32; the width-4 schedule on the matrix-core kernel takes every size (images beyond 64x64 as overlapping tiles)
-        const int pw = h->fwd.lay[NF_PATH_SCALAR].prog.width;
-        const size_t tile_px = ((size_t)(a.H + 2) * (a.W + 2) + 1) & ~(size_t)1;
-        const bool scalar_fits = sizeof(float) * (tile_px * (2 + (size_t)pw) + 64) <= 160 * 1024 && !(pw >= 32 && a.H * a.W > 1024) && h->scalar_ok && !h->fwd.tiled;
-        const bool mc4 = pw == 4 && !h->fwd.lay[NF_PATH_MFMA4].block.empty() && use_matrix_core();
-        // NF_BS_WIDE=1: A/B aid; read per call on purpose (tests/test_gpu_batchstats.py flips it inside one process), =0 means off
-        const char *bw = getenv("NF_BS_WIDE");
-        // width 32 on 32x32 patches (the paper's coupling CNN on the training patch size): the evaluator runs the trainer's patch-resident
-        // forward stages on the matrix cores (csrc/nf_train_pr.h) — 3 launches per coupling instead of the scalar-weight schedule
-        // (1 024 patches: 3.7 -> 1.1 ms, 138: 1.24 -> 0.48).  NF_TRAIN_PR=0 keeps the scalar schedule.
-        const char *pe = getenv("NF_TRAIN_PR");   // (read per call, like NF_BS_WIDE: the tests flip it inside one process)
-        const bool pr_off = pe && atoi(pe) == 0;
-        const bool pr32 = h->fwd.raw_width == 32 && a.H == 32 && a.W == 32 && !h->fwd.tiled && !pr_off;
-        if (pw > 32 || pr32 || (!mc4 && !scalar_fits) || (bw && atoi(bw) != 0))
-            return run_batchstats_wide(h, direction, a, cond, moments_out, st);
     }
-    const int wr = h->fwd.raw_width;   // rows of moments_out are [4][wr]; the kernels' rows [4][prog.width] (zero-padded widths)
-    // images beyond 64x64 (nf_device.h, "overlapping tiles"): the width-4 matrix-core schedule below, every launch tiled with
-    // ONE halo for the whole call — 3 = the deepest launch (re-run coupling c-1, then l_1 of coupling c for its statistics) —
-    // so that the tile grid, and with it the per-thread log-det carry, is the same in every launch
-    const bool tiled = h->fwd.tiled;
-    if (tiled && !(h->fwd.lay[NF_PATH_SCALAR].prog.width == 4 && !h->fwd.lay[NF_PATH_MFMA4].block.empty() && use_matrix_core()))
-        return fail(NF_EINVAL, "batch-statistics mode beyond 64x64 pixels (%dx%d given) runs on the width-4 matrix-core kernels only",
-                    h->cfg.height, h->cfg.width);
-    const int bs_halo = 3;
-    const int bs_ny = tiled ? nf_tile_count(h->cfg.height, h->fwd.tile_h, bs_halo) : 1;
-    const int bs_nx = tiled ? nf_tile_count(h->cfg.width, h->fwd.tile_w, bs_halo) : 1;
-    const int bs_nt = bs_ny * bs_nx;
-    std::lock_guard<std::mutex> lock(h->bs_mu);   // one scratch per handle: calls serialise
-    if (!h->bs) h->bs = new (std::nothrow) nf_bs_state();
-    if (!h->bs) return fail(NF_ENOMEM, "out of host memory");
-    nf_bs_state &S = *h->bs;
-    BsPlan &P = S.plan[direction];
-    hipError_t e;
-    if (!P.ready) {
-        int rc = bs_build_plan(h, direction, P);
-        if (rc != NF_OK) return rc;
-    }
-    const int n_cpl = (int)P.cpl_ops.size();
-    const int w = P.ident.lay[NF_PATH_SCALAR].prog.width;
-    const size_t nw1 = P.ident.lay[NF_PATH_SCALAR].block.size(), nw2 = P.ident.lay[NF_PATH_MFMA4].block.size();
-    auto grow = [&](float *&ptr, size_t &cap, size_t need) -> hipError_t {
-        if (cap >= need) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-        hipError_t er = hipMalloc((void **)&ptr, need * sizeof(float));
-        if (er == hipSuccess) cap = need;
-        return er;
-    };
-    if ((e = grow(S.d_work, S.work_cap, nw1)) != hipSuccess || (nw2 && (e = grow(S.d_work2, S.work2_cap, nw2)) != hipSuccess))
-        return fail_hip(e, "hipMalloc(batch-statistics parameters)");
-    if (!S.d_stats && (e = hipMalloc((void **)&S.d_stats, NF_STATS_SLOTS * 64 * sizeof(double))) != hipSuccess) {
-        S.d_stats = nullptr;
-        return fail_hip(e, "hipMalloc(batch-statistics accumulators)");
-    }
-    if (!S.d_mom && (e = hipMalloc((void **)&S.d_mom, (size_t)std::max(n_cpl, 1) * 4 * 32 * sizeof(float))) != hipSuccess) {
-        S.d_mom = nullptr;
-        return fail_hip(e, "hipMalloc(batch-statistics moments)");
-    }
-    const size_t tensor = (size_t)a.B * a.H * a.W * 4;
-    if (n_cpl > 1 && S.T_cap < tensor) {
-        for (int i = 0; i < 2; ++i) {
-            if (S.d_T[i]) (void)hipFree(S.d_T[i]);
-            S.d_T[i] = nullptr;
-        }
-        S.T_cap = 0;
-        if ((e = hipMalloc((void **)&S.d_T[0], tensor * sizeof(float))) != hipSuccess ||
-            (e = hipMalloc((void **)&S.d_T[1], tensor * sizeof(float))) != hipSuccess)
-            return fail_hip(e, "hipMalloc(batch-statistics scratch tensors)");
-        S.T_cap = tensor;
-    }
-    // the log-det only matters to the outputs that contain it
-    const bool carry = n_cpl > 1 && (a.nll_out || a.ld_out || a.sums);
-    if (carry && (e = grow(S.d_carry, S.carry_cap, (size_t)a.B * bs_nt * 1024)) != hipSuccess) return fail_hip(e, "hipMalloc(batch-statistics log-det carry)");
-    // the final launch: from the last resident tensor when there is one
-    auto final_args = [&](NfLaunch &f) {
-        if (n_cpl < 2) return;
-        f.in = S.d_T[(n_cpl - 1) & 1];
-        f.in_scale = 1.0f;
-        f.flags &= ~(uint32_t)NF_K_PHILOX_IN;
-        if (carry) {
-            f.flags |= NF_K_CARRY_IN;
-            f.ld_carry = S.d_carry;
-        }
-    };
-    if (nw2 && P.ident.lay[NF_PATH_SCALAR].prog.width == 4 && use_matrix_core()) {
-        // ---- width 4: every launch on the matrix-core kernel, the re-fold fused into the consumer's prologue ----
-        // launch k gathers the sums of pass k into its own block of `d_stats_mc`; launch k+1 (every workgroup, in LDS)
-        // turns them into moments and rescales the layer, workgroup 0 writes the patched image to the OTHER working
-        // copy, which launch k+2 reads.  2 launches per coupling + the final fused pass, nothing else on the stream.
-        const size_t passes = 2 * (size_t)n_cpl;
-        if ((e = grow(S.d_work2b, S.work2b_cap, nw2)) != hipSuccess) return fail_hip(e, "hipMalloc(batch-statistics parameters)");
-        if (S.stats_mc_passes < passes) {
-            if (S.d_stats_mc) (void)hipFree(S.d_stats_mc);
-            S.d_stats_mc = nullptr;
-            S.stats_mc_passes = 0;
-            if ((e = hipMalloc((void **)&S.d_stats_mc, passes * NF_STATS_SLOTS * 8 * sizeof(double))) != hipSuccess)
-                return fail_hip(e, "hipMalloc(batch-statistics accumulators)");
-            S.stats_mc_passes = passes;
-        }
-        if ((e = hipMemsetAsync(S.d_stats_mc, 0, passes * NF_STATS_SLOTS * 8 * sizeof(double), st)) != hipSuccess)
+    virtual int prepare(int n_cpl) = 0;                                   // its own scratch, and what it puts on the stream in front of the first launch
+    virtual double *stats_of(int c, int stage) const = 0;                 // the block of sums of that pass
+    virtual hipError_t launch(const NfProgram &prog, NfLaunch &s) = 0;    // one launch on its kernel: the parameter block and whatever else it adds to a launch
+    virtual int after_pass(int c, int stage, const NfLaunch &s, float *mom) = 0;   // what becomes of the sums of the pass just launched (`mom`: the coupling's [4][w] moments)
+    virtual int final(const NfProgram &prog, NfLaunch &a) = 0;            // the last launch, with the outputs of the call
+
+protected:
+    ~BsRoute() = default;
+};
+
+struct BsScalarRoute final : BsRoute {
+    BsScalarRoute(nf_handle *h_, nf_bs_state &S_, const BsPlan &P_, hipStream_t st_, double n_) : BsRoute(h_, S_, P_, st_, NF_PATH_SCALAR, n_) {}
+    int prepare(int) override
+    {
+        hipError_t e;
+        const size_t nw = P.ident.lay[path].block.size();
+        if ((e = S.work.reserve(nw)) != hipSuccess) return fail_hip(e, "hipMalloc(batch-statistics parameters)");
+        if ((e = S.stats.reserve(NF_STATS_SLOTS * 64)) != hipSuccess) return fail_hip(e, "hipMalloc(batch-statistics accumulators)");
+        if ((e = hipMemcpyAsync(S.work.ptr, P.d_ident[path].ptr, nw * sizeof(float), hipMemcpyDeviceToDevice, st)) != hipSuccess ||
+            (e = hipMemsetAsync(S.stats.ptr, 0, NF_STATS_SLOTS * 2 * (size_t)w * sizeof(double), st)) != hipSuccess)
             return fail_hip(e, "batch-statistics set-up");
-        const double n = (double)a.B * a.H * a.W * h->sync_world;   // with nf_set_sync the moments are over all ranks' patches
-        const float *cur = P.d_ident2;          // parameter block the next launch reads
-        float *bufs[2] = {S.d_work2, S.d_work2b};
-        int nbuf = 0;
-        // the fix a launch has to apply = the pass of the launch before it
-        const double *pend_stats = nullptr;
-        int pend_off = 0, pend_stage = 0;
-        float *pend_mom = nullptr;
-        auto launch = [&](const NfProgram &prog, NfLaunch &s) -> hipError_t {
-            s.params = cur;
-            s.n_params = (int32_t)nw2;
-            s.flags |= NF_K_BATCHSTATS;
-            if (tiled) {   // every "patch" of the launch is one tile of an image (tensors stay image-shaped)
-                s.flags |= NF_K_TILED;
-                s.img_H = h->cfg.height;
-                s.img_W = h->cfg.width;
-                s.H = h->fwd.tile_h;
-                s.W = h->fwd.tile_w;
-                s.tile_ny = bs_ny;
-                s.tile_nx = bs_nx;
-                s.tile_halo = bs_halo;
-                s.B = a.B * bs_nt;
-            }
-            s.fix_stats = pend_stats;
-            s.fix_n = n;
-            s.fix_off = pend_off;
-            s.fix_stage = pend_stage;
-            s.fix_mom_out = pend_mom;
-            s.fix_params_out = pend_stats ? bufs[nbuf] : nullptr;
-            hipError_t er = nf_launch_flow(prog, s, h->n_cu, st, true);
-            if (pend_stats) {
-                cur = bufs[nbuf];
-                nbuf ^= 1;
-            }
-            return er;
-        };
-        const float *const in0 = a.in;
-        const float in_scale0 = a.in_scale;
-        const uint32_t flags0 = a.flags;
-        for (int c = 0; c < n_cpl; ++c) {
-            float *mom = S.d_mom + (size_t)P.cpl_row[c] * 16;
-            for (int stage = 1; stage <= 2; ++stage) {
-                const NfProgram &prog = stage == 1 ? P.progA2[c] : P.progB2[c];
-                NfLaunch s = a;
-                s.nll_out = s.sd_out = s.ld_out = nullptr;
-                s.sums = nullptr;
-                s.stats = S.d_stats_mc + (size_t)(2 * c + stage - 1) * NF_STATS_SLOTS * 8;
-                s.stats_op = prog.n_ops - 1;
-                s.stats_stage = stage;
-                const int tin = stage == 1 ? (c > 0 ? c - 1 : 0) : c;
-                const bool from_input = tin == 0;
-                s.in = from_input ? in0 : S.d_T[tin & 1];
-                s.in_scale = from_input ? in_scale0 : 1.0f;
-                s.flags = from_input ? flags0 : (flags0 & ~(uint32_t)NF_K_PHILOX_IN);
-                s.out = (stage == 1 && c > 0) ? S.d_T[c & 1] : nullptr;
-                if (carry && s.out) {
-                    s.flags |= NF_K_CARRY_OUT | (c > 1 ? NF_K_CARRY_ADD : 0u);
-                    s.ld_carry = S.d_carry;
-                }
-                if ((e = launch(prog, s)) != hipSuccess) return fail_hip(e, "batch-statistics launch");
-                {
-                    const int rc = bs_sync(h, s.stats, 8, st);
-                    if (rc != NF_OK) return rc;
-                }
-                pend_stats = s.stats;
-                pend_off = P.ident.lay[NF_PATH_MFMA4].prog.ops[P.cpl_ops[c]].off;
-                pend_stage = stage;
-                pend_mom = mom + (stage == 1 ? 0 : 8);
-            }
-        }
-        a.ld_const = a.ld_const + (direction == 0 ? P.ident.ld_const : 0.0);
-        final_args(a);
-        if (tiled) {
-            // the final launch leaves per-tile sums; one more kernel forms the per-image results (as launch_tiled)
-            const bool want = direction == 0 && (a.nll_out || a.sd_out || a.ld_out || a.sums);
-            NfLaunch f = a;
-            f.nll_out = f.sd_out = f.ld_out = nullptr;
-            f.sums = nullptr;
-            float *part = nullptr;
-            if (want && (e = hipMallocAsync((void **)&part, (size_t)a.B * bs_nt * 4 * sizeof(float), st)) != hipSuccess)
-                return fail_hip(e, "hipMallocAsync(tile sums)");
-            f.tile_part = part;
-            e = launch(n_cpl > 1 ? P.progF2 : P.ident.lay[NF_PATH_MFMA4].prog, f);
-            if (e == hipSuccess && want) {
-                NfTileParts tp;
-                memset(&tp, 0, sizeof(tp));
-                tp.n_seg = 1;
-                tp.nt[0] = bs_nt;
-                e = nf_launch_tile_combine(part, tp, a.B, (double)h->cfg.height * h->cfg.width * kC, a.ld_const, nullptr, a.flags, a.nll_out,
-                                           a.sd_out, a.ld_out, a.sums, st);
-            }
-            if (part) {
-                hipError_t e2 = hipFreeAsync(part, st);
-                if (e == hipSuccess) e = e2;
-            }
-            if (e != hipSuccess) return fail_hip(e, "batch-statistics final launch");
-        } else if ((e = launch(n_cpl > 1 ? P.progF2 : P.ident.lay[NF_PATH_MFMA4].prog, a)) != hipSuccess) return fail_hip(e, "batch-statistics final launch");
-        std::vector<float> mom_h((size_t)std::max(n_cpl, 1) * 16);
-        if (moments_out && n_cpl &&
-            (e = hipMemcpyAsync(mom_h.data(), S.d_mom, (size_t)n_cpl * 16 * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess) {
-            (void)hipStreamSynchronize(st);
-            return fail_hip(e, "batch-statistics moments readback");
-        }
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail_hip(e, "batch-statistics final sync");   // the scratch is reused
-        if (moments_out && n_cpl) {
-            for (int c = 0; c < n_cpl; ++c)          // rows are in NLL layer order, like P.shift
-                for (int j = 0; j < 4; ++j) {
-                    mom_h[(size_t)c * 16 + j] += P.shift[(size_t)c * 8 + j];
-                    mom_h[(size_t)c * 16 + 8 + j] += P.shift[(size_t)c * 8 + 4 + j];
-                }
-            for (int c = 0; c < n_cpl; ++c)          // the caller's rows hold the model's own channels
-                for (int q = 0; q < 4; ++q) memcpy(moments_out + ((size_t)c * 4 + q) * wr, mom_h.data() + (size_t)c * 16 + q * 4, (size_t)wr * sizeof(float));
-        }
         return NF_OK;
     }
-    {   // the generic schedule runs on the scalar-weight kernel: both LDS tiles of a patch on one CU, one pixel per lane at width 32
-        const size_t tile_px = ((size_t)(a.H + 2) * (a.W + 2) + 1) & ~(size_t)1;
-        const size_t lds = sizeof(float) * (tile_px * (2 + (size_t)w) + 64);
-        if (lds > 160 * 1024 || (w >= 32 && a.H * a.W > 1024))
-            return fail(NF_EINVAL, "batch-statistics mode at coupling width %d covers patches of up to %s pixels (%dx%d given); "
-                        "evaluation mode has no such limit", w, w >= 32 ? "1024" : w == 16 ? "~2270 (e.g. 45x48)" : "~4090 (e.g. 62x62)",
-                        a.H, a.W);
+    double *stats_of(int, int) const override { return S.stats.ptr; }
+    hipError_t launch(const NfProgram &prog, NfLaunch &s) override
+    {
+        s.params = S.work.ptr;
+        s.n_params = 0;
+        return nf_launch_flow(prog, s, h->n_cu, st, false);
     }
-    if ((e = hipMemcpyAsync(S.d_work, P.d_ident, nw1 * sizeof(float), hipMemcpyDeviceToDevice, st)) != hipSuccess ||
-        (nw2 && (e = hipMemcpyAsync(S.d_work2, P.d_ident2, nw2 * sizeof(float), hipMemcpyDeviceToDevice, st)) != hipSuccess) ||
-        (e = hipMemsetAsync(S.d_stats, 0, NF_STATS_SLOTS * 2 * (size_t)w * sizeof(double), st)) != hipSuccess)
-        return fail_hip(e, "batch-statistics set-up");
+    // a one-workgroup kernel turns the sums into moments and re-folds the layer in place
+    int after_pass(int c, int stage, const NfLaunch &, float *mom) override
+    {
+        float *blk = S.work.ptr + P.ident.lay[path].prog.ops[P.cpl_ops[c]].off;
+        float *Wm = blk + (stage == 1 ? nf_cpl_off_W1(w) : nf_cpl_off_W2(w));
+        float *Bv = blk + (stage == 1 ? nf_cpl_off_B1(w) : nf_cpl_off_B2(w));
+        const hipError_t e = nf_launch_bs_finalize(S.stats.ptr, w, n, Wm, stage == 1 ? 18 : w, Bv, mom + (stage == 1 ? 0 : 2 * w),
+                                                   mom + (stage == 1 ? w : 3 * w), st);
+        return e == hipSuccess ? NF_OK : fail_hip(e, "batch-statistics finalise");
+    }
+    int final(const NfProgram &prog, NfLaunch &a) override
+    {
+        const hipError_t e = launch(prog, a);
+        return e == hipSuccess ? NF_OK : fail_hip(e, "batch-statistics final launch");
+    }
+};
 
-    const double n = (double)a.B * a.H * a.W * h->sync_world;
-    const double ld_call = a.ld_const;
+// Width 4: every launch on the matrix-core kernel, the re-fold fused into the consumer's prologue.  Launch k gathers the sums of
+// pass k into its own block of `stats_mc`; launch k+1 (every workgroup, in LDS) turns them into moments and rescales the layer,
+// workgroup 0 writes the patched image to the OTHER working copy, which launch k+2 reads.  2 launches per coupling + the final
+// fused pass, nothing else on the stream.  Images beyond 64x64 (nf_device.h, "overlapping tiles"): every launch tiled with ONE halo
+// for the whole call — 3 = the deepest launch (re-run coupling c-1, then l_1 of coupling c for its statistics) — so that the tile
+// grid, and with it the per-thread log-det carry, is the same in every launch.
+struct BsMfma4Route final : BsRoute {
+    static constexpr int halo = 3;
+    const int64_t B;   // images of the call
+    const int direction;
+    const bool tiled;
+    int ny = 1, nx = 1;
+    const float *cur = nullptr;   // parameter block the next launch reads
+    int nbuf = 0;                 // working copy the next fix writes
+    // the fix a launch has to apply = the pass of the launch before it
+    const double *pend_stats = nullptr;
+    int pend_off = 0, pend_stage = 0;
+    float *pend_mom = nullptr;
+
+    BsMfma4Route(nf_handle *h_, nf_bs_state &S_, const BsPlan &P_, hipStream_t st_, double n_, int64_t B_, int direction_)
+        : BsRoute(h_, S_, P_, st_, NF_PATH_MFMA4, n_), B(B_), direction(direction_), tiled(h_->fwd.tiled)
+    {
+        if (tiled) {
+            ny = nf_tile_count(h->cfg.height, h->fwd.tile_h, halo);
+            nx = nf_tile_count(h->cfg.width, h->fwd.tile_w, halo);
+            nt = ny * nx;
+        }
+    }
+    int prepare(int n_cpl) override
+    {
+        hipError_t e;
+        const size_t nw = P.ident.lay[path].block.size(), nstats = 2 * (size_t)n_cpl * NF_STATS_SLOTS * 8;
+        if ((e = S.work_mc[0].reserve(nw)) != hipSuccess || (e = S.work_mc[1].reserve(nw)) != hipSuccess)
+            return fail_hip(e, "hipMalloc(batch-statistics parameters)");
+        if ((e = S.stats_mc.reserve(nstats)) != hipSuccess) return fail_hip(e, "hipMalloc(batch-statistics accumulators)");
+        if ((e = hipMemsetAsync(S.stats_mc.ptr, 0, nstats * sizeof(double), st)) != hipSuccess) return fail_hip(e, "batch-statistics set-up");
+        cur = P.d_ident[path].ptr;
+        return NF_OK;
+    }
+    double *stats_of(int c, int stage) const override { return S.stats_mc.ptr + (size_t)(2 * c + stage - 1) * NF_STATS_SLOTS * 8; }
+    hipError_t launch(const NfProgram &prog, NfLaunch &s) override
+    {
+        s.params = cur;
+        s.n_params = (int32_t)P.ident.lay[path].block.size();
+        s.flags |= NF_K_BATCHSTATS;
+        if (tiled) {   // every "patch" of the launch is one tile of an image (tensors stay image-shaped)
+            s.flags |= NF_K_TILED;
+            s.img_H = h->cfg.height;
+            s.img_W = h->cfg.width;
+            s.H = h->fwd.tile_h;
+            s.W = h->fwd.tile_w;
+            s.tile_ny = ny;
+            s.tile_nx = nx;
+            s.tile_halo = halo;
+            s.B = B * nt;
+        }
+        s.fix_stats = pend_stats;
+        s.fix_n = n;
+        s.fix_off = pend_off;
+        s.fix_stage = pend_stage;
+        s.fix_mom_out = pend_mom;
+        s.fix_params_out = pend_stats ? S.work_mc[nbuf].ptr : nullptr;
+        const hipError_t e = nf_launch_flow(prog, s, h->n_cu, st, true);
+        if (pend_stats) {
+            cur = S.work_mc[nbuf].ptr;
+            nbuf ^= 1;
+        }
+        return e;
+    }
+    int after_pass(int c, int stage, const NfLaunch &s, float *mom) override
+    {
+        pend_stats = s.stats;
+        pend_off = P.ident.lay[path].prog.ops[P.cpl_ops[c]].off;
+        pend_stage = stage;
+        pend_mom = mom + (stage == 1 ? 0 : 2 * w);
+        return NF_OK;
+    }
+    int final(const NfProgram &prog, NfLaunch &a) override
+    {
+        hipError_t e;
+        if (!tiled) return (e = launch(prog, a)) == hipSuccess ? NF_OK : fail_hip(e, "batch-statistics final launch");
+        // the final launch leaves per-tile sums; one more kernel forms the per-image results (as launch_tiled)
+        const bool want = direction == 0 && (a.nll_out || a.sd_out || a.ld_out || a.sums);
+        NfLaunch f = a;
+        f.nll_out = f.sd_out = f.ld_out = nullptr;
+        f.sums = nullptr;
+        float *part = nullptr;
+        if (want && (e = hipMallocAsync((void **)&part, (size_t)B * nt * 4 * sizeof(float), st)) != hipSuccess)
+            return fail_hip(e, "hipMallocAsync(tile sums)");
+        f.tile_part = part;
+        e = launch(prog, f);
+        if (e == hipSuccess && want) {
+            NfTileParts tp;
+            memset(&tp, 0, sizeof(tp));
+            tp.n_seg = 1;
+            tp.nt[0] = nt;
+            e = nf_launch_tile_combine(part, tp, B, (double)h->cfg.height * h->cfg.width * kC, a.ld_const, nullptr, a.flags, a.nll_out,
+                                       a.sd_out, a.ld_out, a.sums, st);
+        }
+        if (part) {
+            const hipError_t e2 = hipFreeAsync(part, st);
+            if (e == hipSuccess) e = e2;
+        }
+        return e == hipSuccess ? NF_OK : fail_hip(e, "batch-statistics final launch");
+    }
+};
+
+// The schedule: per coupling two statistics passes, then the final pass, then the moments.
+static int bs_walk(BsRoute &R, int direction, NfLaunch &a, float *moments_out)
+{
+    nf_handle *const h = R.h;
+    nf_bs_state &S = R.S;
+    const BsPlan &P = R.P;
+    const hipStream_t st = R.st;
+    const BsProgs &G = P.progs[R.path];
+    const int n_cpl = (int)P.cpl_ops.size();
+    const int w = R.w, wr = h->fwd.raw_width;   // the kernels' rows of moments are [4][w]; moments_out's [4][wr] (zero-padded widths)
+    hipError_t e;
+    int rc;
+    if ((e = S.mom.reserve((size_t)std::max(n_cpl, 1) * 4 * 32)) != hipSuccess) return fail_hip(e, "hipMalloc(batch-statistics moments)");
+    if (n_cpl > 1 && ((e = S.T[0].reserve((size_t)a.B * a.H * a.W * 4)) != hipSuccess || (e = S.T[1].reserve((size_t)a.B * a.H * a.W * 4)) != hipSuccess))
+        return fail_hip(e, "hipMalloc(batch-statistics scratch tensors)");
+    // the log-det only matters to the outputs that contain it
+    const bool carry = n_cpl > 1 && (a.nll_out || a.ld_out || a.sums);
+    if (carry && (e = S.carry.reserve((size_t)a.B * R.nt * 1024)) != hipSuccess) return fail_hip(e, "hipMalloc(batch-statistics log-det carry)");
+    if ((rc = R.prepare(n_cpl)) != NF_OK) return rc;
+
     const float *const in0 = a.in;
     const float in_scale0 = a.in_scale;
     const uint32_t flags0 = a.flags;
     for (int c = 0; c < n_cpl; ++c) {
-        const int blk = P.ident.lay[NF_PATH_SCALAR].prog.ops[P.cpl_ops[c]].off;
-        float *mom = S.d_mom + (size_t)P.cpl_row[c] * 4 * w;
+        float *mom = S.mom.ptr + (size_t)P.cpl_row[c] * 4 * w;
         for (int stage = 1; stage <= 2; ++stage) {
-            const NfProgram &prog = stage == 1 ? P.progA[c] : P.progB[c];
+            const NfProgram &prog = stage == 1 ? G.A[c] : G.B[c];
             NfLaunch s = a;
-            s.params = S.d_work;
-            s.n_params = 0;
             s.nll_out = s.sd_out = s.ld_out = nullptr;
             s.sums = nullptr;
-            s.stats = S.d_stats;
+            s.stats = R.stats_of(c, stage);
             s.stats_op = prog.n_ops - 1;
             s.stats_stage = stage;
             // launch A_c reads T_{c-1} (it re-runs coupling c-1), launch B_c reads T_c;  T_0 = the caller's input
             const int tin = stage == 1 ? (c > 0 ? c - 1 : 0) : c;
             const bool from_input = tin == 0;
-            s.in = from_input ? in0 : S.d_T[tin & 1];
+            s.in = from_input ? in0 : S.T[tin & 1].ptr;
             s.in_scale = from_input ? in_scale0 : 1.0f;
             s.flags = from_input ? flags0 : (flags0 & ~(uint32_t)NF_K_PHILOX_IN);
-            s.out = (stage == 1 && c > 0) ? S.d_T[c & 1] : nullptr;
+            s.out = (stage == 1 && c > 0) ? S.T[c & 1].ptr : nullptr;
             if (carry && s.out) {
                 s.flags |= NF_K_CARRY_OUT | (c > 1 ? NF_K_CARRY_ADD : 0u);
-                s.ld_carry = S.d_carry;
+                s.ld_carry = S.carry.ptr;
             }
-            if ((e = nf_launch_flow(prog, s, h->n_cu, st, false)) != hipSuccess) return fail_hip(e, "batch-statistics launch");
-            {
-                const int rc = bs_sync(h, S.d_stats, 2 * w, st);
-                if (rc != NF_OK) return rc;
-            }
-            float *Wm = S.d_work + blk + (stage == 1 ? nf_cpl_off_W1(w) : nf_cpl_off_W2(w));
-            float *Bv = S.d_work + blk + (stage == 1 ? nf_cpl_off_B1(w) : nf_cpl_off_B2(w));
-            if ((e = nf_launch_bs_finalize(S.d_stats, w, n, Wm, stage == 1 ? 18 : w, Bv, mom + (stage == 1 ? 0 : 2 * w),
-                                           mom + (stage == 1 ? w : 3 * w), st)) != hipSuccess)
-                return fail_hip(e, "batch-statistics finalise");
+            if ((e = R.launch(prog, s)) != hipSuccess) return fail_hip(e, "batch-statistics launch");
+            if ((rc = bs_sync(h, s.stats, 2 * w, st)) != NF_OK) return rc;
+            if ((rc = R.after_pass(c, stage, s, mom)) != NF_OK) return rc;
         }
     }
 
-    // final pass with the batch moments folded in
-    const bool mc = nw2 != 0 && use_matrix_core();
-    if (mc && (e = nf_launch_gather(S.d_work2, S.d_work, P.d_pairs, P.n_pairs, st)) != hipSuccess)
-        return fail_hip(e, "batch-statistics re-layout");
-    a.params = mc ? S.d_work2 : S.d_work;
-    a.n_params = mc ? (int32_t)nw2 : 0;
-    a.ld_const = ld_call + (direction == 0 ? P.ident.ld_const : 0.0);
-    if (!mc) final_args(a);   // (a final pass on the matrix-core kernel maps pixels to threads differently: whole stack, no carry)
-    if ((e = nf_launch_flow(mc ? P.ident.lay[NF_PATH_MFMA4].prog : n_cpl > 1 ? P.progF : P.ident.lay[NF_PATH_SCALAR].prog, a, h->n_cu, st, mc)) != hipSuccess)
-        return fail_hip(e, "batch-statistics final launch");
+    // final pass with the batch moments folded in: from the last resident tensor when there is one
+    a.ld_const = a.ld_const + (direction == 0 ? P.ident.ld_const : 0.0);
+    if (n_cpl > 1) {
+        a.in = S.T[(n_cpl - 1) & 1].ptr;
+        a.in_scale = 1.0f;
+        a.flags &= ~(uint32_t)NF_K_PHILOX_IN;
+        if (carry) {
+            a.flags |= NF_K_CARRY_IN;
+            a.ld_carry = S.carry.ptr;
+        }
+    }
+    if ((rc = R.final(G.F, a)) != NF_OK) return rc;
     std::vector<float> mom_h((size_t)std::max(n_cpl, 1) * 4 * w);
     if (moments_out && n_cpl &&
-        (e = hipMemcpyAsync(mom_h.data(), S.d_mom, (size_t)n_cpl * 4 * w * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess) {
+        (e = hipMemcpyAsync(mom_h.data(), S.mom.ptr, (size_t)n_cpl * 4 * w * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess) {
         (void)hipStreamSynchronize(st);
         return fail_hip(e, "batch-statistics moments readback");
     }
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail_hip(e, "batch-statistics final sync");   // the scratch is reused
     if (moments_out && n_cpl) {
-        for (int c = 0; c < n_cpl; ++c)              // [mean1, var1, mean2, var2][w] per coupling, NLL layer order
+        for (int c = 0; c < n_cpl; ++c)              // [mean1, var1, mean2, var2][w] per coupling, NLL layer order, like P.shift
             for (int j = 0; j < w; ++j) {
                 mom_h[(size_t)c * 4 * w + j] += P.shift[(size_t)c * 2 * w + j];
                 mom_h[(size_t)c * 4 * w + 2 * w + j] += P.shift[(size_t)c * 2 * w + w + j];
@@ -2708,6 +2663,34 @@ static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moment
                 memcpy(moments_out + ((size_t)c * 4 + q) * wr, mom_h.data() + ((size_t)c * 4 + q) * w, (size_t)wr * sizeof(float));
     }
     return NF_OK;
+}
+
+static int run_batchstats(nf_handle *h, int direction, NfLaunch a, float *moments_out, hipStream_t st, const nf_cond *cond)
+{
+    if (h->cfg.flags & NF_CFG_FP16_CNN) return fail(NF_EINVAL, "batch-statistics mode is fp32 only");
+    const int route = bs_route(h);   // (the trainer route has its own evaluator, lock and scratch)
+    if (route == NF_BS_ROUTE_TRAINER) return run_batchstats_wide(h, direction, a, cond, moments_out, st);
+    std::lock_guard<std::mutex> lock(h->bs_mu);   // one scratch per handle: calls serialise
+    if (!h->bs) h->bs = new (std::nothrow) nf_bs_state();
+    if (!h->bs) return fail(NF_ENOMEM, "out of host memory");
+    nf_bs_state &S = *h->bs;
+    BsPlan &P = S.plan[direction];
+    if (!P.ready) {
+        int rc = bs_build_plan(h, direction, P);
+        if (rc != NF_OK) return rc;
+    }
+    const double n = (double)a.B * a.H * a.W * h->sync_world;   // with nf_set_sync the moments are over all ranks' patches
+    switch (route) {
+    case NF_BS_ROUTE_MFMA4: {
+        BsMfma4Route R(h, S, P, st, n, a.B, direction);
+        return bs_walk(R, direction, a, moments_out);
+    }
+    case NF_BS_ROUTE_SCALAR: {
+        BsScalarRoute R(h, S, P, st, n);
+        return bs_walk(R, direction, a, moments_out);
+    }
+    }
+    return fail(NF_EINVAL, "internal: unknown batch-statistics route %d", route);
 }
 
 static void nf_bs_destroy(nf_bs_state *s) { delete s; }

@@ -1818,13 +1818,6 @@ __global__ __launch_bounds__(64) void nf_bs_finalize_kernel(double *__restrict__
     for (int i = j; i < NF_STATS_SLOTS * 2 * w; i += 64) stats[i] = 0.0;
 }
 
-// dst[pairs[2i]] = src[pairs[2i+1]]: the normalisation-dependent entries of the matrix-core layout from the working scalar layout
-__global__ __launch_bounds__(256) void nf_gather_kernel(float *__restrict__ dst, const float *__restrict__ src, const int32_t *__restrict__ pairs, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[pairs[2 * i]] = src[pairs[2 * i + 1]];
-}
-
 // fold the slotted sums into the plain (sum nll, sum sd, count) triple — one wavefront
 __global__ __launch_bounds__(64) void nf_sums_reduce_kernel(const double *__restrict__ wide, double *__restrict__ out3,
                                                             int accumulate)
@@ -2141,13 +2134,6 @@ hipError_t nf_launch_bs_finalize(double *stats, int w, double n, float *Wm, int 
                                  hipStream_t stream)
 {
     hipLaunchKernelGGL(nf_bs_finalize_kernel, dim3(1), dim3(64), 0, stream, stats, w, n, Wm, rows, Bv, mean_out, var_out);
-    return hipGetLastError();
-}
-
-hipError_t nf_launch_gather(float *dst, const float *src, const int32_t *pairs, int n, hipStream_t stream)
-{
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(nf_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dst, src, pairs, n);
     return hipGetLastError();
 }
 

@@ -1,9 +1,11 @@
 """Wall time of one batch-statistics call (2 statistics passes per coupling + the fused pass)."""
-import sys, time
+import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, ".")
-from noise_flow_amd import NoiseFlow, default_hps, patches
+from noise_flow_amd import NoiseFlow, default_hps, patches, _lib as _nf_lib
 from noise_flow_amd.ckpt import load_checkpoint
+if os.environ.get("NF_TOOL_LIB"):   # A/B a differently-built library (this tool only)
+    _nf_lib.LIB_PATH = os.path.abspath(os.environ["NF_TOOL_LIB"])
 
 v = load_checkpoint("models/NoiseFlow/ckpt/model.ckpt.best")
 for B in (138, 1024, 4096):

@@ -1,8 +1,10 @@
 """is_training=True evaluation (batch statistics) against the evaluation under running statistics, at coupling widths 32 / 4 / 64:  python tools/time_batchstats_width.py"""
-import sys, time
+import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, ".")
-from noise_flow_amd import NoiseFlow, default_hps, patches, params as _params
+from noise_flow_amd import NoiseFlow, default_hps, patches, params as _params, _lib as _nf_lib
+if os.environ.get("NF_TOOL_LIB"):   # A/B a differently-built library (this tool only)
+    _nf_lib.LIB_PATH = os.path.abspath(os.environ["NF_TOOL_LIB"])
 for w in (32, 4, 64):
     hps = default_hps(width=w)
     var = _params.init_variables(hps.arch, w, 4, 1234)
