@@ -24,8 +24,10 @@
  *     16-32 Python threads sharing one tf.Session, job_noise_flow.sh:36,
  *     train_dncnn_noiseflow.py:195); they never synchronise and — patches of
  *     up to 64x64 — never allocate; images beyond 64x64 use scratch the handle
- *     owns (nf_reserve_workspace; grown on demand otherwise).  The
- *     nf_*_batchstats variants are the documented exception.
+ *     owns (nf_reserve_workspace; grown on demand otherwise), and so does
+ *     nf_nll_grad on the shapes it evaluates as tiles (NF_CFG_GRAD_TILED;
+ *     nf_reserve_grad_workspace).  The nf_*_batchstats variants are the
+ *     documented exception.
  */
 #ifndef NOISEFLOW_HIP_H
 #define NOISEFLOW_HIP_H
@@ -138,6 +140,11 @@ typedef struct nf_config {
 #define NF_CFG_GRAD_MFMA 4  /* nf_nll_grad at coupling widths 17 .. 32: the matrix-core gradient kernel
                               (csrc/nf_grad_wide.hip, patches up to 32x32) and its weight image, uploaded by
                               nf_create.  No effect on any other call, nor on widths up to 16. */
+#define NF_CFG_GRAD_TILED 16 /* nf_nll_grad at padded coupling widths 4 / 8 / 16 on every H, W up to NF_MAX_IMAGE_SIDE: a
+                              shape the whole-patch kernel does not hold is evaluated as overlapping 32-pixel tiles, the
+                              program cut into segments (see nf_nll_grad, nf_grad_tile_segments).  The flag only adds: a
+                              shape held whole stays on the whole-patch kernel, no other call changes.  (Bit 8 is not
+                              assigned.) */
 
 /* Per-call conditioning: ONE value per call, not per patch — the reference
  * feeds length-1 lists (MiniBatchSampler.py:61-64, NoiseFlowWrapper.py:85-86).
@@ -270,8 +277,15 @@ int nf_sample_percond(nf_handle *h, const float *y, const float *eps, uint64_t s
  * H, W <= 32, up to 12 couplings on a 32x32 patch (the gate record, 8 KiB per coupling there, must fit the LDS beside the
  * tiles); a shape beyond 32x32 stays with the scalar kernel where that kernel holds it (the flag only adds), and is refused
  * otherwise.  nf_grad_path reports which kernel a handle launches.
- * Not covered: images beyond 64x64 (tiled evaluation), widths beyond 32 (the GEMM families), batch-statistics mode, and
- * host-fed variants. */
+ * With NF_CFG_GRAD_TILED, a shape at padded coupling width 4 / 8 / 16 that the whole-patch kernel does not hold (beyond 64x64;
+ * width 16 beyond 1024 pixels; LDS) is NF_GRAD_PATH_TILED: the program is cut after couplings into segments of at most 3
+ * couplings (nf_grad_tile_segments), the tiled forward launches of nf_nll run segment by segment with EVERY tensor between two
+ * segments kept, and then one launch of the scalar gradient kernel per segment, last to first, works on overlapping
+ * min(H,32) x min(W,32) tiles with a halo of 4 x the segment's couplings and stores core windows only.  Same contract (any
+ * subset of the outputs, cond or rows — rows are per image —, no synchronisation); scratch ((segments - 1) tensors, 2
+ * gradient tensors, the tile sums) comes from the handle's workspace set and is allocated only when a call needs more than
+ * any earlier one (nf_workspace_bytes(h, 2, B), nf_reserve_grad_workspace).  Width 32 has no tile mode.
+ * Not covered: widths beyond 32 (the GEMM families), NF_CFG_FP16_CNN, batch-statistics mode, and host-fed variants. */
 int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond,
                 const nf_cond_row *rows, float *nll_out, float *gx_out, float *gy_out, void *stream);
 
@@ -285,7 +299,16 @@ int nf_grad_supported(const nf_config *cfg, const nf_layer_desc *layers, const f
  * (A/B aid, like NF_KERNEL=valu). */
 #define NF_GRAD_PATH_SCALAR 0   /* nf_grad_kernel (csrc/nf_grad.hip) */
 #define NF_GRAD_PATH_WIDE32 1   /* nf_grad_wide_kernel (csrc/nf_grad_wide.hip), v_mfma_f32_32x32x2_f32 */
+#define NF_GRAD_PATH_TILED 2    /* NF_CFG_GRAD_TILED: nf_grad_kernel on 32-pixel tiles, one launch per segment */
 int nf_grad_path(const nf_handle *h);
+
+/* How nf_nll_grad cuts a model under NF_CFG_GRAD_TILED, in the format of nf_tile_segments: returns the number of segments (0:
+ * the shape is held whole by a whole-patch kernel; negative: NF_E*, e.g. what nf_grad_supported refuses) and for i < cap
+ * out5[5 i ..] = first op, one-past-last op, GRADIENT halo (4 x the segment's couplings), tiles along H, tiles along W of the
+ * backward launch (tiles of min(H,32) x min(W,32)).  Host arithmetic only.  NF_GRAD_TILE_SEGMENTS=<n> in the environment, read
+ * at nf_create, forces the count (A/B and test aid); a count that leaves a segment more than 3 couplings fails. */
+int nf_grad_tile_segments(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params,
+                          int32_t *out5, int32_t cap);
 
 /* Host-only: the program and parameter block nf_nll_grad would run for this model ("gradient block": A^-1 beside every 1x1
  * matrix, 1/s beside every scale; couplings in the generic layout or, *path == NF_GRAD_PATH_WIDE32, in the fetch-order layout of
@@ -528,8 +551,10 @@ int nf_batchstats_route(const nf_handle *h);
  * what one call of B images needs (0 for patches of up to 64x64: they need none); nf_reserve_workspace allocates that for
  * `calls_in_flight` concurrent calls up front (synchronous; at nf_create time, so to speak), after which no call of up to B
  * images allocates anything.  No reference counterpart (TF sizes its arena inside sess.run). */
-int64_t nf_workspace_bytes(const nf_handle *h, int32_t direction, int64_t B);
+int64_t nf_workspace_bytes(const nf_handle *h, int32_t direction, int64_t B);   /* direction 2: one tiled nf_nll_grad call */
 int nf_reserve_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
+/* the same for nf_nll_grad under NF_CFG_GRAD_TILED (nothing to do for a handle whose shape is held whole) */
+int nf_reserve_grad_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
 
 /* Host-only: the SDN5 scalars the kernels receive for a given (iso, cam):
  * out[0] = beta1/gain, out[1] = beta2 (cond_utils.py:205-239). */

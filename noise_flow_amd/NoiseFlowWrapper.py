@@ -32,7 +32,7 @@ from .noise_flow_model import NoiseFlow
 
 class NoiseFlowWrapper:
     def __init__(self, path, sampling_temperature=0.6, binding="loss_first", device=None, seed=None,
-                 bn_mode="running", compat=None, patch_shape=None, grad_kernel=None):
+                 bn_mode="running", compat=None, patch_shape=None, grad_kernel=None, grad_tiles=None):
         if compat not in (None, "reference"):
             raise ValueError("compat must be None or 'reference'")
         if compat == "reference":
@@ -54,6 +54,7 @@ class NoiseFlowWrapper:
         self.binding = binding
         self.device = device
         self.grad_kernel = grad_kernel   # 'scalar' | 'mfma' (NoiseFlow); None: hps.grad_kernel, else 'scalar'
+        self.grad_tiles = grad_tiles     # True: input gradients of images beyond 64x64 (NoiseFlow); None: hps.grad_tiles, else False
         self.hps = self.hps_loader(os.path.join(self.nf_path, "hps.txt"))
         if seed is not None:
             self.hps.seed = seed
@@ -67,7 +68,7 @@ class NoiseFlowWrapper:
             setattr(self.hps, "x_shape", self.x_shape)
         self.logger.info("Building Noise Flow")
         self.nf_model = NoiseFlow(self.x_shape[1:], self.bn_mode == "batch", self.hps, binding=self.binding, device=self.device,
-                                  grad_kernel=self.grad_kernel)
+                                  grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles)
         self.logger.info("Restoring best model")
         self.nf_model.restore(self.model_checkpoint_path)
 

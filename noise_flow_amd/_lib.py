@@ -25,6 +25,7 @@ NF_LAYER_CONV1X1_NONE, NF_LAYER_CONV1X1_LU2, NF_LAYER_PERMUTE = 15, 16, 17
 NF_CFG_FP16_CNN = 1
 NF_CFG_EXACT_FP32 = 2
 NF_CFG_GRAD_MFMA = 4
+NF_CFG_GRAD_TILED = 16   # (bit 8 is not assigned)
 
 NF_ACCUMULATE = 1
 NF_NO_PRIOR = 2
@@ -183,6 +184,11 @@ def load() -> C.CDLL:
     lib.nf_grad_fold.restype = C.c_int
     lib.nf_grad_fold.argtypes = [C.POINTER(nf_config), C.POINTER(nf_layer_desc), C.POINTER(C.c_float), C.c_size_t, C.POINTER(i32),
                                  C.POINTER(i32), i32, C.POINTER(i32), C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.nf_grad_tile_segments.restype = C.c_int
+    lib.nf_grad_tile_segments.argtypes = [C.POINTER(nf_config), C.POINTER(nf_layer_desc), C.POINTER(C.c_float), C.c_size_t,
+                                          C.POINTER(i32), i32]
+    lib.nf_reserve_grad_workspace.restype = C.c_int
+    lib.nf_reserve_grad_workspace.argtypes = [vp, i64, i32]
     if lib.nf_abi_version() != 1:
         raise ImportError("noiseflow_hip ABI version mismatch")
     _lib = lib
@@ -202,9 +208,9 @@ EXPORTED_SYMBOLS = (
     "nf_trainer_create", "nf_trainer_destroy", "nf_trainer_forward_backward", "nf_trainer_forward", "nf_trainer_apply", "nf_trainer_step",
     "nf_trainer_get_params", "nf_trainer_set_params", "nf_trainer_steps", "nf_trainer_set_sync",
     "nf_cond_rows", "nf_nll_percond", "nf_sample_percond",
-    "nf_nll_grad", "nf_grad_supported", "nf_grad_path", "nf_grad_fold",
+    "nf_nll_grad", "nf_grad_supported", "nf_grad_path", "nf_grad_fold", "nf_grad_tile_segments", "nf_reserve_grad_workspace",
 )
-NF_GRAD_PATH_SCALAR, NF_GRAD_PATH_WIDE32 = 0, 1
+NF_GRAD_PATH_SCALAR, NF_GRAD_PATH_WIDE32, NF_GRAD_PATH_TILED = 0, 1, 2
 NF_PATH_SCALAR, NF_PATH_MFMA4, NF_PATH_FP16, NF_PATH_WIDE32, NF_PATH_WIDE16, NF_PATH_WIDE32_FP16, NF_PATH_GEMM, NF_PATH_GEMM_FP16 = 0, 1, 2, 3, 4, 5, 6, 7
 NF_PATH_SPLIT_BF16 = 8
 NF_BS_ROUTE_MFMA4, NF_BS_ROUTE_SCALAR, NF_BS_ROUTE_TRAINER = 0, 1, 2

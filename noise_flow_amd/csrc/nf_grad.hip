@@ -12,6 +12,12 @@
 // (the fp32 round trip through the stack loses ~1e-4 of x, which the leading sdn layer's gy term would inherit).
 // LDS: the forward kernel's two zero-bordered tiles (z0: 2 words, relu(h2): w words per tile pixel); in the backward sweep the
 // relu(h2) tile is overlaid, once consumed, by d(shift, raw) (4 words of a pixel's w) and then by d h1 (w words).
+//
+// TILED (NF_CFG_GRAD_TILED, nf_device.h "gradient tiles"): a "patch" of the launch is one H x W tile of an img_H x img_W image and
+// `prog` one SEGMENT of the program.  The tile loads the tensor in front of the segment (z_in), runs the same forward sweep over
+// the segment's ops, takes g from its own z (last segment) or from the gradient the segment behind it left (g_in), runs the same
+// backward sweep and stores its CORE window only (g_out; gy_out stored or added to).  Border masks follow the image border,
+// conditioning rows are per image, and nll_b is not formed here (the tiled forward launches and nf_tile_combine form it).
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stdint.h>
@@ -24,7 +30,7 @@
 
 namespace {
 
-template <int WIDTH, int THREADS, int PX>
+template <int WIDTH, int THREADS, int PX, bool TILED = false>
 __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, const NfGradLaunch a)
 {
     static_assert(WIDTH == 4 || WIDTH == 8 || WIDTH == 16 || WIDTH == 32, "gate sets of WIDTH bits must tile a 32-bit word");
@@ -42,6 +48,7 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
     const int t = threadIdx.x;
     int lidx[PX], gidx[PX], bmask[PX];
     bool act[PX];
+    [[maybe_unused]] int prow[PX], pcol[PX];   // TILED: row / column of the slot's pixel inside the tile
 #pragma unroll
     for (int k = 0; k < PX; ++k) {
         const int p = t + THREADS * k;
@@ -49,6 +56,8 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
         const int pp = act[k] ? p : 0;
         const int r = pp / W, c = pp - r * W;
         gidx[k] = pp;
+        prow[k] = r;
+        pcol[k] = c;
         lidx[k] = (r + 1) * Wp + (c + 1);
         bmask[k] = (r == 0 ? 1 : 0) | (r == H - 1 ? 2 : 0) | (c == 0 ? 4 : 0) | (c == W - 1 ? 8 : 0);
     }
@@ -60,10 +69,30 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
     const int first_cpl = a.first_cpl;
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const size_t patch_off = (size_t)b * (size_t)HW;
-        const float4 *const x4 = reinterpret_cast<const float4 *>(a.x) + patch_off;
+        // Where this "patch" sits: on its own, or — TILED — as tile b % tiles of image b / tiles (nf_device.h, "overlapping tiles"):
+        // addresses and border masks follow the image, own[] is the tile's core window
+        int64_t img = b;
+        [[maybe_unused]] bool own[PX];
+        if constexpr (TILED) {
+            const int nt = a.tile_ny * a.tile_nx;
+            img = b / nt;
+            const int ti = (int)(b - img * nt);
+            const int ty = ti / a.tile_nx, tx = ti - ty * a.tile_nx;
+            const int oy = nf_tile_origin(ty, a.img_H, H, a.tile_halo), ox = nf_tile_origin(tx, a.img_W, W, a.tile_halo);
+            const int cy0 = nf_tile_core0(ty, a.img_H, H, a.tile_halo), cy1 = nf_tile_core1(ty, a.tile_ny, a.img_H, H, a.tile_halo);
+            const int cx0 = nf_tile_core0(tx, a.img_W, W, a.tile_halo), cx1 = nf_tile_core1(tx, a.tile_nx, a.img_W, W, a.tile_halo);
+#pragma unroll
+            for (int k = 0; k < PX; ++k) {
+                const int R = oy + prow[k], C = ox + pcol[k];
+                gidx[k] = R * a.img_W + C;
+                bmask[k] = (R == 0 ? 1 : 0) | (R == a.img_H - 1 ? 2 : 0) | (C == 0 ? 4 : 0) | (C == a.img_W - 1 ? 8 : 0);
+                own[k] = act[k] && R >= cy0 && R < cy1 && C >= cx0 && C < cx1;
+            }
+        }
+        const size_t patch_off = TILED ? (size_t)img * (size_t)a.img_H * (size_t)a.img_W : (size_t)b * (size_t)HW;
+        const float4 *const x4 = reinterpret_cast<const float4 *>(TILED ? a.z_in : a.x) + patch_off;
         const float4 *const y4 = reinterpret_cast<const float4 *>(a.y) + patch_off;   // (not dereferenced when a.y is null)
-        const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + b;
+        const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + img;
         auto cond_a = [&](int slot) { return a.cond_rows ? crow->a[slot & 3] : a.cond_a[slot & 3]; };
         auto cond_b = [&](int slot) { return a.cond_rows ? crow->b[slot & 3] : a.cond_b[slot & 3]; };
 
@@ -273,7 +302,7 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
             }
         }
         // nll_b = -(log-det) + prior, as nf_flow_kernel forms it
-        if (a.nll_out) {
+        if (!TILED && a.nll_out) {
             float s2 = 0.f;
 #pragma unroll
             for (int k = 0; k < PX; ++k)
@@ -315,6 +344,17 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
                 g[k][c] = z[k][c];
                 gy[k][c] = 0.0f;
             }
+        if constexpr (TILED) {
+            if (a.g_in) {   // not the last segment: the gradient the segment behind this one stored, whole tile
+                const float4 *const g4 = reinterpret_cast<const float4 *>(a.g_in) + patch_off;
+#pragma unroll
+                for (int k = 0; k < PX; ++k) {
+                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (act[k]) v = g4[gidx[k]];
+                    g[k][0] = v.x; g[k][1] = v.y; g[k][2] = v.z; g[k][3] = v.w;
+                }
+            }
+        }
         int cidx = 0;
         for (int op = 0; op < n_ops; ++op) cidx += prog.ops[op].type == NF_OP_COUPLING_FWD ? 1 : 0;
         for (int op = n_ops - 1; op >= 0; --op) {
@@ -488,27 +528,52 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
             }
         }
 
-        if (a.gx_out) {
-            float4 *const o4 = reinterpret_cast<float4 *>(a.gx_out) + patch_off;
+        if constexpr (TILED) {
+            // the core window only; every pixel of the image is in exactly one tile's core, so an accumulating launch adds to gy
+            // without atomics (the launch that wrote it is ahead of this one in the stream)
+            if (a.g_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.g_out) + patch_off;
 #pragma unroll
-            for (int k = 0; k < PX; ++k)
-                if (act[k]) o4[gidx[k]] = make_float4(g[k][0], g[k][1], g[k][2], g[k][3]);
-        }
-        if (a.gy_out) {
-            float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+                for (int k = 0; k < PX; ++k)
+                    if (own[k]) o4[gidx[k]] = make_float4(g[k][0], g[k][1], g[k][2], g[k][3]);
+            }
+            if (a.gy_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+                const bool acc = (a.tflags & NF_GT_GY_ACC) != 0;
 #pragma unroll
-            for (int k = 0; k < PX; ++k)
-                if (act[k]) o4[gidx[k]] = make_float4(gy[k][0], gy[k][1], gy[k][2], gy[k][3]);
+                for (int k = 0; k < PX; ++k)
+                    if (own[k]) {
+                        float4 v = make_float4(gy[k][0], gy[k][1], gy[k][2], gy[k][3]);
+                        if (acc) {
+                            const float4 p = o4[gidx[k]];
+                            v = make_float4(p.x + v.x, p.y + v.y, p.z + v.z, p.w + v.w);
+                        }
+                        o4[gidx[k]] = v;
+                    }
+            }
+        } else {
+            if (a.gx_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gx_out) + patch_off;
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+                    if (act[k]) o4[gidx[k]] = make_float4(g[k][0], g[k][1], g[k][2], g[k][3]);
+            }
+            if (a.gy_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+                    if (act[k]) o4[gidx[k]] = make_float4(gy[k][0], gy[k][1], gy[k][2], gy[k][3]);
+            }
         }
     }
 }
 
-template <int WIDTH, int THREADS, int PX>
+template <int WIDTH, int THREADS, int PX, bool TILED = false>
 hipError_t launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
 {
     int dev = 0;
     (void)hipGetDevice(&dev);
-    return flow_launch<&nf_grad_kernel<WIDTH, THREADS, PX>>(THREADS, lds, prog, a, n_cu, dev, stream);
+    return flow_launch<&nf_grad_kernel<WIDTH, THREADS, PX, TILED>>(THREADS, lds, prog, a, n_cu, dev, stream);
 }
 
 template <int WIDTH>
@@ -528,6 +593,17 @@ hipError_t dispatch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cu,
     return hipErrorInvalidValue;
 }
 
+// tiles are at most 32x32 (nf_device.h, NF_GRAD_TILE): the three geometries that hold them without scratch, widths 4 / 8 / 16
+template <int WIDTH>
+hipError_t dispatch_grad_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
+{
+    const int hw = a.H * a.W;
+    if (hw <= 64) return launch_grad<WIDTH, 64, 1, true>(prog, a, n_cu, lds, stream);
+    if (hw <= 256) return launch_grad<WIDTH, 256, 1, true>(prog, a, n_cu, lds, stream);
+    if (hw <= 1024) return launch_grad<WIDTH, 256, 4, true>(prog, a, n_cu, lds, stream);
+    return hipErrorInvalidValue;
+}
+
 }  // namespace
 
 // entry point used by nf_host.hip (which has checked the supported set: nf_grad_supported)
@@ -540,6 +616,22 @@ hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cp
     case 8: return dispatch_grad<8>(prog, a, n_cu, lds, stream);
     case 16: return dispatch_grad<16>(prog, a, n_cu, lds, stream);
     case 32: return dispatch_grad<32>(prog, a, n_cu, lds, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// one segment of a tiled call (NF_CFG_GRAD_TILED): `prog` = the segment's ops, a.H x a.W = the tile, a.B = images x tiles,
+// n_cpl = the couplings of the call's largest segment (what a.gate_words was sized by)
+hipError_t nf_launch_grad_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream)
+{
+    if (a.H > NF_GRAD_TILE || a.W > NF_GRAD_TILE || a.H > a.img_H || a.W > a.img_W || a.tile_ny < 1 || a.tile_nx < 1 || !a.z_in)
+        return hipErrorInvalidValue;
+    const size_t lds = sizeof(float) * nf_grad_lds_floats(a.H, a.W, prog.width, n_cpl);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    switch (prog.width) {
+    case 4: return dispatch_grad_tiled<4>(prog, a, n_cu, lds, stream);
+    case 8: return dispatch_grad_tiled<8>(prog, a, n_cu, lds, stream);
+    case 16: return dispatch_grad_tiled<16>(prog, a, n_cu, lds, stream);
     default: return hipErrorInvalidValue;
     }
 }

@@ -48,6 +48,7 @@ hipError_t nf_launch_tile_combine(const float *part, const NfTileParts &tp, int6
                                   float *nll_out, float *sd_out, float *ld_out, double *sums, hipStream_t stream);
 hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
+hipError_t nf_launch_grad_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 
 namespace {
 
@@ -872,13 +873,29 @@ struct Built {
 // chosen for the least estimated work, in units of one coupling on one tile: tiles of a segment x (its couplings + 0.75 for the
 // tile's load / store / set-up and the pointwise layers) + 1 per 4096 image pixels and segment boundary (32 B per pixel
 // through HBM) — fitted to tools/time_large_patches.py at 256^2 and 1024^2.  NF_TILE_SEGMENTS=<n> forces S (A/B and test aid).
-static int plan_tile_segments(const NfProgram &prog, int H, int W, int th, int tw, std::vector<Built::TileSeg> &segs)
+// The same planner cuts the program for the tiled gradient (NF_CFG_GRAD_TILED, nf_device.h "gradient tiles"): 32-pixel tiles, a
+// halo of 4 per coupling, NF_GRAD_TILE_SEGMENTS.  Its constants are fitted to tools/time_nll_grad.py --legs tiled
+// (profiles/nll_grad_tiled.txt: the shipped model at 256^2 x 16 and 1024^2 x 1, S = 8 / 4 / 3, six timings): least squares over
+// (tile-couplings, tiles, boundary pixels) gives 17.9 ns per tile-coupling, 31.0 ns per tile and -0.003 ns per boundary pixel —
+// no boundary cost these runs can resolve, so the term is 0 — and over the first two alone 18.5 ns and 29.1 ns (residuals within
+// 3.1 %): a tile costs its couplings + 1.57.  One coupling per segment wins on every image of more than a few tiles.
+struct SegRule {
+    const char *env;       // forces S
+    int tile;              // tile side the core must fit
+    int halo_per_cpl;
+    double per_tile;       // cost of a tile beside its couplings, in tile-couplings
+    double per_boundary_px;   // cost of one image pixel of a segment boundary, in tile-couplings
+    const char *what;
+};
+static const SegRule kFwdSegs = {"NF_TILE_SEGMENTS", 64, 2, 0.75, 1.0 / 4096.0, "patches beyond 64x64"};
+static const SegRule kGradSegs = {"NF_GRAD_TILE_SEGMENTS", NF_GRAD_TILE, 4, 1.57, 0.0, "nf_nll_grad on tiles"};
+static int plan_tile_segments(const NfProgram &prog, int H, int W, int th, int tw, std::vector<Built::TileSeg> &segs, const SegRule &rule = kFwdSegs)
 {
     std::vector<int> cpl;
     for (int i = 0; i < prog.n_ops; ++i)
         if (prog.ops[i].type == NF_OP_COUPLING_FWD || prog.ops[i].type == NF_OP_COUPLING_REV) cpl.push_back(i);
     const int n_cpl = (int)cpl.size();
-    const char *e = getenv("NF_TILE_SEGMENTS");
+    const char *e = getenv(rule.env);
     const int forced = e ? atoi(e) : 0;
     double best = 0.0;
     segs.clear();
@@ -895,13 +912,13 @@ static int plan_tile_segments(const NfProgram &prog, int H, int W, int th, int t
             Built::TileSeg t;
             t.op0 = op0;
             t.op1 = sgm == S - 1 ? prog.n_ops : cpl[c0 + nc - 1] + 1;
-            t.halo = 2 * nc;
-            if ((H > th || W > tw) && 64 - 2 * t.halo < 8) ok = false;   // no core left in a 64-pixel tile
+            t.halo = rule.halo_per_cpl * nc;
+            if ((H > th || W > tw) && rule.tile - 2 * t.halo < 8) ok = false;   // no core left in a tile
             if (!ok) break;
             t.ny = nf_tile_count(H, th, t.halo);
             t.nx = nf_tile_count(W, tw, t.halo);
-            cost += (double)t.ny * t.nx * (nc + 0.75);
-            if (sgm > 0) cost += (double)H * W / 4096.0;   // the tensor between two segments: ~ one tile-coupling per 4096 pixels
+            cost += (double)t.ny * t.nx * (nc + rule.per_tile);
+            if (sgm > 0) cost += (double)H * W * rule.per_boundary_px;   // the tensor between two segments (forward: one tile-coupling per 4096 pixels; x 2^-12 is exact)
             cand.push_back(t);
             c0 += nc;
             op0 = t.op1;
@@ -912,7 +929,7 @@ static int plan_tile_segments(const NfProgram &prog, int H, int W, int th, int t
             segs.swap(cand);
         }
     }
-    if (segs.empty()) return fail(NF_EINVAL, "patches beyond 64x64: %d coupling layers cannot be cut into at most %d tiled segments", n_cpl, NF_MAX_TILE_SEGS);
+    if (segs.empty()) return fail(NF_EINVAL, "%s: %d coupling layers cannot be cut into at most %d tiled segments", rule.what, n_cpl, NF_MAX_TILE_SEGS);
     return NF_OK;
 }
 
@@ -958,7 +975,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     out.tile_w = tw;
     out.segs.clear();
     if (cfg->n_layers < 1) return fail(NF_EINVAL, "n_layers must be >= 1");
-    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
+    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
     const double HW = (double)cfg->height * cfg->width;
 
     // intermediate list in NLL order
@@ -1224,11 +1241,15 @@ bool grad_force_scalar()
 
 // THE place that decides what nf_nll_grad supports and which kernel runs it (`path`: NF_GRAD_PATH_*): `fwd` = the NLL-direction
 // program of the model.
-int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr)
+// `tiles` (NF_GRAD_PATH_TILED only): the segments of the tiled route, gradient halos and the backward launches' tile counts.
+int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, std::vector<Built::TileSeg> *tiles = nullptr)
 {
     if (path) *path = NF_GRAD_PATH_SCALAR;
+    if (tiles) tiles->clear();
     if (cfg->flags & NF_CFG_FP16_CNN) return fail(NF_EINVAL, "nf_nll_grad: fp32 handles only (NF_CFG_FP16_CNN is set)");
-    if (cfg->height > 64 || cfg->width > 64)
+    const bool whole = cfg->height <= 64 && cfg->width <= 64;   // one workgroup's patch
+    const bool tile_flag = (cfg->flags & NF_CFG_GRAD_TILED) != 0;
+    if (!whole && !tile_flag)
         return fail(NF_EINVAL, "nf_nll_grad: patches of up to 64x64 (%dx%d given; no tiled evaluation)", cfg->height, cfg->width);
     const NfProgram &prog = fwd.lay[NF_PATH_SCALAR].prog;
     const int w = prog.width, hw = cfg->height * cfg->width;
@@ -1236,7 +1257,21 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr)
     int n_cpl = 0;
     for (int i = 0; i < prog.n_ops; ++i) n_cpl += prog.ops[i].type == NF_OP_COUPLING_FWD ? 1 : 0;
     const size_t lds = sizeof(float) * nf_grad_lds_floats(cfg->height, cfg->width, w, n_cpl);
-    const bool scalar_holds = !(hw > 1024 && w > 8) && lds <= 160 * 1024;
+    const bool scalar_holds = whole && !(hw > 1024 && w > 8) && lds <= 160 * 1024;
+    if (!whole && w == 32)
+        return fail(NF_EINVAL, "nf_nll_grad: coupling width %d has no tile mode (NF_CFG_GRAD_TILED covers padded widths 4, 8 and 16): patches of up "
+                               "to 64x64 as far as its whole-patch kernels hold them (%dx%d given)", fwd.raw_width, cfg->height, cfg->width);
+    if (tile_flag && w <= 16 && !scalar_holds) {
+        // The flag only adds: a shape the whole-patch kernel does not hold goes to the same kernel on 32-pixel tiles, one launch per
+        // segment (nf_device.h, "gradient tiles")
+        std::vector<Built::TileSeg> segs;
+        const int th = cfg->height < NF_GRAD_TILE ? cfg->height : NF_GRAD_TILE, tw = cfg->width < NF_GRAD_TILE ? cfg->width : NF_GRAD_TILE;
+        const int rc = plan_tile_segments(prog, cfg->height, cfg->width, th, tw, segs, kGradSegs);
+        if (rc != NF_OK) return rc;
+        if (path) *path = NF_GRAD_PATH_TILED;
+        if (tiles) tiles->swap(segs);
+        return NF_OK;
+    }
     if ((cfg->flags & NF_CFG_GRAD_MFMA) && w == 32) {
         // The flag only adds: the matrix-core kernel (nf_grad_wide.hip) takes every shape up to 32x32 — unless NF_GRAD=scalar asks for
         // the other arm where that one holds the shape — and a shape beyond it (16x48, 8x64) stays with the scalar kernel as far as
@@ -1451,6 +1486,8 @@ struct nf_handle {
     int grad_rc = NF_EINVAL;
     int grad_path = NF_GRAD_PATH_SCALAR;   // NF_GRAD_PATH_*: which kernel nf_nll_grad launches (grad_support)
     std::string grad_why;
+    std::vector<Built::TileSeg> grad_segs;   // NF_GRAD_PATH_TILED: the segments (gradient halo, tiles of the backward launches)
+    int grad_seg_cpl = 0;                    // ... and the couplings of the largest one (sizes the gate record)
     // scratch of the tiled calls (images beyond 64x64): the per-tile sums and the tensors between two segments.  A small set of
     // device buffers owned by the handle, one per call in flight; a call takes a free one (waiting, on ITS stream, for the work
     // that last used it), so nf_nll / nf_sample allocate only when a call needs more than any earlier one did, or when more
@@ -1620,8 +1657,9 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
         }
     {   // the gradient kernel's block, where nf_nll_grad supports the model (otherwise the call reports grad_why)
         const std::string keep = g_last_error;
-        h->grad_rc = grad_support(cfg, h->fwd, &h->grad_path);
+        h->grad_rc = grad_support(cfg, h->fwd, &h->grad_path, &h->grad_segs);
         h->grad_why = g_last_error;
+        for (const Built::TileSeg &g : h->grad_segs) h->grad_seg_cpl = std::max(h->grad_seg_cpl, g.halo / kGradSegs.halo_per_cpl);
         g_last_error = keep;
         if (h->grad_rc == NF_OK) {
             std::vector<float> gb;
@@ -1908,6 +1946,52 @@ static hipError_t launch_path(const nf_handle *h, int direction, int path, const
     }
 }
 
+// One tiled launch per segment of `segs` (ops [op0, op1) of the path's program, its halo and tile counts) on the direction's tiles:
+// segment s reads what segment s - 1 stored (the first one a.in) and stores to outs[s] (null: nowhere); with `part`, every launch
+// leaves its per-tile sums at part + tp.off[s].  a.B = images.  launch_tiled (nf_nll / nf_sample) and the forward half of a tiled
+// nf_nll_grad (grad_tiled) walk their segments through here.
+static hipError_t launch_segments(const nf_handle *h, int direction, const NfLaunch &a, const Built::TileSeg *segs, int n, const NfTileParts &tp,
+                                  float *part, float *const *outs, hipStream_t st)
+{
+    const Built &b = direction == 0 ? h->fwd : h->rev;
+    // kernel family: fp16-CNN mode and widths 8 / 16 / 32 on the width-32 matrix-core kernel (zero-padded), width 4 in fp32 on
+    // the fused width-4 kernels (select_path)
+    const int path = select_path(h, direction);
+    const NfProgram &full = b.lay[path].prog;
+    const float *cur = a.in;
+    hipError_t e = hipSuccess;
+    for (int s = 0; s < n && e == hipSuccess; ++s) {
+        const Built::TileSeg &g = segs[s];
+        NfProgram sp;
+        memset(&sp, 0, sizeof(sp));
+        sp.width = full.width;
+        sp.n_ops = g.op1 - g.op0;
+        memcpy(sp.ops, full.ops + g.op0, sizeof(NfOp) * (size_t)sp.n_ops);
+        NfLaunch t = a;
+        t.B = a.B * tp.nt[s];
+        t.H = b.tile_h;
+        t.W = b.tile_w;
+        t.img_H = h->cfg.height;
+        t.img_W = h->cfg.width;
+        t.tile_ny = g.ny;
+        t.tile_nx = g.nx;
+        t.tile_halo = g.halo;
+        t.flags |= NF_K_TILED;
+        if (s > 0) {   // only the first segment draws / scales the input
+            t.flags &= ~(uint32_t)NF_K_PHILOX_IN;
+            t.in_scale = 1.0f;
+        }
+        t.in = cur;
+        t.out = outs[s];
+        t.nll_out = t.sd_out = t.ld_out = nullptr;
+        t.sums = nullptr;
+        t.tile_part = part ? part + tp.off[s] * 4 : nullptr;
+        e = launch_path(h, direction, path, sp, t, st);
+        cur = t.out;
+    }
+    return e;
+}
+
 // Images beyond 64x64 (nf_device.h, "overlapping tiles"): per segment of the program one launch of the fused width-4 kernel
 // (or, at widths 8 / 16 / 32 and in fp16-CNN mode, of the width-32 matrix-core kernel) over B x tiles tile-sized "patches" that reads and writes image-shaped tensors in place (the caller's, and between two
 // segments a scratch tensor), then — in the NLL direction — a one-wavefront-per-image kernel that adds the tiles' sums up.  Scratch
@@ -1942,40 +2026,9 @@ static int launch_tiled(nf_handle *h, int direction, NfLaunch &a, hipStream_t st
         }
         for (int i = 0; i < 2 && i < S - 1; ++i, q += img_bytes) scratch[i] = reinterpret_cast<float *>(q);
     }
-    // kernel family: fp16-CNN mode and widths 8 / 16 / 32 on the width-32 matrix-core kernel (zero-padded), width 4 in fp32 on
-    // the fused width-4 kernels (select_path)
-    const int path = select_path(h, direction);
-    const NfProgram &full = b.lay[path].prog;
-    const float *cur = a.in;
-    for (int s = 0; s < S && e == hipSuccess; ++s) {
-        const Built::TileSeg &g = b.segs[s];
-        NfProgram sp;
-        memset(&sp, 0, sizeof(sp));
-        sp.width = full.width;
-        sp.n_ops = g.op1 - g.op0;
-        memcpy(sp.ops, full.ops + g.op0, sizeof(NfOp) * (size_t)sp.n_ops);
-        NfLaunch t = a;
-        t.B = B * tp.nt[s];
-        t.H = b.tile_h;
-        t.W = b.tile_w;
-        t.img_H = h->cfg.height;
-        t.img_W = h->cfg.width;
-        t.tile_ny = g.ny;
-        t.tile_nx = g.nx;
-        t.tile_halo = g.halo;
-        t.flags |= NF_K_TILED;
-        if (s > 0) {   // only the first segment draws / scales the input
-            t.flags &= ~(uint32_t)NF_K_PHILOX_IN;
-            t.in_scale = 1.0f;
-        }
-        t.in = cur;
-        t.out = s == S - 1 ? a.out : scratch[s & 1];
-        t.nll_out = t.sd_out = t.ld_out = nullptr;
-        t.sums = nullptr;
-        t.tile_part = want ? part + tp.off[s] * 4 : nullptr;
-        e = launch_path(h, direction, path, sp, t, st);
-        cur = t.out;
-    }
+    float *outs[NF_MAX_TILE_SEGS];
+    for (int s = 0; s < S; ++s) outs[s] = s == S - 1 ? a.out : scratch[s & 1];
+    e = launch_segments(h, direction, a, b.segs.data(), S, tp, want ? part : nullptr, outs, st);
     if (e == hipSuccess && want)
         e = nf_launch_tile_combine(part, tp, B, (double)h->cfg.height * h->cfg.width * kC, a.ld_const, a.cond_rows, a.flags, a.nll_out, a.sd_out,
                                    a.ld_out, a.sums, st);
@@ -1996,16 +2049,18 @@ static int launch_resident(nf_handle *h, int direction, NfLaunch &a, hipStream_t
     return NF_OK;
 }
 
+static size_t grad_workspace_bytes(const nf_handle *h, int64_t B);
+
 int64_t nf_workspace_bytes(const nf_handle *h, int32_t direction, int64_t B)
 {
-    if (!h || (direction != 0 && direction != 1) || B < 0) return fail(NF_EINVAL, "bad argument");
+    if (!h || direction < 0 || direction > 2 || B < 0) return fail(NF_EINVAL, "bad argument");
+    if (direction == 2) return (int64_t)grad_workspace_bytes(h, B);   // one tiled nf_nll_grad call
     return (int64_t)tiled_workspace_bytes(h, direction, B, direction == 0);
 }
 
-int nf_reserve_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight)
+// `calls_in_flight` buffers of `need` bytes in the handle's workspace set
+static int reserve_workspace(nf_handle *h, size_t need, int calls_in_flight)
 {
-    if (!h || B < 0 || calls_in_flight < 1 || calls_in_flight > 64) return fail(NF_EINVAL, "bad argument");
-    const size_t need = std::max(tiled_workspace_bytes(h, 0, B, true), tiled_workspace_bytes(h, 1, B, false));
     if (need == 0) return NF_OK;
     DeviceGuard guard;
     int rc = guard.enter(h->device);
@@ -2018,6 +2073,12 @@ int nf_reserve_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight)
     }
     for (nf_handle::Workspace *w : got) ws_release(h, w, nullptr, false);
     return rc;
+}
+
+int nf_reserve_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight)
+{
+    if (!h || B < 0 || calls_in_flight < 1 || calls_in_flight > 64) return fail(NF_EINVAL, "bad argument");
+    return reserve_workspace(h, std::max(tiled_workspace_bytes(h, 0, B, true), tiled_workspace_bytes(h, 1, B, false)), calls_in_flight);
 }
 
 int nf_kernel_path(const nf_handle *h, int32_t direction)
@@ -2166,6 +2227,153 @@ int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float 
     return export_layout(l, ops_out, ops_cap, n_ops, folded, folded_cap, n_folded);
 }
 
+// ---- nf_nll_grad on tiles (NF_CFG_GRAD_TILED; nf_device.h, "gradient tiles") ----
+// The forward launch of segment s runs on the forward direction's own tiles (tile_h x tile_w, halo 2 per coupling)
+static Built::TileSeg grad_fwd_seg(const nf_handle *h, int s)
+{
+    Built::TileSeg g = h->grad_segs[s];
+    g.halo = g.halo / kGradSegs.halo_per_cpl * kFwdSegs.halo_per_cpl;
+    g.ny = nf_tile_count(h->cfg.height, h->fwd.tile_h, g.halo);
+    g.nx = nf_tile_count(h->cfg.width, h->fwd.tile_w, g.halo);
+    return g;
+}
+
+static size_t grad_img_bytes(const nf_handle *h, int64_t B) { return (((size_t)B * h->cfg.height * h->cfg.width * kC * sizeof(float)) + 255) & ~(size_t)255; }
+
+// scratch of one call: the forward launches' tile sums, the S - 1 tensors between two segments, two gradient tensors (ping-pong)
+static size_t grad_workspace_bytes(const nf_handle *h, int64_t B)
+{
+    if (h->grad_rc != NF_OK || h->grad_path != NF_GRAD_PATH_TILED || B <= 0) return 0;
+    const int S = (int)h->grad_segs.size();
+    size_t part4 = 0;
+    for (int s = 0; s < S; ++s) {
+        const Built::TileSeg f = grad_fwd_seg(h, s);
+        part4 += (size_t)B * f.ny * f.nx;
+    }
+    return ((part4 * 4 * sizeof(float) + 255) & ~(size_t)255) + grad_img_bytes(h, B) * (size_t)(S - 1 + (S - 1 < 2 ? S - 1 : 2));
+}
+
+// Forward: the tiled launches of nf_nll cut at the gradient plan's boundaries, every tensor between two segments kept, and
+// nf_tile_combine for nll_out.  Backward: one launch of nf_grad_kernel<.., TILED> per segment, last to first; segment s reads the
+// tensor in front of it and the gradient segment s + 1 stored, and stores core windows — to gx_out (s = 0) or to the other of two
+// scratch tensors.  gy_out: the first launch (in this order) whose segment has an SDN-kind op stores it, later ones add to it.
+// Everything is enqueued on `st`.
+static int grad_tiled(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond_row &r, const nf_cond_row *rows, float *nll_out,
+                      float *gx_out, float *gy_out, hipStream_t st)
+{
+    const int S = (int)h->grad_segs.size(), H = h->cfg.height, W = h->cfg.width;
+    NfTileParts tp;
+    memset(&tp, 0, sizeof(tp));
+    tp.n_seg = S;
+    Built::TileSeg fseg[NF_MAX_TILE_SEGS];
+    int64_t part4 = 0;
+    for (int s = 0; s < S; ++s) {
+        fseg[s] = grad_fwd_seg(h, s);
+        tp.nt[s] = fseg[s].ny * fseg[s].nx;
+        tp.off[s] = part4;
+        const int64_t most = std::max<int64_t>(tp.nt[s], (int64_t)h->grad_segs[s].ny * h->grad_segs[s].nx);
+        if (B > (INT64_MAX / 64) / most) return fail(NF_EINVAL, "B too large");
+        part4 += B * tp.nt[s];
+    }
+    nf_handle::Workspace *wsp = nullptr;
+    const int rc = ws_acquire(h, grad_workspace_bytes(h, B), st, &wsp);
+    if (rc != NF_OK) return rc;
+    const size_t img_bytes = grad_img_bytes(h, B);
+    char *q = wsp->p;
+    float *const part = reinterpret_cast<float *>(q);
+    q += ((size_t)part4 * 4 * sizeof(float) + 255) & ~(size_t)255;
+    float *inter[NF_MAX_TILE_SEGS] = {}, *gbuf[2] = {nullptr, nullptr};
+    for (int s = 0; s < S - 1; ++s, q += img_bytes) inter[s] = reinterpret_cast<float *>(q);
+    for (int i = 0; i < 2 && i < S - 1; ++i, q += img_bytes) gbuf[i] = reinterpret_cast<float *>(q);
+
+    hipError_t e = hipSuccess;
+    const int n_fwd = nll_out ? S : S - 1;   // the last segment's forward launch only leaves its tile sums
+    if (n_fwd > 0) {
+        NfLaunch a;
+        memset(&a, 0, sizeof(a));
+        a.in = x;
+        a.y = y;
+        a.B = B;
+        a.in_scale = 1.0f;
+        memcpy(a.cond_a, r.a, sizeof(r.a));
+        memcpy(a.cond_b, r.b, sizeof(r.b));
+        a.cond_rows = rows;
+        a.flags = NF_K_PRIOR;
+        e = launch_segments(h, 0, a, fseg, n_fwd, tp, nll_out ? part : nullptr, inter, st);   // inter[S - 1] is null: the last one stores nothing
+        if (e == hipSuccess && nll_out)
+            e = nf_launch_tile_combine(part, tp, B, (double)H * W * kC, r.ld + h->fwd.ld_const, rows, NF_K_PRIOR, nll_out, nullptr, nullptr, nullptr, st);
+    }
+    if (e == hipSuccess && (gx_out || gy_out)) {
+        NfGradLaunch a;
+        memset(&a, 0, sizeof(a));
+        a.params = h->d_grad;
+        a.y = y;
+        memcpy(a.cond_a, r.a, sizeof(r.a));
+        memcpy(a.cond_b, r.b, sizeof(r.b));
+        a.cond_rows = rows;
+        a.H = H < NF_GRAD_TILE ? H : NF_GRAD_TILE;
+        a.W = W < NF_GRAD_TILE ? W : NF_GRAD_TILE;
+        a.img_H = H;
+        a.img_W = W;
+        a.gate_words = nf_grad_gate_words(h->grad_seg_cpl, h->gprog.width);
+        bool gy_written = false;
+        for (int s = S - 1; s >= 0 && e == hipSuccess; --s) {
+            const Built::TileSeg &g = h->grad_segs[s];
+            NfProgram sp;
+            memset(&sp, 0, sizeof(sp));
+            sp.width = h->gprog.width;
+            sp.n_ops = g.op1 - g.op0;
+            memcpy(sp.ops, h->gprog.ops + g.op0, sizeof(NfOp) * (size_t)sp.n_ops);
+            NfGradLaunch t = a;
+            t.first_cpl = sp.n_ops;
+            bool sdn = false;
+            for (int i = sp.n_ops - 1; i >= 0; --i) {
+                if (sp.ops[i].type == NF_OP_COUPLING_FWD) t.first_cpl = i;
+                sdn = sdn || sp.ops[i].type == NF_OP_SDN_DIV;
+            }
+            t.B = B * g.ny * g.nx;
+            t.tile_ny = g.ny;
+            t.tile_nx = g.nx;
+            t.tile_halo = g.halo;
+            t.z_in = s == 0 ? x : inter[s - 1];
+            t.g_in = s == S - 1 ? nullptr : gbuf[(S - 2 - s) & 1];
+            t.g_out = s == 0 ? gx_out : gbuf[(S - 1 - s) & 1];
+            // a model without an SDN-kind op: the first segment stores the zeros
+            const bool wr = gy_out && (sdn || (s == 0 && !gy_written));
+            t.gy_out = wr ? gy_out : nullptr;
+            t.tflags = wr && gy_written ? NF_GT_GY_ACC : 0u;
+            gy_written = gy_written || wr;
+            e = nf_launch_grad_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st);
+        }
+    }
+    ws_release(h, wsp, st);
+    if (e != hipSuccess) return fail_hip(e, "nf_nll_grad launch (tiles)");
+    return NF_OK;
+}
+
+int nf_grad_tile_segments(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params, int32_t *out5, int32_t cap)
+{
+    Built b;
+    int rc = build_program(cfg, layers, params, n_params, 0, b);
+    if (rc != NF_OK) return rc;
+    int path = NF_GRAD_PATH_SCALAR;
+    std::vector<Built::TileSeg> segs;
+    if ((rc = grad_support(cfg, b, &path, &segs)) != NF_OK) return rc;
+    if (path != NF_GRAD_PATH_TILED) return 0;
+    for (int i = 0; i < (int)segs.size() && i < cap && out5; ++i) {
+        const Built::TileSeg &g = segs[i];
+        const int32_t v[5] = {g.op0, g.op1, g.halo, g.ny, g.nx};
+        memcpy(out5 + 5 * i, v, sizeof(v));
+    }
+    return (int)segs.size();
+}
+
+int nf_reserve_grad_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight)
+{
+    if (!h || B < 0 || calls_in_flight < 1 || calls_in_flight > 64) return fail(NF_EINVAL, "bad argument");
+    return reserve_workspace(h, grad_workspace_bytes(h, B), calls_in_flight);
+}
+
 int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond, const nf_cond_row *rows, float *nll_out,
                 float *gx_out, float *gy_out, void *stream)
 {
@@ -2188,6 +2396,12 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
         if (rc != NF_OK) return rc;
     }
     if (B == 0) return NF_OK;
+    if (h->grad_path == NF_GRAD_PATH_TILED) {
+        DeviceGuard guard;
+        int rc = guard.enter(h->device);
+        if (rc != NF_OK) return rc;
+        return grad_tiled(h, x, y, B, r, rows, nll_out, gx_out, gy_out, (hipStream_t)stream);
+    }
     NfGradLaunch a;
     memset(&a, 0, sizeof(a));
     a.params = h->d_grad;

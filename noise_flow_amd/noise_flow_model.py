@@ -184,7 +184,8 @@ class FlowHandle:
 
     def __init__(self, arch, variables: Dict[str, np.ndarray], x_shape, width: int,
                  binding: str = "loss_first", device: Optional[int] = None, layers=None, tmpl=None,
-                 cnn_dtype: str = "fp32", flow_permutation: int = 1, decomp: str = "LU", grad_kernel: str = "scalar"):
+                 cnn_dtype: str = "fp32", flow_permutation: int = 1, decomp: str = "LU", grad_kernel: str = "scalar",
+                 grad_tiles: bool = False):
         self.lib = _lib.load()
         if layers is None:
             self.layers, descs, flat = _params.pack(arch, variables, width, binding, flow_permutation, decomp)
@@ -200,6 +201,7 @@ class FlowHandle:
             raise ValueError("grad_kernel='mfma' needs an fp32 handle (cnn_dtype='fp16' has no gradient kernel)")
         flags = {"fp32": 0, "fp16": _lib.NF_CFG_FP16_CNN, "fp32_exact": _lib.NF_CFG_EXACT_FP32}[cnn_dtype]
         flags |= _lib.NF_CFG_GRAD_MFMA if grad_kernel == "mfma" else 0
+        flags |= _lib.NF_CFG_GRAD_TILED if grad_tiles else 0
         cfg = _lib.nf_config(H, W, Cc, len(self.layers), -1 if device is None else int(device), flags)
         self._model_args = (cfg, descs, flat)   # what nf_cond_rows takes (kept alive with the handle)
         h = C.c_void_p()
@@ -262,11 +264,14 @@ class NoiseFlow(object):
     grad_kernel : 'scalar' (default) | 'mfma' — which kernel ``nll_and_grad`` / ``nll_torch`` run at coupling widths 17 .. 32:
           'mfma' is the matrix-core gradient kernel (patches up to 32x32, ``NF_CFG_GRAD_MFMA``); no effect on narrower models.
           Also selectable as ``hps.grad_kernel``; not with cnn_dtype='fp16'.
+    grad_tiles : ``True`` lets ``nll_and_grad`` / ``nll_torch`` take every H, W up to 4096 at coupling widths up to 16: a shape
+          the whole-patch gradient kernel does not hold is evaluated as overlapping 32-pixel tiles (``NF_CFG_GRAD_TILED``); a
+          shape it holds is untouched.  Default ``False``; also selectable as ``hps.grad_tiles``.
     binding : 'loss_first' | 'sample_first' — template→layer binding (quirk Q1).
     """
 
     def __init__(self, x_shape, is_training=False, hps=None, variables=None, binding="loss_first", device=None,
-                 cnn_dtype=None, grad_kernel=None):
+                 cnn_dtype=None, grad_kernel=None, grad_tiles=None):
         if hps is None:
             raise ValueError("hps is required (arch, width, ...)")
         self.x_shape = [int(v) for v in x_shape]
@@ -297,9 +302,10 @@ class NoiseFlow(object):
         # (BASELINE configs[4]); also selectable as hps.cnn_dtype.  Default: all fp32.
         self.cnn_dtype = cnn_dtype or str(getattr(hps, "cnn_dtype", "fp32"))
         self.grad_kernel = grad_kernel or str(getattr(hps, "grad_kernel", "scalar"))
+        self.grad_tiles = bool(getattr(hps, "grad_tiles", False) if grad_tiles is None else grad_tiles)
         self._flow = FlowHandle(self.arch, self._variables, self.x_shape, self.width, binding, self._dev.device.index,
                                 cnn_dtype=self.cnn_dtype, flow_permutation=self.flow_permutation, decomp=self.decomp,
-                                grad_kernel=self.grad_kernel)
+                                grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles)
 
     # ------------------------------------------------------------------ variables
     @property
@@ -317,7 +323,7 @@ class NoiseFlow(object):
         old = self._flow
         self._flow = FlowHandle(self.arch, self._variables, self.x_shape, self.width, self.binding,
                                 self._dev.device.index, cnn_dtype=self.cnn_dtype, flow_permutation=self.flow_permutation,
-                                decomp=self.decomp, grad_kernel=self.grad_kernel)
+                                decomp=self.decomp, grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles)
         old.close()
         if getattr(self, "_sync", None) is not None:
             self._install_sync()

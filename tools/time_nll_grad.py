@@ -1,7 +1,7 @@
 """nf_nll_grad next to nf_nll: the shipped model at 32x32 and 64x64, and the paper-scale model (width 32, 8 couplings) on the
 matrix-core gradient kernel, B = 1 024, same box, same process.
 
-    python tools/time_nll_grad.py [--launches 200] [--legs shipped,wide] [--out FILE.json]
+    python tools/time_nll_grad.py [--launches 200] [--legs shipped,wide,tiled] [--out FILE.json]
 
 Every figure is the mean over a window of `--launches` (at least 200) back-to-back launches between two device events, after
 a warm-up of a quarter of that; three windows per entry, their median is reported.  The yardstick is nf_nll (the forward
@@ -14,6 +14,13 @@ Legs `wide` (the full architecture at width 32; variables: paper_like_variables 
       difference of the medians exceeds twice the larger spread.
       `--ab-sides 8,16,24` adds other shapes both kernels hold.
   32x32: the matrix-core gradient kernel next to nf_nll of the same model (NF_PATH_WIDE32), as for the shipped model.
+
+Leg `tiled` (not in the default set): whole images through the tiled gradient (grad_tiles=True, NF_CFG_GRAD_TILED), the shipped
+model at 256x256 x 16 and 1024x1024 x 1.  One handle per segment count S = 8 / 4 / 3 (NF_GRAD_TILE_SEGMENTS, read at nf_create),
+the arms alternated `--reps` times in one process, same window protocol; per arm the median and spread of its repetitions,
+pixels/s, and the ratio to nf_nll of the same images (median of as many repetitions).  Beside every arm the terms of the
+planner's cost model (csrc/nf_host.hip, plan_tile_segments): sum over segments of tiles x couplings, of tiles, and the segment
+boundaries x image pixels — what the planner's constants are fitted to.
 """
 import argparse
 import ctypes as C
@@ -79,6 +86,8 @@ def main():
               % (side, side, t_nll, r["nll_patches_per_s"], t_grad, r["grad_patches_per_s"], r["grad_over_nll"]), flush=True)
     if "wide" in legs:
         res["wide32"] = wide_legs(a, timed, B)
+    if "tiled" in legs:
+        res["tiled"] = tiled_legs(a, timed, v)
     print("RESULT " + json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -173,6 +182,62 @@ def wide_legs(a, timed, B):
                     "grad_over_nll": t_grad / t_nll}
     print("width 32, 32x32  nf_nll %.4f ms (%.3e patches/s)   nf_nll_grad (matrix-core) %.4f ms (%.3e patches/s)   ratio %.2f"
           % (t_nll, B / t_nll * 1e3, t_grad, B / t_grad * 1e3, t_grad / t_nll), flush=True)
+    return out
+
+
+def tiled_legs(a, timed, v):
+    import numpy as np
+    import torch
+    from noise_flow_amd import NoiseFlow, _lib, default_hps
+    cond = _lib.nf_cond(100.0, 2.0, 0.0, 0.0)
+    med = lambda t: float(np.median(t))   # noqa: E731
+    out = {}
+    for side, B in ((256, 16), (1024, 1)):
+        rng = np.random.RandomState(0)
+        y = torch.as_tensor(rng.rand(B, side, side, 4).astype(np.float32)).cuda()
+        x = torch.as_tensor((rng.randn(B, side, side, 4) * 0.02).astype(np.float32)).cuda()
+        nll, sd, ld = (torch.empty((B,), device="cuda") for _ in range(3))
+        gx, gy = torch.empty_like(x), torch.empty_like(y)
+        arms = {}
+        for S in (8, 4, 3):
+            os.environ["NF_GRAD_TILE_SEGMENTS"] = str(S)
+            m = NoiseFlow([side, side, 4], False, default_hps(), variables=v, device=0, grad_tiles=True)
+            os.environ.pop("NF_GRAD_TILE_SEGMENTS")
+            lib, h, st = m._flow.lib, m._flow.ptr, m._dev.stream_ptr()
+            assert lib.nf_grad_path(h) == _lib.NF_GRAD_PATH_TILED
+            _lib.check(lib.nf_reserve_grad_workspace(h, B, 1))
+            cfg, descs, flat = m._flow._model_args
+            seg = (C.c_int32 * 80)()
+            os.environ["NF_GRAD_TILE_SEGMENTS"] = str(S)
+            n = lib.nf_grad_tile_segments(C.byref(cfg), descs, flat.ctypes.data_as(C.POINTER(C.c_float)), flat.size, seg, 16)
+            os.environ.pop("NF_GRAD_TILE_SEGMENTS")
+            assert n == S
+            rows = [tuple(seg[5 * i:5 * i + 5]) for i in range(n)]
+            plan = {"segments": n, "tile_couplings": sum(r[3] * r[4] * (r[2] // 4) for r in rows), "tiles": sum(r[3] * r[4] for r in rows),
+                    "boundary_pixels": (n - 1) * side * side}
+            grad = (lambda lib=lib, h=h, st=st: _lib.check(lib.nf_nll_grad(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), None, nll.data_ptr(),
+                                                                          gx.data_ptr(), gy.data_ptr(), st)))
+            fwd = (lambda lib=lib, h=h, st=st: _lib.check(lib.nf_nll(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), nll.data_ptr(), sd.data_ptr(),
+                                                                    ld.data_ptr(), None, None, 0, st)))
+            arms[S] = {"model": m, "grad": grad, "fwd": fwd, "plan": plan, "ms": []}
+        t_nll = []
+        for rep in range(a.reps):
+            t_nll.append(timed(arms[8]["fwd"]))
+            for S in (8, 4, 3):
+                arms[S]["ms"].append(timed(arms[S]["grad"]))
+            print("%dx%d x %d rep %d  nf_nll %.4f ms   nf_nll_grad S=8 %.4f  S=4 %.4f  S=3 %.4f ms"
+                  % (side, side, B, rep, t_nll[-1], arms[8]["ms"][-1], arms[4]["ms"][-1], arms[3]["ms"][-1]), flush=True)
+        px = float(B) * side * side
+        r = {"B": B, "nll_ms": t_nll, "nll_median_ms": med(t_nll), "nll_pixels_per_s": px / med(t_nll) * 1e3, "arms": {}}
+        for S in (8, 4, 3):
+            t = arms[S]["ms"]
+            r["arms"]["S=%d" % S] = dict(arms[S]["plan"], ms=t, median_ms=med(t), spread_ms=max(t) - min(t), pixels_per_s=px / med(t) * 1e3,
+                                        grad_over_nll=med(t) / med(t_nll))
+            print("%dx%d x %d  S=%d  %.4f ms (spread %.4f)  %.3e pixels/s  grad / nll %.2f   tile-couplings %d  tiles %d  boundary pixels %d"
+                  % (side, side, B, S, med(t), max(t) - min(t), px / med(t) * 1e3, med(t) / med(t_nll), arms[S]["plan"]["tile_couplings"],
+                     arms[S]["plan"]["tiles"], arms[S]["plan"]["boundary_pixels"]), flush=True)
+        out["%dx%d" % (side, side)] = r
+        del arms
     return out
 
 
