@@ -385,7 +385,7 @@ struct NfLaunch {
     // matrix-core kernels (filled by nf_launch_flow from the program, not by callers): the first run of `mix, coupling` pairs whose
     // parameter blocks sit a constant stride apart — walked as a counted loop without scalar loads — and the number of couplings
     int32_t run_first, run_n, run_moff, run_coff, run_stride, run_type, n_cpl;
-    int32_t fair_t1, fair_t2, fair_t3;   // progress-based wave priority (NF_FAIR): the smallest coupling count c with 4 c / n_cpl >= 1, 2, 3
+    int32_t fair_t1, fair_t2, fair_t3;   // progress-based wave priority: the smallest coupling count c with 4 c / n_cpl >= 1, 2, 3
     // split-bf16 kernel: the A image of pair i of that run starts run_aoff + i * run_astride floats into the block (what the pairs'
     // NF12_CPL_AOFF fields say, verified on the host: a run whose fields are no such progression is not described at all, and its
     // pairs then go through the loop one by one with the field read at its door); params_floats = the whole block, A images included

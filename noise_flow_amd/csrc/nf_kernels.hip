@@ -18,7 +18,6 @@
 // Gaussian prior noise_flow_model.py:486-541.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 #include <atomic>
 #include "../../include/noiseflow_hip.h"   // NF_SUMS_SLOTS / NF_SUMS_STRIDE
@@ -26,44 +25,9 @@
 #include "nf_dev_util.h"
 #include "nf_flow_common.h"   // flow_launch: the persistent-grid launcher
 
-// s_setprio level of a wave while it streams MFMAs (0 = off): keeps bursts of matrix
-// instructions contiguous on a SIMD that other waves share (+5 % at 512-thread geometry)
-#ifndef NF_PRIO
-#define NF_PRIO 2
-#endif
-// NF_FAIR: progress-based wave priority.  A SIMD arbitrates its resident waves oldest-first, so of the 4 workgroups
-// that share a CU the oldest runs ahead and the youngest starves: at B = 1024 (one patch per workgroup) workgroup
-// lifetimes spread 37..57 us around a 48 us mean and the launch lasts as long as the slowest one (tools/timeline.py).
-// Lowering a wave's priority as it advances through the couplings (3,3,2,2,1,1,0,0) is a negative feedback that keeps
-// co-resident workgroups level.  0 = off (MFMA bursts at NF_PRIO, the round-1 behaviour).
-#ifndef NF_BR_SWIZZLE
-#define NF_BR_SWIZZLE 1
-#endif
-#ifndef NF_WAVE_PRIO
-#define NF_WAVE_PRIO 1
-#endif
-#ifndef NF_FAIR
-#define NF_FAIR 1
-#endif
-#if NF_FAIR
-#define NF_PRIO_UP()   do { } while (0)
-#define NF_PRIO_DOWN() do { } while (0)
-#else
-#define NF_PRIO_UP()   do { if (NF_PRIO) __builtin_amdgcn_s_setprio(NF_PRIO); } while (0)
-#define NF_PRIO_DOWN() do { if (NF_PRIO) __builtin_amdgcn_s_setprio(0); } while (0)
-#endif
-// occupancy target (waves per SIMD) the register allocator must honour, per geometry
-#ifndef NF_WPE_512
-#define NF_WPE_512 5
-#endif
-#ifndef NF_WPE_256
-#define NF_WPE_256 3
-#endif
-// warm-up touches before the LDS set-up: every NF_WARM_STEP-th owned pixel (2x2-blocked lanes: 2 = one per image row)
-#ifndef NF_WARM_STEP
-#define NF_WARM_STEP 2
-#endif
-#define NF_MIN_WAVES(T, P, M) (((T) == 512 && (P) == 2 && (M)) ? NF_WPE_512 : ((T) == 256 && (P) == 4 && (M)) ? NF_WPE_256 : 1)
+// occupancy target (waves per SIMD) the register allocator must honour: 3 for the 256 x 4 matrix-core geometry, else 1
+constexpr int NF_WPE_256x4 = 3;
+#define NF_MIN_WAVES(T, P, M) (((T) == 256 && (P) == 4 && (M)) ? NF_WPE_256x4 : 1)
 
 // Instrumented build (-DNF_TIMELINE, tools/timeline.py only): thread 0 of every workgroup stamps the 100 MHz
 // s_memrealtime counter at the phase boundaries of its MIDDLE patch (the first one when it has one) into NfLaunch::sd_out, reinterpreted as
@@ -75,6 +39,54 @@
 #endif
 
 namespace {
+
+// The dynamic LDS of the fused flow kernel: the size of every section, in floats, in ONE place.  The kernel steps its pointers by
+// these sizes and the launcher asks for their sum, so the two cannot drift apart.
+//   tiles   z0 / h2 exchange tiles, zero-bordered: TILE_WORDS 32-bit words per pixel, (H + 2) rows of `pitch` pixels
+//   red     reduction scratch [2][3][THREADS/64] (+ pad), alternating by patch
+//   model   matrix-core kernels: the whole folded model, j-major, rounded up to 16 bytes (`ident` floats), and a 4x4 identity
+//           behind it: the `mix` of a coupling that has none in front, so that the pair loop has ONE shape
+//   bs      batch-statistics kernel: [THREADS/64][8] per-wavefront partials, then 8 doubles (scale[4], mean[4]) of the re-fold
+// Order (the kernel's): tiles | red | model | bs.  PREC 2 / 3 (WFIRST): the model image FIRST — every weight read of a coupling
+// is then `coupling base + lane term` plus an immediate below 64 KiB (behind 63 KiB of tiles the A3 / A2 operands were not, and
+// cost a v_add_u32 each), while the tile accesses keep their compile-time immediates relative to lane addresses that carry the
+// (run-time) tile base.
+template <int WIDTH, int THREADS, int PREC, bool MFMA, bool BS>
+struct NfFlowLds {
+    static constexpr bool WFIRST = PREC == 2 || PREC == 3;
+    static constexpr int TILE_WORDS = PREC == 3 ? 6 : PREC != 0 ? 3 : 2 + WIDTH;   // 32-bit words per tile pixel
+    static constexpr int RED_WORDS = (6 * (THREADS / 64) + 3) & ~3;
+    static constexpr int IDENT_WORDS = 16;
+    static constexpr int BS_WORDS = (THREADS / 64) * 8 + 16;
+    // row pitch of the plain row-major tiles, in pixels; fp16 4x4x4 mode at 32x32: 48, so that the next block row (2 tile rows down)
+    // starts a multiple of 128 B (half2) / 256 B (4 x half) away
+    __host__ __device__ static constexpr int pitch(int H, int W) { return PREC == 3 ? NF12_PITCH : PREC == 2 ? nf11_pitch(H) : (PREC == 1 && H == 32) ? 48 : W + 2; }
+    __host__ __device__ static constexpr int tile_px(int H, int W) { return ((H + 2) * pitch(H, W) + 1) & ~1; }   // even -> 16-byte aligned sections
+    __host__ __device__ static constexpr int ident(int n_params) { return (n_params + 3) & ~3; }   // the identity block, in floats from `model`
+    __host__ __device__ static constexpr int total(int H, int W, int n_params)
+    {
+        return TILE_WORDS * tile_px(H, W) + RED_WORDS + (MFMA ? ident(n_params) + IDENT_WORDS : 0) + (BS ? BS_WORDS : 0);
+    }
+};
+// Nothing moved when the launcher's own formula became this record: its former totals, for every (PREC, THREADS, side) with a
+// full-geometry instantiation, two masked shapes and the batch-statistics variant, at two model sizes
+template <int WIDTH, int THREADS, int PREC, bool MFMA, bool BS = false>
+constexpr bool nf_lds_is(int H, int W, int n_params, int total)
+{
+    return NfFlowLds<WIDTH, THREADS, PREC, MFMA, BS>::total(H, W, n_params) == total;
+}
+static_assert(nf_lds_is<4, 256, 0, true>(32, 32, 1480, 8456));   static_assert(nf_lds_is<4, 256, 0, true>(32, 32, 1483, 8460));
+static_assert(nf_lds_is<4, 1024, 0, true>(64, 64, 1480, 27728));   static_assert(nf_lds_is<4, 1024, 0, true>(64, 64, 1483, 27732));
+static_assert(nf_lds_is<4, 256, 1, true>(32, 32, 1480, 6416));   static_assert(nf_lds_is<4, 256, 1, true>(32, 32, 1483, 6420));
+static_assert(nf_lds_is<4, 1024, 1, true>(64, 64, 1480, 14660));   static_assert(nf_lds_is<4, 1024, 1, true>(64, 64, 1483, 14664));
+static_assert(nf_lds_is<4, 256, 2, true>(32, 32, 1480, 6416));   static_assert(nf_lds_is<4, 256, 2, true>(32, 32, 1483, 6420));
+static_assert(nf_lds_is<4, 1024, 2, true>(64, 64, 1480, 17432));   static_assert(nf_lds_is<4, 1024, 2, true>(64, 64, 1483, 17436));
+static_assert(nf_lds_is<4, 256, 3, true>(32, 32, 1480, 8456));   static_assert(nf_lds_is<4, 256, 3, true>(32, 32, 1483, 8460));
+static_assert(nf_lds_is<4, 256, 0, false>(32, 32, 1480, 6960));   static_assert(nf_lds_is<4, 256, 0, false>(32, 32, 1483, 6960));
+static_assert(nf_lds_is<4, 64, 0, true>(1, 1, 1480, 1564));   static_assert(nf_lds_is<4, 64, 0, true>(1, 1, 1483, 1568));
+static_assert(nf_lds_is<32, 1024, 0, false>(24, 24, 1480, 23080));   static_assert(nf_lds_is<32, 1024, 0, false>(24, 24, 1483, 23080));
+static_assert(nf_lds_is<4, 256, 0, true, true>(32, 32, 1480, 8504));   static_assert(nf_lds_is<4, 256, 0, true, true>(32, 32, 1483, 8508));
+static_assert(nf_lds_is<4, 1024, 0, true, true>(64, 64, 1480, 27872));   static_assert(nf_lds_is<4, 1024, 0, true, true>(64, 64, 1483, 27876));
 
 // Batch-statistics pass (nf_nll_batchstats / nf_sample_batchstats): per-channel sum and sum of
 // squares of one pixel's pre-normalisation activations, reduced over the wavefront and added to
@@ -166,20 +178,13 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     constexpr int SIDE = THREADS * PX == 1024 ? 32 : THREADS * PX == 4096 ? 64 : 0;
     static_assert(!FULL || SIDE != 0, "FULL needs a 32x32 or 64x64 workgroup footprint");
     const int H = FULL ? SIDE : a.H, W = FULL ? SIDE : a.W, HW = H * W;
-    // row pitch of the plain row-major tiles; fp16 mode at 32x32: 48 entries so that the next
-    // block row (2 tile rows down) starts a multiple of 128 B (half2) / 256 B (4 x half) away
-    const int Wp = SB ? NF12_PITCH : HB ? nf11_pitch(SIDE) : (H16 && SIDE == 32) ? 48 : W + 2;
-    const int tile_px = ((H + 2) * Wp + 1) & ~1;         // even -> 16-byte aligned sections
-    // MFMA: a 4x4 identity behind the model (the `mix` of a coupling that has none in front: the pair loop below has ONE shape)
-    [[maybe_unused]] const int ident_off = (a.n_params + 3) & ~3;
-    // LDS order.  Default: tiles | reduction scratch | model image (+ identity) | BS partials.  HB: the model image FIRST — every
-    // weight read of a coupling is then `coupling base + lane term` plus an immediate below 64 KiB (behind 63 KiB of tiles the
-    // A3 / A2 operands were not, and cost a v_add_u32 each), while the tile accesses keep their compile-time immediates relative to
-    // lane addresses that carry the (run-time) tile base
-    constexpr bool WFIRST = HB || SB;
-    constexpr int TILE_WORDS = SB ? 6 : HALF ? 3 : 2 + WIDTH;          // 32-bit words per tile pixel
-    constexpr int RED_WORDS = (6 * (THREADS / 64) + 3) & ~3;
-    float *const tiles = WFIRST ? smem + ident_off + 16 : smem;
+    // LDS (NfFlowLds above); Wp = row pitch of the plain row-major tiles
+    using Lds = NfFlowLds<WIDTH, THREADS, PREC, MFMA, BS>;
+    const int Wp = Lds::pitch(H, W), tile_px = Lds::tile_px(H, W);
+    [[maybe_unused]] const int ident_off = Lds::ident(a.n_params);   // MFMA: the 4x4 identity behind the model, as a model offset
+    constexpr int TILE_WORDS = Lds::TILE_WORDS;          // 32-bit words per tile pixel
+    // the sections: every pointer a step of one NfFlowLds size from the one before (pointer steps, not summed offsets: DESIGN.md 4.1)
+    float *const tiles = Lds::WFIRST ? smem + ident_off + Lds::IDENT_WORDS : smem;
     float2 *const t0 = reinterpret_cast<float2 *>(tiles);  // z0 tile  [tile_px] float2
     float *const th = tiles + 2 * tile_px;                 // h2 tile  [tile_px][WIDTH]
     // fp16-CNN mode: the same two tiles hold half2 / 4 x half per pixel, plain row-major
@@ -189,10 +194,9 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     [[maybe_unused]] uint2 *const sr0 = reinterpret_cast<uint2 *>(tiles);
     [[maybe_unused]] uint2 *const sr1 = reinterpret_cast<uint2 *>(tiles + 2 * tile_px);
     [[maybe_unused]] uint2 *const sr2 = reinterpret_cast<uint2 *>(tiles + 4 * tile_px);
-    float *const red = tiles + TILE_WORDS * tile_px;       // reduction scratch [2][3][THREADS/64] (+pad), alternating by patch
-    float *const wl = WFIRST ? smem : red + RED_WORDS;     // MFMA: the whole folded model, j-major
-    // BS: [THREADS/64][8] per-wavefront statistics partials, then 8 doubles (scale[4], mean[4]) of the pending re-fold
-    [[maybe_unused]] float *const bs_part = WFIRST ? red + RED_WORDS : wl + ident_off + 16;
+    float *const red = tiles + TILE_WORDS * tile_px;       // reduction scratch, alternating by patch
+    float *const wl = Lds::WFIRST ? smem : red + Lds::RED_WORDS;   // MFMA: the whole folded model, j-major
+    [[maybe_unused]] float *const bs_part = Lds::WFIRST ? red + Lds::RED_WORDS : wl + ident_off + Lds::IDENT_WORDS;   // BS: per-wavefront statistics partials, then the pending re-fold
 
     const int t = threadIdx.x;
     const int j4 = t & 3;   // MFMA: which output channel's weights this lane feeds as the A operand
@@ -241,7 +245,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     } else if constexpr (BLK) {
         const int bw = W >> 1;
         int br = t / bw, bc = t - br * bw;
-#if NF_BR_SWIZZLE
         // 32x32, fp32 tiles: a block row is 16 lanes and the tile entries of two neighbouring block rows sit 4*PW = 68 entries
         // apart, i.e. 4 bank quads (mod 16) — the 16-byte LDS reads of a half-wavefront are served in lane groups that mix
         // lanes of two block rows ({0-3,12-15,20-27}, ...), and a quad offset of 4 makes a quarter of them collide
@@ -251,7 +254,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
             br = (t >> 6) + 4 * ((t >> 4) & 3);
             bc = t & 15;
         }
-#endif
         wbase = H16 ? (2 * br) * Wp + 2 * bc : (2 * br * 2) * PW + bc;
 #pragma unroll
         for (int k = 0; k < PX; ++k) {
@@ -284,13 +286,10 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     // The model image on its way to LDS: every lane's share is requested HERE, in one batch ahead of everything else (the copy loop
     // at the end of the set-up was np4 / THREADS dependent round trips to L2 — 3 at 32x32 —, and requests issued behind the x / y
     // touches below would make the stores wait for those HBM loads too: the counter retires loads in order); the stores follow the
-    // tile zeroing.  NF_WSTAGE 0: the old loop.
-#ifndef NF_WSTAGE
-#define NF_WSTAGE 1
-#endif
-    constexpr int WU = MFMA && NF_WSTAGE ? (THREADS >= 1024 ? 3 : 6) : 1;   // float4 per lane in the batch: NF11_MAX_FLOATS / NF2_MAX_FLOATS fit
+    // tile zeroing.
+    constexpr int WU = MFMA ? (THREADS >= 1024 ? 3 : 6) : 1;   // float4 per lane in the batch: NF11_MAX_FLOATS / NF2_MAX_FLOATS fit
     [[maybe_unused]] float4 wreg[WU];
-    if constexpr (MFMA && NF_WSTAGE) {
+    if constexpr (MFMA) {
         const int np4 = a.n_params >> 2;
         const float4 *const p4 = reinterpret_cast<const float4 *>(a.params);
 #pragma unroll
@@ -312,28 +311,20 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     // YPF — one 1024-thread workgroup per CU (64x64 patches): nothing else on the CU covers the HBM latency of the clean image
     // the leading sdn layer reads (tools/timeline.py: 2.3 us between two patches, 12 % of a patch), so y of the next patch
     // travels with its x, and the leading sdn layer is peeled off the op loop so that these registers are dead inside it
-#ifndef NF_YPF
-#define NF_YPF 1
-#endif
-    constexpr bool YPF = NF_YPF && MFMA && FULL && !PHILOX && THREADS == 1024 && !TF && !BS && (PREC != 0 || NF_YPF > 1);   // fp32 at 64x64 has no 16 registers to spare
+    constexpr bool YPF = MFMA && FULL && !PHILOX && THREADS == 1024 && !TF && !BS && PREC != 0;   // fp32 at 64x64 has no 16 registers to spare
     [[maybe_unused]] float4 yin[YPF ? PX : 1];
     [[maybe_unused]] const bool sdn_first = YPF && a.y && prog.n_ops > 0 && prog.ops[0].type == NF_OP_SDN_DIV;
     if constexpr (YPF) {
 #pragma unroll
         for (int k = 0; k < PX; ++k) yin[k] = make_float4(1.f, 1.f, 1.f, 1.f);
     }
-    // NF_STAGGER: a one-round launch (B = the resident capacity) would request all its 32 MiB of inputs in the same
-    // microsecond and compute nothing until the last byte arrives (tools/timeline.py).  Only the first quarter of the
+    // Staggered first requests: a one-round launch (B = the resident capacity) would request all its 32 MiB of inputs in the
+    // same microsecond and compute nothing until the last byte arrives (tools/timeline.py).  Only the first quarter of the
     // grid — with round-robin dispatch the first workgroup of every CU — asks before its LDS set-up; the second quarter
-    // asks after it, the third and fourth NF_STAGGER_SLEEP x 64 cycles later each: the early ones compute while the late
+    // asks after it, the third and fourth STAGGER_SLEEP x 64 cycles later each: the early ones compute while the late
     // ones load (53.3 -> 49.8 us per 1 024 patches together with the progress-based priority; neutral in steady state)
-#ifndef NF_STAGGER
-#define NF_STAGGER 2
-#endif
-#ifndef NF_STAGGER_SLEEP
-#define NF_STAGGER_SLEEP 16
-#endif
-    const bool early = !NF_STAGGER || PHILOX || blockIdx.x < (NF_STAGGER >= 2 ? (gridDim.x >> 2) : (gridDim.x >> 1));
+    constexpr int STAGGER_SLEEP = 16;
+    const bool early = PHILOX || blockIdx.x < (gridDim.x >> 2);
     // NF_K_TILED (nf_device.h): the pixel -> address map changes from tile to tile, so the loads sit at the top of the
     // patch loop instead of one patch ahead
     bool tiled = TF;
@@ -351,29 +342,20 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 for (int k = 0; k < PX; ++k) yin[k] = reinterpret_cast<const float4 *>(a.y)[off0 + gidx[k]];
             }
         } else {
-#ifndef NF_NO_WARM
 #pragma unroll
-        for (int k = 0; k < PX; k += NF_WARM_STEP)
-            if (a.y && act[k]) warm += reinterpret_cast<const float *>(a.y)[4 * (off0 + gidx[k])];
-#endif
+            for (int k = 0; k < PX; k += 2)   // every second owned pixel (2x2-blocked lanes: one per image row)
+                if (a.y && act[k]) warm += reinterpret_cast<const float *>(a.y)[4 * (off0 + gidx[k])];
         }
     }
 
     // zero both tiles once (the 1-pixel border is never written again) and stage the weight image, 16 bytes per lane
     {
-#ifndef NF_ZERO_BORDER
-#define NF_ZERO_BORDER 0
-#endif
-#ifndef NF_HB_ZB
-#define NF_HB_ZB 1
-#endif
-        if constexpr (NF_ZERO_BORDER && BLK && !HALF) {
-            // blocked fp32 tiles: every interior entry has an owner that writes it (z0 / h2 of each coupling) before anyone
-            // reads it, so only the 2 (W + 2) + 2 H border entries need the zero — 3 KiB instead of 27 KiB of LDS stores per
-            // 32x32 workgroup.  Measured and left OFF: + 0.7 % with a freshly initialised model (49.46 ->
-            // 49.10 us per launch), - 2 .. 5 % with the shipped checkpoint, i.e. through bench.py (50.0 -> 52.5 us;
-            // tools/ab_headline.py, tools/ab_bench.sh): the shorter set-up lets three quarters of the grid ask for their
-            // first inputs almost at once, which is what NF_STAGGER exists to prevent
+        if constexpr (SB || HB) {
+            // every interior entry of the tiles (SB: of the three regions) has an owner that writes it before anyone reads it, and no
+            // operand read reaches beyond column W + 1 of the padded rows: only the border ring needs the zero (HB: 3.5 KiB instead
+            // of 63 KiB at 64x64) — the top row, the bottom row, then the left / right ends of the rows between.
+            // (The blocked fp32 tiles are zeroed whole: ring-only zeroing measured + 0.7 % with a fresh model, - 2 .. 5 % through
+            //  bench.py, because the shorter set-up undoes the stagger of the first requests — DESIGN.md 4.1, removed variants.)
             const int nb = 2 * (W + 2) + 2 * H;
             for (int i = t; i < nb; i += THREADS) {
                 int rp, cp;
@@ -388,84 +370,43 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                     rp = 1 + (j >> 1);
                     cp = (j & 1) ? W + 1 : 0;
                 }
-                const int e = (rp * 2 + (cp & 1)) * PW + (cp >> 1);
-                t0[e] = make_float2(0.f, 0.f);
-                *reinterpret_cast<float4 *>(th + (size_t)e * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        } else if constexpr (SB) {
-            // as below, for the three regions (every interior slot is written by its owner before anyone reads it)
-            const int nb = 2 * (W + 2) + 2 * H;
-            for (int i = t; i < nb; i += THREADS) {
-                int rp, cp;
-                if (i < W + 2) {
-                    rp = 0;
-                    cp = i;
-                } else if (i < 2 * (W + 2)) {
-                    rp = H + 1;
-                    cp = i - (W + 2);
+                if constexpr (SB) {
+                    sr0[rp * Wp + cp] = make_uint2(0u, 0u);
+                    sr1[rp * Wp + cp] = make_uint2(0u, 0u);
+                    sr2[rp * Wp + cp] = make_uint2(0u, 0u);
                 } else {
-                    const int j = i - 2 * (W + 2);
-                    rp = 1 + (j >> 1);
-                    cp = (j & 1) ? W + 1 : 0;
+                    t0h[rp * Wp + cp] = 0u;
+                    thh[rp * Wp + cp] = make_uint2(0u, 0u);
                 }
-                sr0[rp * Wp + cp] = make_uint2(0u, 0u);
-                sr1[rp * Wp + cp] = make_uint2(0u, 0u);
-                sr2[rp * Wp + cp] = make_uint2(0u, 0u);
-            }
-        } else if constexpr (NF_HB_ZB && HB) {
-            // every interior entry of both tiles has an owner that writes it before anyone reads it, and no operand read reaches
-            // beyond column W + 1 of the padded rows: only the border ring needs the zero (3.5 KiB instead of 63 KiB at 64x64)
-            const int nb = 2 * (W + 2) + 2 * H;
-            for (int i = t; i < nb; i += THREADS) {
-                int rp, cp;
-                if (i < W + 2) {
-                    rp = 0;
-                    cp = i;
-                } else if (i < 2 * (W + 2)) {
-                    rp = H + 1;
-                    cp = i - (W + 2);
-                } else {
-                    const int j = i - 2 * (W + 2);
-                    rp = 1 + (j >> 1);
-                    cp = (j & 1) ? W + 1 : 0;
-                }
-                t0h[rp * Wp + cp] = 0u;
-                thh[rp * Wp + cp] = make_uint2(0u, 0u);
             }
         } else {
-        const int nz4 = (tile_px * TILE_WORDS) >> 2;
-        float4 *const s4 = reinterpret_cast<float4 *>(tiles);
-        for (int i = t; i < nz4; i += THREADS) s4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int i = (nz4 << 2) + t; i < tile_px * TILE_WORDS; i += THREADS) tiles[i] = 0.0f;
+            const int nz4 = (tile_px * TILE_WORDS) >> 2;
+            float4 *const s4 = reinterpret_cast<float4 *>(tiles);
+            for (int i = t; i < nz4; i += THREADS) s4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int i = (nz4 << 2) + t; i < tile_px * TILE_WORDS; i += THREADS) tiles[i] = 0.0f;
         }
         if (MFMA) {
             const int np4 = a.n_params >> 2;   // every section of the matrix-core layouts is a multiple of 4 floats
             const float4 *const p4 = reinterpret_cast<const float4 *>(a.params);
             float4 *const w4 = reinterpret_cast<float4 *>(wl);
-            if constexpr (NF_WSTAGE) {
 #pragma unroll
-                for (int u = 0; u < WU; ++u) {
-                    const int i = t + u * THREADS;
-                    if (i < np4) w4[i] = wreg[u];
-                }
-                for (int i = t + WU * THREADS; i < np4; i += THREADS) w4[i] = p4[i];   // (beyond the batch: models that barely fit)
-            } else {
-                for (int i = t; i < np4; i += THREADS) w4[i] = p4[i];
+            for (int u = 0; u < WU; ++u) {
+                const int i = t + u * THREADS;
+                if (i < np4) w4[i] = wreg[u];
             }
+            for (int i = t + WU * THREADS; i < np4; i += THREADS) w4[i] = p4[i];   // (beyond the batch: models that barely fit)
             for (int i = (np4 << 2) + t; i < a.n_params; i += THREADS) wl[i] = a.params[i];
             if (t < 16) wl[ident_off + t] = (t >> 2) == (t & 3) ? 1.0f : 0.0f;
         }
     }
     __syncthreads();
     asm volatile("" ::"v"(warm));   // keep the warm-up loads
-    if (NF_STAGGER && !early && (int64_t)blockIdx.x < a.B && !tiled) {
-#if NF_STAGGER >= 2
+    if (!early && (int64_t)blockIdx.x < a.B && !tiled) {
         {   // quarters of the grid = the 4 workgroups of a CU: the 3rd and 4th wait a little longer still
             const int q = (int)((blockIdx.x * 4u) / gridDim.x);
-            if (q == 2) __builtin_amdgcn_s_sleep(NF_STAGGER_SLEEP);
-            if (q == 3) { __builtin_amdgcn_s_sleep(NF_STAGGER_SLEEP); __builtin_amdgcn_s_sleep(NF_STAGGER_SLEEP); }
+            if (q == 2) __builtin_amdgcn_s_sleep(STAGGER_SLEEP);
+            if (q == 3) { __builtin_amdgcn_s_sleep(STAGGER_SLEEP); __builtin_amdgcn_s_sleep(STAGGER_SLEEP); }
         }
-#endif
         const size_t off0 = (size_t)blockIdx.x * (size_t)HW;
         if constexpr (!PHILOX) {
 #pragma unroll
@@ -521,17 +462,15 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     }
     NF_STAMP(1);
 
-#if NF_WAVE_PRIO
     if constexpr (MFMA && THREADS == 1024) {
         // one workgroup per CU, 4 waves per SIMD (waves w, w+4, w+8, w+12), all in the same phase between two barriers:
         // a fixed, distinct priority per wave of a SIMD lets the leaders' VALU tail run under the followers' MFMA burst
-        const int wq = NF_WAVE_PRIO == 1 ? ((t >> 8) & 3) : NF_WAVE_PRIO == 2 ? ((t >> 8) & 1) : (((t >> 8) & 3) == 0 ? 1 : 0);
+        const int wq = (t >> 8) & 3;
         if (wq == 0) __builtin_amdgcn_s_setprio(0);
         else if (wq == 1) __builtin_amdgcn_s_setprio(1);
         else if (wq == 2) __builtin_amdgcn_s_setprio(2);
         else __builtin_amdgcn_s_setprio(3);
     }
-#endif
     const int n_ops = prog.n_ops;
     double acc_nll = 0.0, acc_sd = 0.0;   // thread 0 only
     const double inv_n = 1.0 / ((double)HW * 4.0);   // once per launch: two fp64 divisions per patch were a third of the epilogue
@@ -556,13 +495,11 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
     // SB: the A images of the run's pairs sit a constant stride apart as well (verified on the host: nf_find_run), so the offset of
     // the image is a scalar that the counted loop advances, and the A operands are buffer loads — descriptor and offset in SGPRs, one
     // 32-bit lane offset — instead of global loads from three 64-bit vector addresses formed per coupling behind an LDS read of the
-    // field.  The range check covers the whole block.  NF_SB_AOFF 0: the field read and the global loads (A/B aid).
-#ifndef NF_SB_AOFF
-#define NF_SB_AOFF 1
-#endif
+    // field.  The range check covers the whole block.  (Carrying the offset as a VECTOR address in the counted loop instead: two
+    // more live registers, 8 B more scratch, 1.3 % slower on the headline — DESIGN.md 4.1, removed variants.)
     [[maybe_unused]] const int run_aoff = a.run_aoff, run_astride = a.run_astride;
     [[maybe_unused]] __amdgpu_buffer_rsrc_t sb_rsrc;
-    if constexpr (SB && NF_SB_AOFF) sb_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.params), 0, a.params_floats * 4, 0x00020000);
+    if constexpr (SB) sb_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.params), 0, a.params_floats * 4, 0x00020000);
 
     // nll / sd / log-det of patch (tile) pb from its three sums: the wavefronts' partials in `rd`, or (one wavefront) r0 r1 r2
     auto finish_patch = [&](const float *rd, int64_t pb, float r0, float r1, float r2) {
@@ -665,7 +602,7 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
         float ld2 = 0.0f;   // ... and the part accumulated in log2 units (matrix-core couplings)
         [[maybe_unused]] int n_cpl = 0;
         [[maybe_unused]] int cpl_seen = 0;
-        [[maybe_unused]] int fair_next = 0;   // the coupling count at which the priority level changes next (NF_FAIR, split-bf16 kernel)
+        [[maybe_unused]] int fair_next = 0;   // the coupling count at which the priority level changes next (split-bf16 kernel)
 
         // Conv2d1x1 on the matrix cores: per-pixel z <- z @ M   (layers.py:108-124)
         [[maybe_unused]] auto mix_load = [&](int moff) { return *reinterpret_cast<const float4 *>(wl + moff + 4 * j4); };   // M[0..3][j4]
@@ -693,9 +630,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 // log-det, -sum_c log scale_c = ln2 * log2(prod_c rsq(v_c)): ONE v_log_f32 per pixel on the product of the four
                 // reciprocal roots (3 multiplies instead of 3 more quarter-rate logarithms; the product stays finite while every
                 // v_c > 1e-18, i.e. a noise sd above 1e-9 — variances of raw images in [0, 1] are 1e-7 .. 1e-2)
-#ifndef NF_SDN_1LOG
-#define NF_SDN_1LOG 1
-#endif
                 float rp = 1.0f;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
@@ -703,13 +637,12 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                     if (stype == NF_OP_SDN_DIV) {
                         const float r = __builtin_amdgcn_rsqf(v);
                         z[k][c] = z[k][c] * r;
-                        if (NF_SDN_1LOG) rp = c == 0 ? r : rp * r;
-                        else if (own[k]) ld = fmaf(-0.34657359027997264f, __builtin_amdgcn_logf(v), ld);
+                        rp = c == 0 ? r : rp * r;
                     } else {
                         z[k][c] = z[k][c] * __builtin_amdgcn_sqrtf(v);
                     }
                 }
-                if (NF_SDN_1LOG && stype == NF_OP_SDN_DIV && own[k]) ld = fmaf(0.6931471805599453f, __builtin_amdgcn_logf(rp), ld);
+                if (stype == NF_OP_SDN_DIV && own[k]) ld = fmaf(0.6931471805599453f, __builtin_amdgcn_logf(rp), ld);
             }
         };
         int op_begin = 0;
@@ -753,7 +686,7 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                     pr_moff = ident_off;
                     pr_coff = prog.ops[op].off;
                 }
-                if constexpr (SB && NF_SB_AOFF) {   // a pair outside the counted run: its field, read once at the door of the loop
+                if constexpr (SB) {   // a pair outside the counted run: its field, read once at the door of the loop
                     if (pr_n == 1 && (type == NF_OP_COUPLING_FWD || type == NF_OP_COUPLING_REV))
                         pr_aoff = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wl[pr_coff + NF12_CPL_AOFF]));
                 }
@@ -791,26 +724,23 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 bool patch_done = false;
                 synced = true;   // every coupling passes barriers (the exchange of the pass-through half and of h2)
                 if constexpr (MFMA) op -= 2;
-                // NF_MIX_AHEAD 1: the mix matrix of a pair is read one coupling ahead (in front of the previous coupling's second
-                // barrier) instead of at the head of the loop body, where the read sits between the affine stage and the mix's first
-                // MFMA.  Measured neutral (fp32 32x32: 2.131e7 / 2.130e7; fp16 64x64 within the 1 % run-to-run band): left off
-#ifndef NF_MIX_AHEAD
-#define NF_MIX_AHEAD 0
-#endif
-                [[maybe_unused]] float4 mix_m = make_float4(0.f, 0.f, 0.f, 0.f);
-                if constexpr (MFMA) mix_m = mix_load(pr_moff);
+                // (reading a pair's mix matrix one coupling ahead, in front of the previous coupling's second barrier, measured
+                //  neutral: fp32 32x32 2.131e7 / 2.130e7 patches/s — DESIGN.md 4.1, removed variants)
 #pragma nounroll
                 for (int pr_i = 0; pr_i < pr_n; ++pr_i) {
                 if constexpr (MFMA) {
-                    if (!NF_MIX_AHEAD) mix_m = mix_load(pr_moff);
-                    mix_apply(mix_m);
+                    mix_apply(mix_load(pr_moff));
                     coff = pr_coff;
                     pr_moff += pr_i + 1 < pr_n ? pr_stride : 0;   // (the last pair re-reads its own matrix: always inside the image)
                     pr_coff += pr_stride;
                     op += 2;
                 }
-#if NF_FAIR
-                if constexpr (MFMA && !(NF_WAVE_PRIO && THREADS == 1024)) {
+                // Progress-based wave priority.  A SIMD arbitrates its resident waves oldest-first, so of the 4 workgroups that share
+                // a CU the oldest runs ahead and the youngest starves: at B = 1024 (one patch per workgroup) workgroup lifetimes spread
+                // 37..57 us around a 48 us mean and the launch lasts as long as the slowest one (tools/timeline.py).  Lowering a wave's
+                // priority as it advances through the couplings (3,3,2,2,1,1,0,0) is a negative feedback that keeps co-resident
+                // workgroups level.  (1 024 threads: the fixed per-wave priorities set above.)
+                if constexpr (MFMA && THREADS != 1024) {
                     // lvl = (cpl_seen * 4) / cpl_total, 0 .. 3, wave-uniform — against thresholds formed once per launch (the division
                     // was ~30 scalar instructions per coupling)
                     // SB: the level changes three times a patch and nothing else sets the priority, so it is written only when cpl_seen
@@ -826,60 +756,41 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                     }
                     ++cpl_seen;
                 }
-#endif
                 // HB: every weight operand of the coupling is requested before the barriers, so that after a barrier only the
-                // tile reads stand between a wavefront and its matrix instructions (NF_HB_EARLY=0: at first use, A/B aid)
-#ifndef NF_HB_EARLY
-#define NF_HB_EARLY 1
-#endif
+                // tile reads stand between a wavefront and its matrix instructions
                 [[maybe_unused]] v8h hb_a1, hb_a3a, hb_a3b, hb_a2a, hb_a2b;
                 [[maybe_unused]] v4h hb_w2h;
                 // l_2 on v_mfma_f32_16x16x32_f16 as well (nf_device.h, NF11_CPL_A2; 64x64 layouts only)
-#ifndef NF_HB_L2BIG
-#define NF_HB_L2BIG 1
-#endif
-                constexpr bool L2B = NF_HB_L2BIG && HB && THREADS == 1024;
+                constexpr bool L2B = HB && THREADS == 1024;
                 [[maybe_unused]] float4 hb_b1, hb_b2, hb_e[PX];
                 // SB: this lane's A operands of l_1 (pairs x halves) and l_last (pieces x m3), from the coupling's A image in global
                 // memory (the same bytes for every wavefront: L1 / L2 hits); l_last's are requested while l_1 runs
                 [[maybe_unused]] uint4 sb_a1[6], sb_a3[6];
-                [[maybe_unused]] const uint4 *sb_ag = nullptr;
                 // operand q of section `sec` (NF12_A_A1 / NF12_A_A3) of the image at byte offset ab: 1 KiB per operand, all of it in the
                 // scalar offset (a constant added to the lane offset is loop-invariant and would be hoisted into a register of its own)
                 [[maybe_unused]] int sb_ab = 0;
                 [[maybe_unused]] auto sb_aload = [&](int ab, int sec, int q) {
                     return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(sb_rsrc, (t & 63) * 16, ab + sec * 4 + q * 1024, 0));
                 };
-                if constexpr (SB && NF_SB_AOFF) {
+                if constexpr (SB) {
                     sb_ab = pr_aoff * 4;
                     pr_aoff += pr_astride;
 #pragma unroll
                     for (int q = 0; q < 6; ++q) sb_a1[q] = sb_aload(sb_ab, NF12_A_A1, q);
                     hb_b1 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_B1);
                     hb_b2 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_B2);
-                } else if constexpr (SB) {
-                    // (the field read: NF_SB_AOFF 0.  Carrying the offset as a VECTOR address in the counted loop cost two more live
-                    // registers, 8 B more scratch, and measured 1.3 % SLOWER on the headline)
-                    const int aoff = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wl[coff + NF12_CPL_AOFF]));
-                    sb_ag = reinterpret_cast<const uint4 *>(a.params + aoff) + (t & 63);
-#pragma unroll
-                    for (int q = 0; q < 6; ++q) sb_a1[q] = sb_ag[NF12_A_A1 / 4 + 64 * q];
-                    hb_b1 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_B1);
-                    hb_b2 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_B2);
                 }
                 if constexpr (HB) {
                     const float *wb = wl + coff;
                     const uint32_t *wbw = reinterpret_cast<const uint32_t *>(wb);
-                    if (NF_HB_EARLY) {
-                        hb_b1 = *reinterpret_cast<const float4 *>(wb + NF11_CPL_B1);
-                        hb_b2 = *reinterpret_cast<const float4 *>(wb + NF11_CPL_B2);
-                        hb_a1 = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A1 + (t & 63) * 4));
-                        if constexpr (L2B) {
-                            hb_a2a = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A2 + (t & 63) * 4));
-                            hb_a2b = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A2 + 256 + (t & 63) * 4));
-                        } else {
-                            hb_w2h = *reinterpret_cast<const v4h *>(wbw + NF11_CPL_W2H + j4 * 2);
-                        }
+                    hb_b1 = *reinterpret_cast<const float4 *>(wb + NF11_CPL_B1);
+                    hb_b2 = *reinterpret_cast<const float4 *>(wb + NF11_CPL_B2);
+                    hb_a1 = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A1 + (t & 63) * 4));
+                    if constexpr (L2B) {
+                        hb_a2a = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A2 + (t & 63) * 4));
+                        hb_a2b = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A2 + 256 + (t & 63) * 4));
+                    } else {
+                        hb_w2h = *reinterpret_cast<const v4h *>(wbw + NF11_CPL_W2H + j4 * 2);
                     }
                 }
                 // 1) publish the pass-through half
@@ -907,81 +818,38 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                     const float4 w2 = *reinterpret_cast<const float4 *>(wl + coff + NF12_CPL_W2T + 4 * j4);
                     v4f h1[PX];
                     // K slot of this lane: one window row, two columns per instruction (16-byte reads of two slots): [region][half]
-                    // NF_SB_RDAHEAD: the operand reads of unit k + 1 are requested while the chain of unit k is being issued instead
-                    // of behind its last instruction — 1: each into the registers the chain has just finished with (region 1's pair
-                    // behind the chain's second instruction, region 0's behind its last), 2: all of them behind the second instruction
-                    // (a second operand set).  0: where the compiler puts them (behind the chain).  The barriers let plain VALU and
-                    // SALU instructions pass (mask 0x406) and hold matrix and LDS instructions in the order written.
-                    // Measured and left at 0: 1 LOSES 0.8 % against 0 and 2 (16 registers more, scratch 12 -> 84 B)
-                    // 6 % — with four wavefronts per SIMD the reads behind a chain are already covered by the other wavefronts'
-                    // chains, and the pinned order costs more than the exposed round trips
-#ifndef NF_SB_RDAHEAD
-#define NF_SB_RDAHEAD 0
-#endif
-                    constexpr int RDA = NF_SB_RDAHEAD;
+                    // (Requesting unit k + 1's reads under the chain of unit k, pinned with sched_barriers: 0.8 % slower into the same
+                    //  registers, 6 % slower into a second operand set; the four l_2 chains side by side: + 0.2 %, within the spread —
+                    //  DESIGN.md 4.1, removed variants.  The compiler places the reads behind each chain.)
                     uint4 q1[PX][2][2];
                     auto rd1 = [&](int k, int r) {
 #pragma unroll
                         for (int hf = 0; hf < 2; ++hf) q1[k][r][hf] = *reinterpret_cast<const uint4 *>((r ? sr1 : sr0) + wbase + 2 * k * Wp + 2 * hf);
                     };
-                    if (RDA) { rd1(0, 1); rd1(0, 0); }
 #pragma unroll
                     for (int k = 0; k < PX; ++k) {
-                        if (!RDA) { rd1(k, 0); rd1(k, 1); }
+                        rd1(k, 0);
+                        rd1(k, 1);
                         // smallest products first: hl + lh, mh + mm, hh + hm
                         v4f acc = v4f{b1.x, b1.y, b1.z, b1.w};
                         acc = nf_mfma_bf16(sb_a1[4], q1[k][1][0], acc);
                         acc = nf_mfma_bf16(sb_a1[5], q1[k][1][1], acc);
-                        if (RDA && k + 1 < PX) {
-                            __builtin_amdgcn_sched_barrier(0x406);
-                            rd1(k + 1, 1);
-                            if (RDA >= 2) rd1(k + 1, 0);
-                            __builtin_amdgcn_sched_barrier(0x406);
-                        }
                         acc = nf_mfma_bf16(sb_a1[2], q1[k][0][0], acc);
                         acc = nf_mfma_bf16(sb_a1[3], q1[k][0][1], acc);
                         acc = nf_mfma_bf16(sb_a1[0], q1[k][0][0], acc);
                         acc = nf_mfma_bf16(sb_a1[1], q1[k][0][1], acc);
-                        if (RDA == 1 && k + 1 < PX) {
-                            __builtin_amdgcn_sched_barrier(0x406);
-                            rd1(k + 1, 0);
-                            __builtin_amdgcn_sched_barrier(0x406);
-                        }
                         h1[k] = acc;
                     }
 #pragma unroll
-                    for (int q = 0; q < 6; ++q) sb_a3[q] = NF_SB_AOFF ? sb_aload(sb_ab, NF12_A_A3, q) : sb_ag[NF12_A_A3 / 4 + 64 * q];
+                    for (int q = 0; q < 6; ++q) sb_a3[q] = sb_aload(sb_ab, NF12_A_A3, q);
                     uint2 hs[PX][3];   // relu(h2) of the lane's pixels, three pieces
-                    // NF_SB_L2IL 1: the four units' l_2 chains issued side by side (one product of each in turn, held in that order),
-                    // so that no s_nop stands between two dependent v_mfma_f32_4x4x1; each chain's own order is unchanged.  0: unit by
-                    // unit in the source, interleaved where the scheduler sees fit (units 2 and 3).  Measured with NF_SB_RDAHEAD 1: + 0.2 %,
-                    // inside the run-to-run spread (the s_nop that remain wait for the v_max in front of each product): left at 0
-#ifndef NF_SB_L2IL
-#define NF_SB_L2IL 0
-#endif
-                    [[maybe_unused]] v4f h2s[PX];
-                    if (NF_SB_L2IL) {
-                        const float w2v[4] = {w2.x, w2.y, w2.z, w2.w};
-#pragma unroll
-                        for (int k = 0; k < PX; ++k) h2s[k] = v4f{b2.x, b2.y, b2.z, b2.w};
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-                            for (int k = 0; k < PX; ++k) h2s[k] = __builtin_amdgcn_mfma_f32_4x4x1f32(w2v[c], nf_relu(h1[k][c]), h2s[k], 0, 0, 0);
-                            __builtin_amdgcn_sched_barrier(0x406);
-                        }
-                    }
 #pragma unroll
                     for (int k = 0; k < PX; ++k) {
                         v4f h2 = {b2.x, b2.y, b2.z, b2.w};
-                        if (NF_SB_L2IL) {
-                            h2 = h2s[k];
-                        } else {
                         h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.x, nf_relu(h1[k][0]), h2, 0, 0, 0);
                         h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.y, nf_relu(h1[k][1]), h2, 0, 0, 0);
                         h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.z, nf_relu(h1[k][2]), h2, 0, 0, 0);
                         h2 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2.w, nf_relu(h1[k][3]), h2, 0, 0, 0);
-                        }
                         uint32_t p01[3], p23[3];
                         nf_split3(nf_relu(h2[0]), nf_relu(h2[1]), p01[0], p01[1], p01[2]);
                         nf_split3(nf_relu(h2[2]), nf_relu(h2[3]), p23[0], p23[1], p23[2]);
@@ -1000,17 +868,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 } else if constexpr (HB) {
                     const float *wb = wl + coff;
                     const uint32_t *wbw = reinterpret_cast<const uint32_t *>(wb);
-                    if (!NF_HB_EARLY) {
-                        hb_b1 = *reinterpret_cast<const float4 *>(wb + NF11_CPL_B1);
-                        hb_b2 = *reinterpret_cast<const float4 *>(wb + NF11_CPL_B2);
-                        hb_a1 = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A1 + (t & 63) * 4));
-                        if constexpr (L2B) {
-                            hb_a2a = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A2 + (t & 63) * 4));
-                            hb_a2b = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A2 + 256 + (t & 63) * 4));
-                        } else {
-                            hb_w2h = *reinterpret_cast<const v4h *>(wbw + NF11_CPL_W2H + j4 * 2);
-                        }
-                    }
                     const float4 b1 = hb_b1, b2 = hb_b2;
                     const v8h a1 = hb_a1;
                     [[maybe_unused]] v4h w2h = {0, 0, 0, 0};
@@ -1054,12 +911,11 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                             v4h{(_Float16)h2[k][0], (_Float16)h2[k][1], (_Float16)h2[k][2], (_Float16)h2[k][3]}, v4h{0, 0, 0, 0});
                         thh[lidx[k]] = __builtin_bit_cast(uint2, r2);
                     }
-                    if (NF_HB_EARLY) {   // l_last's weights and border-table rows: in flight across the barrier
-                        hb_a3a = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A3 + (t & 63) * 4));
-                        hb_a3b = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A3 + 256 + (t & 63) * 4));
+                    // l_last's weights and border-table rows: in flight across the barrier
+                    hb_a3a = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A3 + (t & 63) * 4));
+                    hb_a3b = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A3 + 256 + (t & 63) * 4));
 #pragma unroll
-                        for (int k = 0; k < PX; ++k) hb_e[k] = *reinterpret_cast<const float4 *>(wb + NF11_CPL_E + 4 * bmask[k]);
-                    }
+                    for (int k = 0; k < PX; ++k) hb_e[k] = *reinterpret_cast<const float4 *>(wb + NF11_CPL_E + 4 * bmask[k]);
                 } else if constexpr (H16) {
                     const float *wb = wl + coff;
                     const uint32_t *wbw = reinterpret_cast<const uint32_t *>(wb);
@@ -1080,7 +936,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                     v4f h1[PX];
 #pragma unroll
                     for (int k = 0; k < PX; ++k) h1[k] = v4f{b1.x, b1.y, b1.z, b1.w};
-                    NF_PRIO_UP();
 #pragma unroll
                     for (int wr = 0; wr < 4; ++wr) {
                         // one window row = two 8-byte pairs of horizontally adjacent pixels (2 ch each)
@@ -1098,7 +953,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                             }
                         }
                     }
-                    NF_PRIO_DOWN();
 #pragma unroll
                     for (int k = 0; k < PX; ++k) {
                         // ReLU after the conversion, two halves per instruction (v_pk_max_f16)
@@ -1125,7 +979,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                             const float2 wB = *reinterpret_cast<const float2 *>(wb + NF2_CPL_W1T + 24 * j4 + 8 * di + 4);
                             w1[di][0] = wA.x; w1[di][1] = wA.y; w1[di][2] = wA.z; w1[di][3] = wA.w; w1[di][4] = wB.x; w1[di][5] = wB.y;
                         }
-                        NF_PRIO_UP();
 #pragma unroll
                         for (int wr = 0; wr < 4; ++wr) {
                             float2 v[4];   // one row of the 4x4 window, shared by the 2x2 output pixels
@@ -1146,7 +999,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                             }
                         }
                     } else {
-                    NF_PRIO_UP();
 #pragma unroll
                     for (int di = 0; di < 3; ++di) {
                         // this lane's A operands of one filter row: W1[(di,dj,c)][j4]
@@ -1165,7 +1017,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                         }
                     }
                     }
-                    NF_PRIO_DOWN();
                     [[maybe_unused]] int bs_stage = 0;
                     [[maybe_unused]] float bs1[4] = {0.f, 0.f, 0.f, 0.f}, bs2[4] = {0.f, 0.f, 0.f, 0.f};
                     if constexpr (BS) bs_stage = (a.stats && op == a.stats_op) ? a.stats_stage : 0;
@@ -1277,7 +1128,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                         if (stats_stage) stats_flush<WIDTH>(st1, st2, stats, t);
                     }
                 }
-                if constexpr (MFMA && NF_MIX_AHEAD) mix_m = mix_load(pr_moff);
                 __syncthreads();
                 if constexpr (BS) {
                     if (a.stats && op == a.stats_op && t < 8) {
@@ -1298,96 +1148,45 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                 {
                     float o[PX][4];
                     float sc;
-                    // SB, NF_SB_AFFINE 1: ls * log2(e) of unit k (two exp2, two rcp, two fma: the part of the affine stage that does not
-                    // depend on the direction) is formed in the source under the chain of unit k + 1, between the same barriers as
-                    // that chain's read-ahead.  0: behind the last chain, where the scheduler moves what it likes.  Measured with
-                    // NF_SB_RDAHEAD 1: no difference (+0.01 %), 16 B more scratch: left at 0
-#ifndef NF_SB_AFFINE
-#define NF_SB_AFFINE 0
-#endif
-                    [[maybe_unused]] float sb_l[PX][2];
-                    [[maybe_unused]] float sb_scl = 0.f, sb_m2scl = 0.f;
                     if constexpr (SB) {
                         sc = 0.0f;
-                        if (NF_SB_AFFINE) {
-                            sb_scl = wl[coff + NF12_CPL_S + 1];
-                            sb_m2scl = wl[coff + NF12_CPL_S + 2];
-                        }
-                        [[maybe_unused]] auto affine_ls = [&](int k) {
-                            sb_l[k][0] = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][2]) + 1.0f), sb_m2scl, sb_scl);
-                            sb_l[k][1] = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][3]) + 1.0f), sb_m2scl, sb_scl);
-                        };
                         uint2 *const srp[3] = {sr0, sr1, sr2};
                         // smallest products first: (h l, l h, m m), (h m, m h), h h — weight piece x activation piece
                         constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-                        // NF_SB_RDAHEAD (l_1 above): activation piece 2 is last used by product 0 of a chain, piece 1 by product 3 and
-                        // piece 0 by product 5 — 1: unit k + 1's reads of a piece follow the last use of that piece in unit k's chain,
-                        // 2: all six follow product 0
-                        constexpr int RDA = NF_SB_RDAHEAD;
-                        constexpr int AFTER[3] = {RDA >= 2 ? 0 : 5, RDA >= 2 ? 0 : 3, 0};   // by piece: the product its read-ahead follows
+                        // (reads of unit k + 1 pinned under the chain of unit k, and the direction-free part of the affine stage
+                        //  formed under the next chain: slower / no difference, see l_1 above and DESIGN.md 4.1, removed variants)
                         uint4 qb[PX][3][2];   // [unit][piece][m3]: K slot = two adjacent window pixels x 4 channels, one 16-byte read
                         auto rd3 = [&](int k, int p) {
 #pragma unroll
                             for (int m3 = 0; m3 < 2; ++m3) qb[k][p][m3] = *reinterpret_cast<const uint4 *>(srp[p] + wbase3 + (2 * k + m3) * Wp);
                         };
-                        if (RDA) { rd3(0, 2); rd3(0, 0); rd3(0, 1); }
 #pragma unroll
                         for (int k = 0; k < PX; ++k) {
-                            if (!RDA) { rd3(k, 0); rd3(k, 1); rd3(k, 2); }
+                            rd3(k, 0);
+                            rd3(k, 1);
+                            rd3(k, 2);
                             const float4 e = hb_e[k];
                             v4f acc = v4f{e.x, e.y, e.z, e.w};
 #pragma unroll
-                            for (int t6 = 0; t6 < 6; ++t6) {
+                            for (int t6 = 0; t6 < 6; ++t6)
 #pragma unroll
                                 for (int m3 = 0; m3 < 2; ++m3) acc = nf_mfma_bf16(sb_a3[2 * PA[t6] + m3], qb[k][PB[t6]][m3], acc);
-                                if (RDA && k + 1 < PX && (t6 == AFTER[0] || t6 == AFTER[1] || t6 == AFTER[2])) {
-                                    __builtin_amdgcn_sched_barrier(0x406);
-#pragma unroll
-                                    for (int p = 2; p >= 0; --p)
-                                        if (AFTER[p] == t6) rd3(k + 1, p);
-                                    __builtin_amdgcn_sched_barrier(0x406);
-                                }
-                                if (NF_SB_AFFINE && t6 == 0 && k > 0) affine_ls(k - 1);
-                            }
 #pragma unroll
                             for (int j = 0; j < 4; ++j) o[k][j] = acc[j];
                         }
-                        if (NF_SB_AFFINE) affine_ls(PX - 1);
                     } else if constexpr (HB) {
-                        const float *wb = wl + coff;
-                        const uint32_t *wbw = reinterpret_cast<const uint32_t *>(wb);
                         sc = 0.0f;
-                        if (!NF_HB_EARLY) {
-                            hb_a3a = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A3 + (t & 63) * 4));
-                            hb_a3b = __builtin_bit_cast(v8h, *reinterpret_cast<const uint4 *>(wbw + NF11_CPL_A3 + 256 + (t & 63) * 4));
-#pragma unroll
-                            for (int k = 0; k < PX; ++k) hb_e[k] = *reinterpret_cast<const float4 *>(wb + NF11_CPL_E + 4 * bmask[k]);
-                        }
                         const v8h a3a = hb_a3a, a3b = hb_a3b;
                         // K slot of this lane: two adjacent window pixels x 4 channels = one aligned 16-byte read per instruction.
-                        // NF_HB_RDAHEAD units' reads are requested before the first matrix instruction.  Left to itself (0) the compiler
-                        // reads two operands, waits, multiplies, and only then reads the next two — four LDS latencies per phase;
-                        // requesting all eight first (4) needs the whole 128-register budget of a 16-wavefront workgroup and measured
-                        // SLOWER (same box, 64x64 fp16, B = 1 024: 1.226e7 against 1.258e7 patches/s; 2: 1.241e7): left at 0
-#ifndef NF_HB_RDAHEAD
-#define NF_HB_RDAHEAD 0
-#endif
-                        uint4 q0[PX], q1[PX];
-#pragma unroll
-                        for (int k = 0; k < PX && k < NF_HB_RDAHEAD; ++k) {
-                            q0[k] = *reinterpret_cast<const uint4 *>(thh + wbase3 + 2 * k * Wp);
-                            q1[k] = *reinterpret_cast<const uint4 *>(thh + wbase3 + (2 * k + 1) * Wp);
-                        }
-                        if (NF_HB_RDAHEAD) __builtin_amdgcn_sched_barrier(0);
+                        // (Requesting 2 or all 4 units' reads before the first matrix instruction measured slower, 1.241e7 / 1.226e7
+                        //  against 1.258e7 patches/s at 64x64 fp16 — DESIGN.md 4.2, removed variants)
 #pragma unroll
                         for (int k = 0; k < PX; ++k) {
                             const float4 e = hb_e[k];
-                            if (k >= NF_HB_RDAHEAD) {
-                                q0[k] = *reinterpret_cast<const uint4 *>(thh + wbase3 + 2 * k * Wp);
-                                q1[k] = *reinterpret_cast<const uint4 *>(thh + wbase3 + (2 * k + 1) * Wp);
-                            }
-                            v4f acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a3a, __builtin_bit_cast(v8h, q0[k]), v4f{e.x, e.y, e.z, e.w}, 0, 0, 0);
-                            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a3b, __builtin_bit_cast(v8h, q1[k]), acc, 0, 0, 0);
+                            const uint4 q0 = *reinterpret_cast<const uint4 *>(thh + wbase3 + 2 * k * Wp);
+                            const uint4 q1 = *reinterpret_cast<const uint4 *>(thh + wbase3 + (2 * k + 1) * Wp);
+                            v4f acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a3a, __builtin_bit_cast(v8h, q0), v4f{e.x, e.y, e.z, e.w}, 0, 0, 0);
+                            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a3b, __builtin_bit_cast(v8h, q1), acc, 0, 0, 0);
 #pragma unroll
                             for (int j = 0; j < 4; ++j) o[k][j] = acc[j];
                         }
@@ -1409,7 +1208,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                             const float4 e = *reinterpret_cast<const float4 *>(wb + NF3_CPL_E + 4 * bmask[k]);
                             acc[k] = v4f{e.x, e.y, e.z, e.w};
                         }
-                        NF_PRIO_UP();
 #pragma unroll
                         for (int wr = 0; wr < 4; ++wr) {
                             const uint4 q01 = *reinterpret_cast<const uint4 *>(thh + wbase + wr * Wp);
@@ -1429,7 +1227,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                                     }
                             }
                         }
-                        NF_PRIO_DOWN();
 #pragma unroll
                         for (int k = 0; k < PX; ++k)
 #pragma unroll
@@ -1451,7 +1248,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                                 w3[q / 3][4 * (q % 3) + 0] = w.x; w3[q / 3][4 * (q % 3) + 1] = w.y;
                                 w3[q / 3][4 * (q % 3) + 2] = w.z; w3[q / 3][4 * (q % 3) + 3] = w.w;
                             }
-                            NF_PRIO_UP();
 #pragma unroll
                             for (int wr = 0; wr < 4; ++wr) {
                                 float4 hv[4];   // one row of the 4x4 window of h2
@@ -1476,7 +1272,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                                 }
                             }
                         } else {
-                        NF_PRIO_UP();
 #pragma unroll
                         for (int di = 0; di < 3; ++di) {
                             float w3[12];   // this lane's A operands of one filter row: W3[(di,dj,i)][j4]
@@ -1499,7 +1294,6 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                             }
                         }
                         }
-                        NF_PRIO_DOWN();
 #pragma unroll
                         for (int k = 0; k < PX; ++k)
 #pragma unroll
@@ -1547,14 +1341,8 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                         if (type == NF_OP_COUPLING_FWD) {
 #pragma unroll
                             for (int k = 0; k < PX; ++k) {
-                                float l0, l1;
-                                if constexpr (SB && NF_SB_AFFINE) {
-                                    l0 = sb_l[k][0];
-                                    l1 = sb_l[k][1];
-                                } else {
-                                    l0 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][2]) + 1.0f), m2scl, scl);
-                                    l1 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][3]) + 1.0f), m2scl, scl);
-                                }
+                                const float l0 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][2]) + 1.0f), m2scl, scl);
+                                const float l1 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][3]) + 1.0f), m2scl, scl);
                                 z[k][2] = fmaf(z[k][2], __builtin_amdgcn_exp2f(l0), o[k][0]);
                                 z[k][3] = fmaf(z[k][3], __builtin_amdgcn_exp2f(l1), o[k][1]);
                                 if (own[k]) ld2 += l0 + l1;
@@ -1562,14 +1350,8 @@ __device__ __forceinline__ void nf_flow_body(const NfProgram &prog, const NfLaun
                         } else {
 #pragma unroll
                             for (int k = 0; k < PX; ++k) {
-                                float l0, l1;
-                                if constexpr (SB && NF_SB_AFFINE) {
-                                    l0 = sb_l[k][0];
-                                    l1 = sb_l[k][1];
-                                } else {
-                                    l0 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][2]) + 1.0f), m2scl, scl);
-                                    l1 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][3]) + 1.0f), m2scl, scl);
-                                }
+                                const float l0 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][2]) + 1.0f), m2scl, scl);
+                                const float l1 = fmaf(__builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(o[k][3]) + 1.0f), m2scl, scl);
                                 z[k][2] = (z[k][2] - o[k][0]) * __builtin_amdgcn_exp2f(-l0);
                                 z[k][3] = (z[k][3] - o[k][1]) * __builtin_amdgcn_exp2f(-l1);
                             }
@@ -1750,26 +1532,18 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(NF_MIN_
 
 // split-bf16 convs (NF_K_SPLIT_BF16, nf_device.h NF12_*): full 32x32 patches, 4 workgroups of 4 wavefronts per CU, i.e. at most 128
 // registers a lane
-// NF_SPLIT_PK_SUB 0: the kernel is compiled without packed fp32, so the 48 subtractions of the operand split (nf_split3) are plain
-// v_sub_f32 and the affine stage's 8 packed multiply-adds 16 plain ones; 1: packed fp32 allowed, 24 v_pk_add_f32 (A/B aid).  Packed
-// fp32 is dear beside matrix instructions and its register pairs cost 24 B more scratch — headline, one box, builds alternated 4 x:
-// double-rounding split 2.125e7 patches/s, this split with v_pk_add_f32 2.089e7, with v_sub_f32 2.200e7 (profiles/r08_ab_split_once.txt)
-#ifndef NF_SPLIT_PK_SUB
-#define NF_SPLIT_PK_SUB 0
-#endif
-#if NF_SPLIT_PK_SUB
-#define NF_SPLIT_KATTR
-#else
-#define NF_SPLIT_KATTR NF_NO_PK_F32
-#endif
+// The kernel is compiled without packed fp32 (NF_NO_PK_F32), so the 48 subtractions of the operand split (nf_split3) are plain
+// v_sub_f32 and the affine stage's 8 packed multiply-adds 16 plain ones.  Packed fp32 is dear beside matrix instructions and its
+// register pairs cost 24 B more scratch — headline, one box, builds alternated 4 x: double-rounding split 2.125e7 patches/s, this
+// split with 24 v_pk_add_f32 2.089e7, with v_sub_f32 2.200e7 (profiles/r08_ab_split_once.txt)
 template <bool PHILOX>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) NF_SPLIT_KATTR void nf_flow_split_kernel(const NfProgram prog, const NfLaunch a)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) NF_NO_PK_F32 void nf_flow_split_kernel(const NfProgram prog, const NfLaunch a)
 {
     nf_flow_body<4, 256, 4, PHILOX, true, true, 3, false, false>(prog, a);
 }
 
 template <bool PHILOX>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) NF_SPLIT_KATTR void nf_flow_split_pc_kernel(const NfProgram prog, const NfLaunch a)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) NF_NO_PK_F32 void nf_flow_split_pc_kernel(const NfProgram prog, const NfLaunch a)
 {
     nf_flow_body<4, 256, 4, PHILOX, true, true, 3, false, false, true>(prog, a);
 }
@@ -1937,12 +1711,6 @@ __global__ __launch_bounds__(256) void nf_eps_kernel(uint64_t seed, int64_t patc
     }
 }
 
-inline int env_int(const char *name)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : 0;
-}
-
 template <int WIDTH, int THREADS, int PX, bool PHILOX, bool MFMA, bool FULL, int PREC, bool BS = false, bool TF = false, bool PC = false>
 hipError_t launch_flow_p(const NfProgram &prog, const NfLaunch &a, int n_cu, hipStream_t stream)
 {
@@ -1952,14 +1720,7 @@ hipError_t launch_flow_p(const NfProgram &prog, const NfLaunch &a, int n_cu, hip
             else return launch_flow_p<WIDTH, THREADS, PX, PHILOX, MFMA, FULL, PREC, false, TF, true>(prog, a, n_cu, stream);
         }
     }
-    const int tile_px = ((a.H + 2) * (a.W + 2) + 1) & ~1;
-    size_t lds_f = (size_t)tile_px * (PREC != 0 ? 3 : 2 + WIDTH) + ((6 * (THREADS / 64) + 3) & ~3);
-    if (PREC == 1 && a.H == 32) lds_f = (size_t)(34 * 48) * 3 + ((6 * (THREADS / 64) + 3) & ~3);   // padded row pitch
-    if (PREC == 2) lds_f = (size_t)((a.H + 2) * nf11_pitch(a.H)) * 3 + ((6 * (THREADS / 64) + 3) & ~3);
-    if (PREC == 3) lds_f = (size_t)((a.H + 2) * NF12_PITCH) * 6 + ((6 * (THREADS / 64) + 3) & ~3);
-    if (MFMA) lds_f += (size_t)((a.n_params + 3) & ~3) + 16;   // + the identity block
-    if (BS) lds_f += (size_t)(THREADS / 64) * 8 + 16;
-    const size_t lds = sizeof(float) * lds_f;
+    const size_t lds = sizeof(float) * (size_t)NfFlowLds<WIDTH, THREADS, PREC, MFMA, BS>::total(a.H, a.W, a.n_params);
     constexpr auto kern = [] {
         if constexpr (PC && TF) return &nf_flow_tile64_pc_kernel<PHILOX, PREC>;
         else if constexpr (PC && PREC == 3) return &nf_flow_split_pc_kernel<PHILOX>;
@@ -2002,8 +1763,7 @@ hipError_t launch_flow_v(const NfProgram &prog, const NfLaunch &a, int n_cu, hip
             // tiled launches: full 64x64 tiles have their own instantiation of the blocked geometry, everything else is masked
             if constexpr (MFMA && WIDTH == 4 && THREADS == 1024 && PX == 4) {
                 if (a.flags & NF_K_FP16_BIG) return launch_flow_p<WIDTH, THREADS, PX, PHILOX, MFMA, true, 2, false, true>(prog, a, n_cu, stream);
-                static const bool masked = env_int("NF_TILE_MASKED") != 0;   // A/B aid
-                if (!masked && !(a.flags & NF_K_BATCHSTATS)) return launch_flow_p<WIDTH, THREADS, PX, PHILOX, MFMA, true, 0, false, true>(prog, a, n_cu, stream);
+                if (!(a.flags & NF_K_BATCHSTATS)) return launch_flow_p<WIDTH, THREADS, PX, PHILOX, MFMA, true, 0, false, true>(prog, a, n_cu, stream);
             }
         }
     }
@@ -2041,13 +1801,7 @@ hipError_t dispatch_geom(const NfProgram &prog, const NfLaunch &a, int n_cu, hip
         if (hw <= 1024) return launch_flow<WIDTH, 1024, 1, MFMA>(prog, a, n_cu, stream);
         return hipErrorInvalidValue;
     } else {
-        if (hw <= 1024) {
-            // workgroup geometry for the 32x32 patch; NF_GEOM=<threads> overrides (tuning aid)
-            static const int geom = env_int("NF_GEOM");
-            if (geom == 512) return launch_flow<WIDTH, 512, 2, MFMA>(prog, a, n_cu, stream);
-            if (geom == 1024) return launch_flow<WIDTH, 1024, 1, MFMA>(prog, a, n_cu, stream);
-            return launch_flow<WIDTH, 256, 4, MFMA>(prog, a, n_cu, stream);
-        }
+        if (hw <= 1024) return launch_flow<WIDTH, 256, 4, MFMA>(prog, a, n_cu, stream);   // 32x32: 4 pixels per lane, 4 workgroups per CU
         if (hw <= 4096) return launch_flow<WIDTH, 1024, 4, MFMA>(prog, a, n_cu, stream);
         return hipErrorInvalidValue;
     }

@@ -12,7 +12,13 @@ change in the work.
 --one-workgroup-per-cu THREADS: the kernels are launched as at most ONE workgroup of THREADS threads per CU (the GEMM coupling
 kernels: grid = min(B, CUs), 512 threads, because a workgroup takes most of a CU's LDS).  Then a SIMD never holds more than
 THREADS / 64 / 4 wavefronts whatever the register count would allow, and the occupancy that is compared is
-min(compiler's occupancy, THREADS / 64 / 4) — the wavefronts that are resident; the compiler's figure is still printed."""
+min(compiler's occupancy, THREADS / 64 / 4) — the wavefronts that are resident; the compiler's figure is still printed.
+
+--exact before.s after.s: for a refactor that must not move a single instruction.  Kernels are matched by name; per kernel the
+whole instruction text and the .amdhsa_* block (registers, scratch, LDS, next_free_*) are compared after the labels that carry the
+function's ordinal in the module have been renumbered.  Prints the kernels only in `before` (instantiations the change removed),
+those only in `after`, and every kernel that differs with its first differing line; exit status 1 if any kernel differs or
+`after` has a kernel that `before` has not."""
 import re
 import subprocess
 import sys
@@ -48,9 +54,63 @@ def kernels(path):
     return out
 
 
+def exact_kernels(text):
+    """{symbol: [lines]} of every .amdhsa_kernel of an assembly text: its instructions and labels from `symbol:` to its
+    .Lfunc_end, then its .amdhsa_* block, without comments and with what depends on the function's ordinal in the module
+    (.LBB<n>_, .Lfunc_begin<n>, .Lfunc_end<n>, .Ltmp<n>) renumbered: a removed instantiation elsewhere shifts those numbers."""
+    out = {}
+    for name in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M):
+        start = text.index("\n%s:" % name) + 1
+        end = re.compile(r"^\.Lfunc_end\d+:", re.M).search(text, start).end()
+        meta = text.index(".amdhsa_kernel %s\n" % name)
+        body = text[start:end] + "\n" + text[meta:text.index(".end_amdhsa_kernel", meta)]
+        tmp = {}
+        lines = []
+        for line in body.split("\n"):
+            line = line.split(";")[0].strip()
+            if not line or line.startswith(".ident"):
+                continue
+            line = re.sub(r"\.LBB\d+_", ".LBB_", line)
+            line = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", line)
+            line = re.sub(r"\.Ltmp\d+", lambda m: ".Ltmp%d" % tmp.setdefault(m.group(0), len(tmp)), line)
+            lines.append(" ".join(line.split()))
+        out[name] = lines
+    return out
+
+
+def exact(before, after):
+    """--exact: kernel by kernel (matched by name, whatever their order), the full instruction text and the .amdhsa_* block."""
+    a, b = exact_kernels(open(before).read()), exact_kernels(open(after).read())
+    only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+    common = sorted(set(a) & set(b))
+
+    def demangle(names):
+        return subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n") if names else []
+    print("== exact: %s -> %s: %d / %d kernels, %d in both" % (before.split("/")[-1], after.split("/")[-1], len(a), len(b), len(common)))
+    print("only in %s: %d" % (before.split("/")[-1], len(only_a)))
+    for dem in demangle(only_a):
+        print("    " + dem)
+    print("only in %s: %d" % (after.split("/")[-1], len(only_b)))
+    for dem in demangle(only_b):
+        print("    " + dem)
+    differ = 0
+    for name, dem in zip(common, demangle(common)):
+        x, y = a[name], b[name]
+        if x == y:
+            continue
+        differ += 1
+        i = next((i for i, (p, q) in enumerate(zip(x, y)) if p != q), min(len(x), len(y)))
+        print("DIFFERS %s\n    line %d of %d / %d: %r -> %r" % (dem, i + 1, len(x), len(y), x[i] if i < len(x) else None, y[i] if i < len(y) else None))
+    print("instruction lines compared: %d" % sum(len(a[n]) for n in common))
+    print("RESULT: %d kernels in both, %d different, %d only in the first, %d only in the second" % (len(common), differ, len(only_a), len(only_b)))
+    return 1 if differ or only_b else 0
+
+
 def main():
     bad = 0
     args = sys.argv[1:]
+    if args and args[0] == "--exact":
+        sys.exit(exact(args[1], args[2]))
     cap = None      # wavefronts per SIMD of the one resident workgroup
     if args and args[0] == "--one-workgroup-per-cu":
         cap = int(args[1]) // 64 // 4

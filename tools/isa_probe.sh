@@ -1,5 +1,6 @@
 #!/bin/bash
-# Assembly of the kernels under study only (-DNF_ISA_PROBE: seconds):  bash tools/isa_probe.sh out.s [-DFLAG=..]...
+# Assembly of the kernels under study only (-DNF_ISA_PROBE: seconds):  bash tools/isa_probe.sh out.s [hipcc options]...
+# (the flow kernel has no -D experiment switches: an experiment is an edit, compared with tools/asm_compare.py --exact)
 # then  python tools/isa_budget.py out.s '<kernel name>' [labels]
 set -e
 OUT=$1; shift
