@@ -2,22 +2,28 @@
 (``oracle/nf_grad_oracle.py``; itself pinned to the forward oracle and to finite differences in
 ``tests/test_oracle.py``).
 
-Tolerances: loss / sd_z 1e-5 relative; every gradient tensor within 2e-4 of its own max |entry|
-(fp32 activations, fp64 accumulation of the parameter sums; the gradients of l_1/b and l_2/b are
-analytically ZERO — BN subtracts the batch mean — so those are compared on an absolute scale);
-BN running statistics 1e-5 of their scale; optimizer updates bit-level vs a float32 numpy
-restatement of the same update rule.
+Tolerances: loss / sd_z 1e-5 relative.  Gradients are held to fp32 resolution by the rule of tests/train_grad_rule.py: per
+entry of every trainable tensor T,  |g - g64| <= max(max(1e-5, 4 e32_T) s_T, grad_noise_allowance),  s_T the tensor's largest
+fp64 entry and e32_T the distance of the same op sequence in float32 (on the fp64 evaluation's ReLU gates) from the fp64 one;
+every case asserts from the oracle alone that e32_T <= 2.5e-5 (so the relative part is at most 1e-4) and that at most 64
+activations sit on their ReLU kink, of which at most 2 may take the other branch.  The CPU tier
+(tests/test_train_grad_rule_cpu.py) shows on the same (model, input) pairs that a plain fp32 evaluation passes and that a BN
+backward normalised by N - 1, one that drops an element of its batch sums, and an unbiased forward variance do not.
+The gradients of l_1/b and l_2/b are analytically ZERO (BN subtracts the batch mean): those are compared on an absolute scale.
+BN running statistics 1e-5 of their scale; optimizer updates bit-level vs a float32 numpy restatement of the same update rule.
+
+On-kink candidate counts of the cases (from the oracle alone) stand next to each case; measured worst |g - g64| / s_T per
+kernel path stand in the docstring of the test that holds the path (run with -s for the per-family figures of every case).
 """
 import os
 
 import numpy as np
 import pytest
 
+import train_grad_rule as R
 from conftest import FULL_ARCH, SHIPPED_DIR, make_inputs, trained_like_variables
 
 pytestmark = pytest.mark.gpu
-
-GRAD_RTOL = 2e-4
 
 
 def _trainer(arch, variables, x_shape=(32, 32, 4), width=4, optim="adam", max_batch=64):
@@ -31,49 +37,46 @@ def _grad_oracle(arch, variables):
     return GradOracle(arch, variables)
 
 
-def _check_grads(tr, grads_dev, ref_grads, loss_scale=1.0, rtol=GRAD_RTOL, oracle=None):
-    """`oracle` (optional): the GradOracle whose evaluation `ref_grads` is; an entry may then also be within the round-off
-    allowance of the sum it is (conftest.py::grad_noise_allowance — a bound the fp64 oracle computes, not a second GPU run)."""
-    from conftest import grad_noise_allowance
-    got = tr.raw_to_variables(grads_dev.cpu().numpy())
-    from oracle.nf_grad_oracle import is_trainable
+def _case(arch, v, x, y, iso, cam, **kw):
+    """The memoised (model, input) of the rule: fp64 and pinned fp32 evaluations, e32, candidate count (tests/train_grad_rule.py)."""
+    return R.case(arch, v, x, y, iso, cam, **kw)
+
+
+def _layer_names(tr):
     from noise_flow_amd import params as P
-    names = [nm for L in tr.layers for nm in P.layer_variable_names(L, tr._tmpl) if nm is not None]
-    gmax = max(np.abs(ref_grads[nm]).max() for nm in names if is_trainable(nm))
-    checked = 0
+    return [nm for L in tr.layers for nm in P.layer_variable_names(L, tr._tmpl) if nm is not None]
+
+
+def _check_grads(tr, grads_dev, c, ref_grads=None, abs_terms=None, old_tol=2e-4, old_allowance=True, exclude=()):
+    """The trainer's gradient against the case's fp64 evaluation (or `ref_grads`: a fixture of it) under the rule, no ReLU branch
+    excused.  `old_tol` / `old_allowance`: what the comparison was before the rule, which the rule may not exceed."""
+    from oracle.nf_grad_oracle import is_trainable
+    got = tr.raw_to_variables(grads_dev.cpu().numpy())
+    names = _layer_names(tr)
     for nm in names:
         if not is_trainable(nm):
             assert np.all(np.asarray(got[nm]) == 0), nm      # masked out
-            continue
-        ref = np.asarray(ref_grads[nm], np.float64)
-        g = np.asarray(got[nm], np.float64).reshape(ref.shape)
-        scale = np.abs(ref).max()
-        if nm.endswith("l_1/b") or nm.endswith("l_2/b"):
-            assert scale < 1e-9 * gmax                       # analytically zero
-            tol0 = 1e-5 * gmax                               # ... and round-off of a sum whose terms cancel exactly
-            if oracle is not None:
-                tol0 = np.maximum(tol0, grad_noise_allowance(oracle, nm).reshape(ref.shape))
-            assert (np.abs(g) <= tol0).all(), (nm, np.abs(g).max(), gmax)
-        else:
-            floor = 1e-6 * gmax
-            tol = rtol * max(scale, floor)
-            if oracle is not None:
-                tol = np.maximum(tol, grad_noise_allowance(oracle, nm).reshape(ref.shape))
-            assert (np.abs(g - ref) <= tol).all(), (nm, np.abs(g - ref).max(), scale, np.max(tol))
-        checked += ref.size
+    c.assert_admissible(exclude)                             # from the reference alone
+    checked, report = R.check_grads(c, got, ref_grads, abs_terms, names, old_tol, old_allowance, exclude)
+    print("train_grad_rule: candidates %d, none excused;  %s" % (c.candidates, R.format_report(report)))
     return checked
+
+
+def _full_arch_case(shipped_variables):
+    x, y = make_inputs(6, seed=41, b1=0.003696)
+    return _case(FULL_ARCH, shipped_variables, x, y, 800, 2)
 
 
 def test_gradients_full_arch_shipped(shipped_variables):
     x, y = make_inputs(6, seed=41, b1=0.003696)
     tr = _trainer(FULL_ARCH, shipped_variables)
     grads, loss = tr.forward_backward(x, y, [0.0], [0.0], [800], [2])
-    o = _grad_oracle(FULL_ARCH, shipped_variables)
-    ref_loss, ref_sd, ref_grads, new_running = o.loss_and_grads(x, y, 800, 2)
+    c = _full_arch_case(shipped_variables)
+    ref_loss, ref_sd, ref_grads, new_running = c.ref
     lv = loss.cpu().numpy()
     assert abs(lv[0] - ref_loss) <= 1e-5 * abs(ref_loss)
     assert abs(lv[1] - ref_sd) <= 1e-5 * ref_sd
-    n = _check_grads(tr, grads, ref_grads)
+    n = _check_grads(tr, grads, c, old_allowance=False)
     assert n == 2431          # 2433 trainables minus the two rescaling_scale variables of sdn_0 / gain_5 (unused)
     # BN running statistics moved by the EMA of the batch moments (layers.py:392-393)
     v = tr.variables
@@ -86,40 +89,56 @@ def test_gradients_full_arch_shipped(shipped_variables):
             assert np.array_equal(np.asarray(v[k], np.float32).reshape(-1), np.asarray(shipped_variables[k], np.float32).reshape(-1)), k
 
 
-@pytest.mark.parametrize("arch,width,hw,B,iso,cam", [("unc|unc", 8, (24, 40), 5, 400, 1),
-                                                     ("sdn5|unc|gain4|unc", 16, (16, 16), 7, 1600, 3),
-                                                     ("sdn5|unc|gain4|unc", 4, (20, 12), 3, 250, 0),     # unknown ISO
-                                                     ("unc", 32, (8, 8), 9, 100, 2),
-                                                     ("sdn4|gain4", 4, (32, 32), 4, 800, 9),            # job_noise_flow.sh "S-G"
-                                                     ("sdn4|unc|gain4", 4, (16, 16), 4, 123, 2),
-                                                     ("sdn5|gain4", 4, (32, 32), 4, 3200, 4),           # "S-G-CAM"
-                                                     ("unc|unc|unc|unc", 4, (32, 32), 3, 100, 2),       # "Ax4"
-                                                     ("sdn5|unc|gain4|unc", 4, (72, 80), 2, 400, 2)])   # beyond 64x64: layer kernels
+# [n] next to a case of the lists below: its on-kink candidate count, from the oracle alone (the rule allows 64).  Of the cases built
+# in a test's body: full arch shipped 6, its fixture 2, the width-48 fixture 0, reversed binding 0, shared variables 0, gain at its optimum 0.
+OTHER_CASES = [("unc|unc", 8, (24, 40), 5, 400, 1),   # [4]
+               ("sdn5|unc|gain4|unc", 16, (16, 16), 7, 1600, 3),   # [6]
+               ("sdn5|unc|gain4|unc", 4, (20, 12), 3, 250, 0),   # [0] unknown ISO
+               ("unc", 32, (8, 8), 9, 100, 2),   # [5]
+               ("sdn4|gain4", 4, (32, 32), 4, 800, 9),   # [0] job_noise_flow.sh "S-G"
+               ("sdn4|unc|gain4", 4, (16, 16), 4, 123, 2),   # [0]
+               ("sdn5|gain4", 4, (32, 32), 4, 3200, 4),   # [0] "S-G-CAM"
+               ("unc|unc|unc|unc", 4, (32, 32), 3, 100, 2),   # [0] "Ax4"
+               ("sdn5|unc|gain4|unc", 4, (72, 80), 2, 400, 2)]   # [5] beyond 64x64: layer kernels
+
+
+@pytest.mark.parametrize("arch,width,hw,B,iso,cam", OTHER_CASES)
 def test_gradients_other_widths_and_shapes(arch, width, hw, B, iso, cam):
+    """Layer kernels (72x80, width 16 and 32 on 8x8 .. 16x16) and tiled stages (width 4 / 8 up to 32x32) on their default routes.
+    Measured worst |g - g64| / s_T: 1.1e-5 (l_2/W of ``unc|unc|unc`` at width 4 on 10x12, e32 3.2e-6: see
+    the tiled test, all four modes the same) on the tiled routes, 4.8e-6 (a mixing vector of width 16 on 16x16, e32 6.1e-7, one branch
+    excused) on the layer kernels; full arch shipped: 6.4e-6 (mixing, e32 8.9e-6)."""
+    c = _other_case(arch, width, hw, B, iso, cam)
+    tr = _trainer(arch, c.variables, (hw[0], hw[1], 4), width)
+    _oracle_check_next_to_kinks(tr, c, old_tol=2e-4)
+
+
+def _other_case(arch, width, hw, B, iso, cam):
     v = trained_like_variables(arch, width, seed=6)
     x, y = make_inputs(B, hw[0], hw[1], seed=17)
-    tr = _trainer(arch, v, (hw[0], hw[1], 4), width)
-    _oracle_check_next_to_kinks(tr, arch, v, x, y, iso, cam, width)
+    return _case(arch, v, x, y, iso, cam)
 
 
-def _oracle_check_next_to_kinks(tr, arch, v, x, y, iso, cam, width, rtol=GRAD_RTOL):
-    """Loss, sd_z and every gradient tensor against the fp64 oracle — ONE evaluation, no re-draws.  The loss is piecewise
-    smooth: an activation within float32 round-off of its ReLU kink may take one branch in the fp64 oracle and the other on
-    the GPU.  The oracle names exactly those activations (margin < 32 units of the round-off of the sum that produced them)
-    and `grads_match_up_to_kinks` accepts the other branch at those and nowhere else; the number it had to excuse is
-    returned (0 on almost every input)."""
-    from conftest import grads_match_up_to_kinks
-    grads, loss = tr.forward_backward(x, y, [0.0], [0.0], [iso], [cam])
+def _oracle_check_next_to_kinks(tr, c, old_tol, label="", exclude=(), admissible=True):
+    """Loss, sd_z and every gradient tensor against the fp64 oracle under the rule of tests/train_grad_rule.py — ONE evaluation,
+    no re-draws.  The loss is piecewise smooth: an activation within float32 round-off of its ReLU kink may take one branch in
+    the fp64 oracle and the other on the GPU.  The oracle names exactly those activations (margin < 32 units of the round-off
+    of the sum that produced them; at most 64 of them, asserted from the oracle alone) and `grads_match_up_to_kinks` accepts the
+    other branch at those and nowhere else; the number it had to excuse (at most 2) is returned (0 on almost every input).
+    `old_tol`: the tolerance this comparison had before the rule, which the rule's bound is asserted not to exceed; `exclude`:
+    tensors that keep it (an open item, named where it is passed); `admissible=False`: a case that cannot meet the rule's
+    preconditions and keeps `old_tol` on every tensor (NOT_ADMISSIBLE)."""
+    from oracle.nf_grad_oracle import is_trainable
+    grads, loss = tr.forward_backward(c.x, c.y, [0.0], [0.0], [c.iso], [c.cam])
     lv = loss.cpu().numpy()
-    o = _grad_oracle(arch, v)
-
-    def compare(ref_loss, ref_sd, ref_grads):
-        assert abs(lv[0] - ref_loss) <= 1e-5 * abs(ref_loss)
-        assert abs(lv[1] - ref_sd) <= 1e-5 * ref_sd
-        _check_grads(tr, grads, ref_grads, rtol=rtol, oracle=o)     # o.grad_abs_terms belongs to the evaluation being compared
+    got = tr.raw_to_variables(grads.cpu().numpy().copy())
+    names = _layer_names(tr)
+    for nm in names:
+        if not is_trainable(nm):
+            assert np.all(np.asarray(got[nm]) == 0), nm      # masked out
     # (an input with MANY on-kink candidates: the branch subset is solved for from the gradients and re-evaluated exactly)
-    excused = grads_match_up_to_kinks(o, x, y, iso, cam, compare, max_kinks=64, got=tr.raw_to_variables(grads.cpu().numpy().copy()))
-    assert excused <= 2, excused
+    _, excused = R.hold_to_rule(c, got, float(lv[0]), float(lv[1]), old_tol=old_tol, names=names, label=label, exclude=exclude,
+                                admissible=admissible)
     return excused
 
 
@@ -593,10 +612,11 @@ def test_gradients_with_the_reversed_template_binding():
     x, y = make_inputs(5, seed=23, b1=0.003696)
     tr = Trainer([32, 32, 4], default_hps(arch=arch), variables=v, binding="sample_first", max_batch=8)
     grads, loss = tr.forward_backward(x, y, [0.0], [0.0], [800], [2])
-    ref_loss, ref_sd, ref_grads, _ = GradOracle(arch, v, binding="sample_first").loss_and_grads(x, y, 800, 2)
+    c = _case(arch, v, x, y, 800, 2, binding="sample_first")
+    ref_loss, ref_sd, ref_grads, _ = c.ref
     lv = loss.cpu().numpy()
     assert abs(lv[0] - ref_loss) <= 1e-5 * abs(ref_loss)
-    _check_grads(tr, grads, ref_grads)
+    _check_grads(tr, grads, c, old_allowance=False)
     # and the two bindings really differ
     other = GradOracle(arch, v, binding="loss_first").loss_and_grads(x, y, 800, 2)[0]
     assert abs(other - ref_loss) > 1e-3 * abs(ref_loss)
@@ -615,7 +635,8 @@ def test_training_golden_fixture(shipped_variables):
     assert abs(lv[0] - float(g["loss"])) <= 1e-5 * abs(float(g["loss"]))
     assert abs(lv[1] - float(g["sd_z"])) <= 1e-5 * float(g["sd_z"])
     ref_grads = {k[len("grad/"):]: g[k] for k in g.files if k.startswith("grad/")}
-    assert _check_grads(tr, grads, ref_grads) == 2431
+    c = _case(FULL_ARCH, shipped_variables, x, y, iso, cam)      # e32 and the allowance: the oracle on the fixture's model and input
+    assert _check_grads(tr, grads, c, ref_grads, c.abs_terms, old_allowance=False) == 2431
     v = tr.variables
     for k in g.files:
         if k.startswith("bn/"):
@@ -636,11 +657,18 @@ def test_training_golden_fixture(shipped_variables):
             assert np.abs(got[solid] - want[solid]).max() <= 0.02 * lr + 1e-6 * np.abs(want[solid]).max(), k
 
 
+def _wide_golden_case():
+    from conftest import ROOT
+    g = np.load(os.path.join(ROOT, "tests", "golden", "train_step_width48.npz"))
+    v = {k[4:]: g[k] for k in g.files if k.startswith("var/")}
+    return _case(str(g["arch"]), v, g["x"], g["y"], float(g["iso"]), float(g["cam"]))
+
+
 def test_wide_training_golden_fixture():
     """tests/golden/train_step_width48.npz (tools/make_golden_train.py wide, from the fp64 autograd oracle; the model is part of
-    the fixture): loss, sd_z, every gradient tensor (2e-4 of its scale or the fixture's round-off allowance of the entry) and the
-    BN EMA of a step at width 48 — the trainer's library-GEMM path (csrc/nf_train_gemm.h)."""
-    from conftest import ROOT, GRAD_NOISE_C
+    the fixture): loss, sd_z, every gradient tensor (the rule of tests/train_grad_rule.py, with the fixture's round-off allowance
+    of the entry) and the BN EMA of a step at width 48 — the trainer's GEMM path (csrc/nf_train_gemm.h)."""
+    from conftest import ROOT
     from oracle.nf_grad_oracle import is_trainable
     from noise_flow_amd import params as P
     g = np.load(os.path.join(ROOT, "tests", "golden", "train_step_width48.npz"))
@@ -654,17 +682,11 @@ def test_wide_training_golden_fixture():
     assert abs(lv[1] - float(g["sd_z"])) <= 1e-5 * float(g["sd_z"])
     got = tr.raw_to_variables(grads.cpu().numpy())
     names = [nm for L in tr.layers for nm in P.layer_variable_names(L, tr._tmpl) if nm is not None and is_trainable(nm)]
-    gmax = max(np.abs(g["grad/" + nm]).max() for nm in names)
-    n = 0
-    for nm in names:
-        ref = np.asarray(g["grad/" + nm], np.float64)
-        allow = GRAD_NOISE_C * 2.0 ** -24 * np.asarray(g["abs/" + nm], np.float64).reshape(ref.shape)
-        a = np.asarray(got[nm], np.float64).reshape(ref.shape)
-        if nm.endswith("l_1/b") or nm.endswith("l_2/b"):
-            assert (np.abs(a) <= np.maximum(1e-5 * gmax, allow)).all(), nm
-        else:
-            assert (np.abs(a - ref) <= np.maximum(GRAD_RTOL * max(np.abs(ref).max(), 1e-6 * gmax), allow)).all(), (nm, np.abs(a - ref).max())
-        n += ref.size
+    c = _wide_golden_case()          # e32 of the rule: the oracle on the fixture's model and input; the fixture is the reference
+    c.assert_admissible()
+    assert c.candidates == 0         # tests/test_grad_oracle_cpu.py: the fixture has no activation on its kink
+    n, report = R.check_grads(c, got, {nm: g["grad/" + nm] for nm in names}, {nm: g["abs/" + nm] for nm in names}, names, old_tol=2e-4)
+    print("train_grad_rule (width 48 fixture):  %s" % R.format_report(report))
     assert n > 10000
     after = tr.variables
     for k in g.files:
@@ -682,9 +704,10 @@ def test_variables_shared_between_layers_receive_the_summed_gradient():
     x, y = make_inputs(5, 16, 16, seed=9)
     tr = _trainer(arch, v, (16, 16, 4), 4)
     grads, loss = tr.forward_backward(x, y, [0.0], [0.0], [800], [2])
-    ref_loss, _, ref_grads, _ = _grad_oracle(arch, v).loss_and_grads(x, y, 800, 2)
+    c = _case(arch, v, x, y, 800, 2)
+    ref_loss, _, ref_grads, _ = c.ref
     assert abs(loss.cpu().numpy()[0] - ref_loss) <= 1e-5 * abs(ref_loss)
-    _check_grads(tr, grads, ref_grads)
+    _check_grads(tr, grads, c, old_allowance=False)
     for _ in range(3):
         tr.step(x, y, [0.0], [0.0], [800], [2], lr=1e-3)
     raw = tr.raw_params()
@@ -723,28 +746,39 @@ def test_a_training_run_is_reproducible_bit_for_bit(shipped_variables, width):
     assert np.array_equal(outs[0][1].view(np.uint32), outs[1][1].view(np.uint32))
 
 
-@pytest.mark.parametrize("arch,width,hw,B", [(FULL_ARCH, 4, (32, 32), 9),          # 1024 threads per patch
-                                             ("sdn5|unc|unc|gain4|unc", 8, (16, 24), 6),   # 512, width 8
-                                             ("unc|unc|unc", 4, (10, 12), 11),      # 256, threads beyond the patch idle
-                                             ("unc|sdn5|unc|unc", 8, (32, 32), 3),  # a coupling chain cut by another layer
-                                             ("unc|gain4|unc|unc|gain4", 4, (8, 8), 40)])
+TILED_CASES = [(FULL_ARCH, 4, (32, 32), 9),   # [5] 1024 threads per patch
+               ("sdn5|unc|unc|gain4|unc", 8, (16, 24), 6),   # [4] 512, width 8
+               ("unc|unc|unc", 4, (10, 12), 11),   # [1] 256, threads beyond the patch idle
+               ("unc|sdn5|unc|unc", 8, (32, 32), 3),   # [3] a coupling chain cut by another layer
+               ("unc|gain4|unc|unc|gain4", 4, (8, 8), 40)]   # [0]
+
+
+def _tiled_case(arch, width, hw, B):
+    v = trained_like_variables(arch, width, seed=8)
+    x, y = make_inputs(B, hw[0], hw[1], seed=23)
+    return _case(arch, v, x, y, 800, 2)
+
+
+@pytest.mark.parametrize("arch,width,hw,B", TILED_CASES)
 def test_tiled_stages_and_layer_kernels_agree(arch, width, hw, B, monkeypatch):
     """The trainer runs couplings of width <= 8 on patches of <= 1024 pixels through one-workgroup-per-patch tiled stages
     (two launches per coupling and pass) and everything else through one kernel per layer stage; NF_TRAIN_TILED selects
     (bit 0 backward, bit 1 forward).  Both must give the oracle's loss and gradients; between themselves they only differ
-    in how the fp32 partial sums are grouped, so the logged loss agrees to 1e-6 and gradients to 1e-4 of their scale."""
-    v = trained_like_variables(arch, width, seed=8)
-    x, y = make_inputs(B, hw[0], hw[1], seed=23)
+    in how the fp32 partial sums are grouped, so the logged loss agrees to 1e-6 and gradients to 1e-4 of their scale.
+    Every mode is held to the oracle under the rule of tests/train_grad_rule.py, no ReLU branch excused.
+    Measured worst |g - g64| / s_T: 1.08e-5 (l_2/W, 10x12 patches, e32 3.2e-6, bound 1.3e-5) in every mode; elsewhere
+    at most 6.0e-6 (a mixing vector, full arch, e32 6.6e-6)."""
+    c = _tiled_case(arch, width, hw, B)
+    v, x, y = c.variables, c.x, c.y
     res = {}
     for mode in ("0", "1", "2", "3"):
         monkeypatch.setenv("NF_TRAIN_TILED", mode)
         tr = _trainer(arch, v, (hw[0], hw[1], 4), width)
         grads, loss = tr.forward_backward(x, y, [0.0], [0.0], [800], [2])
         res[mode] = (grads.cpu().numpy().copy(), loss.cpu().numpy().copy(), tr.raw_params())
-        if mode == "3":
-            ref_loss, ref_sd, ref_grads, _ = _grad_oracle(arch, v).loss_and_grads(x, y, 800, 2)
-            assert abs(res[mode][1][0] - ref_loss) <= 1e-5 * abs(ref_loss)
-            _check_grads(tr, grads, ref_grads)
+        assert abs(res[mode][1][0] - c.ref[0]) <= 1e-5 * abs(c.ref[0]), mode
+        print("NF_TRAIN_TILED=%s" % mode, end="  ")
+        _check_grads(tr, grads, c, old_allowance=False)
         tr.close()
     g0, l0, p0 = res["0"]
     for mode in ("1", "2", "3"):
@@ -754,27 +788,48 @@ def test_tiled_stages_and_layer_kernels_agree(arch, width, hw, B, monkeypatch):
         assert np.allclose(p, p0, rtol=1e-5, atol=1e-7), mode      # the BN running moments moved by the forward pass
 
 
-@pytest.mark.parametrize("arch,width,hw,B", [("sdn5|unc|unc|gain4|unc", 32, (32, 32), 5),
-                                             ("unc|unc", 32, (20, 12), 7),          # ragged: tiles of 32 pixels straddle rows
-                                             ("unc", 32, (5, 7), 3),                # a patch smaller than one 64-pixel step
-                                             ("unc|gain4|unc", 32, (64, 64), 2),    # per-patch operand tiles too large for LDS
-                                             ("sdn5|unc|unc", 16, (16, 24), 6),     # width 16: the same templates
-                                             ("unc|unc", 32, (8, 8), 1100)])        # more patches than slots: the persistent loops
+WIDE_CASES = [("sdn5|unc|unc|gain4|unc", 32, (32, 32), 5),   # [44]
+              ("unc|unc", 32, (20, 12), 7),   # [16] ragged: tiles of 32 pixels straddle rows
+              ("unc", 32, (5, 7), 3),   # [0] a patch smaller than one 64-pixel step
+              ("unc|gain4|unc", 32, (64, 64), 2),   # [45] per-patch operand tiles too large for LDS
+              ("sdn5|unc|unc", 16, (16, 24), 6),   # [3] width 16: the same templates
+              ("unc|unc", 32, (8, 8), 1100),   # [373] more patches than slots: the persistent loops, 138 slots in the finalisers
+              ("unc|unc", 32, (2, 3), 1100)]   # [42] more patches than slots, under the rule
+# The 8x8 x 1100 case is NOT ADMISSIBLE under the rule: 9 million ReLU inputs put 373 activations on their kink at any input of that
+# size (the rule allows 64).  It stays, with the comparison it had (1e-3 of each tensor's scale, both modes, the two-path distance),
+# for what only its size reaches: 138 slots (the finalisers' second and third pass, their ragged tail), 138 workgroups of the flat
+# kernels.  The same 1100 patches of 2x3 pixels (13 slots) are held to the rule next to it.
+NOT_ADMISSIBLE = {("unc|unc", 32, (8, 8), 1100), ("unc|unc", 96, (32, 32), 6)}
+
+
+def _wide_case(arch, width, hw, B):
+    v = trained_like_variables(arch, width, seed=9)
+    x, y = make_inputs(B, hw[0], hw[1], seed=29)
+    return _case(arch, v, x, y, 400, 1)
+
+
+@pytest.mark.parametrize("arch,width,hw,B", WIDE_CASES)
 def test_wide_matrix_core_stages_and_layer_kernels_agree(arch, width, hw, B, monkeypatch):
     """At width 32 the l_2 forward / backward stages and the three filter gradients run as GEMMs on v_mfma_f32_32x32x2_f32
     (exact fp32), the slot sums are added up by one-pass finaliser kernels and the BN1 backward walks the tensors flat;
     NF_TRAIN_WIDE_MFMA=0 keeps the one-kernel-per-layer-stage path.  Both give the oracle's gradients and differ from
-    each other only by summation order."""
-    v = trained_like_variables(arch, width, seed=9)
-    x, y = make_inputs(B, hw[0], hw[1], seed=29)
+    each other only by summation order; each is held to the oracle under the rule of tests/train_grad_rule.py.
+    Measured worst |g - g64| / s_T: layer kernels 5.7e-6 (a mixing vector, 20x12, e32 1.2e-6); matrix-core stages 1.7e-5 and
+    1.4e-5 (mixing vectors on 20x12 and at width 16, e32 1.2e-6 and 5.3e-7: inside the oracle's round-off allowance), filter gradients
+    at most 7.1e-6 — but on the 5x7 patches, where l_1/W is at 1.1e-5 and l_2/W at 1.43e-5 (e32 5e-7): OPEN, see below."""
+    c = _wide_case(arch, width, hw, B)
+    v, x, y = c.variables, c.x, c.y
     res = {}
     for mode in ("0", "4095"):
         monkeypatch.setenv("NF_TRAIN_WIDE_MFMA", mode)
         tr = _trainer(arch, v, (hw[0], hw[1], 4), width, max_batch=max(64, B))
         grads, loss = tr.forward_backward(x, y, [0.0], [0.0], [400], [1])
         res[mode] = (grads.cpu().numpy().copy(), loss.cpu().numpy().copy(), tr.raw_params())
-        if mode == "4095":
-            _oracle_check_next_to_kinks(tr, arch, v, x, y, 400, 1, width, rtol=1e-3)
+        # OPEN: on the 5x7 patches the matrix-core stages are at 1.1e-5 (l_1/W) and 1.4e-5 (l_2/W) of the tensor's scale, the rule
+        # allows 1e-5 (e32 5e-7); those two tensors keep 1e-3 there (tests/train_grad_rule.py, "Open")
+        still_open = tuple(k for k in c.e32 if k.endswith(("l_1/W", "l_2/W"))) if (mode == "4095" and hw == (5, 7)) else ()
+        _oracle_check_next_to_kinks(tr, c, old_tol=1e-3, label="NF_TRAIN_WIDE_MFMA=%s" % mode, exclude=still_open,
+                                    admissible=(arch, width, hw, B) not in NOT_ADMISSIBLE)
         tr.close()
     (g0, l0, p0), (g1, l1, p1) = res["0"], res["4095"]
     assert np.allclose(l1, l0, rtol=1e-6, atol=0), (l1, l0)
@@ -820,7 +875,8 @@ def test_round_off_allowance_where_a_gradient_cancels():
     v = trained_like_variables(arch, 4, seed=2)
     v[key] = np.asarray([0.016486794], np.float32)
     x, y = make_inputs(8, 32, 32, seed=5)
-    o = _grad_oracle(arch, v)
+    c = _case(arch, v, x, y, 800, 2)
+    o = c.oracle
     ref_loss, _, ref_grads, _ = o.loss_and_grads(x, y, 800, 2)
     ref = float(np.asarray(ref_grads[key]).reshape(-1)[0])
     terms = float(np.asarray(o.grad_abs_terms[key]).reshape(-1)[0])
@@ -834,38 +890,69 @@ def test_round_off_allowance_where_a_gradient_cancels():
     seen = max(abs(a - ref), abs(b - ref), abs(a - b))
     assert abs(a - ref) <= allow and abs(b - ref) <= allow and abs(a - b) <= allow, (a, b, ref, allow)
     assert seen > 0 and allow <= 1000.0 * seen, (a, b, ref, allow, seen)
-    _check_grads(tr, grads, ref_grads, oracle=o)                      # and every other tensor of the step at the usual tolerance
+    # ... and every other tensor of the step under the rule — but for the other variables of the sdn / gain layers, whose gradients
+    # cancel with the gain's (pinned e32 of beta2: 1.2e-4, beyond the rule's precondition): those stay at 2e-4 of their scale
+    _check_grads(tr, grads, c, exclude=tuple(k for k in c.e32 if k.startswith("model/sdn_gain/")))
 
 
-@pytest.mark.parametrize("arch,width,hw,B,iso,cam", [("sdn5|unc|gain4|unc", 128, (8, 8), 3, 800, 2),
-                                                     ("unc|unc", 64, (12, 10), 4, 100, 1),
-                                                     ("sdn5|unc|unc|gain4|unc", 50, (9, 7), 5, 400, 0),      # not a multiple of 4
-                                                     ("unc", 512, (6, 6), 2, 1600, 3),                        # the reference's default width
-                                                     ("unc|unc", 96, (32, 32), 6, 800, 2),
-                                                     ("sdn5|unc|unc|gain4", 24, (10, 12), 4, 800, 2),        # between two kernel widths
-                                                     ("unc|unc", 5, (8, 8), 3, 100, 0),
-                                                     ("|".join(["unc"] * 17), 12, (6, 6), 3, 400, 1),       # more couplings than one store / reduce launch holds
-                                                     ("unc|unc", 36, (64, 64), 2, 800, 2),                  # 64x64 patches; a ragged 64-channel tile
-                                                     ("unc", 200, (16, 24), 1, 100, 0),                     # one patch; two channel tiles, the second ragged
-                                                     ("sdn5|unc|gain4", 132, (7, 5), 3, 1600, 3),           # 35 pixels per patch; 128 + 4 channels
-                                                     ("unc", 2, (8, 6), 3, 3200, 4)])    # (width 1: torch's CPU conv backward refuses the oracle's graph)
+BEYOND_32_CASES = [("sdn5|unc|gain4|unc", 128, (8, 8), 3, 800, 2),   # [8]
+                   ("unc|unc", 64, (12, 10), 4, 100, 1),   # [8]
+                   ("sdn5|unc|unc|gain4|unc", 50, (9, 7), 5, 400, 0),   # [4] not a multiple of 4
+                   ("unc", 512, (6, 6), 2, 1600, 3),   # [19] the reference's default width
+                   ("unc|unc", 96, (32, 32), 6, 800, 2),   # [215] NOT ADMISSIBLE (more than 64 on their kink): keeps 1e-3; the last case is its admissible twin
+                   ("sdn5|unc|unc|gain4", 24, (10, 12), 4, 800, 2),   # [1] between two kernel widths
+                   ("unc|unc", 5, (8, 8), 3, 100, 0),   # [0]
+                   ("|".join(["unc"] * 17), 12, (6, 6), 3, 400, 1),   # [1] more couplings than one store / reduce launch holds
+                   ("unc|unc", 36, (64, 64), 2, 800, 2),   # [57] 64x64 patches; a ragged 64-channel tile
+                   ("unc", 200, (16, 24), 1, 100, 0),   # [17] one patch; two channel tiles, the second ragged
+                   ("sdn5|unc|gain4", 132, (7, 5), 3, 1600, 3),   # [4] 35 pixels per patch; 128 + 4 channels
+                   ("unc", 2, (8, 6), 3, 3200, 4),   # [0] (width 1: torch's CPU conv backward refuses the oracle's graph)
+                   ("unc", 96, (32, 32), 2, 800, 2)]   # [54] width 96 on 32x32 under the rule (unc|unc on 6 patches above is not admissible)
+
+
+def _beyond_32_case(arch, width, hw, B, iso, cam):
+    # Inputs of seed 19, except where the pinned e32 of the reference on them is at or near the rule's cap of 2.5e-5: width 24,
+    # 3.1e-5 (one U_vec) -> 1.2e-6 on seed 22; width 132, 2.1e-5 -> 1.0e-6 on seed 21.  The 17 couplings of width 12 are the case
+    # nearest the cap, and e32 of one and the same input differs between host CPUs there (seed 19: 2.3e-5 on one, 3.2e-5 on another;
+    # a scalar rescaling_scale0 or log_S that nearly cancels).  Of 48 inputs (seeds 19 .. 34 at three noise levels), evaluated on two
+    # hosts, seed 33 has the smallest worst e32: 1.3e-5 and 1.2e-5, a factor 1.9 inside the cap; no input has more room.
+    seed = {24: 22, 132: 21, 12: 33}.get(width, 19)
+    x, y = make_inputs(B, hw[0], hw[1], seed=seed)
+    return _case(arch, _wide_variables(arch, width), x, y, iso, cam)
+
+
+def _still_open_beyond_32(c, width):
+    """OPEN (tests/train_grad_rule.py, "Open"): two tensors of the GEMM route that are just outside the rule and keep 1e-3.
+    Width 200 on one 16x24 patch: l_1/W at 1.44e-5 of its scale, the rule allows 1e-5 (e32 4e-7).  Width 132 on three 7x5 patches:
+    l_2/W at 1.08e-5, the rule allows 1e-5 (e32 6e-7) — the fp32 products and the forced bf16 x 6 modes alike.
+    And one whole case: the 17 couplings of width 12 on three 6x6 patches, where l_1/W is at 2.4e-5 of its scale (the rule allows 1e-5,
+    e32 2.2e-6), a mixing L_vec at 2.6e-5 (1.9e-5, e32 4.7e-6), l_2/W at 1.4e-5 (1.3e-5) and further tensors beside them: every tensor
+    of that case keeps 1e-3 (its preconditions are asserted all the same)."""
+    if width == 12:
+        return tuple(c.e32)
+    sfx = {200: "l_1/W", 132: "l_2/W"}.get(width)
+    return tuple(k for k in c.e32 if sfx and k.endswith(sfx))
+
+
+@pytest.mark.parametrize("arch,width,hw,B,iso,cam", BEYOND_32_CASES)
 def test_gradients_at_coupling_widths_beyond_32(arch, width, hw, B, iso, cam):
     """sidd/ArgParser.py:43 defaults --width to 512 and train_noise_flow.py:50-77 trains at whatever width is set: beyond 32 the
     step's dense products are this repo's fp32 matrix-core GEMMs (csrc/nf_train_mm.h: pixels on M resp. on K, BN + ReLU and the BN
     backward formed while the operands are staged, batch sums in the epilogues) between kernels over [pixel][w] tensors of run-time
     width (csrc/nf_train_gemm.h) — and so are the widths below 32 that have no kernels of their own (1 .. 31 except 4, 8, 16):
     the trainer refuses nothing the reference's flag accepts up to 512.  Loss, sd_z, every gradient tensor and the BN running statistics against the fp64 autograd
-    oracle; one Adam step against the float32 restatement of TF's update rule."""
+    oracle (gradients under the rule of tests/train_grad_rule.py); one Adam step against the float32 restatement of TF's update rule.
+    Measured worst |g - g64| / s_T on the fp32 products: 9.5e-6 (l_1/W at width 512, e32 9.1e-7), at most 5.9e-6 elsewhere — but
+    l_1/W at width 200 (1.44e-5), l_2/W at width 132 (1.08e-5) and the 17 couplings of width 12 (l_1/W 2.4e-5, e32 2.2e-6): OPEN,
+    _still_open_beyond_32.  The unc|unc case of width 96 on six patches is not admissible (NOT_ADMISSIBLE) and keeps 1e-3; it is at
+    1.6e-6 (a mixing vector)."""
     from oracle.nf_grad_oracle import adam_step
-    v = trained_like_variables(arch, width, seed=width)
-    for k in v:     # activations of O(1) at every width (the helper's weights are tuned for width 4)
-        if k.endswith("l_2/W") or k.endswith("l_last/W"):
-            v[k] = (v[k] * np.float32((4.0 / width) ** 0.5)).astype(np.float32)
-    x, y = make_inputs(B, hw[0], hw[1], seed=19)
+    c = _beyond_32_case(arch, width, hw, B, iso, cam)      # activations of O(1) at every width: _wide_variables
+    v, x, y = c.variables, c.x, c.y
     tr = _trainer(arch, v, (hw[0], hw[1], 4), width)
-    _oracle_check_next_to_kinks(tr, arch, v, x, y, iso, cam, width, rtol=1e-3)
-    o = _grad_oracle(arch, v)
-    _, _, ref_grads, new_running = o.loss_and_grads(x, y, iso, cam)
+    _oracle_check_next_to_kinks(tr, c, old_tol=1e-3, exclude=_still_open_beyond_32(c, width),
+                                admissible=(arch, width, hw, B) not in NOT_ADMISSIBLE)
+    _, _, ref_grads, new_running = c.ref
     got = tr.variables
     for k, want in new_running.items():          # BN running statistics moved by the EMA of the batch moments (layers.py:392-393)
         assert np.abs(np.asarray(got[k], np.float64).reshape(want.shape) - want).max() <= 1e-5 * max(np.abs(want).max(), 1e-3), k
@@ -912,26 +999,31 @@ def _child(mode, *args):
 def _child_oracle_check(arch, width, H, W, B, iso, cam, out):
     """(child) the step under the NF_MM_MODE of this process against the fp64 oracle, exactly as
     test_gradients_at_coupling_widths_beyond_32 holds the default dispatch; leaves the raw gradient in `out`."""
-    v = _wide_variables(arch, width)
-    x, y = make_inputs(B, H, W, seed=19)
+    c = _beyond_32_case(arch, width, (H, W), B, iso, cam)
+    v, x, y = c.variables, c.x, c.y
     tr = _trainer(arch, v, (H, W, 4), width)
-    _oracle_check_next_to_kinks(tr, arch, v, x, y, iso, cam, width, rtol=1e-3)
-    _check_running_statistics(tr, _grad_oracle(arch, v).loss_and_grads(x, y, iso, cam)[3])
+    _oracle_check_next_to_kinks(tr, c, old_tol=1e-3, label="NF_MM_MODE=%s" % os.environ.get(MM_MODE), exclude=_still_open_beyond_32(c, width),
+                                admissible=(arch, width, (H, W), B) not in NOT_ADMISSIBLE)
+    _check_running_statistics(tr, c.ref[3])
     tr.close()
     g, _ = _trainer(arch, v, (H, W, 4), width).forward_backward(x, y, [0.0], [0.0], [iso], [cam])      # a fresh trainer's first step, as the parent's
     np.save(out, g.cpu().numpy())
 
 
 @pytest.mark.parametrize("mode", [2, 3])
-@pytest.mark.parametrize("arch,width,hw,B,iso,cam", [("sdn5|unc|gain4", 132, (7, 5), 3, 1600, 3), ("unc|unc", 96, (32, 32), 6, 800, 2)])
+@pytest.mark.parametrize("arch,width,hw,B,iso,cam", [("sdn5|unc|gain4", 132, (7, 5), 3, 1600, 3), ("unc|unc", 96, (32, 32), 6, 800, 2),
+                                                     ("unc", 96, (32, 32), 2, 800, 2)])
 def test_forced_bf16x6_modes_against_the_oracle(arch, width, hw, B, iso, cam, mode, tmp_path):
     """NF_MM_MODE = 2 (8 wavefronts) and 3 (4 wavefronts, one operand buffer) at sizes the default dispatch leaves to the fp32 twin
     and the kink rule handles: loss, sd_z, every gradient tensor and the BN running statistics against the fp64 oracle, in a fresh
-    child process.  That the switch was taken: the child's raw gradient is not, bit for bit, the default dispatch's."""
+    child process.  That the switch was taken: the child's raw gradient is not, bit for bit, the default dispatch's.
+    Measured worst |g - g64| / s_T, modes 2 and 3 alike: width 96, 3.2e-6 (l_1/W, e32 7.4e-7); width 132, 7.2e-6 (l_1/W, e32 4.4e-7)
+    and l_2/W at 1.08e-5 (e32 6.4e-7) — as the fp32 products there: OPEN, _still_open_beyond_32."""
     out = os.path.join(str(tmp_path), "grad.npy")
     _child(mode, "oracle", arch, width, hw[0], hw[1], B, iso, cam, out)
-    x, y = make_inputs(B, hw[0], hw[1], seed=19)
-    tr = _trainer(arch, _wide_variables(arch, width), (hw[0], hw[1], 4), width)
+    c = _beyond_32_case(arch, width, hw, B, iso, cam)
+    x, y = c.x, c.y
+    tr = _trainer(arch, c.variables, (hw[0], hw[1], 4), width)
     g, _ = tr.forward_backward(x, y, [0.0], [0.0], [iso], [cam])
     g = g.cpu().numpy()
     forced = np.load(out)
