@@ -10,6 +10,63 @@ accepts a set of ReLU gates to invert, and reports per patch the activations tha
 On-kink, exactly as ``oracle.nf_grad_oracle.GradOracle._relu`` but with the RUNNING mean: margin |h - mean| below
 ``KINK_ULPS`` = 32 units of u = 2^-24 * (sum |input| |weight| + |bias| + |mean|) + err_in, err_in = the round-off l_2's inputs
 carry (l_1's u / sqrt(var + eps) pushed through |W2|).
+
+THE RULE the three nf_nll_grad kernels are held to (``compare_with_kink_rule``; tests/test_gpu_nll_grad.py, _wide.py, _tiled.py), per
+patch and tensor g in (gx, gy), in two norms that must BOTH hold:
+
+    raw        max_e |g - g64|[e]          <=  max(1e-5, 4 e32)   max_e |g64[e]|
+    whitened   max_e |g - g64|[e] / w[e]   <=  max(1e-5, 4 e32w)  max_e |g64[e]| / w[e]
+
+g64 is torch.autograd of ``NllGradRef.nll`` in float64.  e32 / e32w is the distance, in the same norm, of the same graph in
+float32 with every ReLU gate pinned to the gate the float64 evaluation took (``PinnedRef``): round-off alone.  1e-5 is the
+project's tensor tolerance, 4 covers another summation order plus the rounding of the reversible sweep's reconstruction.  A patch
+that misses either norm is excused only by ONE subset of at most MAX_EXCUSED_KINKS of its on-kink gates whose inversion in the
+float64 reference makes both norms pass.  Nothing a kernel computes enters the bound.
+
+The weights (``rule_weights``) come from the model, y, ISO and cam alone, in fp64.  w_x[p] is the product of 1 / scale[p] over the
+leading run of elementwise layers (sdn and gain kinds in front of the first mixing or coupling layer; 1 if the model starts with
+a mixing layer); w_y[p] is the sum over all sdn-kind layers k of a_k / (2 s_k^2[p]).  Why: with the shipped model's leading sdn5,
+gx ~ 1 / s(y) and gy ~ a / (2 s^2(y)), and the few pixels with y near 0 set the patch maximum — max / median |gx| is 170 .. 260 and
+max / median |gy| 800 .. 4300 on 32x32 .. 96x80 patches, so the raw norm alone allows the MEDIAN element of gy an error of 1 .. 4 %
+of itself.  Divided by w the ranges are 31 .. 34 and 7 .. 8.  On models whose sdn scale is flat (``trained_like_variables``,
+``paper_like_variables``) the two norms coincide.  Each GPU file has at least one case with max / median |gy| >= 100, asserted.
+
+Preconditions (``reference_conditions``), asserted from the reference alone before a kernel's output is read: pinned e32 <= E32_MAX
+= 5e-6 for every patch and tensor in both norms, so the tolerance never exceeds 2e-5; at most 6 on-kink activations per patch.  A
+case that misses one gets another seed; the caps do not move.  (One did: the shipped 1x5 case at seed 0 has e32 5.3e-6 / 5.7e-6.)
+
+The sweep (``backward_sweep``): the same gradient written out layer by layer, last layer first — mixing, coupling (l_last, l_2, l_1
+transposed through the recorded gates), sdn and gain kinds, the prior.  In float64 it is autograd to 2e-15 of max|grad|.  It hosts
+what autograd cannot express: the REVERSIBLE float32 flavour, the arithmetic csrc/nf_grad.hip documents (every layer's input is
+rebuilt from its output, the Jacobians are taken from the rebuilt values, the layers in front of the first coupling take their
+values forward from x), and the mutants of tests/test_nll_grad_rule_cpu.py.
+
+Measured on the CPU, float32 flavours against float64, worst patch of every accuracy case of the three GPU files (49 cases):
+  * pinned autograd (e32): 1.3e-7 .. 2.9e-6 in either norm (3.6e-6 on a second host CPU; it moves by up to a third between hosts);
+  * stored-activation sweep: the same within a few 1e-7; reversible sweep: at most 0.40 of the bound — shipped 32x32 gx 1.1e-6 raw /
+    1.8e-6 whitened, gy 1.3e-6 / 1.2e-6; shipped 64x64 4.1e-6 whitened (bound 1.14e-5) — with ONE case beyond half of it: shipped 65x64, gx of image 0
+    7.2e-6 raw (bound 1e-5; 1.7e-6 whitened), the pixel with the largest 1 / s carrying a quarter of max|gx s|;
+  * ``sdn5|unc|unc|gain4|unc`` at width 16 on 16x16: 1.2e-6 (gx) / 5.6e-7 (gy) reversible, as the stored flavour.  With the leading
+    sdn layer ALSO rebuilt through the stack gy is 1.9e-5 and misses the rule: that is why the kernel takes those values forward.
+
+Teeth (fp64 mutants, ratio of the worst element to the smaller of the two bounds, over all cases they apply to):
+  * l_1's transposed conv of the middle coupling drops one corner tap along the last row: 255 .. 4.3e4;
+  * the -1 of d nll / d ls omitted in the last column (every coupling): 183 .. 1e5;
+  * gy of the trailing sdn layer not added (``sdn5|unc|gain|unc|sdn3``): 1e5;
+  * one gy element (the one with the median w_y) off by 1e-3 of itself: 3.0 .. 100, on the shipped model 9.5 .. 31 — where
+    the raw norm alone has it at 0.04 .. 0.13 of ITS bound on every case from 32x32 upward (the wide file's shipped-sdn case
+    included): MISSED; one gx element (linear pixel 256) off by 1e-3: 0.58 .. 78, missed by the raw norm alone on shipped 64x64,
+    65x64, 64x65, 80x72;
+  * a halo one pixel short in a segment of ONE coupling (shipped leading layers, 90x70): 60.
+DROPPED (the rule does not resolve them; measured ratio): the halo one pixel short in a segment of TWO couplings, 2.9e-4 (fp64 pins
+it, tests/test_grad_tiles_cpu.py); the single gx element on tiled shipped 80x72 0.58, tiled vocab rows 1.81, tiled shipped 64x65 2.5
+(host-dependent through e32) — there linear pixel 256 is an element below 2 % of the patch's largest |gx| / w_x.  Never dropped on
+the shipped model: the two coupling mutants and the gy element.
+
+Open: nothing.  Measured on an MI355X, every kernel meets both norms on every case (one patch of the wide 31x29 case by the kink
+rule, as before): worst distance raw / whitened — scalar kernel gx 2.4e-6 / 3.4e-6, gy 2.6e-6 / 3.2e-6; matrix-core kernel gx 2.1e-6 /
+2.1e-6, gy 1.9e-6 / 1.9e-6 (shipped-sdn case: figures in its docstring); tiled mode gx 2.6e-6 / 3.1e-6, gy 4.9e-6 / 3.3e-6 (0.49 of
+the bound, the largest ratio of all).
 """
 import itertools
 
@@ -21,6 +78,9 @@ from oracle import nf_oracle as O
 
 KINK_ULPS = 32.0
 MAX_EXCUSED_KINKS = 3        # conftest.MAX_EXCUSED_KINKS
+REL_TOL = 1e-5               # the project's tensor tolerance (conftest.close_elem)
+E32_FACTOR = 4.0             # another summation order plus the rounding of the reversible sweep's reconstruction
+E32_MAX = 5e-6               # precondition on the pinned e32 of every patch and tensor, in both norms
 
 
 def _scalar_pair(L, iso, cam):
@@ -163,39 +223,161 @@ class NllGradRef:
         return nll.detach().double().numpy(), back(grads[0]), (back(grads[1]) if needs_y else None)
 
 
-def patch_rel_err(got, ref):
-    """max|got - ref| / max|ref| per patch → [B]."""
+class PinnedRef(NllGradRef):
+    """NllGradRef with two additions, neither of which touches the fp64 reference the kernel is compared with.
+
+    Every (input, precision, flips) is evaluated once: the conditions, the comparison and the sweeps below share it.
+
+    The float32 flavour applies the ReLU gates of the float64 evaluation of the same input instead of its own signs.  e32 is the
+    yardstick for fp32 ROUNDING; an on-kink activation whose sign a plain float32 evaluation flips (which depends on the host
+    library's fp32 summation order) puts e32 of that patch at the size of a real error — 5.5e-3 has been seen for patch 0 of the
+    31x29 case of tests/test_gpu_nll_grad_wide.py, whose pinned e32 is 8e-7 — and the tolerance 4 e32 with it.  With the gates
+    pinned e32 is round-off alone, so the tolerance max(1e-5, 4 e32) can only be tighter than with the plain helper.  The
+    precondition e32 <= E32_MAX is then a statement about the PINNED e32: it is easier to meet than the same bound on a plain
+    float32 evaluation (which that 31x29 patch would miss where the flip occurs), and says that round-off alone never inflates the
+    tolerance; what a flipped gate does to the kernel is the kink rule's business, with the kink count asserted first."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self._memo = {}
+        self._record = self._pin = None
+
+    def _relu(self, hn, h, mean, var, amp, site, flips, err_in=None):
+        out, err = super()._relu(hn, h, mean, var, amp, site, flips, err_in)
+        if self._record is not None:
+            self._record[site] = hn.detach() > 0
+        if self._pin is not None:
+            out = hn * self._pin[site].to(hn.dtype)
+        return out, err
+
+    def nll_and_grads(self, x, y, iso=None, cam=None, dtype=np.float64, flips=()):
+        inp = (id(x), id(y), repr(iso), repr(cam))
+        key = inp + (np.dtype(dtype).name, tuple(flips))
+        if key not in self._memo:
+            f32 = np.dtype(dtype) == np.float32
+            if f32:
+                self.nll_and_grads(x, y, iso, cam, np.float64)   # its gates
+            self._record = {} if (not f32 and not flips) else None
+            self._pin = self._memo[inp + ("float64", ())][4] if f32 else None
+            try:
+                out = super().nll_and_grads(x, y, iso, cam, dtype, flips)
+            finally:
+                gates, self._record, self._pin = self._record, None, None
+            self._memo[key] = (out, list(self.kinks), x, y, gates)
+        out, kinks = self._memo[key][:2]
+        self.kinks = list(kinks)
+        return out
+
+    def gates(self, x, y, iso=None, cam=None):
+        """{(layer index, 1 | 2): bool [B, C, H, W]} of the float64 evaluation without flips."""
+        self.nll_and_grads(x, y, iso, cam, np.float64)
+        return self._memo[(id(x), id(y), repr(iso), repr(cam), "float64", ())][4]
+
+
+def patch_rel_err(got, ref, w=None):
+    """max|got - ref| / max|ref| per patch → [B]; with weights `w`, both maxima over the elements divided by w."""
     B = ref.shape[0]
-    d = np.abs(np.asarray(got, np.float64) - ref).reshape(B, -1).max(axis=1)
-    return d / np.abs(ref).reshape(B, -1).max(axis=1)
+    ref = np.asarray(ref, np.float64)
+    d = np.abs(np.asarray(got, np.float64) - ref)
+    r = np.abs(ref)
+    if w is not None:
+        d, r = d / w, r / w
+    return d.reshape(B, -1).max(axis=1) / r.reshape(B, -1).max(axis=1)
+
+
+def rule_weights(ref, y, iso, cam, shape):
+    """(w_x, w_y) [B, H, W, 4] float64 of the whitened norm — from the model, y, ISO and cam alone.
+
+    w_x: the product of 1 / scale over the leading run of elementwise layers (sdn and gain kinds in front of the first mixing or
+    coupling layer), 1 if the model starts with a mixing layer.  w_y: the sum over all sdn-kind layers k of a_k / (2 s_k^2),
+    None if the model has no sdn layer (gy is not compared then)."""
+    B = shape[0]
+    n = 4 * shape[1] * shape[2]
+    isos = np.broadcast_to(np.asarray(iso, np.float64).reshape(-1), (B,)) if iso is not None else [None] * B
+    cams = np.broadcast_to(np.asarray(cam, np.float64).reshape(-1), (B,)) if cam is not None else [None] * B
+    y64 = None if y is None else np.asarray(y, np.float64)
+    wx, wy, leading = np.ones(shape, np.float64), None, True
+    for L in ref.layers:
+        t = L["type"]
+        if t.startswith("sdn"):
+            ab = [_scalar_pair(L, isos[b], cams[b]) for b in range(B)]
+            a, b_ = (np.asarray([v[k] for v in ab], np.float64).reshape(B, 1, 1, 1) for k in (0, 1))
+            s2 = a * y64 + b_
+            wy = (0.0 if wy is None else wy) + np.abs(a) / (2.0 * s2)
+            if leading:
+                wx = wx / np.sqrt(s2)
+        elif t in ("conv1x1", "coupling"):
+            leading = False
+        elif leading:
+            wx = wx / np.asarray([_gain(L, isos[b], n)[0] for b in range(B)], np.float64).reshape(B, 1, 1, 1)
+    assert np.all(wx > 0) and np.all(np.isfinite(wx)) and (wy is None or (np.all(wy > 0) and np.all(np.isfinite(wy))))
+    return wx, wy
+
+
+def kinks_per_patch(ref, width, x, y, iso, cam):
+    """[(site, flat index)] of the on-kink activations of every patch, from the float64 evaluation."""
+    ref.nll_and_grads(x, y, iso, cam, np.float64)
+    B, H, W, _ = x.shape
+    return [[(s, k) for s, k, _ in ref.kinks if k // (width * H * W) == b] for b in range(B)]
+
+
+def reference_conditions(ref, width, x, y, iso, cam, max_on_kink=6, min_gy_range=None, log=print):
+    """The preconditions of a case, from the reference alone, before a kernel's output is looked at: the pinned e32 of every patch
+    and tensor, in the raw and in the whitened norm, is at most E32_MAX; no patch has more than `max_on_kink` on-kink activations;
+    and, where the case is one of those that carry the dynamic range, max / median |gy| >= `min_gy_range` over the case.
+    → {"gx": e32 [B], "gx/w": .., "gy": .., "gy/w": ..}."""
+    _, gx64, gy64 = ref.nll_and_grads(x, y, iso, cam, np.float64)
+    kinks = list(ref.kinks)
+    _, gx32, gy32 = ref.nll_and_grads(x, y, iso, cam, np.float32)
+    ref.kinks = kinks
+    wx, wy = rule_weights(ref, y, iso, cam, x.shape)
+    e32 = {"gx": patch_rel_err(gx32, gx64), "gx/w": patch_rel_err(gx32, gx64, wx)}
+    if gy64 is not None:
+        e32.update({"gy": patch_rel_err(gy32, gy64), "gy/w": patch_rel_err(gy32, gy64, wy)})
+    counts = [len(p) for p in kinks_per_patch(ref, width, x, y, iso, cam)]
+    if log is not None:
+        log("reference: on-kink %r  e32 %s" % (counts, "  ".join("%s %s" % (k, " ".join("%.2e" % v for v in e)) for k, e in e32.items())))
+    assert all(np.all(e <= E32_MAX) for e in e32.values()), e32
+    assert max(counts) <= max_on_kink, "kink condition: %r on-kink activations per patch" % counts
+    if min_gy_range is not None:
+        a = np.abs(gy64)
+        rng = float(a.max() / np.median(a))
+        if log is not None:
+            log("reference: max / median |gy| %.0f" % rng)
+        assert rng >= min_gy_range, rng
+    return e32
 
 
 def compare_with_kink_rule(ref, width, x, y, iso, cam, got_gx, got_gy, max_on_kink=6, log=None):
-    """The comparison and kink rules of tests/test_gpu_nll_grad.py.
+    """The comparison and kink rules of the module docstring.
 
-    Per patch and tensor (gx, gy):  max|got - ref64| <= tol * max|ref64|,  tol = max(1e-5, 4 * e32), e32 = the float32 helper's
-    own distance from the float64 helper on the same tensor and input.  A patch that fails is re-compared against the float64
-    reference with a subset of at most MAX_EXCUSED_KINKS of THAT patch's on-kink gates inverted.  Asserts first that no patch
-    has more than `max_on_kink` on-kink activations.  Returns per-tensor lists of (kernel distance, e32) per patch."""
+    Per patch and tensor (gx, gy):  max|got - ref64| <= tol * max|ref64|,  tol = max(1e-5, 4 * e32), e32 = the pinned float32
+    flavour's own distance from the float64 helper on the same tensor and input — and the same once more on got / w, ref64 / w
+    with e32 measured in that norm (``rule_weights``).  A patch that
+    fails either is re-compared against the float64 reference with a subset of at most MAX_EXCUSED_KINKS of THAT patch's on-kink
+    gates inverted: one subset has to make both norms pass.  Asserts first that no patch has more than `max_on_kink` on-kink
+    activations.  Returns {"gx": [(kernel distance, e32) per patch], "gx/w": .., "gy": .., "gy/w": ..}."""
+    assert isinstance(ref, PinnedRef), "the rule needs the pinned float32 flavour: build the reference as PinnedRef"
     nll64, gx64, gy64 = ref.nll_and_grads(x, y, iso, cam, np.float64)
     kinks = list(ref.kinks)
-    B, H, W, _ = x.shape
-    per_patch = [[(s, k) for s, k, _ in kinks if k // (width * H * W) == b] for b in range(B)]
+    per_patch = kinks_per_patch(ref, width, x, y, iso, cam)
     assert max(len(p) for p in per_patch) <= max_on_kink, "kink condition: %r on-kink activations per patch" % [len(p) for p in per_patch]
     _, gx32, gy32 = ref.nll_and_grads(x, y, iso, cam, np.float32)
     ref.kinks = kinks
+    wx, wy = rule_weights(ref, y, iso, cam, x.shape)
     out = {}
     failing = set()
-    tensors = [("gx", got_gx, gx64, gx32)] + ([("gy", got_gy, gy64, gy32)] if gy64 is not None else [])
+    tensors = [("gx", got_gx, gx64, gx32, wx)] + ([("gy", got_gy, gy64, gy32, wy)] if gy64 is not None else [])
     tols = {}
-    for name, got, r64, r32 in tensors:
-        e32 = patch_rel_err(r32, r64)
-        dist = patch_rel_err(got, r64)
-        tols[name] = np.maximum(1e-5, 4.0 * e32)
-        out[name] = list(zip(dist.tolist(), e32.tolist()))
-        if log is not None:
-            log("%s: kernel-to-fp64 %s   e32 %s" % (name, " ".join("%.2e" % v for v in dist), " ".join("%.2e" % v for v in e32)))
-        failing |= set(np.nonzero(~(dist <= tols[name]))[0].tolist())
+    for name, got, r64, r32, w in tensors:
+        for tag, wt in (("", None), ("/w", w)):
+            e32 = patch_rel_err(r32, r64, wt)
+            dist = patch_rel_err(got, r64, wt)
+            tols[name + tag] = np.maximum(REL_TOL, E32_FACTOR * e32)
+            out[name + tag] = list(zip(dist.tolist(), e32.tolist()))
+            if log is not None:
+                log("%s: kernel-to-fp64 %s   e32 %s" % (name + tag, " ".join("%.2e" % v for v in dist), " ".join("%.2e" % v for v in e32)))
+            failing |= set(np.nonzero(~(dist <= tols[name + tag]))[0].tolist())
     for b in sorted(failing):
         cands = per_patch[b]
         assert cands, "patch %d: %r and no on-kink activation to excuse it" % (b, {n: out[n][b] for n in out})
@@ -203,8 +385,10 @@ def compare_with_kink_rule(ref, width, x, y, iso, cam, got_gx, got_gy, max_on_ki
         for size in range(1, min(len(cands), MAX_EXCUSED_KINKS) + 1):
             for subset in itertools.combinations(cands, size):
                 _, ax, ay = ref.nll_and_grads(x, y, iso, cam, np.float64, flips=subset)
-                ok = all(patch_rel_err(got[b:b + 1], alt[b:b + 1])[0] <= tols[name][b]
-                         for (name, got, _, _), alt in zip(tensors, (ax, ay)))
+                # ONE subset has to explain both tensors in both norms (the weights do not depend on the gates)
+                ok = all(patch_rel_err(got[b:b + 1], alt[b:b + 1], None if wt is None else wt[b:b + 1])[0] <= tols[name + tag][b]
+                         for (name, got, _, _, w), alt in zip(tensors, (ax, ay))
+                         for tag, wt in (("", None), ("/w", w)))
                 if ok:
                     break
             if ok:
@@ -213,3 +397,150 @@ def compare_with_kink_rule(ref, width, x, y, iso, cam, got_gx, got_gy, max_on_ki
             b, {n: out[n][b] for n in out}, MAX_EXCUSED_KINKS, len(cands))
     ref.kinks = kinks
     return nll64, out
+
+
+# ---- the hand-written backward sweep ----------------------------------------------------------------------------------------------
+class _Cnn:
+    """One coupling's CNN in dtype `dt` on GIVEN gates: the forward pass and the transposed pass, layer by layer."""
+
+    def __init__(self, p, dt):
+        g = lambda k: torch.as_tensor(np.asarray(p[k], np.float64)).to(dt)   # noqa: E731
+        self.w1, self.b1 = g("l_1/W").permute(3, 2, 0, 1).contiguous(), g("l_1/b").reshape(-1)
+        w2 = g("l_2/W")
+        self.w2, self.b2 = w2.reshape(w2.shape[-2], w2.shape[-1]).t()[:, :, None, None].contiguous(), g("l_2/b").reshape(-1)
+        self.m1, self.m2 = g("bn1/mean").reshape(1, -1, 1, 1), g("bn2/mean").reshape(1, -1, 1, 1)
+        self.sd1 = torch.sqrt(g("bn1/var").reshape(1, -1, 1, 1) + O.BN_EPS)
+        self.sd2 = torch.sqrt(g("bn2/var").reshape(1, -1, 1, 1) + O.BN_EPS)
+        self.wl, self.bl = g("l_last/W").permute(3, 2, 0, 1).contiguous(), g("l_last/b").reshape(-1)
+        self.el = torch.exp(g("l_last/logs").reshape(1, -1, 1, 1) * O.LOGSCALE_FACTOR)
+        self.sc = float(p["rescaling_scale"])
+
+    def forward(self, z0, g1, g2):
+        a1 = (F.conv2d(z0, self.w1, self.b1, padding=1) - self.m1) / self.sd1 * g1
+        a2 = (F.conv2d(a1, self.w2, self.b2) - self.m2) / self.sd2 * g2
+        hp = F.pad(a2, (1, 1, 1, 1))
+        e = torch.zeros_like(hp[:, :1])
+        e[:, :, 0, :] = 1
+        e[:, :, -1, :] = 1
+        e[:, :, :, 0] = 1
+        e[:, :, :, -1] = 1
+        o = F.conv2d(torch.cat([hp, e], 1), self.wl, self.bl) * self.el
+        return o[:, :2], o[:, 2:]                                        # shift, raw
+
+    def transposed(self, d_shift, d_raw, g1, g2, drop_l1_tap_on_last_row=False):
+        """d nll / d z0 through l_last^T, the gates, l_2^T, l_1^T."""
+        d_o = torch.cat([d_shift, d_raw], 1) * self.el
+        d_a2 = F.conv_transpose2d(d_o, self.wl)[:, :-1, 1:-1, 1:-1]          # the edge channel and the padding carry no gradient
+        d_a1 = F.conv_transpose2d(d_a2 * g2 / self.sd2, self.w2)
+        d_h1 = d_a1 * g1 / self.sd1
+        d_z0 = F.conv_transpose2d(d_h1, self.w1, padding=1)
+        if drop_l1_tap_on_last_row:     # the mutant: d z0[q] loses the term that reads d h1 at q + (-1, -1), for q in the last row
+            tap = torch.zeros_like(self.w1)     # (the opposite corner tap reads row H there: nothing to lose)
+            tap[:, :, 2, 2] = self.w1[:, :, 2, 2]
+            d_z0 = d_z0.clone()
+            d_z0[:, :, -1, :] -= F.conv_transpose2d(d_h1, tap, padding=1)[:, :, -1, :]
+        return d_z0
+
+
+def backward_sweep(ref, x, y, iso=None, cam=None, dtype=np.float64, reversible=False, mutant=None, leading_forward=True):
+    """The gradients of the evaluation-mode NLL by a layer-by-layer backward sweep, last layer first, on the gates of the float64
+    evaluation of the same input (``PinnedRef.gates``): x, y numpy [B, H, W, 4] → (gx, gy or None) float64 numpy.
+
+    reversible=False: every layer's local Jacobian is taken from the activations the forward sweep stored.  In float64 this is
+    torch.autograd of ``NllGradRef.nll`` (1e-12 of max|grad|, tests/test_nll_grad_rule_cpu.py); in float32 it is the stored-activation
+    flavour e32 is measured with, in another order.
+    reversible=True: the arithmetic csrc/nf_grad.hip documents.  Only the last z is kept; going back every layer first rebuilds its
+    input from its output in `dtype` — z A^-1 with A^-1 inverted in fp64 and rounded, z1 = (z1' - shift) exp(-ls) with the CNN
+    evaluated on the rebuilt z0, z s, z g — and takes its Jacobian from the rebuilt values.  The layers in front of the first
+    coupling take their values forward from x, as the kernel does (`leading_forward=False`: they too are rebuilt, which hands the
+    round trip's loss of x to the leading sdn layer's gy).
+    mutant: None or (name, layer index or None) with name one of "l1_tap" (l_1's transposed conv of that coupling drops the
+    (-1, -1) tap — the term that reads d h1 one pixel up and to the left — along the patch's last row), "no_logdet" (that coupling,
+    or with None every coupling, omits the -1 of d nll / d ls in the last column),
+    "gy_not_added" (that sdn layer's part of gy is not added)."""
+    dt = torch.float64 if np.dtype(dtype) == np.float64 else torch.float32
+    gates = ref.gates(x, y, iso, cam)
+    to = lambda a: torch.as_tensor(np.asarray(a, np.float64)).to(dt).permute(0, 3, 1, 2).contiguous()   # noqa: E731
+    layers = ref.layers
+    B, H, W, _ = x.shape
+    n = 4 * H * W
+    isos = np.broadcast_to(np.asarray(iso, np.float64).reshape(-1), (B,)) if iso is not None else [None] * B
+    cams = np.broadcast_to(np.asarray(cam, np.float64).reshape(-1), (B,)) if cam is not None else [None] * B
+    col = lambda v: torch.as_tensor(np.asarray(v, np.float64)).to(dt).reshape(B, 1, 1, 1)   # noqa: E731
+    mname, mlayer = mutant if mutant is not None else (None, None)
+    with torch.no_grad():
+        xt, yt = to(x), (to(y) if y is not None else None)
+        z = xt
+        first_cpl = min([i for i, L in enumerate(layers) if L["type"] == "coupling"], default=len(layers))
+        consts, outs = [], []          # per layer: its constants in dt; the output of the layer (stored mode, or in front of the first coupling)
+        for li, L in enumerate(layers):
+            t = L["type"]
+            if t == "conv1x1":
+                A64 = torch.as_tensor(np.asarray(L["A"], np.float64))
+                c = (A64.to(dt), torch.linalg.inv(A64).to(dt))
+                z = torch.einsum("bchw,ck->bkhw", z, c[0])
+            elif t == "coupling":
+                c = _Cnn(L["p"], dt)
+                g1, g2 = (gates[(li, k)].to(dt) for k in (1, 2))
+                shift, raw = c.forward(z[:, :2], g1, g2)
+                z = torch.cat([z[:, :2], z[:, 2:] * torch.exp(c.sc * torch.tanh(raw)) + shift], 1)
+            elif t.startswith("sdn"):
+                ab = [_scalar_pair(L, isos[b], cams[b]) for b in range(B)]
+                a = col([v[0] for v in ab])
+                s2 = a * yt + col([v[1] for v in ab])
+                c = (a, s2, torch.sqrt(s2))
+                z = z / c[2]
+            else:
+                c = col([_gain(L, isos[b], n)[0] for b in range(B)])
+                z = z / c
+            consts.append(c)
+            outs.append(z if (not reversible or (leading_forward and li < first_cpl)) else None)
+        g = z.clone()                   # the prior: d nll / d z = z
+        gy = torch.zeros_like(z) if (yt is not None and any(L["type"].startswith("sdn") for L in layers)) else None
+        for li in range(len(layers) - 1, -1, -1):
+            t, c = layers[li]["type"], consts[li]
+            z_out = outs[li] if outs[li] is not None else z
+            if t == "conv1x1":
+                z = torch.einsum("bkhw,kc->bchw", z_out, c[1])
+                g = torch.einsum("bkhw,ck->bchw", g, c[0])
+            elif t == "coupling":
+                g1, g2 = (gates[(li, k)].to(dt) for k in (1, 2))
+                z0 = z_out[:, :2]
+                shift, raw = c.forward(z0, g1, g2)
+                th = torch.tanh(raw)
+                ls = c.sc * th
+                e = torch.exp(ls)
+                z1 = (z_out[:, 2:] - shift) * torch.exp(-ls) if reversible else (outs[li - 1] if li else xt)[:, 2:]
+                one = torch.ones_like(ls)
+                if mname == "no_logdet" and mlayer in (None, li):
+                    one[:, :, :, -1] = 0
+                d_ls = g[:, 2:] * z1 * e - one
+                d_z0 = c.transposed(g[:, 2:], c.sc * (1 - th * th) * d_ls, g1, g2, mname == "l1_tap" and mlayer == li)
+                g = torch.cat([g[:, :2] + d_z0, g[:, 2:] * e], 1)
+                z = torch.cat([z0, z1], 1)
+            elif t.startswith("sdn"):
+                a, s2, s = c
+                if not (mname == "gy_not_added" and mlayer == li):
+                    gy = gy + 0.5 * a / s2 * (1 - g * z_out)
+                g = g / s
+                z = z_out * s
+            else:
+                g = g / c
+                z = z_out * c
+        back = lambda v: v.permute(0, 2, 3, 1).double().numpy()   # noqa: E731
+        return back(g), (back(gy) if gy is not None else None)
+
+
+def combined_bound(ref, x, y, iso, cam):
+    """{"gx": [B, H, W, 4], "gy": ..}: per element the smaller of the two norms' bounds, min(tol max|g64|, tol_w max|g64 / w| w[e])."""
+    _, gx64, gy64 = ref.nll_and_grads(x, y, iso, cam, np.float64)
+    _, gx32, gy32 = ref.nll_and_grads(x, y, iso, cam, np.float32)
+    wx, wy = rule_weights(ref, y, iso, cam, x.shape)
+    out = {}
+    for name, r64, r32, w in (("gx", gx64, gx32, wx),) + ((("gy", gy64, gy32, wy),) if gy64 is not None else ()):
+        B = r64.shape[0]
+        sh = (B, 1, 1, 1)
+        raw = np.maximum(REL_TOL, E32_FACTOR * patch_rel_err(r32, r64)).reshape(sh) * np.abs(r64).reshape(B, -1).max(axis=1).reshape(sh)
+        wh = np.maximum(REL_TOL, E32_FACTOR * patch_rel_err(r32, r64, w)).reshape(sh) * (np.abs(r64) / w).reshape(B, -1).max(axis=1).reshape(sh) * w
+        out[name] = (np.minimum(np.broadcast_to(raw, r64.shape), wh), np.broadcast_to(raw, r64.shape))
+    return out

@@ -6,6 +6,11 @@ activations per image, asserted from the reference before the kernel's output is
 upward that meet the kink condition on the CPU reference (seed 0 in every case; counts per image in the comments).  A halo that
 is one pixel short shows at fp32 resolution only when a segment holds ONE coupling (1.2e-3; tests/test_grad_tiles_cpu.py pins the
 deeper segments in fp64): the S = 8 cases of the shipped model are the ones that catch a core / halo slip.
+
+Both norms of tests/nll_grad_ref.py are enforced (raw and whitened; the reference is the shared pinned one), and every case first
+asserts from the reference alone that the pinned e32 is at most E32_MAX = 5e-6 in both norms; (65,64) and (96,80) also assert
+max / median |gy| >= 100.  Measured on an MI355X, worst image of all cases, raw / whitened: gx 2.6e-6 / 3.1e-6, gy 4.9e-6 / 3.3e-6
+(the 80x72 image of test_python_surface: 0.49 of the bound).
 """
 import ctypes as C
 
@@ -13,8 +18,8 @@ import numpy as np
 import pytest
 
 from conftest import FULL_ARCH, make_inputs, trained_like_variables
-from nll_grad_ref import NllGradRef, compare_with_kink_rule
-from test_gpu_nll_grad import ISO, CAM, NLL_RTOL, TUPLES5, VOCAB_ARCH, WIDE_ARCH, _bits, _call, _check, _cond, _dev, _vocab_variables
+from nll_grad_ref import PinnedRef, compare_with_kink_rule, reference_conditions
+from test_gpu_nll_grad import GY_RANGE, ISO, CAM, NLL_RTOL, TUPLES5, VOCAB_ARCH, WIDE_ARCH, _bits, _call, _check, _cond, _dev, _vocab_variables
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +45,7 @@ def _segments(m):
 
 @pytest.fixture(scope="module")
 def shipped_ref(shipped_variables):
-    return NllGradRef(FULL_ARCH, shipped_variables)
+    return PinnedRef(FULL_ARCH, shipped_variables)
 
 
 @pytest.fixture(autouse=True)
@@ -50,13 +55,19 @@ def _no_forced_count(monkeypatch):
 
 # ---- 1. the shipped model -------------------------------------------------------------------------------------------------------
 # on-kink activations per image (seed 0): (65,64) [3,4]  (64,65) [2,2]  (96,80) [4,5]  (120,66) [3,6]
-@pytest.mark.parametrize("hw", [(65, 64), (64, 65), (96, 80), (120, 66)])
+# largest pinned e32 over images, tensors and both norms: 2.0e-6  2.7e-6  1.9e-6  2.2e-6; max / median |gy| of (65,64) 1903, of (96,80) 3969
+SHIPPED_CASES = [(65, 64), (64, 65), (96, 80), (120, 66)]
+GY_RANGE_CASES = ((65, 64), (96, 80))             # max / median |gy| >= GY_RANGE, asserted from the reference
+TRAINED_CASES = [(8, (64, 64), 0), (16, (40, 33), 0), (4, (70, 20), 0), (8, (56, 56), 0)]
+
+
+@pytest.mark.parametrize("hw", SHIPPED_CASES)
 def test_shipped_model(shipped_variables, shipped_ref, hw):
     from noise_flow_amd import _lib
     m = _flow(FULL_ARCH, shipped_variables, hw)
     assert _path(m) == _lib.NF_GRAD_PATH_TILED and _segments(m)[0] >= 3      # at most 3 couplings per segment
     x, y = make_inputs(2, hw[0], hw[1], seed=0)
-    _check(m, shipped_ref, 4, x, y, ISO, CAM)
+    _check(m, shipped_ref, 4, x, y, ISO, CAM, min_gy_range=GY_RANGE if hw in GY_RANGE_CASES else None)
 
 
 @pytest.mark.parametrize("forced,halos", [(8, [4] * 8), (4, [8] * 4), (3, [12, 12, 8])])
@@ -85,27 +96,28 @@ def test_infeasible_forced_count_is_refused(monkeypatch, shipped_variables):
 
 # ---- 2. widths 4 / 8 / 16 ---------------------------------------------------------------------------------------------------------
 # on-kink per image (seed 0): width 8 (64,64) [1,1]   width 16 (40,33) [1,1]   width 4 (70,20) [0,1]   width 8 (56,56) [0,2]
+# largest pinned e32: 2.7e-7  1.1e-6  3.2e-7  3.2e-7
 # (56x56 at width 8 is the smallest square the whole-patch kernel's LDS does not hold; its forward launches are the scalar-weight
 #  kernel's, those of 64x64 the width-32 matrix-core kernel's, those of width 16 the width-16 kernel's, of width 4 the MFMA4 one's)
-@pytest.mark.parametrize("width,hw,seed", [(8, (64, 64), 0), (16, (40, 33), 0), (4, (70, 20), 0), (8, (56, 56), 0)])
+@pytest.mark.parametrize("width,hw,seed", TRAINED_CASES)
 def test_trained_like_widths(width, hw, seed):
     from noise_flow_amd import _lib
     v = trained_like_variables(WIDE_ARCH, width)
     m = _flow(WIDE_ARCH, v, hw, width)
     assert _path(m) == _lib.NF_GRAD_PATH_TILED
     x, y = make_inputs(2, hw[0], hw[1], seed=seed)
-    _check(m, NllGradRef(WIDE_ARCH, v), width, x, y, ISO, CAM)
+    _check(m, PinnedRef(WIDE_ARCH, v), width, x, y, ISO, CAM)
 
 
 # ---- 3. vocabulary and conditioning: the trailing sdn3 makes gy come from two segments -------------------------------------------------
-# on-kink per image (seed 0): per-call cond [0,1,1], per-image rows [0,0,0]
+# on-kink per image (seed 0): per-call cond [0,1,1], per-image rows [0,0,0]; largest pinned e32 1.4e-6, 1.3e-6
 def test_vocabulary_per_call_cond(monkeypatch):
     monkeypatch.setenv("NF_GRAD_TILE_SEGMENTS", "2")      # sdn5 in the first segment, sdn3 in the second, whatever the cost model says
     v = _vocab_variables()
     m = _flow(VOCAB_ARCH, v, (70, 36))
     assert _segments(m)[0] == 2
     x, y = make_inputs(3, 70, 36, seed=0)
-    _check(m, NllGradRef(VOCAB_ARCH, v), 4, x, y, 1600.0, 3.0)
+    _check(m, PinnedRef(VOCAB_ARCH, v), 4, x, y, 1600.0, 3.0)
 
 
 def test_vocabulary_per_image_rows(monkeypatch):
@@ -116,7 +128,7 @@ def test_vocabulary_per_image_rows(monkeypatch):
     x, y = make_inputs(3, 70, 36, seed=0)
     table = np.array([(i, c, 0, 0) for i, c in TUPLES5[:3]], np.float32)
     rows = m._rows_to_dev(PatchCond(table), 0)
-    _check(m, NllGradRef(VOCAB_ARCH, v), 4, x, y, table[:, 0], table[:, 1], rows=rows)
+    _check(m, PinnedRef(VOCAB_ARCH, v), 4, x, y, table[:, 0], table[:, 1], rows=rows)
 
 
 # ---- 4. a model without an SDN layer: y = NULL ---------------------------------------------------------------------------------------
@@ -126,8 +138,8 @@ def test_model_without_sdn():
     v = trained_like_variables(NO_SDN_ARCH, 4, seed=3)
     m = _flow(NO_SDN_ARCH, v, (66, 12))
     assert _path(m) == _lib.NF_GRAD_PATH_TILED
-    x = np.random.RandomState(0).randn(2, 66, 12, 4).astype(np.float32)     # on-kink per image: [0, 0]
-    _check(m, NllGradRef(NO_SDN_ARCH, v), 4, x, None, None, None)
+    x = np.random.RandomState(0).randn(2, 66, 12, 4).astype(np.float32)     # on-kink per image: [0, 0], pinned e32 1.8e-7
+    _check(m, PinnedRef(NO_SDN_ARCH, v), 4, x, None, None, None)
     xd = _dev(x)
     gy = torch.empty_like(xd)
     rc = m._flow.lib.nf_nll_grad(m._flow.ptr, xd.data_ptr(), None, 2, C.byref(_cond()), None, None, None, gy.data_ptr(), m._dev.stream_ptr())
@@ -264,7 +276,8 @@ def test_python_surface(shipped_variables, shipped_ref):
     hw, B = (80, 72), 2
     m = _flow(FULL_ARCH, shipped_variables, hw)
     assert _path(m) == _lib.NF_GRAD_PATH_TILED
-    x, y = make_inputs(B, hw[0], hw[1], seed=0)                                            # on-kink per image: [5, 4]
+    x, y = make_inputs(B, hw[0], hw[1], seed=0)                                            # on-kink per image: [5, 4], pinned e32 1.6e-6
+    reference_conditions(shipped_ref, 4, x, y, ISO, CAM)
     n_np, gx_np, gy_np = m.nll_and_grad(x, y, iso=[ISO], cam=[CAM])                        # numpy in, numpy out
     assert isinstance(gx_np, np.ndarray) and gx_np.shape == x.shape and gy_np.shape == y.shape
     compare_with_kink_rule(shipped_ref, 4, x, y, ISO, CAM, gx_np, gy_np, log=print)

@@ -1,7 +1,7 @@
 """CPU tier of the tiled input gradients (NF_CFG_GRAD_TILED, csrc/nf_grad.hip TILED): what ``nf_grad_supported`` accepts and refuses
 with the flag, the plan ``nf_grad_tile_segments`` reports, and the arithmetic the design rests on — the gradient of a tile
 evaluated alone is exact 4 x (couplings) pixels inside every tile border that is not an image border, and one pixel less is not —
-pinned in fp64 with ``NllGradRef`` and the tile arithmetic of ``nf_tile_plan``.  No device is touched.
+pinned in fp64 with ``PinnedRef`` and the tile arithmetic of ``nf_tile_plan``.  No device is touched.
 """
 import ctypes as C
 
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import FULL_ARCH, make_inputs, trained_like_variables
-from nll_grad_ref import NllGradRef
+from nll_grad_ref import PinnedRef
 from test_cond_rows_cpu import cond_variables
 from test_nll_grad_ref_cpu import WIDE_ARCH, _supported
 
@@ -201,7 +201,7 @@ def test_gradient_halo_is_four_per_coupling_in_fp64(arch, c):
     the tiled gradient IS the whole image's (<= 1e-13 of max|grad|; measured 0), with 4c - 1 it is not (> 1e-12; measured, gx /
     gy: 1 coupling 1.6e-3 / 2.5e-5, 2 couplings 1.9e-6 / 4.0e-8, 3 couplings 1.3e-10 / 1.1e-12 — gy of the deepest case sits AT the
     bound, so gx carries it).  90x70 image, 64-pixel tiles, trained_like_variables(arch, 4, seed=1)."""
-    ref = NllGradRef(arch, trained_like_variables(arch, 4, seed=1))
+    ref = PinnedRef(arch, trained_like_variables(arch, 4, seed=1))
     x, y = make_inputs(1, 90, 70, seed=0)
     x, y = x.astype(np.float64), y.astype(np.float64)
     _, gx, gy = ref.nll_and_grads(x, y, 800.0, 2.0)

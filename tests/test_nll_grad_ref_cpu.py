@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import FULL_ARCH, make_inputs, trained_like_variables
-from nll_grad_ref import NllGradRef, _scalar_pair
+from nll_grad_ref import PinnedRef, _scalar_pair
 from oracle.nf_oracle import NoiseFlowOracle
 
 ISO, CAM = 800.0, 2.0
@@ -15,7 +15,7 @@ ISO, CAM = 800.0, 2.0
 
 @pytest.fixture(scope="module")
 def shipped_ref(shipped_variables):
-    return NllGradRef(FULL_ARCH, shipped_variables)
+    return PinnedRef(FULL_ARCH, shipped_variables)
 
 
 @pytest.mark.parametrize("hw", [(32, 32), (9, 13)])
@@ -57,7 +57,7 @@ def test_closed_form_without_couplings():
     gx = x / s^2 and gy = (a g^2 / 2 s^2) (1 - x^2 / s^2)."""
     arch = "sdn5|gain4"
     v = trained_like_variables(arch, 4, seed=2)
-    ref = NllGradRef(arch, v)
+    ref = PinnedRef(arch, v)
     x, y = make_inputs(2, 5, 7, seed=6)
     _, gx, gy = ref.nll_and_grads(x, y, ISO, CAM)
     a, b = _scalar_pair(ref.layers[0], ISO, CAM)
