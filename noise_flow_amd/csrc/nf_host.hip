@@ -5,7 +5,7 @@
 //   matrix_param.py:100-140      PLU -> A, A^-1, log|det|        (fold_conv1x1)
 //   layers.py:378-401            BN eval folded into l_1 / l_2    (fold_coupling)
 //   layers.py:555-583,651-674    edge channel + exp(3*logs)       (fold_coupling)
-//   cond_utils.py:205-239        sdn5 scalars                     (sdn5_scalars)
+//   cond_utils.py:205-239        sdn5 scalars                     (nf_layers.h: nf_sdn_eval)
 //   cond_utils.py:432-440        gain4                            (build_program)
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -22,6 +22,7 @@
 #include "nf_device.h"
 #include "nf_gemm_layout.h"
 #include "nf_internal.h"
+#include "nf_layers.h"
 
 hipError_t nf_launch_flow(const NfProgram &prog, const NfLaunch &a, int n_cu, hipStream_t stream, bool matrix_core, const float *block12 = nullptr,
                           size_t n_block12 = 0);
@@ -70,80 +71,12 @@ int fail_hip(hipError_t e, const char *what)
     return fail(NF_EHIP, "%s: %s", what, hipGetErrorString(e));
 }
 
-constexpr double kBnEps = 1e-4;          // layers.py:378
-constexpr double kLogscaleFactor = 3.0;  // layers.py:653
-constexpr int kC = 4;
-
-int64_t layer_param_count(int32_t type, int32_t w)
-{
-    switch (type) {
-    case NF_LAYER_CONV1X1: return 16 + 4 + 4 + 6 + 6;
-    case NF_LAYER_CONV1X1_NONE: return 16;
-    case NF_LAYER_CONV1X1_LU2: return 16 + 16 + 4 + 4 + 16;
-    case NF_LAYER_PERMUTE: return 0;
-    case NF_LAYER_COUPLING:
-        if (w <= 0) return -1;
-        return 9 * 2 * (int64_t)w + w + w + w      // l_1/W, l_1/b, bn1 mean, var
-               + (int64_t)w * w + w + w + w        // l_2/W, l_2/b, bn2 mean, var
-               + 9 * ((int64_t)w + 1) * 4 + 4 + 4  // l_last/W, b, logs
-               + 1;                                // rescaling_scale
-    case NF_LAYER_SDN5: return 1 + 1 + 5 + 15 + 1;
-    case NF_LAYER_GAIN4: return 1;
-    case NF_LAYER_SDN4: return 7;
-    case NF_LAYER_SDN: return 2;
-    case NF_LAYER_GAIN: return 2;
-    case NF_LAYER_SDN1:
-    case NF_LAYER_SDN2:
-    case NF_LAYER_SDN3: return 7;
-    case NF_LAYER_SDN6: return 13;
-    case NF_LAYER_GAIN1: return 2;
-    case NF_LAYER_GAIN2:
-    case NF_LAYER_GAIN3: return 5;
-    default: return -1;
-    }
-}
-
-// ---- PLU parameterisation (matrix_param.py:31-56, 100-140) -----------------
-struct Mat4 {
-    double m[4][4];
-};
-
-Mat4 matmul(const Mat4 &a, const Mat4 &b)
-{
-    Mat4 r;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < 4; ++k) s += a.m[i][k] * b.m[k][j];
-            r.m[i][j] = s;
-        }
-    return r;
-}
-
+// ---- Conv2d1x1 (matrix_param.py): the matrices come from nf_layers.h, the inverses are formed as the reference forms them
 void fold_conv1x1(const float *p, Mat4 &A, Mat4 &Ainv, double &log_abs_det)
 {
-    const float *P = p, *sign_s = p + 16, *log_s = p + 20, *lv = p + 24, *uv = p + 30;
     Mat4 Pm, L, U;
-    memset(&L, 0, sizeof(L));
-    memset(&U, 0, sizeof(U));
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) Pm.m[i][j] = P[i * 4 + j];
-    // tfdist.fill_triangular(v, lower) for the 3x3 strict triangle, padded by one
-    // zero row on top and one zero column on the right:  [[v3,0,0],[v5,v4,0],[v2,v1,v0]]
-    L.m[1][0] = lv[3];
-    L.m[2][0] = lv[5]; L.m[2][1] = lv[4];
-    L.m[3][0] = lv[2]; L.m[3][1] = lv[1]; L.m[3][2] = lv[0];
-    for (int i = 0; i < 4; ++i) L.m[i][i] = 1.0;
-    // upper: [[v0,v1,v2],[0,v4,v5],[0,0,v3]] padded by a zero row at the bottom and a zero column on the left
-    U.m[0][1] = uv[0]; U.m[0][2] = uv[1]; U.m[0][3] = uv[2];
-    U.m[1][2] = uv[4]; U.m[1][3] = uv[5];
-    U.m[2][3] = uv[3];
-    log_abs_det = 0.0;
-    for (int i = 0; i < 4; ++i) {
-        U.m[i][i] = (double)sign_s[i] * exp((double)log_s[i]);
-        log_abs_det += (double)log_s[i];
-    }
-    A = matmul(Pm, matmul(L, U));
+    log_abs_det = nf_plu_matrices(p, Pm, L, U);
+    nf_plu_product(Pm, L, U, &A.m[0][0]);
     // A^-1 = U^-1 L^-1 P^T by two triangular solves (matrix_param.py:132-136)
     Mat4 X;   // X = L^-1 P^T  (forward substitution, unit diagonal)
     for (int c = 0; c < 4; ++c)
@@ -160,65 +93,15 @@ void fold_conv1x1(const float *p, Mat4 &A, Mat4 &Ainv, double &log_abs_det)
         }
 }
 
-// General 4x4 inverse + log|det| by Gauss-Jordan with partial pivoting, in double (tf.matrix_inverse / tf.linalg.slogdet
-// of matrix_param.py:26-27, :177-179).  false = singular.
-bool invert4(const Mat4 &M, Mat4 &inv, double &log_abs_det)
-{
-    double a[4][8];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            a[i][j] = M.m[i][j];
-            a[i][4 + j] = i == j ? 1.0 : 0.0;
-        }
-    log_abs_det = 0.0;
-    for (int c = 0; c < 4; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < 4; ++r)
-            if (fabs(a[r][c]) > fabs(a[piv][c])) piv = r;
-        if (!(fabs(a[piv][c]) > 0.0)) return false;
-        if (piv != c)
-            for (int j = 0; j < 8; ++j) std::swap(a[piv][j], a[c][j]);
-        const double d = a[c][c];
-        log_abs_det += log(fabs(d));
-        for (int j = 0; j < 8; ++j) a[c][j] /= d;
-        for (int r = 0; r < 4; ++r) {
-            if (r == c) continue;
-            const double f = a[r][c];
-            if (f != 0.0)
-                for (int j = 0; j < 8; ++j) a[r][j] -= f * a[c][j];
-        }
-    }
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) inv.m[i][j] = a[i][4 + j];
-    return true;
-}
-
-// decomp = 'NONE' (matrix_param.py:23-29): the matrix is the variable.
-bool fold_conv1x1_none(const float *p, Mat4 &A, Mat4 &Ainv, double &log_abs_det)
-{
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) A.m[i][j] = p[i * 4 + j];
-    return invert4(A, Ainv, log_abs_det);
-}
-
-// decomp = 'LU2' (matrix_param.py:143-188): full-matrix L / U variables masked to their strict triangles, evaluated in
-// float64; A^-1 = U^-1 L^-1 P^-1 from the three separate inverses, as the reference forms it (:177-180).
+// decomp = 'LU2': A^-1 = U^-1 L^-1 P^-1 from the three separate inverses, as the reference forms it (matrix_param.py:177-180)
 bool fold_conv1x1_lu2(const float *p, Mat4 &A, Mat4 &Ainv, double &log_abs_det)
 {
-    const float *P = p, *Lf = p + 16, *sign_s = p + 32, *log_s = p + 36, *Uf = p + 40;
     Mat4 Pm, L, U, Pi, Li, Ui;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            Pm.m[i][j] = P[i * 4 + j];
-            L.m[i][j] = j < i ? (double)Lf[i * 4 + j] : (i == j ? 1.0 : 0.0);
-            U.m[i][j] = j > i ? (double)Uf[i * 4 + j] : (i == j ? (double)sign_s[i] * exp((double)log_s[i]) : 0.0);
-        }
-    log_abs_det = 0.0;
-    for (int i = 0; i < 4; ++i) log_abs_det += (double)log_s[i];           // :187
-    A = matmul(Pm, matmul(L, U));
+    log_abs_det = nf_lu2_matrices(p, Pm, L, U);
+    nf_plu_product(Pm, L, U, &A.m[0][0]);
     double d;
-    if (!invert4(Pm, Pi, d) || !invert4(L, Li, d) || !invert4(U, Ui, d)) return false;
-    Ainv = matmul(Ui, matmul(Li, Pi));
+    if (!nf_invert4(Pm, Pi, d) || !nf_invert4(L, Li, d) || !nf_invert4(U, Ui, d)) return false;
+    Ainv = nf_matmul(Ui, nf_matmul(Li, Pi));
     return true;
 }
 
@@ -227,18 +110,11 @@ bool fold_conv1x1_lu2(const float *p, Mat4 &A, Mat4 &Ainv, double &log_abs_det)
 // w .. wk-1 keep zero weights and zero bias
 void fold_coupling(const float *p, int w, int wk, float *out)
 {
-    const float *W1 = p;
-    const float *b1 = W1 + 18 * w;
-    const float *m1 = b1 + w;
-    const float *v1 = m1 + w;
-    const float *W2 = v1 + w;
-    const float *b2 = W2 + w * w;
-    const float *m2 = b2 + w;
-    const float *v2 = m2 + w;
-    const float *W3 = v2 + w;            // [3][3][w+1][4]
-    const float *b3 = W3 + 9 * (w + 1) * 4;
-    const float *logs = b3 + 4;
-    const float *resc = logs + 4;
+    const CplOff o = cpl_off(0, w);
+    const float *W1 = p + o.w1, *b1 = p + o.b1, *m1 = p + o.m1, *v1 = m1 + w;
+    const float *W2 = p + o.w2, *b2 = p + o.b2, *m2 = p + o.m2, *v2 = m2 + w;
+    const float *W3 = p + o.w3;          // [3][3][w+1][4]
+    const float *b3 = p + o.tail3, *logs = b3 + 4, *resc = logs + 4;
 
     std::vector<double> s1(w), s2(w);
     for (int j = 0; j < w; ++j) {
@@ -706,127 +582,39 @@ void relayout_coupling_wide32_fp16(const float *v1, int w, float *out)
                 }
 }
 
-// ---- sdn5 host scalars (cond_utils.py:205-239) -------------------------------
-int sdn5_scalars(const float *sp, const nf_cond *cond, double out[2])
-{
-    if (!cond) return fail(NF_EINVAL, "model has an SDN5 layer but cond is NULL");
-    const double beta1_v = sp[0], beta2_v = sp[1];
-    const float *gain_params = sp + 2, *cam_params = sp + 7;
-    const double c_i = sp[22];
-    int cam_idx = -1;
-    for (int i = 0; i < 5; ++i)
-        if ((float)i == cond->cam) cam_idx = i;
-    if (cam_idx < 0) return fail(NF_ECOND, "unknown camera id %g (expected 0..4 = IP,GP,S6,N6,G4)", (double)cond->cam);
-    double cp[3];
-    for (int r = 0; r < 3; ++r) cp[r] = exp(c_i * (double)cam_params[r * 5 + cam_idx]);
-    static const float iso_vals[5] = {100.f, 400.f, 800.f, 1600.f, 3200.f};
-    double g = 0.0;   // unknown ISO -> empty one-hot -> reduce_sum = 0 (cond_utils.py:227-229)
-    for (int i = 0; i < 5; ++i)
-        if (iso_vals[i] == cond->iso) g = gain_params[i];
-    const double gain = exp(c_i * g * cp[2]) * (double)cond->iso;
-    const double beta1 = exp(c_i * beta1_v * cp[0]);
-    const double beta2 = exp(c_i * beta2_v * cp[1]);
-    out[0] = beta1 / gain;
-    out[1] = beta2;
-    return NF_OK;
-}
-
+// ---- per-call scalars of the conditional layers (formulas: nf_layers.h) ---------
 struct CondLayer {
-    int kind;                  // NF_LAYER_SDN5 / SDN4 / SDN / GAIN
+    int kind;                  // NF_LAYER_* of an sdn or conditional-gain kind
     std::vector<float> p;      // its raw parameters
 };
 
-double sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
+inline bool is_gain_kind(int k) { return nf_layer_info(k).cls == NF_CLS_COND_GAIN; }
 
-// per-ISO tables of the Ex1-Ex3 layers: nested tf.cond on iso == 100, 400, 800, 1600, 3200 whose last branch is
-// the ISO-800 entry (cond_utils.py:69-88)
-int iso_table_index(float iso)
+// Per-call scalars of one conditional layer -> (a, b): SDN kinds: scale^2 = a*y + b; GAIN: scale = a, and *K = how many
+// log(scale) terms its log-det holds on patches of HW pixels.
+int cond_scalars(int kind, const float *p, const nf_cond *cond, double out[2], int HW = 0, double *K = nullptr)
 {
-    static const float iso_vals[5] = {100.f, 400.f, 800.f, 1600.f, 3200.f};
-    for (int i = 0; i < 5; ++i)
-        if (iso_vals[i] == iso) return i;
-    return 2;
-}
-
-inline bool is_gain_kind(int k) { return k == NF_LAYER_GAIN || k == NF_LAYER_GAIN1 || k == NF_LAYER_GAIN2 || k == NF_LAYER_GAIN3; }
-
-// Per-call scalars of one conditional layer -> (a, b): SDN kinds: scale^2 = a*y + b; GAIN: scale = a.
-int cond_scalars(const CondLayer &L, const nf_cond *cond, double out[2])
-{
-    switch (L.kind) {
-    case NF_LAYER_SDN5: return sdn5_scalars(L.p.data(), cond, out);
-    case NF_LAYER_SDN4: {   // cond_utils.py:178-202 (c = 1)
-        if (!cond) return fail(NF_EINVAL, "model has an SDN4 layer but cond is NULL");
-        static const float iso_vals[5] = {100.f, 400.f, 800.f, 1600.f, 3200.f};
-        double g = 0.0;
-        for (int i = 0; i < 5; ++i)
-            if (iso_vals[i] == cond->iso) g = L.p[2 + i];
-        const double gain = exp(g) * (double)cond->iso;
-        out[0] = exp((double)L.p[0]) / gain;
-        out[1] = exp((double)L.p[1]);
+    const NfLayerInfo &info = nf_layer_info(kind);
+    if (info.cls != NF_CLS_SDN && info.cls != NF_CLS_COND_GAIN) return fail(NF_EINVAL, "bad conditional layer");
+    CondIdx ci{0.f, -1, 0};
+    if (info.iso) {
+        if (!cond) return fail(NF_EINVAL, "model has %s but cond is NULL", info.name);
+        ci = nf_cond_index(cond);
+        if (info.cam && ci.cam_idx < 0) return fail(NF_ECOND, NF_CAM_ERROR, (double)cond->cam);
+    }
+    if (info.cls == NF_CLS_SDN) {
+        NfSdn s;
+        nf_sdn_eval(kind, p, ci, s);
+        out[0] = s.a;
+        out[1] = s.b;
         return NF_OK;
     }
-    case NF_LAYER_SDN:      // cond_utils.py:41-52
-        out[0] = sigmoid(L.p[0]);
-        out[1] = sigmoid(L.p[1]);
-        return NF_OK;
-    case NF_LAYER_GAIN:     // cond_utils.py:319-330 with gain = iso (AffineCouplingGain.py:52,113)
-        if (!cond) return fail(NF_EINVAL, "model has a GAIN layer but cond is NULL");
-        out[0] = sigmoid(L.p[0]) * (double)cond->iso + sigmoid(L.p[1]);
-        out[1] = 0.0;
-        if (!(out[0] > 0.0)) return fail(NF_EINVAL, "gain scale must be > 0");
-        return NF_OK;
-    case NF_LAYER_SDN1:     // cond_utils.py:55-98
-    case NF_LAYER_SDN2:     // cond_utils.py:101-138
-    case NF_LAYER_SDN3: {   // cond_utils.py:141-175
-        if (!cond) return fail(NF_EINVAL, "model has an SDN layer with a per-ISO gain table but cond is NULL");
-        const double c = L.kind == NF_LAYER_SDN1 ? 1e-2 : 1e-1;
-        const double gain = exp(c * (double)L.p[2 + iso_table_index(cond->iso)]) * (double)cond->iso;
-        const double b1 = sigmoid(L.p[0]), b2 = sigmoid(L.p[1]);
-        if (L.kind == NF_LAYER_SDN1) {          // sqrt(b1 y / r_gain + b2)
-            out[0] = b1 / gain;
-            out[1] = b2;
-        } else if (L.kind == NF_LAYER_SDN2) {   // sqrt(gain (b1 y / gain + b2))
-            out[0] = gain * (b1 / gain);
-            out[1] = gain * b2;
-        } else {                                // gain sqrt(b1 y / gain + b2)
-            out[0] = gain * gain * (b1 / gain);
-            out[1] = gain * gain * b2;
-        }
-        return NF_OK;
-    }
-    case NF_LAYER_SDN6: {   // cond_utils.py:242-276: one camera parameter, applied to the gain exponent only
-        if (!cond) return fail(NF_EINVAL, "model has an SDN6 layer but cond is NULL");
-        const double c_i = L.p[12];
-        int cam_idx = -1;
-        for (int i = 0; i < 5; ++i)
-            if ((float)i == cond->cam) cam_idx = i;
-        if (cam_idx < 0) return fail(NF_ECOND, "unknown camera id %g (expected 0..4 = IP,GP,S6,N6,G4)", (double)cond->cam);
-        const double cp = exp(c_i * (double)L.p[7 + cam_idx]);
-        static const float iso_vals[5] = {100.f, 400.f, 800.f, 1600.f, 3200.f};
-        double g = 0.0;   // unknown ISO -> empty one-hot -> 0
-        for (int i = 0; i < 5; ++i)
-            if (iso_vals[i] == cond->iso) g = L.p[2 + i];
-        const double gain = exp(c_i * g * cp) * (double)cond->iso;
-        out[0] = exp(c_i * (double)L.p[0]) / gain;
-        out[1] = exp(c_i * (double)L.p[1]);
-        return NF_OK;
-    }
-    case NF_LAYER_GAIN1:    // cond_utils.py:333-350 with gain = iso
-        if (!cond) return fail(NF_EINVAL, "model has a GAIN1 layer but cond is NULL");
-        out[0] = exp(1e-5 * (double)L.p[0]) * (double)cond->iso + exp(1e-5 * (double)L.p[1]);
-        out[1] = 0.0;
-        return NF_OK;
-    case NF_LAYER_GAIN2:    // cond_utils.py:353-392
-    case NF_LAYER_GAIN3:    // cond_utils.py:395-429
-        if (!cond) return fail(NF_EINVAL, "model has a per-ISO GAIN layer but cond is NULL");
-        if (L.kind == NF_LAYER_GAIN2) out[0] = exp(1e-1 * (double)L.p[iso_table_index(cond->iso)]) * (double)cond->iso;
-        else out[0] = exp(1e-5 * (double)L.p[iso_table_index(cond->iso)]);
-        out[1] = 0.0;
-        if (!(out[0] > 0.0)) return fail(NF_EINVAL, "gain scale must be > 0");
-        return NF_OK;
-    }
-    return fail(NF_EINVAL, "bad conditional layer");
+    double k;
+    nf_gain_eval(kind, p, ci, HW, out[0], k);
+    if (K) *K = k;
+    out[1] = 0.0;
+    if (kind != NF_LAYER_GAIN1 && !(out[0] > 0.0)) return fail(NF_EINVAL, "gain scale must be > 0");
+    return NF_OK;
 }
 
 // ---- program construction -----------------------------------------------------
@@ -994,37 +782,30 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     out.cond.clear();
     for (int li = 0; li < cfg->n_layers; ++li) {
         const nf_layer_desc &L = layers[li];
-        const int64_t cnt = layer_param_count(L.type, L.width);
+        const int64_t cnt = nf_param_count(L.type, L.width);
         if (cnt < 0) return fail(NF_EINVAL, "layer %d: unknown type %d / width %d", li, L.type, L.width);
         if (L.param_offset < 0 || (uint64_t)L.param_offset + (uint64_t)cnt > n_params)
             return fail(NF_EINVAL, "layer %d: parameters [%lld, +%lld) exceed n_params=%zu", li,
                         (long long)L.param_offset, (long long)cnt, n_params);
         const float *p = params + L.param_offset;
         Item it;
-        switch (L.type) {
-        case NF_LAYER_CONV1X1: {
-            double lad;
-            fold_conv1x1(p, it.A, it.Ainv, lad);
+        switch (nf_layer_info(L.type).cls) {
+        case NF_CLS_MIX: {
+            double lad = 0.0;
+            bool ok = true;
+            if (L.type == NF_LAYER_CONV1X1) fold_conv1x1(p, it.A, it.Ainv, lad);
+            else if (L.type == NF_LAYER_CONV1X1_LU2) ok = fold_conv1x1_lu2(p, it.A, it.Ainv, lad);
+            else if (L.type == NF_LAYER_CONV1X1_NONE) ok = nf_invert4(it.A = nf_mat_of(p), it.Ainv, lad);
+            else {
+                nf_mat_reverse(&it.A.m[0][0]);
+                it.Ainv = it.A;
+            }
+            if (!ok) return fail(NF_EINVAL, "layer %d: the 1x1 matrix is singular", li);
             it.type = NF_OP_MIX;
             out.ld_const += HW * lad;                       // layers.py:129-130
             break;
         }
-        case NF_LAYER_CONV1X1_NONE:
-        case NF_LAYER_CONV1X1_LU2: {
-            double lad;
-            const bool ok = L.type == NF_LAYER_CONV1X1_NONE ? fold_conv1x1_none(p, it.A, it.Ainv, lad)
-                                                            : fold_conv1x1_lu2(p, it.A, it.Ainv, lad);
-            if (!ok) return fail(NF_EINVAL, "layer %d: the 1x1 matrix is singular", li);
-            it.type = NF_OP_MIX;
-            out.ld_const += HW * lad;
-            break;
-        }
-        case NF_LAYER_PERMUTE:                              // tfb.Permute(channels reversed), noise_flow_model.py:80-84
-            for (int r = 0; r < 4; ++r)
-                for (int c = 0; c < 4; ++c) it.A.m[r][c] = it.Ainv.m[r][c] = (r + c == 3) ? 1.0 : 0.0;
-            it.type = NF_OP_MIX;
-            break;
-        case NF_LAYER_COUPLING: {
+        case NF_CLS_COUPLING: {
             if (L.width < 1 || L.width > 512)
                 return fail(NF_EINVAL, "layer %d: coupling width %d unsupported (1 .. 512)", li, L.width);
             // layers.py:452-498 takes any width; the kernels exist for 4 / 8 / 16 / 32 and, zero-padded inside their layouts, 33 .. 512.
@@ -1043,34 +824,23 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
             fold_coupling(p, L.width, wk, it.blk.data());
             break;
         }
-        case NF_LAYER_SDN5:
-        case NF_LAYER_SDN4:
-        case NF_LAYER_SDN:
-        case NF_LAYER_GAIN:
-        case NF_LAYER_SDN1:
-        case NF_LAYER_SDN2:
-        case NF_LAYER_SDN3:
-        case NF_LAYER_SDN6:
-        case NF_LAYER_GAIN1:
-        case NF_LAYER_GAIN2:
-        case NF_LAYER_GAIN3: {
+        case NF_CLS_SDN:
+        case NF_CLS_COND_GAIN:
             if (out.cond.size() >= 4) return fail(NF_EINVAL, "at most 4 conditional (sdn/gain) layers per model");
             it.type = is_gain_kind(L.type) ? NF_OP_SCALE_COND : NF_OP_SDN_DIV;
             it.slot = (int)out.cond.size();
-            CondLayer c;
-            c.kind = L.type;
-            c.p.assign(p, p + cnt);
-            if (L.type == NF_LAYER_SDN5) c.p.resize(23);
-            out.cond.push_back(c);
+            out.cond.push_back(CondLayer{L.type, std::vector<float>(p, p + cnt)});
             if (!is_gain_kind(L.type)) out.has_sdn = true;
             break;
-        }
-        case NF_LAYER_GAIN4:
+        case NF_CLS_GAIN: {
             if (!(p[0] > 0.0f)) return fail(NF_EINVAL, "layer %d: gain_val must be > 0", li);
+            double K;
+            nf_gain_eval(L.type, p, CondIdx{}, (int)HW, it.scale, K);
             it.type = NF_OP_SCALE;
-            it.scale = (double)p[0];
-            out.ld_const -= HW * kC * log((double)p[0]);   // AffineCouplingGainEx4.py:114-127
+            out.ld_const -= K * log(it.scale);             // AffineCouplingGainEx4.py:114-127
             break;
+        }
+        case NF_CLS_NONE: break;                            // (refused above)
         }
         items.push_back(it);
     }
@@ -1408,26 +1178,6 @@ bool use_matrix_core()
     return mc;
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    bool changed = false;
-    int enter(int dev)
-    {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
-        if (prev != dev) {
-            e = hipSetDevice(dev);
-            if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-            changed = true;
-        }
-        return NF_OK;
-    }
-    ~DeviceGuard()
-    {
-        if (changed) (void)hipSetDevice(prev);
-    }
-};
-
 // A device buffer that grows: reserve(n) frees and reallocates only when it is too small; empty after a failed allocation.
 template <class T>
 struct DevBuf {
@@ -1530,7 +1280,7 @@ int nf_abi_version(void) { return NF_ABI_VERSION; }
 
 const char *nf_last_error(void) { return g_last_error.c_str(); }
 
-int64_t nf_layer_param_count(int32_t type, int32_t width) { return layer_param_count(type, width); }
+int64_t nf_layer_param_count(int32_t type, int32_t width) { return nf_param_count(type, width); }
 
 int nf_fold_params(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params,
                    int32_t direction, int32_t *ops_out, int32_t ops_cap, int32_t *n_ops, float *folded,
@@ -1581,7 +1331,7 @@ int nf_split_run_info(const int32_t *ops, int32_t n_ops, const float *block, siz
 int nf_sdn5_scalars(const float *sdn_params, const nf_cond *cond, double out[2])
 {
     if (!sdn_params || !out) return fail(NF_EINVAL, "null argument");
-    return sdn5_scalars(sdn_params, cond, out);
+    return cond_scalars(NF_LAYER_SDN5, sdn_params, cond, out);
 }
 
 int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params, nf_handle **out)
@@ -1620,7 +1370,7 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
         delete h;
         return fail_hip(e, "hipGetDevice");
     }
-    DeviceGuard guard;
+    NfDeviceGuard guard;
     if ((rc = guard.enter(h->device)) != NF_OK) {
         delete h;
         return rc;
@@ -1680,7 +1430,7 @@ int nf_destroy(nf_handle *h)
 {
     if (!h) return NF_OK;
     nf_hostpipe_release(h);
-    DeviceGuard guard;
+    NfDeviceGuard guard;
     (void)guard.enter(h->device);
     for (auto &dir : h->d_lay)
         for (float *p : dir)
@@ -1713,14 +1463,12 @@ static int cond_row_of(const Built &b, int H, int W, int direction, const nf_con
     r.ld = 0.0;   // per-call part of the constant log-det (plain `gain` layers)
     r.reserved = 0.0;
     for (size_t i = 0; i < b.cond.size(); ++i) {
-        double sc[2];
-        int rc = cond_scalars(b.cond[i], cond, sc);
+        double sc[2], K = 0.0;
+        int rc = cond_scalars(b.cond[i].kind, b.cond[i].p.data(), cond, sc, H * W, &K);
         if (rc != NF_OK) return rc;
         if (direction == 0 && is_gain_kind(b.cond[i].kind)) {
             r.a[i] = (float)(1.0 / sc[0]);            // NLL direction divides
-            // AffineCouplingGain / GainEx1 / GainEx3 write -log(scale) once per patch (no H*W*C factor, e.g.
-            // AffineCouplingGain.py:113-127); GainEx2 broadcasts the scale first and sums (AffineCouplingGainEx2.py:112-126)
-            r.ld -= (b.cond[i].kind == NF_LAYER_GAIN2 ? (double)H * W * kC : 1.0) * log(sc[0]);
+            r.ld -= K * log(sc[0]);
         } else {
             r.a[i] = (float)sc[0];                    // sampling direction multiplies
             r.b[i] = (float)sc[1];
@@ -2062,7 +1810,7 @@ int64_t nf_workspace_bytes(const nf_handle *h, int32_t direction, int64_t B)
 static int reserve_workspace(nf_handle *h, size_t need, int calls_in_flight)
 {
     if (need == 0) return NF_OK;
-    DeviceGuard guard;
+    NfDeviceGuard guard;
     int rc = guard.enter(h->device);
     if (rc != NF_OK) return rc;
     std::vector<nf_handle::Workspace *> got;
@@ -2125,7 +1873,7 @@ static int nll_call(nf_handle *h, const float *x, const float *y, int64_t B, con
     NfLaunch a;
     int rc = nll_args(h, x, y, B, cond, nll_out, sd_out, logdet_out, z_out, sums_out, flags, a, with_rows, rows);
     if (rc != NF_OK) return rc;
-    DeviceGuard guard;
+    NfDeviceGuard guard;
     if ((rc = guard.enter(h->device)) != NF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (sums_out && !(flags & NF_ACCUMULATE)) {
@@ -2151,7 +1899,7 @@ static int sample_call(nf_handle *h, const float *y, const float *eps, uint64_t 
     int rc = sample_args(h, y, eps, seed, patch_index_base, temp, B, cond, x_out, a, with_rows, rows);
     if (rc != NF_OK) return rc;
     if (B == 0) return NF_OK;
-    DeviceGuard guard;
+    NfDeviceGuard guard;
     if ((rc = guard.enter(h->device)) != NF_OK) return rc;
     return launch_resident(h, 1, a, (hipStream_t)stream, what);
 }
@@ -2397,7 +2145,7 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
     }
     if (B == 0) return NF_OK;
     if (h->grad_path == NF_GRAD_PATH_TILED) {
-        DeviceGuard guard;
+        NfDeviceGuard guard;
         int rc = guard.enter(h->device);
         if (rc != NF_OK) return rc;
         return grad_tiled(h, x, y, B, r, rows, nll_out, gx_out, gy_out, (hipStream_t)stream);
@@ -2420,7 +2168,7 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
     a.first_cpl = h->grad_first_cpl;
     const bool wide = h->grad_path == NF_GRAD_PATH_WIDE32;
     a.gate_words = wide ? nfgw_tpw(h->cfg.height) * h->grad_n_cpl : nf_grad_gate_words(h->grad_n_cpl, h->gprog.width);
-    DeviceGuard guard;
+    NfDeviceGuard guard;
     int rc = guard.enter(h->device);
     if (rc != NF_OK) return rc;
     hipError_t e = wide ? nf_launch_grad_wide(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream)
@@ -2917,7 +2665,7 @@ int nf_nll_batchstats(nf_handle *h, const float *x, const float *y, int64_t B, c
     int rc = nll_args(h, x, y, B, cond, nll_out, sd_out, logdet_out, z_out, sums_out, flags, a);
     if (rc != NF_OK) return rc;
     if (B == 0) return fail(NF_EINVAL, "batch statistics of an empty batch are undefined");
-    DeviceGuard guard;
+    NfDeviceGuard guard;
     if ((rc = guard.enter(h->device)) != NF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (sums_out && !(flags & NF_ACCUMULATE)) {
@@ -2935,7 +2683,7 @@ int nf_sample_batchstats(nf_handle *h, const float *y, const float *eps, uint64_
     int rc = sample_args(h, y, eps, seed, patch_index_base, temp, B, cond, x_out, a);
     if (rc != NF_OK) return rc;
     if (B == 0) return fail(NF_EINVAL, "batch statistics of an empty batch are undefined");
-    DeviceGuard guard;
+    NfDeviceGuard guard;
     if ((rc = guard.enter(h->device)) != NF_OK) return rc;
     return run_batchstats(h, 1, a, moments_out, (hipStream_t)stream, cond);
 }

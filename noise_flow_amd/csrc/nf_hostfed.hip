@@ -392,25 +392,6 @@ int64_t pipe_chunk(const nf_hostpipe *p, int64_t B)
     return std::max<int64_t>(1, std::min(ch, p->cap));
 }
 
-struct DevGuard {
-    int prev = -1;
-    bool changed = false;
-    int enter(int dev)
-    {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) return nf_fail_hip(e, "hipGetDevice");
-        if (prev != dev) {
-            if ((e = hipSetDevice(dev)) != hipSuccess) return nf_fail_hip(e, "hipSetDevice");
-            changed = true;
-        }
-        return NF_OK;
-    }
-    ~DevGuard()
-    {
-        if (changed) (void)hipSetDevice(prev);
-    }
-};
-
 }  // namespace
 
 // called by nf_destroy (nf_host.hip)
@@ -442,7 +423,7 @@ int nf_nll_host(nf_handle *h, const void *x, const void *y, int32_t dtype, int64
     int32_t H = 0, W = 0, device = 0;
     int rc = nf_handle_geometry(h, &H, &W, &device);
     if (rc != NF_OK) return rc;
-    DevGuard guard;
+    NfDeviceGuard guard;
     if ((rc = guard.enter(device)) != NF_OK) return rc;
     nf_hostpipe *p = nullptr;
     int others = 0;
@@ -521,7 +502,7 @@ int nf_sample_host(nf_handle *h, const void *y, int32_t y_dtype, const float *ep
     int32_t H = 0, W = 0, device = 0;
     int rc = nf_handle_geometry(h, &H, &W, &device);
     if (rc != NF_OK) return rc;
-    DevGuard guard;
+    NfDeviceGuard guard;
     if ((rc = guard.enter(device)) != NF_OK) return rc;
     nf_hostpipe *p = nullptr;
     int others = 0;

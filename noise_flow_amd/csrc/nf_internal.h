@@ -3,9 +3,31 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/noiseflow_hip.h"
+
 // record a thread-local error message (returned by nf_last_error) and hand back `code`
 int nf_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int nf_fail_hip(hipError_t e, const char *what);
+
+// "switch to the handle's device, switch back" around every entry point that touches the device
+struct NfDeviceGuard {
+    int prev = -1;
+    bool changed = false;
+    int enter(int dev)
+    {
+        hipError_t e = hipGetDevice(&prev);
+        if (e != hipSuccess) return nf_fail_hip(e, "hipGetDevice");
+        if (prev != dev) {
+            if ((e = hipSetDevice(dev)) != hipSuccess) return nf_fail_hip(e, "hipSetDevice");
+            changed = true;
+        }
+        return NF_OK;
+    }
+    ~NfDeviceGuard()
+    {
+        if (changed) (void)hipSetDevice(prev);
+    }
+};
 
 // geometry / device of a handle (nf_hostfed.hip sizes its staging from them)
 struct nf_handle;
@@ -16,7 +38,6 @@ void nf_hostpipe_release(nf_handle *h);
 // Evaluation under batch statistics at the coupling widths / patch sizes the fused kernels' statistics passes do not take
 // (nf_train.hip: a trimmed trainer whose couplings run on the matrix-core GEMMs of nf_train_mm.h); owned by the handle's
 // batch-statistics state, freed with nf_trainer_destroy
-#include "../../include/noiseflow_hip.h"
 struct nf_bs_wide_args {
     int direction;             // 0: NLL, 1: sampling
     const float *in;           // x (NLL) / epsilon (sampling; NULL: the in-kernel Philox draw keyed by seed, patch_base + b, pixel)

@@ -30,14 +30,12 @@
 
 #include "../../include/noiseflow_hip.h"
 #include "nf_internal.h"
+#include "nf_layers.h"     // the layer table, the coupling offsets and every scalar / matrix formula, shared with the evaluator
 #include "nf_dev_util.h"   // philox_normal4 (the evaluator draws the fused kernels' epsilon)
 
 namespace {
 
 constexpr int TB = 256;                 // threads per block of the pixel kernels
-constexpr float kBnEps = 1e-4f;         // layers.py:378
-constexpr float kBnDecay = 0.1f;        // layers.py:378
-constexpr float kLogscale = 3.0f;       // layers.py:653
 constexpr int kMaxLayers = 64;
 
 struct Geo {
@@ -48,7 +46,8 @@ struct Geo {
 };
 
 struct TLayer {
-    int type;    // NF_LAYER_* of the KERNELS that run it: every 1x1-mix kind is CONV1X1, every sdn kind SDN5, every gain kind GAIN4
+    int type;    // NF_LAYER_* of the KERNELS that run it, from the kind's class in the layer table (nf_layers.h): every 1x1-mix kind is
+                 // CONV1X1, every sdn kind SDN5, every gain kind GAIN4
     int kind;    // NF_LAYER_* as given: which parameterisation k_prep / k_finish evaluate
     int width;
     int off;     // offset of the layer's raw parameters (floats)
@@ -240,189 +239,32 @@ __device__ __forceinline__ void patch_add(float *arr, int b, bool valid, float v
 // ---------------------------------------------------------------------------------------------
 // per-step scalar preparation: A = P L U, sdn5 (a, b), constant log-det
 // ---------------------------------------------------------------------------------------------
-// vector element -> matrix entry of tfdist.fill_triangular padded to a strict triangle
-// (matrix_param.py:31-56); the same table as fold_conv1x1 in nf_host.hip
-__device__ const int kLr[6] = {3, 3, 3, 1, 2, 2}, kLc[6] = {2, 1, 0, 0, 1, 0};
-__device__ const int kUr[6] = {0, 0, 0, 2, 1, 1}, kUc[6] = {1, 2, 3, 3, 2, 3};
-
-__device__ void plu_matrices(const float *p, double Pm[4][4], double L[4][4], double U[4][4])
-{
-    const float *sign_s = p + 16, *log_s = p + 20, *lv = p + 24, *uv = p + 30;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            Pm[i][j] = p[i * 4 + j];
-            L[i][j] = i == j ? 1.0 : 0.0;
-            U[i][j] = 0.0;
-        }
-    for (int k = 0; k < 6; ++k) {
-        L[kLr[k]][kLc[k]] = lv[k];
-        U[kUr[k]][kUc[k]] = uv[k];
-    }
-    for (int i = 0; i < 4; ++i) U[i][i] = (double)sign_s[i] * exp((double)log_s[i]);
-}
-
-struct CondIdx {
-    float iso;
-    int iso_idx;   // index into gain_params or -1 (unknown ISO -> 0, cond_utils.py:227-229)
-    int cam_idx;   // 0..4
-};
-
-__device__ void sdn5_eval(const float *sp, CondIdx ci, double &a, double &b)
-{
-    const double c_i = sp[22];
-    double cp[3];
-    for (int r = 0; r < 3; ++r) cp[r] = exp(c_i * (double)sp[7 + r * 5 + ci.cam_idx]);
-    const double g = ci.iso_idx >= 0 ? (double)sp[2 + ci.iso_idx] : 0.0;
-    const double gain = exp(c_i * g * cp[2]) * (double)ci.iso;
-    a = exp(c_i * (double)sp[0] * cp[0]) / gain;
-    b = exp(c_i * (double)sp[1] * cp[1]);
-}
-
-// 4x4 inverse and log|det| by Gauss-Jordan with partial pivoting (decomp = NONE: tf.matrix_inverse / tf.linalg.slogdet)
-__device__ void inv4(const double M[4][4], double inv[4][4], double &lad)
-{
-    double a[4][8];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            a[i][j] = M[i][j];
-            a[i][4 + j] = i == j ? 1.0 : 0.0;
-        }
-    lad = 0.0;
-    for (int c = 0; c < 4; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < 4; ++r)
-            if (fabs(a[r][c]) > fabs(a[piv][c])) piv = r;
-        for (int j = 0; j < 8; ++j) {
-            const double t = a[piv][j];
-            a[piv][j] = a[c][j];
-            a[c][j] = t;
-        }
-        const double d = a[c][c];
-        lad += log(fabs(d));
-        for (int j = 0; j < 8; ++j) a[c][j] /= d;
-        for (int r = 0; r < 4; ++r) {
-            if (r == c) continue;
-            const double f = a[r][c];
-            for (int j = 0; j < 8; ++j) a[r][j] -= f * a[c][j];
-        }
-    }
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) inv[i][j] = a[i][4 + j];
-}
-
-// P, L, U of decomp = LU2 (matrix_param.py:143-188): full-matrix variables masked to their strict triangles
-__device__ void lu2_matrices(const float *p, double Pm[4][4], double L[4][4], double U[4][4])
-{
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            Pm[i][j] = p[i * 4 + j];
-            L[i][j] = j < i ? (double)p[16 + i * 4 + j] : (i == j ? 1.0 : 0.0);
-            U[i][j] = j > i ? (double)p[40 + i * 4 + j] : (i == j ? (double)p[32 + i] * exp((double)p[36 + i]) : 0.0);
-        }
-}
-
-__device__ __forceinline__ double sigm(double v) { return 1.0 / (1.0 + exp(-v)); }
-
-// the per-ISO tables of the Ex1-Ex3 layers: any ISO outside 100..3200 takes the ISO-800 entry (cond_utils.py:69-88)
-__device__ __forceinline__ int table_idx(CondIdx ci) { return ci.iso_idx >= 0 ? ci.iso_idx : 2; }
-
-// scale^2 = a y + b of every sdn kind (cond_utils.py:41-276)
-__device__ void sdn_ab(int kind, const float *p, CondIdx ci, double &a, double &b)
-{
-    const double iso = ci.iso;
-    if (kind == NF_LAYER_SDN5) {
-        sdn5_eval(p, ci, a, b);
-    } else if (kind == NF_LAYER_SDN4) {                                    // c = 1, no camera
-        const double gpar = ci.iso_idx >= 0 ? (double)p[2 + ci.iso_idx] : 0.0;
-        a = exp((double)p[0]) / (exp(gpar) * iso);
-        b = exp((double)p[1]);
-    } else if (kind == NF_LAYER_SDN) {
-        a = sigm(p[0]);
-        b = sigm(p[1]);
-    } else if (kind == NF_LAYER_SDN6) {                                    // one camera parameter, on the gain exponent
-        const double c = p[12], cp = exp(c * (double)p[7 + ci.cam_idx]);
-        const double g = ci.iso_idx >= 0 ? (double)p[2 + ci.iso_idx] : 0.0;
-        a = exp(c * (double)p[0]) / (exp(c * g * cp) * iso);
-        b = exp(c * (double)p[1]);
-    } else {                                                               // SDN1 / SDN2 / SDN3
-        const double gain = exp((kind == NF_LAYER_SDN1 ? 1e-2 : 1e-1) * (double)p[2 + table_idx(ci)]) * iso;
-        const double A0 = sigm(p[0]), B0 = sigm(p[1]);
-        if (kind == NF_LAYER_SDN1) { a = A0 / gain; b = B0; }
-        else if (kind == NF_LAYER_SDN2) { a = A0; b = gain * B0; }
-        else { a = gain * A0; b = gain * gain * B0; }
-    }
-}
-
-// scale of every gain kind and the number of log(scale) terms its log-det holds (cond_utils.py:319-440 and the layers:
-// GainEx4 / GainEx2 write the full H*W*C sum, Gain / GainEx1 / GainEx3 -log(scale) once per patch)
-__device__ void gain_s(int kind, const float *p, CondIdx ci, int HW, double &sv, double &K)
-{
-    const double iso = ci.iso;
-    K = 1.0;
-    if (kind == NF_LAYER_GAIN4) { sv = p[0]; K = 4.0 * HW; }
-    else if (kind == NF_LAYER_GAIN) sv = sigm(p[0]) * iso + sigm(p[1]);
-    else if (kind == NF_LAYER_GAIN1) sv = exp(1e-5 * (double)p[0]) * iso + exp(1e-5 * (double)p[1]);
-    else if (kind == NF_LAYER_GAIN2) { sv = exp(1e-1 * (double)p[table_idx(ci)]) * iso; K = 4.0 * HW; }
-    else sv = exp(1e-5 * (double)p[table_idx(ci)]);
-}
-
+// (formulas: nf_layers.h)
 __device__ void k_prep_layer(const TLayer L, const float *__restrict__ P, CondIdx ci, int HW, float *__restrict__ Abuf,
                              float *__restrict__ abbuf, float *__restrict__ sbuf, double *ldc)
 {
     const float *p = P + L.off;
-    if (L.kind == NF_LAYER_PERMUTE) {                                      // tfb.Permute(channels reversed), log|det| = 0
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) Abuf[L.aux * 16 + i * 4 + j] = (i + j == 3) ? 1.0f : 0.0f;
+    if (L.kind == NF_LAYER_PERMUTE) {                                      // log|det| = 0
+        nf_mat_reverse(Abuf + L.aux * 16);
     } else if (L.kind == NF_LAYER_CONV1X1_NONE) {
-        double M[4][4], Mi[4][4], lad;
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) {
-                M[i][j] = p[i * 4 + j];
-                Abuf[L.aux * 16 + i * 4 + j] = p[i * 4 + j];
-            }
-        inv4(M, Mi, lad);
+        Mat4 Mi;
+        double lad;
+        for (int k = 0; k < 16; ++k) Abuf[L.aux * 16 + k] = p[k];
+        (void)nf_invert4(nf_mat_of(p), Mi, lad);                           // (a singular matrix: unspecified, as before)
         *ldc += (double)HW * lad;
-    } else if (L.kind == NF_LAYER_CONV1X1_LU2) {
-        double Pm[4][4], Lm[4][4], Um[4][4];
-        lu2_matrices(p, Pm, Lm, Um);
-        double lad = 0.0;
-        for (int i = 0; i < 4; ++i) {
-            lad += (double)p[36 + i];
-            for (int j = 0; j < 4; ++j) {
-                double sacc = 0.0;
-                for (int k = 0; k < 4; ++k)
-                    for (int m = 0; m < 4; ++m) sacc += Pm[i][k] * Lm[k][m] * Um[m][j];
-                Abuf[L.aux * 16 + i * 4 + j] = (float)sacc;
-            }
-        }
-        *ldc += (double)HW * lad;
-    } else if (L.type == NF_LAYER_CONV1X1) {
-        double Pm[4][4], Lm[4][4], Um[4][4], LU[4][4];
-        plu_matrices(p, Pm, Lm, Um);
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) {
-                double s = 0.0;
-                for (int k = 0; k < 4; ++k) s += Lm[i][k] * Um[k][j];
-                LU[i][j] = s;
-            }
-        double lad = 0.0;
-        for (int i = 0; i < 4; ++i) {
-            lad += (double)p[20 + i];
-            for (int j = 0; j < 4; ++j) {
-                double s = 0.0;
-                for (int k = 0; k < 4; ++k) s += Pm[i][k] * LU[k][j];
-                Abuf[L.aux * 16 + i * 4 + j] = (float)s;
-            }
-        }
-        *ldc += (double)HW * lad;                                  // layers.py:129-130
+    } else if (L.type == NF_LAYER_CONV1X1) {                               // PLU / LU2
+        Mat4 Pm, Lm, Um;
+        const double lad = L.kind == NF_LAYER_CONV1X1_LU2 ? nf_lu2_matrices(p, Pm, Lm, Um) : nf_plu_matrices(p, Pm, Lm, Um);
+        nf_plu_product(Pm, Lm, Um, Abuf + L.aux * 16);
+        *ldc += (double)HW * lad;                                          // layers.py:129-130
     } else if (L.type == NF_LAYER_SDN5) {
-        double a, b;
-        sdn_ab(L.kind, p, ci, a, b);
-        abbuf[L.aux * 2] = (float)a;
-        abbuf[L.aux * 2 + 1] = (float)b;
+        NfSdn s;
+        nf_sdn_eval(L.kind, p, ci, s);
+        abbuf[L.aux * 2] = (float)s.a;
+        abbuf[L.aux * 2 + 1] = (float)s.b;
     } else if (L.type == NF_LAYER_GAIN4) {
         double sv, K;
-        gain_s(L.kind, p, ci, HW, sv, K);
+        nf_gain_eval(L.kind, p, ci, HW, sv, K);
         sbuf[L.aux] = (float)sv;
         *ldc += -K * log(sv);                                      // AffineCouplingGainEx4.py:114-127 and siblings
     }
@@ -580,14 +422,14 @@ __device__ __forceinline__ void bn_from_slots(Acc stats, int nslot, double n, fl
         double v = sq / n - m * m;
         if (v < 0.0) v = 0.0;
         if ((threadIdx.x & 63) == 0) {
-            const float mf = (float)m, rf = (float)(1.0 / sqrt(v + (double)kBnEps));
+            const float mf = (float)m, rf = (float)(1.0 / sqrt(v + (double)kBnEpsF));
             sh[j] = mf;
             sh[W + j] = rf;
             if (blockIdx.x == 0 && blockIdx.y == 0) {
                 bn_out[j] = mf;
                 bn_out[W + j] = rf;
-                P[off_mean + j] -= kBnDecay * (P[off_mean + j] - mf);
-                P[off_var + j] -= kBnDecay * (P[off_var + j] - (float)v);
+                P[off_mean + j] -= kBnDecayF * (P[off_mean + j] - mf);
+                P[off_var + j] -= kBnDecayF * (P[off_var + j] - (float)v);
             }
         }
     }
@@ -629,9 +471,9 @@ __global__ __launch_bounds__(64) void k_bn_fin(Acc stats, int W, int nslot, doub
     if (threadIdx.x == 0) {
         const float mf = (float)m;
         bn_out[j] = mf;
-        bn_out[W + j] = (float)(1.0 / sqrt(v + (double)kBnEps));
-        P[off_mean + j] -= kBnDecay * (P[off_mean + j] - mf);
-        P[off_var + j] -= kBnDecay * (P[off_var + j] - (float)v);
+        bn_out[W + j] = (float)(1.0 / sqrt(v + (double)kBnEpsF));
+        P[off_mean + j] -= kBnDecayF * (P[off_mean + j] - mf);
+        P[off_var + j] -= kBnDecayF * (P[off_var + j] - (float)v);
     }
 }
 
@@ -746,8 +588,8 @@ __global__ void k_c3_fwd(Geo g, const float *__restrict__ zin, const float *__re
     bn_from_slots<W>(stats2, g.nslot, n, bn2, P, off_m2, off_m2 + W, bn2_out, fin);
     const float *W3 = Pw + off_w3, *b3 = W3 + 36 * (W + 1), *logs = b3 + 4;
     const float sc = logs[4];
-    const float e30 = expf(kLogscale * logs[0]), e31 = expf(kLogscale * logs[1]), e32 = expf(kLogscale * logs[2]),
-                e33 = expf(kLogscale * logs[3]);   // uniform: once per thread, not once per pixel
+    const float e30 = expf(kLogscaleF * logs[0]), e31 = expf(kLogscaleF * logs[1]), e32 = expf(kLogscaleF * logs[2]),
+                e33 = expf(kLogscaleF * logs[3]);   // uniform: once per thread, not once per pixel
     float l = 0.0f;
     NF_PIXEL_LOOP(g, p) {
         if (p < g.npix) {
@@ -943,7 +785,7 @@ __global__ void k_c3_bwd(Geo g, const float *__restrict__ zin, const float *__re
     const int off_b3 = off_w3 + 36 * (W + 1);
     float e3[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) e3[k] = expf(kLogscale * logs[k]);
+    for (int k = 0; k < 4; ++k) e3[k] = expf(kLogscaleF * logs[k]);
     float g_s = 0.0f, g_logs[4] = {0.f, 0.f, 0.f, 0.f}, g_b3[4] = {0.f, 0.f, 0.f, 0.f};
     NF_PIXEL_LOOP(g, p) {
         if (p < g.npix) {
@@ -979,7 +821,7 @@ __global__ void k_c3_bwd(Geo g, const float *__restrict__ zin, const float *__re
             float guv[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                g_logs[k] = fmaf(kLogscale * go[k], o[k], g_logs[k]);
+                g_logs[k] = fmaf(kLogscaleF * go[k], o[k], g_logs[k]);
                 guv[k] = go[k] * e3[k];
                 g_b3[k] += guv[k];
             }
@@ -1364,74 +1206,75 @@ __global__ void k_finish(TLayers ls, const float *__restrict__ P, CondIdx ci, in
     if (L.kind == NF_LAYER_PERMUTE) {
         // no parameters
     } else if (L.kind == NF_LAYER_CONV1X1_NONE) {                          // A is the variable: dA - H W A^-T
-        double M[4][4], Mi[4][4], lad;
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) M[i][j] = p[i * 4 + j];
-        inv4(M, Mi, lad);
+        Mat4 Mi;
+        double lad;
+        (void)nf_invert4(nf_mat_of(p), Mi, lad);
         const double *dA = dAbuf + L.aux * 16;
         for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) gp[i * 4 + j] = dA[i * 4 + j] - (double)HW * Mi[j][i];
-    } else if (L.kind == NF_LAYER_CONV1X1_LU2) {
-        double Pm[4][4], Lm[4][4], Um[4][4], dM[4][4];
-        lu2_matrices(p, Pm, Lm, Um);
+            for (int j = 0; j < 4; ++j) gp[i * 4 + j] = dA[i * 4 + j] - (double)HW * Mi.m[j][i];
+    } else if (L.type == NF_LAYER_CONV1X1) {                               // PLU / LU2: A = P M, M = L U
+        const bool lu2 = L.kind == NF_LAYER_CONV1X1_LU2;
+        Mat4 Pm, Lm, Um;
+        if (lu2) (void)nf_lu2_matrices(p, Pm, Lm, Um);
+        else (void)nf_plu_matrices(p, Pm, Lm, Um);
+        double dM[4][4], dL[4][4], dU[4][4];
         const double *dA = dAbuf + L.aux * 16;
-        for (int i = 0; i < 4; ++i)          // dM = P^T dA   (A = P M, M = L U)
-            for (int j = 0; j < 4; ++j) {
-                double sacc = 0.0;
-                for (int k = 0; k < 4; ++k) sacc += Pm[k][i] * dA[k * 4 + j];
-                dM[i][j] = sacc;
-            }
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) {
-                double dl = 0.0, du = 0.0;
-                for (int k = 0; k < 4; ++k) {
-                    dl += dM[i][k] * Um[j][k];   // dL = dM U^T
-                    du += Lm[k][i] * dM[k][j];   // dU = L^T dM
-                }
-                gp[16 + i * 4 + j] = j < i ? dl : 0.0;                     // the mask of matrix_param.py:171-173
-                gp[40 + i * 4 + j] = j > i ? du : 0.0;
-                if (i == j) gp[36 + i] = du * Um[i][i] - (double)HW;       // log_S: diagonal + log-det term
-            }
-    } else if (L.type == NF_LAYER_CONV1X1) {
-        double Pm[4][4], Lm[4][4], Um[4][4], dM[4][4], dL[4][4], dU[4][4];
-        plu_matrices(p, Pm, Lm, Um);
-        const double *dA = dAbuf + L.aux * 16;
-        for (int i = 0; i < 4; ++i)          // dM = P^T dA   (A = P M, M = L U)
+        for (int i = 0; i < 4; ++i)          // dM = P^T dA
             for (int j = 0; j < 4; ++j) {
                 double s = 0.0;
-                for (int k = 0; k < 4; ++k) s += Pm[k][i] * dA[k * 4 + j];
+                for (int k = 0; k < 4; ++k) s += Pm.m[k][i] * dA[k * 4 + j];
                 dM[i][j] = s;
             }
         for (int i = 0; i < 4; ++i)
             for (int j = 0; j < 4; ++j) {
                 double s = 0.0, t = 0.0;
                 for (int k = 0; k < 4; ++k) {
-                    s += dM[i][k] * Um[j][k];   // dL = dM U^T
-                    t += Lm[k][i] * dM[k][j];   // dU = L^T dM
+                    s += dM[i][k] * Um.m[j][k];   // dL = dM U^T
+                    t += Lm.m[k][i] * dM[k][j];   // dU = L^T dM
                 }
                 dL[i][j] = s;
                 dU[i][j] = t;
             }
-        for (int i = 0; i < 4; ++i) gp[20 + i] = dU[i][i] * Um[i][i] - (double)HW;   // log_S: diagonal + log-det term
-        for (int k = 0; k < 6; ++k) {
-            gp[24 + k] = dL[kLr[k]][kLc[k]];
-            gp[30 + k] = dU[kUr[k]][kUc[k]];
+        for (int i = 0; i < 4; ++i) gp[(lu2 ? 36 : 20) + i] = dU[i][i] * Um.m[i][i] - (double)HW;   // log_S: diagonal + log-det term
+        if (lu2) {
+            for (int i = 0; i < 4; ++i)
+                for (int j = 0; j < 4; ++j) {
+                    gp[16 + i * 4 + j] = j < i ? dL[i][j] : 0.0;           // the mask of matrix_param.py:171-173
+                    gp[40 + i * 4 + j] = j > i ? dU[i][j] : 0.0;
+                }
+        } else {
+#define NF_X(k, r, c) gp[24 + k] = dL[r][c];
+            NF_TRI_LOWER(NF_X)
+#undef NF_X
+#define NF_X(k, r, c) gp[30 + k] = dU[r][c];
+            NF_TRI_UPPER(NF_X)
+#undef NF_X
         }
-    } else if (L.kind == NF_LAYER_SDN || L.kind == NF_LAYER_SDN1 || L.kind == NF_LAYER_SDN2 || L.kind == NF_LAYER_SDN3 ||
-               L.kind == NF_LAYER_SDN6) {
-        double a, b;
-        sdn_ab(L.kind, p, ci, a, b);
-        const double ga = dabbuf[L.aux * 2], gb = dabbuf[L.aux * 2 + 1];
-        if (L.kind == NF_LAYER_SDN6) {
-            const double c = p[12], cp = exp(c * (double)p[7 + ci.cam_idx]);
-            const double g = ci.iso_idx >= 0 ? (double)p[2 + ci.iso_idx] : 0.0;
+    } else if (L.type == NF_LAYER_SDN5) {                                  // every sdn kind: d(a, b) -> its variables
+        NfSdn s;
+        nf_sdn_eval(L.kind, p, ci, s);
+        const double a = s.a, b = s.b, ga = dabbuf[L.aux * 2], gb = dabbuf[L.aux * 2 + 1];
+        if (L.kind == NF_LAYER_SDN5) {
+            const double c_i = p[22], beta1 = p[0], beta2 = p[1];
+            gp[0] = ga * a * c_i * s.cp[0];
+            gp[1] = gb * b * c_i * s.cp[1];
+            if (ci.iso_idx >= 0) gp[2 + ci.iso_idx] = -ga * a * c_i * s.cp[2];
+            gp[7 + 0 * 5 + ci.cam_idx] = ga * a * c_i * c_i * beta1 * s.cp[0];
+            gp[7 + 1 * 5 + ci.cam_idx] = gb * b * c_i * c_i * beta2 * s.cp[1];
+            gp[7 + 2 * 5 + ci.cam_idx] = -ga * a * c_i * c_i * s.g * s.cp[2];
+        } else if (L.kind == NF_LAYER_SDN4) {
+            gp[0] = ga * a;
+            gp[1] = gb * b;
+            if (ci.iso_idx >= 0) gp[2 + ci.iso_idx] = -ga * a;
+        } else if (L.kind == NF_LAYER_SDN6) {
+            const double c = p[12], cp = s.cp[0];
             gp[0] = ga * a * c;
             gp[1] = gb * b * c;
             if (ci.iso_idx >= 0) gp[2 + ci.iso_idx] = -ga * a * c * cp;
-            gp[7 + ci.cam_idx] = -ga * a * c * c * g * cp;
+            gp[7 + ci.cam_idx] = -ga * a * c * c * s.g * cp;
         } else {
-            const double A0 = sigm(p[0]), B0 = sigm(p[1]), dA0 = A0 * (1.0 - A0), dB0 = B0 * (1.0 - B0);
-            const int k = 2 + table_idx(ci);
+            const double A0 = s.A0, B0 = s.B0, dA0 = A0 * (1.0 - A0), dB0 = B0 * (1.0 - B0);
+            const int k = 2 + nf_table_idx(ci);
             if (L.kind == NF_LAYER_SDN) {
                 gp[0] = ga * dA0;
                 gp[1] = gb * dB0;
@@ -1449,45 +1292,23 @@ __global__ void k_finish(TLayers ls, const float *__restrict__ P, CondIdx ci, in
                 gp[k] = (ga * a + 2.0 * gb * b) * 1e-1;
             }
         }
-    } else if (L.kind == NF_LAYER_GAIN || L.kind == NF_LAYER_GAIN1 || L.kind == NF_LAYER_GAIN2 || L.kind == NF_LAYER_GAIN3) {
+    } else if (L.type == NF_LAYER_GAIN4) {                                 // every gain kind
         double sv, K;
-        gain_s(L.kind, p, ci, HW, sv, K);
+        nf_gain_eval(L.kind, p, ci, HW, sv, K);
         const double gs = dgbuf[L.aux] + K / sv;                            // data path + the log-det term
         const double iso = ci.iso;
-        if (L.kind == NF_LAYER_GAIN) {
-            const double A0 = sigm(p[0]), B0 = sigm(p[1]);
+        if (L.kind == NF_LAYER_GAIN4) {
+            gp[0] = gs;
+        } else if (L.kind == NF_LAYER_GAIN) {
+            const double A0 = nf_sigmoid(p[0]), B0 = nf_sigmoid(p[1]);
             gp[0] = gs * iso * A0 * (1.0 - A0);
             gp[1] = gs * B0 * (1.0 - B0);
         } else if (L.kind == NF_LAYER_GAIN1) {
             gp[0] = gs * iso * exp(1e-5 * (double)p[0]) * 1e-5;
             gp[1] = gs * exp(1e-5 * (double)p[1]) * 1e-5;
         } else {
-            gp[table_idx(ci)] = gs * sv * (L.kind == NF_LAYER_GAIN2 ? 1e-1 : 1e-5);
+            gp[nf_table_idx(ci)] = gs * sv * (L.kind == NF_LAYER_GAIN2 ? 1e-1 : 1e-5);
         }
-    } else if (L.kind == NF_LAYER_SDN5) {
-        double a, b;
-        sdn5_eval(p, ci, a, b);
-        const double ga = dabbuf[L.aux * 2], gb = dabbuf[L.aux * 2 + 1];
-        const double c_i = p[22];
-        double cp[3];
-        for (int r = 0; r < 3; ++r) cp[r] = exp(c_i * (double)p[7 + r * 5 + ci.cam_idx]);
-        const double beta1 = p[0], beta2 = p[1];
-        const double gpar = ci.iso_idx >= 0 ? (double)p[2 + ci.iso_idx] : 0.0;
-        gp[0] = ga * a * c_i * cp[0];
-        gp[1] = gb * b * c_i * cp[1];
-        if (ci.iso_idx >= 0) gp[2 + ci.iso_idx] = -ga * a * c_i * cp[2];
-        gp[7 + 0 * 5 + ci.cam_idx] = ga * a * c_i * c_i * beta1 * cp[0];
-        gp[7 + 1 * 5 + ci.cam_idx] = gb * b * c_i * c_i * beta2 * cp[1];
-        gp[7 + 2 * 5 + ci.cam_idx] = -ga * a * c_i * c_i * gpar * cp[2];
-    } else if (L.kind == NF_LAYER_SDN4) {
-        const double gpar = ci.iso_idx >= 0 ? (double)p[2 + ci.iso_idx] : 0.0;
-        const double a = exp((double)p[0]) / (exp(gpar) * (double)ci.iso), b = exp((double)p[1]);
-        const double ga = dabbuf[L.aux * 2], gb = dabbuf[L.aux * 2 + 1];
-        gp[0] = ga * a;
-        gp[1] = gb * b;
-        if (ci.iso_idx >= 0) gp[2 + ci.iso_idx] = -ga * a;
-    } else if (L.kind == NF_LAYER_GAIN4) {
-        gp[0] = dgbuf[L.aux] + (double)HW * 4.0 / (double)p[0];
     }
 }
 
@@ -1530,17 +1351,6 @@ struct Cpl {      // per-coupling workspace
     int f_bn1, f_bn2, f_bb1, f_bb2;       // offsets into the float scalar buffer
     int d_st1, d_st2, d_bs1, d_bs2;       // offsets into the double buffer
 };
-
-// Where a coupling's parameters sit in the raw vector (nf_layer_param_count): l_1/W [18][w], l_1/b, BN1 mean + var, l_2/W [w][w],
-// l_2/b, BN2 mean + var, l_last/W [36][w + 1]; tail3: b3 [4], logs [4], scale.  The ONE place these formulas are written.
-struct CplOff {
-    int w1, b1, m1, w2, b2, m2, w3, tail3;
-};
-inline CplOff cpl_off(int off, int w)
-{
-    const int w2 = off + 21 * w, m2 = w2 + w * w + w, w3 = m2 + 2 * w;
-    return CplOff{off, off + 18 * w, off + 19 * w, w2, w2 + w * w, m2, w3, w3 + 36 * (w + 1)};
-}
 
 // Which kernel family runs the couplings of a handle.  The create-time part (train_family: width, patch size, the switches) is stored
 // on the handle and sizes the workspace; train_path() adds the per-call part (the tiled stages' batch terms).
@@ -1696,25 +1506,6 @@ inline unsigned blocks_for(const nf_trainer *t, int64_t npix)
     if (t->nb_floor) b = std::max<int64_t>(b, std::min<int64_t>(t->nb_floor, (npix + 127) / 128));
     return (unsigned)std::min<int64_t>(b, NSLOT);
 }
-
-struct Guard {
-    int prev = -1;
-    bool changed = false;
-    int enter(int dev)
-    {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) return nf_fail_hip(e, "hipGetDevice");
-        if (prev != dev) {
-            if ((e = hipSetDevice(dev)) != hipSuccess) return nf_fail_hip(e, "hipSetDevice");
-            changed = true;
-        }
-        return NF_OK;
-    }
-    ~Guard()
-    {
-        if (changed) (void)hipSetDevice(prev);
-    }
-};
 
 // all-reduce `count` slotted sums (a, a+1, ...) over the ranks; no-op without nf_trainer_set_sync
 void sync_slots(nf_trainer *t, Acc a, int count, int nslot, hipStream_t st)
@@ -2357,23 +2148,15 @@ bool coupling_backward_tiled(nf_trainer *t, const Geo &g, const CplCtx &x, const
     return nx.L != nullptr;
 }
 
+// the table indices of a step's nf_cond: NULL only where no layer reads it; the camera matters only to the kinds that read it
 int cond_index(const nf_cond *cond, bool needed, bool needs_cam, CondIdx &ci)
 {
-    ci.iso = 0.f;
-    ci.iso_idx = -1;
-    ci.cam_idx = 0;
+    ci = CondIdx{0.f, -1, 0};
     if (!needed) return NF_OK;
     if (!cond) return nf_fail(NF_EINVAL, "model has a signal-dependent layer but cond is NULL");
-    static const float iso_vals[5] = {100.f, 400.f, 800.f, 1600.f, 3200.f};
-    ci.iso = cond->iso;
-    for (int i = 0; i < 5; ++i)
-        if (iso_vals[i] == cond->iso) ci.iso_idx = i;
-    int cam = -1;
-    for (int i = 0; i < 5; ++i)
-        if ((float)i == cond->cam) cam = i;
-    if (cam < 0 && !needs_cam) cam = 0;
-    if (cam < 0) return nf_fail(NF_ECOND, "unknown camera id %g (expected 0..4 = IP,GP,S6,N6,G4)", (double)cond->cam);
-    ci.cam_idx = cam;
+    ci = nf_cond_index(cond);
+    if (ci.cam_idx < 0 && needs_cam) return nf_fail(NF_ECOND, NF_CAM_ERROR, (double)cond->cam);
+    if (ci.cam_idx < 0) ci.cam_idx = 0;
     return NF_OK;
 }
 
@@ -2388,7 +2171,7 @@ int nf_trainer_destroy(nf_trainer *t)
         delete t;
         return NF_OK;
     }
-    Guard guard;
+    NfDeviceGuard guard;
     (void)guard.enter(t->device);
     if (t->side) {
         (void)hipStreamSynchronize(t->side);
@@ -2450,82 +2233,47 @@ static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers
         if (L.param_offset < prev_end) NF_TRY(nf_fail(NF_EINVAL, "layer %d: parameter blocks must be ascending and must not overlap (offset %lld, previous block ends at %lld)",
                            i, (long long)L.param_offset, (long long)prev_end));
         prev_end = L.param_offset + cnt;
+        // the layer table (nf_layers.h) says which kernels run the kind, which of its parameters train and what it reads
+        const NfLayerInfo &info = nf_layer_info(L.type);
         TLayer &T = t->tl.l[i];
-        T.type = L.type;
         T.kind = L.type;
         T.width = L.width;
         T.off = (int)L.param_offset;
         uint8_t *mk = mask.data() + L.param_offset;
-        switch (L.type) {
-        case NF_LAYER_CONV1X1:
+        for (const auto &r : info.train)
+            for (int k = r[0]; k < r[1]; ++k) mk[k] = 1;
+        switch (info.cls) {
+        case NF_CLS_MIX:
+            T.type = NF_LAYER_CONV1X1;
             T.aux = n_mix++;
-            for (int k = 20; k < 36; ++k) mk[k] = 1;   // log_S, L_vec, U_vec (P, sign_S are constants)
             break;
-        case NF_LAYER_COUPLING: {
+        case NF_CLS_COUPLING: {
             const int w = L.width;
             if (w < 1 || w > 512) NF_TRY(nf_fail(NF_EINVAL, "layer %d: the trainer takes the coupling widths 1 .. 512 (%d given)", i, w));
             if (t->width && t->width != w) NF_TRY(nf_fail(NF_EINVAL, "all coupling layers must share one width"));
             t->width = w;
+            T.type = NF_LAYER_COUPLING;
             T.aux = n_cpl++;
+            const CplOff o = cpl_off(0, w);
             for (int64_t k = 0; k < cnt; ++k) mk[k] = 1;
-            for (int k = 0; k < 2 * w; ++k) mk[19 * w + k] = mk[22 * w + w * w + k] = 0;   // BN running statistics
+            for (int k = 0; k < 2 * w; ++k) mk[o.m1 + k] = mk[o.m2 + k] = 0;   // BN running statistics
             break;
         }
-        case NF_LAYER_SDN5:
-            T.aux = n_sdn++;
-            for (int k = 0; k < 22; ++k) mk[k] = 1;    // c_i is a constant
-            t->has_sdn = true;
-            t->needs_cam = true;
-            break;
-        case NF_LAYER_SDN4:
+        case NF_CLS_SDN:
             T.type = NF_LAYER_SDN5;
             T.aux = n_sdn++;
-            for (int k = 0; k < 7; ++k) mk[k] = 1;
             t->has_sdn = true;
             break;
-        case NF_LAYER_GAIN4:
-            T.aux = n_gain++;
-            mk[0] = 1;
-            break;
-        // the other parameterisations run on the same kernels (TLayer::type) and differ in k_prep / k_finish (TLayer::kind)
-        case NF_LAYER_CONV1X1_NONE:
-            T.type = NF_LAYER_CONV1X1;
-            T.aux = n_mix++;
-            for (int k = 0; k < 16; ++k) mk[k] = 1;
-            break;
-        case NF_LAYER_CONV1X1_LU2:
-            T.type = NF_LAYER_CONV1X1;
-            T.aux = n_mix++;
-            for (int k = 16; k < 32; ++k) mk[k] = 1;   // L (P, sign_S are constants)
-            for (int k = 36; k < 56; ++k) mk[k] = 1;   // log_S, U
-            break;
-        case NF_LAYER_PERMUTE:
-            T.type = NF_LAYER_CONV1X1;
-            T.aux = n_mix++;
-            break;
-        case NF_LAYER_SDN:
-        case NF_LAYER_SDN1:
-        case NF_LAYER_SDN2:
-        case NF_LAYER_SDN3:
-        case NF_LAYER_SDN6:
-            T.type = NF_LAYER_SDN5;
-            T.aux = n_sdn++;
-            for (int64_t k = 0; k < (L.type == NF_LAYER_SDN6 ? 12 : cnt); ++k) mk[k] = 1;   // SDN6: c_i is a constant
-            t->has_sdn = true;
-            if (L.type == NF_LAYER_SDN6) t->needs_cam = true;
-            break;
-        case NF_LAYER_GAIN:
-        case NF_LAYER_GAIN1:
-        case NF_LAYER_GAIN2:
-        case NF_LAYER_GAIN3:
+        case NF_CLS_COND_GAIN:
+            t->needs_cond = true;
+            [[fallthrough]];
+        case NF_CLS_GAIN:
             T.type = NF_LAYER_GAIN4;
             T.aux = n_gain++;
-            for (int64_t k = 0; k < cnt; ++k) mk[k] = 1;
-            t->needs_cond = true;
             break;
-        default:
-            NF_TRY(nf_fail(NF_EINVAL, "layer %d: unknown layer type %d", i, L.type));
+        case NF_CLS_NONE: break;   // (refused above: no parameter count)
         }
+        if (info.cam) t->needs_cam = true;
     }
 
     // the step plan: each coupling's folded Conv2d1x1 and its fusable neighbours.  The layer list is fixed, so this is asked once, here.
@@ -2551,7 +2299,7 @@ static int trainer_create_impl(const nf_config *cfg, const nf_layer_desc *layers
     hipError_t e;
     if (cfg->device >= 0) t->device = cfg->device;
     else if ((e = hipGetDevice(&t->device)) != hipSuccess) NF_TRY(nf_fail_hip(e, "hipGetDevice"));
-    Guard guard;
+    NfDeviceGuard guard;
     NF_TRY(guard.enter(t->device));
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess && cus > 0) t->n_cu = cus;
@@ -2709,7 +2457,7 @@ static int trainer_run(nf_trainer *t, const float *x, const float *y, int64_t B,
     CondIdx ci;
     int rc = cond_index(cond, t->has_sdn || t->needs_cond, t->needs_cam, ci);
     if (rc != NF_OK) return rc;
-    Guard guard;
+    NfDeviceGuard guard;
     if ((rc = guard.enter(t->device)) != NF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
 
@@ -2933,7 +2681,7 @@ int nf_trainer_set_sync(nf_trainer *t, nf_allreduce_fn fn, void *user, double *s
 int nf_trainer_apply(nf_trainer *t, const float *grads, float lr, void *stream)
 {
     if (!t) return nf_fail(NF_EINVAL, "trainer is NULL");
-    Guard guard;
+    NfDeviceGuard guard;
     int rc = guard.enter(t->device);
     if (rc != NF_OK) return rc;
     const float *gr = grads ? grads : t->d_gradf;
@@ -2965,7 +2713,7 @@ int nf_trainer_get_params(nf_trainer *t, float *params_out, size_t n_params, voi
 {
     if (!t || !params_out) return nf_fail(NF_EINVAL, "null argument");
     if (n_params != (size_t)t->n_params) return nf_fail(NF_EINVAL, "n_params mismatch (%zu vs %d)", n_params, t->n_params);
-    Guard guard;
+    NfDeviceGuard guard;
     int rc = guard.enter(t->device);
     if (rc != NF_OK) return rc;
     hipError_t e = hipMemcpyAsync(params_out, t->d_params, n_params * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream);
@@ -2978,7 +2726,7 @@ int nf_trainer_set_params(nf_trainer *t, const float *params, size_t n_params, v
 {
     if (!t || !params) return nf_fail(NF_EINVAL, "null argument");
     if (n_params != (size_t)t->n_params) return nf_fail(NF_EINVAL, "n_params mismatch (%zu vs %d)", n_params, t->n_params);
-    Guard guard;
+    NfDeviceGuard guard;
     int rc = guard.enter(t->device);
     if (rc != NF_OK) return rc;
     hipError_t e = hipMemcpyAsync(t->d_params, params, n_params * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
@@ -3010,7 +2758,7 @@ int nf_bs_wide_run(nf_trainer *t, const nf_bs_wide_args &a, hipStream_t st)
     int rc = cond_index(a.cond, t->has_sdn || t->needs_cond, t->needs_cam, ci);
     if (rc != NF_OK) return rc;
     if (t->has_sdn && !a.y) return nf_fail(NF_EINVAL, "model has a signal-dependent layer but y is NULL");
-    Guard guard;
+    NfDeviceGuard guard;
     if ((rc = guard.enter(t->device)) != NF_OK) return rc;
     t->sync_fn = a.sync_fn;
     t->sync_user = a.sync_user;

@@ -158,10 +158,10 @@ __global__ __launch_bounds__(256) void k_g_c1_fwd(Geo g, int w, const float *__r
 __global__ void k_g_c3_fwd(Geo g, int w, const float *__restrict__ zin, const float *__restrict__ P36, const float *__restrict__ Pw,
                            int off_w3, float *__restrict__ zout, Acc ldacc, float *__restrict__ u_out)
 {
-    const float *W3 = Pw + off_w3, *b3 = W3 + 36 * (w + 1), *logs = b3 + 4;
+    const float *W3 = Pw + off_w3, *b3 = W3 + NF_CPL_W3_LEN(w), *logs = b3 + 4;
     const float sc = logs[4];
-    const float e30 = expf(kLogscale * logs[0]), e31 = expf(kLogscale * logs[1]), e32 = expf(kLogscale * logs[2]),
-                e33 = expf(kLogscale * logs[3]);
+    const float e30 = expf(kLogscaleF * logs[0]), e31 = expf(kLogscaleF * logs[1]), e32 = expf(kLogscaleF * logs[2]),
+                e33 = expf(kLogscaleF * logs[3]);
     float l = 0.0f;
     NF_PIXEL_LOOP(g, p) {
         if (p < g.npix) {
@@ -197,12 +197,12 @@ __global__ void k_g_c3_bwd(Geo g, int w, const float *__restrict__ zin, const fl
                            float *__restrict__ dz, float *__restrict__ gu, Acc G, const float *__restrict__ zlat,
                            const float *__restrict__ u_in)
 {
-    const float *W3 = P + off_w3, *b3 = W3 + 36 * (w + 1), *logs = b3 + 4;
+    const float *W3 = P + off_w3, *b3 = W3 + NF_CPL_W3_LEN(w), *logs = b3 + 4;
     const float sc = logs[4];
-    const int off_b3 = off_w3 + 36 * (w + 1);
+    const int off_b3 = off_w3 + NF_CPL_W3_LEN(w);
     float e3[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) e3[k] = expf(kLogscale * logs[k]);
+    for (int k = 0; k < 4; ++k) e3[k] = expf(kLogscaleF * logs[k]);
     float g_s = 0.0f, g_logs[4] = {0.f, 0.f, 0.f, 0.f}, g_b3[4] = {0.f, 0.f, 0.f, 0.f};
     NF_PIXEL_LOOP(g, p) {
         if (p < g.npix) {
@@ -232,7 +232,7 @@ __global__ void k_g_c3_bwd(Geo g, int w, const float *__restrict__ zin, const fl
             float guv[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                g_logs[k] = fmaf(kLogscale * go[k], o[k], g_logs[k]);
+                g_logs[k] = fmaf(kLogscaleF * go[k], o[k], g_logs[k]);
                 guv[k] = go[k] * e3[k];
                 g_b3[k] += guv[k];
             }
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(64) void k_bn_fin_eval(Acc stats, int W, int nslot,
     if (v < 0.0) v = 0.0;
     if (threadIdx.x == 0) {
         bn_out[j] = (float)m;
-        bn_out[W + j] = (float)(1.0 / sqrt(v + (double)kBnEps));
+        bn_out[W + j] = (float)(1.0 / sqrt(v + (double)kBnEpsF));
         mom[j] = (float)m;
         mom[W + j] = (float)v;
     }
@@ -773,7 +773,8 @@ __global__ void k_e_scale_mul(Geo g, float *__restrict__ z, const float *__restr
 }
 
 // inverse of every Conv2d1x1 matrix k_prep formed (layers.py:108-115: sampling multiplies by A^-1): Gauss-Jordan with partial
-// pivoting in fp64, one thread per matrix
+// pivoting in fp64, one thread per matrix.  The named exception of nf_layers.h: it multiplies the pivot row by a reciprocal where
+// nf_invert4 divides, and the bs-* cases of tests/test_gpu_trainer_bits.py pin its bits, so it keeps its own arithmetic.
 __global__ void k_e_inv4(int n, const float *__restrict__ A, float *__restrict__ Ainv)
 {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -813,9 +814,9 @@ __global__ __launch_bounds__(TB) void k_e_c3(int H, int W, int w, float *__restr
                                               int off_w3, double *__restrict__ ldp)
 {
     __shared__ double sh[TB / 64];
-    const float *W3 = Pw + off_w3, *b3 = W3 + 36 * (w + 1), *logs = b3 + 4;
+    const float *W3 = Pw + off_w3, *b3 = W3 + NF_CPL_W3_LEN(w), *logs = b3 + 4;
     const float sc = logs[4];
-    const float e30 = expf(kLogscale * logs[0]), e31 = expf(kLogscale * logs[1]), e32 = expf(kLogscale * logs[2]), e33 = expf(kLogscale * logs[3]);
+    const float e30 = expf(kLogscaleF * logs[0]), e31 = expf(kLogscaleF * logs[1]), e32 = expf(kLogscaleF * logs[2]), e33 = expf(kLogscaleF * logs[3]);
     const int HW = H * W;
     const int64_t base = (int64_t)blockIdx.x * HW;
     double l = 0.0;

@@ -374,15 +374,15 @@ __device__ __forceinline__ void pr_bn_finalize(Acc stats, int nred, double n, fl
         const double m = sm / n;
         double v = sq / n - m * m;
         if (v < 0.0) v = 0.0;
-        const float mf = (float)m, rf = (float)(1.0 / sqrt(v + (double)kBnEps));
+        const float mf = (float)m, rf = (float)(1.0 / sqrt(v + (double)kBnEpsF));
         bnc[gv] = -mf * rf;
         bnc[32 + gv] = rf;
         if (blockIdx.x == 0) {
             bn_out[c] = mf;
             bn_out[32 + c] = rf;
             if (run_mean) {
-                run_mean[c] -= kBnDecay * (run_mean[c] - mf);
-                run_var[c] -= kBnDecay * (run_var[c] - (float)v);
+                run_mean[c] -= kBnDecayF * (run_mean[c] - mf);
+                run_var[c] -= kBnDecayF * (run_var[c] - (float)v);
             }
             if (mom) {
                 mom[c] = mf;
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(64 * NW) void k_pr_fwd(Geo g, PrFwdArgs a)
     float e3[4] = {1.f, 1.f, 1.f, 1.f}, sc = 0.0f;
     if (STAGE == 2) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) e3[k] = expf(kLogscale * a.tail3[4 + k]);
+        for (int k = 0; k < 4; ++k) e3[k] = expf(kLogscaleF * a.tail3[4 + k]);
         sc = a.tail3[8];
     }
     __syncthreads();

@@ -68,7 +68,7 @@
     [[maybe_unused]] float e3[4] = {1.f, 1.f, 1.f, 1.f}, sc = 0.0f;
     if (STAGE == 0) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) e3[k] = expf(kLogscale * a.tail3[4 + k]);
+        for (int k = 0; k < 4; ++k) e3[k] = expf(kLogscaleF * a.tail3[4 + k]);
         sc = a.tail3[8];
     }
     PrLaneMasks lm;
@@ -108,7 +108,7 @@
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     guv[k] = go[k] * e3[k];
-                    tail[4 + k] = fmaf(kLogscale * go[k], o[k], tail[4 + k]);
+                    tail[4 + k] = fmaf(kLogscaleF * go[k], o[k], tail[4 + k]);
                     tail[k] += guv[k];
                 }
                 gv[m] = make_float4(guv[0], guv[1], guv[2], guv[3]);

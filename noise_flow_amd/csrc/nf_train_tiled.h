@@ -137,7 +137,7 @@ __device__ __forceinline__ void tiled_phase_A(const Geo &g, int b, int r, int c,
         float go[4], o[4], e3[4], guv[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            e3[q] = expf(kLogscale * logs[q]);
+            e3[q] = expf(kLogscaleF * logs[q]);
             o[q] = u[q] * e3[q];
         }
 #pragma unroll
@@ -151,7 +151,7 @@ __device__ __forceinline__ void tiled_phase_A(const Geo &g, int b, int r, int c,
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            tail[4 + q] = kLogscale * go[q] * o[q];
+            tail[4 + q] = kLogscaleF * go[q] * o[q];
             guv[q] = go[q] * e3[q];
             tail[q] = guv[q];
         }
@@ -347,14 +347,14 @@ __device__ __forceinline__ void bn_from_slots_nt(Acc stats, int nslot, double n,
         double v = sq / n - m * m;
         if (v < 0.0) v = 0.0;
         if ((threadIdx.x & 63) == 0) {
-            const float mf = (float)m, rf = (float)(1.0 / sqrt(v + (double)kBnEps));
+            const float mf = (float)m, rf = (float)(1.0 / sqrt(v + (double)kBnEpsF));
             sh[j] = mf;
             sh[W + j] = rf;
             if (blockIdx.x == 0) {
                 bn_out[j] = mf;
                 bn_out[W + j] = rf;
-                P[off_mean + j] -= kBnDecay * (P[off_mean + j] - mf);
-                P[off_var + j] -= kBnDecay * (P[off_var + j] - (float)v);
+                P[off_mean + j] -= kBnDecayF * (P[off_mean + j] - mf);
+                P[off_var + j] -= kBnDecayF * (P[off_var + j] - (float)v);
             }
         }
     }
@@ -447,8 +447,8 @@ __global__ __launch_bounds__(NT) void k_tiled_fwd(Geo g, TiledF3 f3, TiledF1 f1,
             }
             const float sc = logs[4];
             const float4 zi = z;
-            const float sh0 = u[0] * expf(kLogscale * logs[0]), sh1 = u[1] * expf(kLogscale * logs[1]);
-            const float ls0 = sc * tanhf(u[2] * expf(kLogscale * logs[2])), ls1 = sc * tanhf(u[3] * expf(kLogscale * logs[3]));
+            const float sh0 = u[0] * expf(kLogscaleF * logs[0]), sh1 = u[1] * expf(kLogscaleF * logs[1]);
+            const float ls0 = sc * tanhf(u[2] * expf(kLogscaleF * logs[2])), ls1 = sc * tanhf(u[3] * expf(kLogscaleF * logs[3]));
             z = make_float4(zi.x, zi.y, fmaf(zi.z, expf(ls0), sh0), fmaf(zi.w, expf(ls1), sh1));
             reinterpret_cast<float4 *>(f3.zout)[gp] = z;
             lv[0] = ls0 + ls1;

@@ -300,8 +300,8 @@ __global__ __launch_bounds__(256) void k_c3_fwd_mfma(Geo g, const float *__restr
         rs[k] = bn2[W + 4 * (ln % (W / 4)) + k];
     }
     const float sc = logs[4];
-    const float e30 = expf(kLogscale * logs[0]), e31 = expf(kLogscale * logs[1]), e32 = expf(kLogscale * logs[2]),
-                e33 = expf(kLogscale * logs[3]);
+    const float e30 = expf(kLogscaleF * logs[0]), e31 = expf(kLogscaleF * logs[1]), e32 = expf(kLogscaleF * logs[2]),
+                e33 = expf(kLogscaleF * logs[3]);
     float *sa = stage[wv];
     const int npatch = (int)(g.npix / g.HW), nbands = (g.H + BR - 1) / BR, units = npatch * nbands;
     float l = 0.0f;
@@ -640,7 +640,7 @@ __global__ __launch_bounds__(256) void k_c3_dh_mfma(Geo g, const float *__restri
     const float sc = logs[4];
     float e3[4], tail[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < 4; ++k) e3[k] = expf(kLogscale * logs[k]);
+    for (int k = 0; k < 4; ++k) e3[k] = expf(kLogscaleF * logs[k]);
     int *lut = reinterpret_cast<int *>(smem + tile_px * 4);
     for (int i = t; i < tile_px * 4; i += 256) smem[i] = 0.0f;
     for (int px = t; px < g.HW; px += 256) {
@@ -683,7 +683,7 @@ __global__ __launch_bounds__(256) void k_c3_dh_mfma(Geo g, const float *__restri
                 for (int k = 0; k < 4; ++k) {
                     guv[k] = go[k] * e3[k];
                     if (first) {
-                        tail[4 + k] = fmaf(kLogscale * go[k], o[k], tail[4 + k]);
+                        tail[4 + k] = fmaf(kLogscaleF * go[k], o[k], tail[4 + k]);
                         tail[k] += guv[k];
                     }
                 }

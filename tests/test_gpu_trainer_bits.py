@@ -4,7 +4,10 @@ slotted partial sums in a fixed order and use no atomics, so a step gives the sa
 that keeps every launch, grid and operand must give the bits of the code before it: tests/golden/trainer_host_bits.npz was recorded
 with tools/make_golden_trainer_bits.py on an MI355X (the grids depend on the CU count) from the build of commit 336408c, the last
 one before the host code was reorganised around train_path() / the step plan / the coupling context.  array_equal on the uint32
-views; no tolerance — a differing bit is a launch, a grid or an operand that changed, not a rounding question.
+views; no tolerance — a differing bit is a launch, a grid or an operand that changed, not a rounding question.  The vocab-* cases
+were added to the fixture from the build of commit 5e09953 (make_golden_trainer_bits.py --only vocab- --into), the last one in
+which the trainer wrote the layer kinds' formulas out separately from the evaluator: they pin k_prep / k_finish on every sdn and
+gain kind and every 1x1 setting across the move to the shared csrc/nf_layers.h.
 
 CASES are the smallest shapes that reach each branch of the host code (the comment behind each says which).  Every case makes
 `steps` calls of forward_backward + apply on one handle (three where the pending side-stream events have to cross a step
@@ -40,8 +43,15 @@ U3, FOLD, G3 = "unc|unc|unc", "sdn5|unc|unc|gain4|unc", "unc|gain4|unc"
 G8 = {"NF_TRAIN_PR_GRID": "8"}      # 8 "CUs": 1 patch = no side stream, 3 = both products, 5 = d l_last/W only, 20 = persistent loop
 
 
-def _c(cid, arch, width, hw, B, env=None, steps=1, mode="train"):
-    return dict(id=cid, arch=arch, width=width, hw=hw, B=B, env=dict(env or {}), steps=steps, mode=mode)
+def _c(cid, arch, width, hw, B, env=None, steps=1, mode="train", fp=1, decomp="LU", iso=400, cam=1, vocab=False):
+    return dict(id=cid, arch=arch, width=width, hw=hw, B=B, env=dict(env or {}), steps=steps, mode=mode,
+                fp=fp, decomp=decomp, iso=iso, cam=cam, vocab=vocab)
+
+
+def _v(kind, fp, decomp, iso, cam):
+    """One layer of the vocabulary beyond the default kinds with a coupling behind it (and the 1x1 layer of the given
+    flow_permutation / decomp setting in between): width 4, 8x8 patches (64 pixels: (loss, sd_z) is kept), B = 3, one step."""
+    return _c("vocab-%s-fp%d-%s-iso%d" % (kind, fp, decomp, iso), kind + "|unc", 4, (8, 8), 3, fp=fp, decomp=decomp, iso=iso, cam=cam, vocab=True)
 
 
 CASES = [
@@ -88,6 +98,12 @@ CASES = [
     _c("bs-pr-u3", U3, 32, (32, 32), 3, mode="bs"),                                 # the patch-resident evaluator, no Conv2d1x1 in front
     _c("bs-pr-fold", FOLD, 32, (32, 32), 3, mode="bs"),                             # ... with one
     _c("bs-gemm-w24", G3, 24, (16, 16), 4, {"NF_BS_WIDE": "1"}, mode="bs"),         # the GEMM evaluator
+    # ---- the layer vocabulary beyond sdn5 / sdn4 / gain4 / PLU (recorded from commit 5e09953, the last one with the layer kinds
+    #      written out separately in the trainer): every other sdn / gain kind, the LU2 / NONE / permutation 1x1 settings spread
+    #      over them, two cases at an ISO outside the table (sdn6: the gain exponent is 0; gain3: the ISO-800 entry)
+    _v("sdn", 1, "LU2", 400, 0), _v("sdn1", 1, "NONE", 800, 1), _v("sdn2", 0, "LU", 1600, 2), _v("sdn3", 2, "LU", 100, 3),
+    _v("sdn6", 1, "LU2", 250, 4), _v("gain", 1, "NONE", 3200, 0), _v("gain1", 0, "LU", 400, 1), _v("gain2", 1, "LU2", 800, 2),
+    _v("gain3", 1, "NONE", 250, 3), _v("sdn6", 1, "LU", 1600, 2), _v("gain3", 2, "LU", 100, 4),
 ]
 CASE_IDS = [c["id"] for c in CASES]
 assert len(set(CASE_IDS)) == len(CASE_IDS)
@@ -98,6 +114,12 @@ def _seed(case):
 
 
 def _variables(case):
+    if case.get("vocab"):      # (test_gpu_batchstats_bits.py passes case records of its own) the random sweep's recipe: variables of the 1x1 setting, trained-like CNNs, conditional scales of O(1)
+        from noise_flow_amd import params
+        from test_gpu_random_sweep import _condition
+        v = params.init_variables(case["arch"], case["width"], 4, _seed(case), case["fp"], case["decomp"])
+        v.update({k: a for k, a in trained_like_variables(case["arch"], case["width"], seed=_seed(case)).items() if k in v})
+        return _condition(v, case["arch"], case["width"], case["iso"], np.random.RandomState(_seed(case)))
     v = trained_like_variables(case["arch"], case["width"], seed=_seed(case))
     scale = np.float32((4.0 / case["width"]) ** 0.5)      # activations of O(1) at every width (the helper is tuned for width 4)
     for k in v:
@@ -152,16 +174,19 @@ def _keep(res, name, a, blocks=None):
 
 
 def _train_case(case, res):
-    from test_gpu_train import _trainer
+    from noise_flow_amd import default_hps
+    from noise_flow_amd.train import Trainer
     H, W = case["hw"]
+    iso, cam = [case["iso"]], [case["cam"]]
     x, y = make_inputs(case["B"], H, W, seed=_seed(case) + 20)
-    tr = _trainer(case["arch"], _variables(case), (H, W, 4), case["width"], max_batch=case["B"])
+    hps = default_hps(arch=case["arch"], width=case["width"], flow_permutation=case["fp"], decomp=case["decomp"])
+    tr = Trainer([H, W, 4], hps, variables=_variables(case), optim="adam", max_batch=case["B"])
     blocks = _blocks(tr.layers, case["width"])
     losses = []
     if case["mode"] == "forward":
-        losses.append(np.asarray(tr.forward(x, y, [0.0], [0.0], [400], [1]), np.float32))
+        losses.append(np.asarray(tr.forward(x, y, [0.0], [0.0], iso, cam), np.float32))
     for _ in range(case["steps"] if case["mode"] == "train" else 0):
-        g, loss = tr.forward_backward(x, y, [0.0], [0.0], [400], [1])
+        g, loss = tr.forward_backward(x, y, [0.0], [0.0], iso, cam)
         losses.append(loss.cpu().numpy().copy())
         grad = g.cpu().numpy().copy()
         tr.apply(1e-3)

@@ -5,7 +5,9 @@ and larger.  Prints one JSON line per batch size; `--cpu` also times the torch-C
 import argparse, json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from noise_flow_amd import default_hps, patches
+from noise_flow_amd import default_hps, patches, _lib as _nf_lib
+if os.environ.get("NF_TOOL_LIB"):   # A/B a differently-built library (this tool only)
+    _nf_lib.LIB_PATH = os.path.abspath(os.environ["NF_TOOL_LIB"])
 from noise_flow_amd.train import Trainer
 from noise_flow_amd.ckpt import load_checkpoint
 

@@ -6,8 +6,10 @@
  * other (unsanitised) objects into this stand-alone program.  Over a fixed list of (coupling width, H, W, flags) that reaches all
  * nine kernel paths in both directions it calls nf_fold_params, nf_fold_layout (size query, then an exactly-sized malloc buffer,
  * so that one float too many is a heap overflow the sanitizer reports), nf_cond_rows and nf_tile_segments, and — the gradient
- * blocks of nf_nll_grad, with and without NF_CFG_GRAD_MFMA — nf_grad_fold.  Exit status 0 and the last line "fold_probe ok" =
- * nothing reported, every path seen with a block in both directions and both gradient blocks seen. */
+ * blocks of nf_nll_grad, with and without NF_CFG_GRAD_MFMA — nf_grad_fold.  Three more layer lists hold every one of the 17 layer
+ * kinds (csrc/nf_layers.h) between them, again with exactly sized parameter vectors, so a fold or a conditional layer that reads
+ * past its block is reported.  Exit status 0 and the last line "fold_probe ok" = nothing reported, every path seen with a block in
+ * both directions, both gradient blocks seen and every kind folded. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,6 +19,7 @@
 
 #define N_PATHS 9
 #define N_LAYERS 7
+#define MAX_LAYERS 12
 
 static uint32_t lcg_state = 12345u;
 static float uniform(void) /* (-0.4, 0.4) */
@@ -25,13 +28,17 @@ static float uniform(void) /* (-0.4, 0.4) */
     return ((float)(lcg_state >> 8) / 16777216.0f - 0.5f) * 0.8f;
 }
 
-/* sdn | 1x1, coupling | gain4 | 1x1, coupling | gain: every op kind, two conditioning slots */
-static float *make_model(int w, nf_layer_desc *layers, size_t *n_params)
+static void permutation(float *q)
 {
-    static const int32_t types[N_LAYERS] = {NF_LAYER_SDN, NF_LAYER_CONV1X1, NF_LAYER_COUPLING, NF_LAYER_GAIN4,
-                                            NF_LAYER_CONV1X1, NF_LAYER_COUPLING, NF_LAYER_GAIN};
+    static const int perm[4] = {2, 0, 3, 1};
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) q[r * 4 + c] = perm[r] == c ? 1.0f : 0.0f;
+}
+
+static float *make_model_of(const int32_t *types, int n_layers, int w, nf_layer_desc *layers, size_t *n_params)
+{
     size_t n = 0;
-    for (int i = 0; i < N_LAYERS; ++i) {
+    for (int i = 0; i < n_layers; ++i) {
         layers[i].type = types[i];
         layers[i].width = types[i] == NF_LAYER_COUPLING ? w : 0;
         layers[i].param_offset = (int64_t)n;
@@ -42,13 +49,13 @@ static float *make_model(int w, nf_layer_desc *layers, size_t *n_params)
     float *p = (float *)malloc(n * sizeof(float));   /* exactly sized: a read past the model is reported too */
     if (!p) return NULL;
     for (size_t i = 0; i < n; ++i) p[i] = uniform();
-    for (int i = 0; i < N_LAYERS; ++i) {
+    for (int i = 0; i < n_layers; ++i) {
         float *q = p + layers[i].param_offset;
-        if (types[i] == NF_LAYER_CONV1X1) {
-            static const int perm[4] = {2, 0, 3, 1};
-            for (int r = 0; r < 4; ++r)
-                for (int c = 0; c < 4; ++c) q[r * 4 + c] = perm[r] == c ? 1.0f : 0.0f;
-            for (int r = 0; r < 4; ++r) q[16 + r] = (r & 1) ? -1.0f : 1.0f;
+        if (types[i] == NF_LAYER_CONV1X1 || types[i] == NF_LAYER_CONV1X1_LU2) {   /* P, then sign_S (LU2: behind L) */
+            permutation(q);
+            for (int r = 0; r < 4; ++r) q[(types[i] == NF_LAYER_CONV1X1 ? 16 : 32) + r] = (r & 1) ? -1.0f : 1.0f;
+        } else if (types[i] == NF_LAYER_CONV1X1_NONE) {
+            for (int r = 0; r < 4; ++r) q[r * 5] += 2.0f;   /* diagonally dominant: not singular */
         } else if (types[i] == NF_LAYER_COUPLING) {
             for (int j = 0; j < w; ++j) {   /* the two batch-norm variances */
                 q[20 * w + j] = 0.9f + uniform();
@@ -60,6 +67,66 @@ static float *make_model(int w, nf_layer_desc *layers, size_t *n_params)
     }
     *n_params = n;
     return p;
+}
+
+/* sdn | 1x1, coupling | gain4 | 1x1, coupling | gain: every op kind, two conditioning slots */
+static float *make_model(int w, nf_layer_desc *layers, size_t *n_params)
+{
+    static const int32_t types[N_LAYERS] = {NF_LAYER_SDN, NF_LAYER_CONV1X1, NF_LAYER_COUPLING, NF_LAYER_GAIN4,
+                                            NF_LAYER_CONV1X1, NF_LAYER_COUPLING, NF_LAYER_GAIN};
+    return make_model_of(types, N_LAYERS, w, layers, n_params);
+}
+
+/* every layer kind in one of three lists (a model takes at most 4 conditional layers), folded in both directions at widths 4 and 5
+ * and asked for its rows at every table ISO, an ISO outside the table and every camera */
+static int vocabulary(void)
+{
+    static const struct { int n; int32_t t[MAX_LAYERS]; } lists[3] = {
+        {11, {NF_LAYER_SDN5, NF_LAYER_CONV1X1, NF_LAYER_COUPLING, NF_LAYER_SDN4, NF_LAYER_CONV1X1_LU2, NF_LAYER_COUPLING, NF_LAYER_GAIN4,
+              NF_LAYER_SDN1, NF_LAYER_PERMUTE, NF_LAYER_COUPLING, NF_LAYER_SDN2}},
+        {7, {NF_LAYER_SDN3, NF_LAYER_CONV1X1_NONE, NF_LAYER_COUPLING, NF_LAYER_SDN6, NF_LAYER_GAIN1, NF_LAYER_COUPLING, NF_LAYER_GAIN2}},
+        {4, {NF_LAYER_GAIN3, NF_LAYER_SDN, NF_LAYER_GAIN, NF_LAYER_COUPLING}},
+    };
+    static const nf_cond conds[6] = {{100.f, 0.f, 0.f, 0.f}, {400.f, 1.f, 0.f, 0.f}, {800.f, 2.f, 0.f, 0.f}, {1600.f, 3.f, 0.f, 0.f},
+                                     {3200.f, 4.f, 0.f, 0.f}, {250.f, 0.f, 0.f, 0.f}};
+    int kinds[NF_LAYER_PERMUTE + 1];
+    memset(kinds, 0, sizeof(kinds));
+    for (int k = 0; k < 3; ++k)
+        for (int w = 4; w <= 5; ++w) {
+            nf_layer_desc layers[MAX_LAYERS];
+            size_t n_params = 0, n_folded = 0;
+            float *params = make_model_of(lists[k].t, lists[k].n, w, layers, &n_params);
+            if (!params) return 0;
+            const nf_config cfg = {8, 8, 4, lists[k].n, -1, 0};
+            for (int32_t direction = 0; direction < 2; ++direction) {
+                int32_t n_ops = 0;
+                double ld = 0.0;
+                int rc = nf_fold_params(&cfg, layers, params, n_params, direction, NULL, 0, &n_ops, NULL, 0, &n_folded, &ld);
+                if (rc == NF_OK) {
+                    int32_t *ops = (int32_t *)malloc(2 * (size_t)n_ops * sizeof(int32_t));
+                    float *blk = (float *)malloc(n_folded * sizeof(float));
+                    nf_cond_row *rows = (nf_cond_row *)malloc(6 * sizeof(nf_cond_row));
+                    rc = nf_fold_params(&cfg, layers, params, n_params, direction, ops, n_ops, &n_ops, blk, n_folded, &n_folded, &ld);
+                    if (rc == NF_OK) rc = nf_cond_rows(&cfg, layers, params, n_params, direction, conds, 6, rows);
+                    free(rows);
+                    free(blk);
+                    free(ops);
+                }
+                if (rc != NF_OK) {
+                    fprintf(stderr, "vocabulary list %d width %d direction %d: %s\n", k, w, direction, nf_last_error());
+                    return 0;
+                }
+            }
+            for (int i = 0; i < lists[k].n; ++i) kinds[lists[k].t[i]]++;
+            free(params);
+        }
+    for (int t = 1; t <= NF_LAYER_PERMUTE; ++t)
+        if (!kinds[t]) {
+            fprintf(stderr, "no vocabulary list holds layer kind %d\n", t);
+            return 0;
+        }
+    printf("vocabulary: %d layer kinds folded\n", NF_LAYER_PERMUTE);
+    return 1;
 }
 
 int main(void)
@@ -161,6 +228,7 @@ int main(void)
     }
     printf("gradient blocks: %d scalar, %d matrix-core\n", gseen[0], gseen[1]);
     if (!gseen[0] || !gseen[1]) return 1;
+    if (!vocabulary()) return 1;
     for (int d = 0; d < 2; ++d)
         for (int p = 0; p < N_PATHS; ++p) {
             printf("direction %d path %d: %d blocks\n", d, p, seen[d][p]);

@@ -7,8 +7,9 @@
  * other (unsanitised) objects into this stand-alone program.  Without a device nf_trainer_create works through everything that
  * needs none — for a valid layer list that is the whole plan construction — and then fails at its first HIP call, which frees
  * the half-built handle through the one clean-up route.  Layer lists: every neighbour pattern the plan distinguishes (couplings
- * chained directly, behind one Conv2d1x1, behind two, cut by another layer; a Conv2d1x1 first / last; kMaxLayers layers; exactly
- * sized parameter vectors, so a mask write past a block is a heap overflow) and every validation failure.
+ * chained directly, behind one Conv2d1x1, behind two, cut by another layer; a Conv2d1x1 first / last; kMaxLayers layers; every
+ * one of the 17 layer kinds in some list; exactly sized parameter vectors, so a mask write past a block is a heap overflow) and
+ * every validation failure.
  * Exit status 0 and the last line "train_plan_probe ok" = nothing reported and every call ended as expected. */
 #include <stdint.h>
 #include <stdio.h>
@@ -18,7 +19,9 @@
 #include "../../include/noiseflow_hip.h"
 
 #define MAXL 64
-enum { C = NF_LAYER_COUPLING, M = NF_LAYER_CONV1X1, S = NF_LAYER_SDN5, G = NF_LAYER_GAIN4, P = NF_LAYER_PERMUTE, L2 = NF_LAYER_CONV1X1_LU2 };
+enum { C = NF_LAYER_COUPLING, M = NF_LAYER_CONV1X1, S = NF_LAYER_SDN5, G = NF_LAYER_GAIN4, P = NF_LAYER_PERMUTE, L2 = NF_LAYER_CONV1X1_LU2,
+       N0 = NF_LAYER_CONV1X1_NONE, S0 = NF_LAYER_SDN, S1 = NF_LAYER_SDN1, S2 = NF_LAYER_SDN2, S3 = NF_LAYER_SDN3, S4 = NF_LAYER_SDN4,
+       S6 = NF_LAYER_SDN6, G0 = NF_LAYER_GAIN, G1 = NF_LAYER_GAIN1, G2 = NF_LAYER_GAIN2, G3 = NF_LAYER_GAIN3 };
 
 static int build(const int32_t *types, int n, int w, nf_layer_desc *layers, float **params, size_t *n_params)
 {
@@ -66,6 +69,8 @@ int main(void)
         {5, {C, L2, C, G, G}},
         {1, {C}}, {1, {M}}, {2, {S, G}},        /* one coupling; no coupling at all */
         {12, {S, M, C, M, C, M, C, G, M, C, M, C}},
+        {9, {S0, N0, C, S1, C, S2, C, S3, G0}}, /* the rest of the vocabulary (csrc/nf_layers.h): every kind's mask, a block at the very end */
+        {8, {S4, C, S6, C, G1, G2, C, G3}},
     };
     static const int widths[] = {4, 8, 5, 32, 96};
     int ok = 1, calls = 0;
