@@ -145,6 +145,11 @@ typedef struct nf_config {
                               program cut into segments (see nf_nll_grad, nf_grad_tile_segments).  The flag only adds: a
                               shape held whole stays on the whole-patch kernel, no other call changes.  (Bit 8 is not
                               assigned.) */
+#define NF_CFG_GRAD_TILED_WIDE 32 /* nf_nll_grad at coupling widths 17 .. 32 on every H, W up to NF_MAX_IMAGE_SIDE: everything
+                              NF_CFG_GRAD_MFMA does (shapes up to 32x32 held whole by the matrix-core gradient kernel), and every
+                              other shape on overlapping 32-pixel tiles of that kernel, the program cut into segments
+                              (NF_GRAD_PATH_TILED_WIDE32).  No effect at widths up to 16, on NF_CFG_FP16_CNN handles or beyond
+                              width 32; NF_CFG_GRAD_TILED | NF_CFG_GRAD_MFMA without this bit stays refused beyond 32x32. */
 
 /* Per-call conditioning: ONE value per call, not per patch — the reference
  * feeds length-1 lists (MiniBatchSampler.py:61-64, NoiseFlowWrapper.py:85-86).
@@ -284,7 +289,12 @@ int nf_sample_percond(nf_handle *h, const float *y, const float *eps, uint64_t s
  * min(H,32) x min(W,32) tiles with a halo of 4 x the segment's couplings and stores core windows only.  Same contract (any
  * subset of the outputs, cond or rows — rows are per image —, no synchronisation); scratch ((segments - 1) tensors, 2
  * gradient tensors, the tile sums) comes from the handle's workspace set and is allocated only when a call needs more than
- * any earlier one (nf_workspace_bytes(h, 2, B), nf_reserve_grad_workspace).  Width 32 has no tile mode.
+ * any earlier one (nf_workspace_bytes(h, 2, B), nf_reserve_grad_workspace).
+ * With NF_CFG_GRAD_TILED_WIDE, widths 17 .. 32 have the same tile mode on the matrix-core kernel (NF_GRAD_PATH_TILED_WIDE32): a shape
+ * of up to 32x32 whose gate record fits stays NF_GRAD_PATH_WIDE32 as under NF_CFG_GRAD_MFMA, every other shape up to
+ * NF_MAX_IMAGE_SIDE per side (a <= 32x32 model with more couplings than the record holds included) runs segment by segment on
+ * min(H,32) x min(W,32) tiles of csrc/nf_grad_wide.hip, never on the scalar kernel.  Plan, workspace, outputs and conditioning are
+ * those of NF_GRAD_PATH_TILED.
  * Not covered: widths beyond 32 (the GEMM families), NF_CFG_FP16_CNN, batch-statistics mode, and host-fed variants. */
 int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond,
                 const nf_cond_row *rows, float *nll_out, float *gx_out, float *gy_out, void *stream);
@@ -300,9 +310,10 @@ int nf_grad_supported(const nf_config *cfg, const nf_layer_desc *layers, const f
 #define NF_GRAD_PATH_SCALAR 0   /* nf_grad_kernel (csrc/nf_grad.hip) */
 #define NF_GRAD_PATH_WIDE32 1   /* nf_grad_wide_kernel (csrc/nf_grad_wide.hip), v_mfma_f32_32x32x2_f32 */
 #define NF_GRAD_PATH_TILED 2    /* NF_CFG_GRAD_TILED: nf_grad_kernel on 32-pixel tiles, one launch per segment */
+#define NF_GRAD_PATH_TILED_WIDE32 3   /* NF_CFG_GRAD_TILED_WIDE: nf_grad_wide_kernel on 32-pixel tiles, one launch per segment */
 int nf_grad_path(const nf_handle *h);
 
-/* How nf_nll_grad cuts a model under NF_CFG_GRAD_TILED, in the format of nf_tile_segments: returns the number of segments (0:
+/* How nf_nll_grad cuts a model under NF_CFG_GRAD_TILED (or, at widths 17 .. 32, NF_CFG_GRAD_TILED_WIDE), in the format of nf_tile_segments: returns the number of segments (0:
  * the shape is held whole by a whole-patch kernel; negative: NF_E*, e.g. what nf_grad_supported refuses) and for i < cap
  * out5[5 i ..] = first op, one-past-last op, GRADIENT halo (4 x the segment's couplings), tiles along H, tiles along W of the
  * backward launch (tiles of min(H,32) x min(W,32)).  Host arithmetic only.  NF_GRAD_TILE_SEGMENTS=<n> in the environment, read
@@ -311,7 +322,7 @@ int nf_grad_tile_segments(const nf_config *cfg, const nf_layer_desc *layers, con
                           int32_t *out5, int32_t cap);
 
 /* Host-only: the program and parameter block nf_nll_grad would run for this model ("gradient block": A^-1 beside every 1x1
- * matrix, 1/s beside every scale; couplings in the generic layout or, *path == NF_GRAD_PATH_WIDE32, in the fetch-order layout of
+ * matrix, 1/s beside every scale; couplings in the generic layout or, *path == NF_GRAD_PATH_WIDE32 / _TILED_WIDE32, in the fetch-order layout of
  * csrc/nf_device.h, NFGW_*).  Argument style and sizing protocol of nf_fold_layout. */
 int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params, int32_t *path,
                  int32_t *ops_out, int32_t ops_cap, int32_t *n_ops, float *folded, size_t folded_cap, size_t *n_folded);
@@ -553,7 +564,7 @@ int nf_batchstats_route(const nf_handle *h);
  * images allocates anything.  No reference counterpart (TF sizes its arena inside sess.run). */
 int64_t nf_workspace_bytes(const nf_handle *h, int32_t direction, int64_t B);   /* direction 2: one tiled nf_nll_grad call */
 int nf_reserve_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
-/* the same for nf_nll_grad under NF_CFG_GRAD_TILED (nothing to do for a handle whose shape is held whole) */
+/* the same for nf_nll_grad under NF_CFG_GRAD_TILED / NF_CFG_GRAD_TILED_WIDE (nothing to do for a handle whose shape is held whole) */
 int nf_reserve_grad_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
 
 /* Host-only: the SDN5 scalars the kernels receive for a given (iso, cam):

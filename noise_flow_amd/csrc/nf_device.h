@@ -421,7 +421,7 @@ struct NfGradLaunch {
     int32_t H, W;
     int32_t first_cpl;     // index of the first coupling op (n_ops when the model has none)
     int32_t gate_words;    // 32-bit words of gate record per pixel slot
-    // Gradient tiles (NF_CFG_GRAD_TILED, nf_grad_kernel<.., TILED>; below): patch b of the launch is tile b % (tile_ny tile_nx) of
+    // Gradient tiles (NF_CFG_GRAD_TILED, nf_grad_kernel<.., TILED>; NF_CFG_GRAD_TILED_WIDE, nf_grad_wide_kernel<.., TILED>; below): patch b of the launch is tile b % (tile_ny tile_nx) of
     // image b / (tile_ny tile_nx), H x W pixels at the nf_tile_origin of `tile_halo`; every tensor is [images][img_H][img_W][4],
     // cond_rows are per image, `prog` is one segment, first_cpl / gate_words count inside it, nll_out / x / gx_out are not used
     const float *z_in;     // the tensor in front of the segment (the caller's x for the first one)
@@ -438,7 +438,8 @@ struct NfGradLaunch {
 // border (tests/test_grad_tiles_cpu.py pins it in fp64) — no masking of the loss, the wrong terms never reach the core.  Tiles
 // are min(H, 32) x min(W, 32), the largest shape the scalar kernel holds at widths 4 / 8 / 16 without scratch; the program is cut
 // into segments as the forward direction's (at most 3 couplings each: 32 - 2 x 12 = 8 core pixels), with every tensor between two
-// segments in HBM.
+// segments in HBM.  Width 32 runs the same scheme on nf_grad_wide_kernel (NF_CFG_GRAD_TILED_WIDE): the same tiles, halo and
+// segments, a.gate_words = nfgw_tpw(tile H) x (couplings of the largest segment), LDS = nfgw_lds_floats of those (<= 81 KiB).
 #define NF_GRAD_TILE 32
 enum : uint32_t {
     NF_GT_GY_ACC = 1u,     // gy_out += instead of gy_out = (a segment behind this one has written it)

@@ -15,6 +15,8 @@
 //                   P[pixel][tap][2] + the same shift-add, added to g0.  h1, h2 and their gradients never exist in memory.
 // 'SAME' padding: the zero borders of the two tiles, the zero-filled lane shifts and the skipped rows of the shift-add.  The border
 // table E is constant and has no gradient.  Everything in front of the first coupling is computed forward from the loaded x.
+// Beyond 32x32 (NF_CFG_GRAD_TILED_WIDE) the TILED instantiations run the same sweeps on one tile of an image and one segment of the
+// program per launch patch, as nf_grad_kernel<.., TILED> does at the narrower widths.
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stdint.h>
@@ -33,7 +35,12 @@ __device__ __forceinline__ float gw_gate(uint32_t word, int bit, float x) { retu
 
 //   NW   wavefronts (strips) of the workgroup
 //   TPW  tiles (= rows of a strip) per wavefront; a lane half owns OWN = TPW / 2 of them
-template <int NW, int TPW>
+//   TILED  NF_CFG_GRAD_TILED_WIDE (nf_device.h, "gradient tiles"), the contract of nf_grad_kernel<.., TILED>: a "patch" of the
+//          launch is one H x W tile of an img_H x img_W image and `prog` one segment.  Addresses and the index into the border table
+//          E follow the IMAGE (recomputed from the tile's origin where they are used: no registers held across the sweeps); the
+//          zero borders of the two LDS tiles, the lane-shift masks and the skipped rows stay the TILE's — a tile is evaluated on its
+//          own, the wrong terms stay inside the halo — and only the core window is stored.  nll_b is not formed here.
+template <int NW, int TPW, bool TILED = false>
 __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram prog, const NfGradLaunch a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -72,6 +79,24 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
 
     const int n_ops = prog.n_ops;
     const int first_cpl = a.first_cpl;
+    // TILED: where the tile of the current launch patch sits in its image (wave-uniform), and what follows from it per owned pixel
+    [[maybe_unused]] int oy = 0, ox = 0, cy0 = 0, cy1 = 0, cx0 = 0, cx1 = 0;
+    auto gidx_of = [&](int m) {
+        if constexpr (TILED) return act[m] ? (oy + row0 + 2 * m + g) * a.img_W + ox + c : 0;
+        else return gidx[m];
+    };
+    auto bmask_of = [&](int m) {
+        if constexpr (TILED) {
+            const int R = oy + row0 + 2 * m + g, C = ox + c;
+            return act[m] ? ((R == 0 ? 1 : 0) | (R == a.img_H - 1 ? 2 : 0) | (C == 0 ? 4 : 0) | (C == a.img_W - 1 ? 8 : 0)) : 0;
+        } else {
+            return bmask[m];
+        }
+    };
+    auto own_of = [&](int m) {   // TILED: the pixel is in the tile's core window
+        const int R = oy + row0 + 2 * m + g, C = ox + c;
+        return act[m] && R >= cy0 && R < cy1 && C >= cx0 && C < cx1;
+    };
 
     // one coupling's block (its first `floats`) into LDS; callers put a barrier behind it
     auto stage = [&](int off, int floats) {
@@ -124,10 +149,23 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
     };
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const size_t patch_off = (size_t)b * (size_t)HW;
-        const float4 *const x4 = reinterpret_cast<const float4 *>(a.x) + patch_off;
+        int64_t img = b;
+        if constexpr (TILED) {   // tile b % tiles of image b / tiles (nf_device.h, "overlapping tiles")
+            const int nt = a.tile_ny * a.tile_nx;
+            img = b / nt;
+            const int ti = (int)(b - img * nt);
+            const int ty = ti / a.tile_nx, tx = ti - ty * a.tile_nx;
+            oy = nf_tile_origin(ty, a.img_H, H, a.tile_halo);
+            ox = nf_tile_origin(tx, a.img_W, W, a.tile_halo);
+            cy0 = nf_tile_core0(ty, a.img_H, H, a.tile_halo);
+            cy1 = nf_tile_core1(ty, a.tile_ny, a.img_H, H, a.tile_halo);
+            cx0 = nf_tile_core0(tx, a.img_W, W, a.tile_halo);
+            cx1 = nf_tile_core1(tx, a.tile_nx, a.img_W, W, a.tile_halo);
+        }
+        const size_t patch_off = TILED ? (size_t)img * (size_t)a.img_H * (size_t)a.img_W : (size_t)b * (size_t)HW;
+        const float4 *const x4 = reinterpret_cast<const float4 *>(TILED ? a.z_in : a.x) + patch_off;
         const float4 *const y4 = reinterpret_cast<const float4 *>(a.y) + patch_off;   // (not dereferenced when a.y is null)
-        const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + b;
+        const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + img;
         auto cond_a = [&](int slot) { return a.cond_rows ? crow->a[slot & 3] : a.cond_a[slot & 3]; };
         auto cond_b = [&](int slot) { return a.cond_rows ? crow->b[slot & 3] : a.cond_b[slot & 3]; };
 
@@ -135,7 +173,7 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
 #pragma unroll
             for (int m = 0; m < OWN; ++m) {
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (act[m]) v = x4[gidx[m]];
+                if (act[m]) v = x4[gidx_of(m)];
                 z[m][0] = v.x; z[m][1] = v.y; z[m][2] = v.z; z[m][3] = v.w;
             }
         };
@@ -143,7 +181,7 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
 #pragma unroll
             for (int m = 0; m < OWN; ++m) {
                 float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
-                if (act[m]) v = y4[gidx[m]];
+                if (act[m]) v = y4[gidx_of(m)];
                 yy[m][0] = v.x; yy[m][1] = v.y; yy[m][2] = v.z; yy[m][3] = v.w;
             }
         };
@@ -290,7 +328,7 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
             finish(cp, o);
 #pragma unroll
             for (int m = 0; m < OWN; ++m) {
-                const float4 eb = *reinterpret_cast<const float4 *>(a.params + off + NFGW_CPL_E + 4 * bmask[m]);
+                const float4 eb = *reinterpret_cast<const float4 *>(a.params + off + NFGW_CPL_E + 4 * bmask_of(m));
                 o[m][0] += eb.x; o[m][1] += eb.y; o[m][2] += eb.z; o[m][3] += eb.w;
             }
         };
@@ -322,7 +360,7 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
             }
         }
         // nll_b = -(log-det) + prior, as nf_flow_kernel forms it
-        if (a.nll_out) {
+        if (!TILED && a.nll_out) {
             float s2 = 0.f;
 #pragma unroll
             for (int m = 0; m < OWN; ++m)
@@ -364,6 +402,17 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
                 gz[m][q] = z[m][q];
                 gy[m][q] = 0.0f;
             }
+        if constexpr (TILED) {
+            if (a.g_in) {   // not the last segment: the gradient the segment behind this one stored, whole tile
+                const float4 *const g4 = reinterpret_cast<const float4 *>(a.g_in) + patch_off;
+#pragma unroll
+                for (int m = 0; m < OWN; ++m) {
+                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (act[m]) v = g4[gidx_of(m)];
+                    gz[m][0] = v.x; gz[m][1] = v.y; gz[m][2] = v.z; gz[m][3] = v.w;
+                }
+            }
+        }
         int cidx = 0;
         for (int op = 0; op < n_ops; ++op) cidx += prog.ops[op].type == NF_OP_COUPLING_FWD ? 1 : 0;
         for (int op = n_ops - 1; op >= 0; --op) {
@@ -531,27 +580,65 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
             }
         }
 
-        if (a.gx_out) {
-            float4 *const o4 = reinterpret_cast<float4 *>(a.gx_out) + patch_off;
+        if constexpr (TILED) {
+            // the core window only; every pixel of the image is in exactly one tile's core, so an accumulating launch adds to gy
+            // without atomics (the launch that wrote it is ahead of this one in the stream)
+            if (a.g_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.g_out) + patch_off;
 #pragma unroll
-            for (int m = 0; m < OWN; ++m)
-                if (act[m]) o4[gidx[m]] = make_float4(gz[m][0], gz[m][1], gz[m][2], gz[m][3]);
-        }
-        if (a.gy_out) {
-            float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+                for (int m = 0; m < OWN; ++m)
+                    if (own_of(m)) o4[gidx_of(m)] = make_float4(gz[m][0], gz[m][1], gz[m][2], gz[m][3]);
+            }
+            if (a.gy_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+                const bool acc = (a.tflags & NF_GT_GY_ACC) != 0;
 #pragma unroll
-            for (int m = 0; m < OWN; ++m)
-                if (act[m]) o4[gidx[m]] = make_float4(gy[m][0], gy[m][1], gy[m][2], gy[m][3]);
+                for (int m = 0; m < OWN; ++m)
+                    if (own_of(m)) {
+                        float4 v = make_float4(gy[m][0], gy[m][1], gy[m][2], gy[m][3]);
+                        if (acc) {
+                            const float4 p = o4[gidx_of(m)];
+                            v = make_float4(p.x + v.x, p.y + v.y, p.z + v.z, p.w + v.w);
+                        }
+                        o4[gidx_of(m)] = v;
+                    }
+            }
+        } else {
+            if (a.gx_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gx_out) + patch_off;
+#pragma unroll
+                for (int m = 0; m < OWN; ++m)
+                    if (act[m]) o4[gidx[m]] = make_float4(gz[m][0], gz[m][1], gz[m][2], gz[m][3]);
+            }
+            if (a.gy_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+#pragma unroll
+                for (int m = 0; m < OWN; ++m)
+                    if (act[m]) o4[gidx[m]] = make_float4(gy[m][0], gy[m][1], gy[m][2], gy[m][3]);
+            }
         }
     }
 }
 
-template <int NW, int TPW>
+template <int NW, int TPW, bool TILED = false>
 hipError_t launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
 {
     int dev = 0;
     (void)hipGetDevice(&dev);
-    return flow_launch<&nf_grad_wide_kernel<NW, TPW>>(64 * NW, lds, prog, a, n_cu, dev, stream);
+    return flow_launch<&nf_grad_wide_kernel<NW, TPW, TILED>>(64 * NW, lds, prog, a, n_cu, dev, stream);
+}
+
+// (strip height, wavefronts) by patch height — nfgw_tpw / nfgw_waves: beyond 4 rows always four wavefronts
+template <bool TILED>
+hipError_t dispatch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
+{
+    if (a.H > 16) return launch_grad_wide<4, 8, TILED>(prog, a, n_cu, lds, stream);
+    if (a.H > 8) return launch_grad_wide<4, 4, TILED>(prog, a, n_cu, lds, stream);
+    switch (nfgw_waves(a.H)) {
+    case 1: return launch_grad_wide<1, 2, TILED>(prog, a, n_cu, lds, stream);
+    case 2: return launch_grad_wide<2, 2, TILED>(prog, a, n_cu, lds, stream);
+    default: return launch_grad_wide<4, 2, TILED>(prog, a, n_cu, lds, stream);
+    }
 }
 
 }  // namespace
@@ -563,12 +650,17 @@ hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int
     if (prog.width != 32 || a.H < 1 || a.W < 1 || a.H > 32 || a.W > 32 || a.gate_words != nfgw_tpw(a.H) * n_cpl) return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * nfgw_lds_floats(a.H, n_cpl);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    // (strip height, wavefronts) by patch height — nfgw_tpw / nfgw_waves: beyond 4 rows always four wavefronts
-    if (a.H > 16) return launch_grad_wide<4, 8>(prog, a, n_cu, lds, stream);
-    if (a.H > 8) return launch_grad_wide<4, 4>(prog, a, n_cu, lds, stream);
-    switch (nfgw_waves(a.H)) {
-    case 1: return launch_grad_wide<1, 2>(prog, a, n_cu, lds, stream);
-    case 2: return launch_grad_wide<2, 2>(prog, a, n_cu, lds, stream);
-    default: return launch_grad_wide<4, 2>(prog, a, n_cu, lds, stream);
-    }
+    return dispatch_grad_wide<false>(prog, a, n_cu, lds, stream);
+}
+
+// one segment of a tiled call (NF_CFG_GRAD_TILED_WIDE): `prog` = the segment's ops, a.H x a.W = the tile, a.B = images x tiles,
+// n_cpl = the couplings of the call's largest segment (what a.gate_words was sized by; at most 3: LDS <= 81 KiB)
+hipError_t nf_launch_grad_wide_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream)
+{
+    if (prog.width != 32 || a.H < 1 || a.W < 1 || a.H > NF_GRAD_TILE || a.W > NF_GRAD_TILE || a.H > a.img_H || a.W > a.img_W || a.tile_ny < 1 ||
+        a.tile_nx < 1 || !a.z_in || a.gate_words != nfgw_tpw(a.H) * n_cpl)
+        return hipErrorInvalidValue;
+    const size_t lds = sizeof(float) * nfgw_lds_floats(a.H, n_cpl);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    return dispatch_grad_wide<true>(prog, a, n_cu, lds, stream);
 }

@@ -50,6 +50,7 @@ hipError_t nf_launch_tile_combine(const float *part, const NfTileParts &tp, int6
 hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 hipError_t nf_launch_grad_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
+hipError_t nf_launch_grad_wide_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 
 namespace {
 
@@ -667,6 +668,12 @@ struct Built {
 // (tile-couplings, tiles, boundary pixels) gives 17.9 ns per tile-coupling, 31.0 ns per tile and -0.003 ns per boundary pixel —
 // no boundary cost these runs can resolve, so the term is 0 — and over the first two alone 18.5 ns and 29.1 ns (residuals within
 // 3.1 %): a tile costs its couplings + 1.57.  One coupling per segment wins on every image of more than a few tiles.
+// Width 32 on tiles (NF_CFG_GRAD_TILED_WIDE, nf_grad_wide_kernel<.., TILED>) has a rule of its own, kGradWideSegs: the same tiles,
+// halo and switch, at most 3 couplings per segment on a single tile too.  Its per-tile constant is the scalar kernel's 1.57: with it
+// the unforced plan is the fastest measured arm (tools/time_nll_grad.py --legs tiled_wide, profiles/nll_grad_tiled_wide.txt: width 32
+// x 8 couplings at 256^2 x 16 and 64^2 x 1 024, unforced and S = 8 / 4 / 3), which is what keeps it.  Least squares over the six forced
+// arms gives 199.6 ns per tile-coupling and -6.3 ns per tile with residuals up to 21 %: a tile of a 3-coupling segment costs more than
+// three one-coupling tiles (80.6 KiB of LDS: one workgroup per CU instead of two), which two terms cannot say.
 struct SegRule {
     const char *env;       // forces S
     int tile;              // tile side the core must fit
@@ -674,9 +681,11 @@ struct SegRule {
     double per_tile;       // cost of a tile beside its couplings, in tile-couplings
     double per_boundary_px;   // cost of one image pixel of a segment boundary, in tile-couplings
     const char *what;
+    int max_cpl = 0;       // most couplings of a segment whatever the tile count (0: no such limit)
 };
 static const SegRule kFwdSegs = {"NF_TILE_SEGMENTS", 64, 2, 0.75, 1.0 / 4096.0, "patches beyond 64x64"};
 static const SegRule kGradSegs = {"NF_GRAD_TILE_SEGMENTS", NF_GRAD_TILE, 4, 1.57, 0.0, "nf_nll_grad on tiles"};
+static const SegRule kGradWideSegs = {"NF_GRAD_TILE_SEGMENTS", NF_GRAD_TILE, 4, 1.57, 0.0, "nf_nll_grad on tiles at coupling width 32", 3};   // 3: the gate record of a 32x32 tile beside the rest, and 32 - 2 x 12 = 8 core pixels
 static int plan_tile_segments(const NfProgram &prog, int H, int W, int th, int tw, std::vector<Built::TileSeg> &segs, const SegRule &rule = kFwdSegs)
 {
     std::vector<int> cpl;
@@ -702,6 +711,7 @@ static int plan_tile_segments(const NfProgram &prog, int H, int W, int th, int t
             t.op1 = sgm == S - 1 ? prog.n_ops : cpl[c0 + nc - 1] + 1;
             t.halo = rule.halo_per_cpl * nc;
             if ((H > th || W > tw) && rule.tile - 2 * t.halo < 8) ok = false;   // no core left in a tile
+            if (rule.max_cpl && nc > rule.max_cpl) ok = false;
             if (!ok) break;
             t.ny = nf_tile_count(H, th, t.halo);
             t.nx = nf_tile_count(W, tw, t.halo);
@@ -763,7 +773,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     out.tile_w = tw;
     out.segs.clear();
     if (cfg->n_layers < 1) return fail(NF_EINVAL, "n_layers must be >= 1");
-    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
+    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
     const double HW = (double)cfg->height * cfg->width;
 
     // intermediate list in NLL order
@@ -1011,7 +1021,8 @@ bool grad_force_scalar()
 
 // THE place that decides what nf_nll_grad supports and which kernel runs it (`path`: NF_GRAD_PATH_*): `fwd` = the NLL-direction
 // program of the model.
-// `tiles` (NF_GRAD_PATH_TILED only): the segments of the tiled route, gradient halos and the backward launches' tile counts.
+// `tiles` (NF_GRAD_PATH_TILED and NF_GRAD_PATH_TILED_WIDE32 only): the segments of the tiled route, gradient halos and the backward
+// launches' tile counts.
 int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, std::vector<Built::TileSeg> *tiles = nullptr)
 {
     if (path) *path = NF_GRAD_PATH_SCALAR;
@@ -1019,30 +1030,39 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
     if (cfg->flags & NF_CFG_FP16_CNN) return fail(NF_EINVAL, "nf_nll_grad: fp32 handles only (NF_CFG_FP16_CNN is set)");
     const bool whole = cfg->height <= 64 && cfg->width <= 64;   // one workgroup's patch
     const bool tile_flag = (cfg->flags & NF_CFG_GRAD_TILED) != 0;
-    if (!whole && !tile_flag)
+    const bool wide_flag = (cfg->flags & NF_CFG_GRAD_TILED_WIDE) != 0;
+    if (!whole && !tile_flag && !wide_flag)
         return fail(NF_EINVAL, "nf_nll_grad: patches of up to 64x64 (%dx%d given; no tiled evaluation)", cfg->height, cfg->width);
     const NfProgram &prog = fwd.lay[NF_PATH_SCALAR].prog;
     const int w = prog.width, hw = cfg->height * cfg->width;
     if (w > 32) return fail(NF_EINVAL, "nf_nll_grad: coupling widths up to 32 (%d given; the GEMM families have no gradient kernel)", fwd.raw_width);
+    // NF_CFG_GRAD_TILED_WIDE: at padded width 32 — and nowhere else — everything NF_CFG_GRAD_MFMA does plus tiles of its kernel
+    const bool wide_tiles = wide_flag && w == 32;
+    if (!whole && !tile_flag && !wide_tiles)
+        return fail(NF_EINVAL, "nf_nll_grad: patches of up to 64x64 (%dx%d given; no tiled evaluation)", cfg->height, cfg->width);
     int n_cpl = 0;
     for (int i = 0; i < prog.n_ops; ++i) n_cpl += prog.ops[i].type == NF_OP_COUPLING_FWD ? 1 : 0;
     const size_t lds = sizeof(float) * nf_grad_lds_floats(cfg->height, cfg->width, w, n_cpl);
     const bool scalar_holds = whole && !(hw > 1024 && w > 8) && lds <= 160 * 1024;
-    if (!whole && w == 32)
+    if (!whole && w == 32 && !wide_tiles)
         return fail(NF_EINVAL, "nf_nll_grad: coupling width %d has no tile mode (NF_CFG_GRAD_TILED covers padded widths 4, 8 and 16): patches of up "
                                "to 64x64 as far as its whole-patch kernels hold them (%dx%d given)", fwd.raw_width, cfg->height, cfg->width);
-    if (tile_flag && w <= 16 && !scalar_holds) {
-        // The flag only adds: a shape the whole-patch kernel does not hold goes to the same kernel on 32-pixel tiles, one launch per
-        // segment (nf_device.h, "gradient tiles")
+    // Widths up to 16 under NF_CFG_GRAD_TILED — the flag only adds: a shape the whole-patch kernel does not hold goes to the same
+    // kernel on 32-pixel tiles, one launch per segment (nf_device.h, "gradient tiles").  Width 32 under NF_CFG_GRAD_TILED_WIDE: a
+    // shape of up to 32x32 whose gate record fits is held whole, exactly as under NF_CFG_GRAD_MFMA (below, NF_GRAD=scalar included);
+    // every other shape goes to the matrix-core kernel on the same tiles — never to the scalar kernel, the slower one at this width
+    const bool narrow_tiled = tile_flag && w <= 16 && !scalar_holds;
+    const bool wide_tiled = wide_tiles && !(cfg->height <= 32 && cfg->width <= 32 && n_cpl <= nfgw_max_couplings(cfg->height));
+    if (narrow_tiled || wide_tiled) {
         std::vector<Built::TileSeg> segs;
         const int th = cfg->height < NF_GRAD_TILE ? cfg->height : NF_GRAD_TILE, tw = cfg->width < NF_GRAD_TILE ? cfg->width : NF_GRAD_TILE;
-        const int rc = plan_tile_segments(prog, cfg->height, cfg->width, th, tw, segs, kGradSegs);
+        const int rc = plan_tile_segments(prog, cfg->height, cfg->width, th, tw, segs, wide_tiled ? kGradWideSegs : kGradSegs);
         if (rc != NF_OK) return rc;
-        if (path) *path = NF_GRAD_PATH_TILED;
+        if (path) *path = wide_tiled ? NF_GRAD_PATH_TILED_WIDE32 : NF_GRAD_PATH_TILED;
         if (tiles) tiles->swap(segs);
         return NF_OK;
     }
-    if ((cfg->flags & NF_CFG_GRAD_MFMA) && w == 32) {
+    if (((cfg->flags & NF_CFG_GRAD_MFMA) || wide_tiles) && w == 32) {
         // The flag only adds: the matrix-core kernel (nf_grad_wide.hip) takes every shape up to 32x32 — unless NF_GRAD=scalar asks for
         // the other arm where that one holds the shape — and a shape beyond it (16x48, 8x64) stays with the scalar kernel as far as
         // that kernel holds it
@@ -1069,6 +1089,10 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
                     cfg->width, w, n_cpl, (lds + 1023) / 1024);
     return NF_OK;
 }
+
+// the paths whose couplings are in the NFGW_* layout (the matrix-core kernel, whole patches or tiles); the tiled paths
+static bool grad_path_is_wide(int path) { return path == NF_GRAD_PATH_WIDE32 || path == NF_GRAD_PATH_TILED_WIDE32; }
+static bool grad_path_is_tiled(int path) { return path == NF_GRAD_PATH_TILED || path == NF_GRAD_PATH_TILED_WIDE32; }
 
 // One coupling of the wide gradient block (nf_device.h, NFGW_*) from its generic block at width 32: the NF4_IMG_* image of the
 // forward chain without the 2 log2(e) factor, and the fetch-order images of the three transposed products.
@@ -1236,7 +1260,7 @@ struct nf_handle {
     int grad_rc = NF_EINVAL;
     int grad_path = NF_GRAD_PATH_SCALAR;   // NF_GRAD_PATH_*: which kernel nf_nll_grad launches (grad_support)
     std::string grad_why;
-    std::vector<Built::TileSeg> grad_segs;   // NF_GRAD_PATH_TILED: the segments (gradient halo, tiles of the backward launches)
+    std::vector<Built::TileSeg> grad_segs;   // NF_GRAD_PATH_TILED / _TILED_WIDE32: the segments (gradient halo, tiles of the backward launches)
     int grad_seg_cpl = 0;                    // ... and the couplings of the largest one (sizes the gate record)
     // scratch of the tiled calls (images beyond 64x64): the per-tile sums and the tensors between two segments.  A small set of
     // device buffers owned by the handle, one per call in flight; a call takes a free one (waiting, on ITS stream, for the work
@@ -1413,7 +1437,7 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
         g_last_error = keep;
         if (h->grad_rc == NF_OK) {
             std::vector<float> gb;
-            build_grad_block(h->fwd.lay[NF_PATH_SCALAR], h->rev.lay[NF_PATH_SCALAR], h->grad_path == NF_GRAD_PATH_WIDE32, h->gprog, gb,
+            build_grad_block(h->fwd.lay[NF_PATH_SCALAR], h->rev.lay[NF_PATH_SCALAR], grad_path_is_wide(h->grad_path), h->gprog, gb,
                              h->grad_n_cpl, h->grad_first_cpl);
             if ((e = hipMalloc((void **)&h->d_grad, gb.size() * sizeof(float))) != hipSuccess ||
                 (e = hipMemcpy(h->d_grad, gb.data(), gb.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) {
@@ -1970,12 +1994,12 @@ int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float 
     if ((rc = grad_support(cfg, f, &gpath)) != NF_OK) return rc;
     Layout l;
     int n_cpl = 0, first_cpl = 0;
-    build_grad_block(f.lay[NF_PATH_SCALAR], r.lay[NF_PATH_SCALAR], gpath == NF_GRAD_PATH_WIDE32, l.prog, l.block, n_cpl, first_cpl);
+    build_grad_block(f.lay[NF_PATH_SCALAR], r.lay[NF_PATH_SCALAR], grad_path_is_wide(gpath), l.prog, l.block, n_cpl, first_cpl);
     if (path) *path = gpath;
     return export_layout(l, ops_out, ops_cap, n_ops, folded, folded_cap, n_folded);
 }
 
-// ---- nf_nll_grad on tiles (NF_CFG_GRAD_TILED; nf_device.h, "gradient tiles") ----
+// ---- nf_nll_grad on tiles (NF_CFG_GRAD_TILED, NF_CFG_GRAD_TILED_WIDE; nf_device.h, "gradient tiles") ----
 // The forward launch of segment s runs on the forward direction's own tiles (tile_h x tile_w, halo 2 per coupling)
 static Built::TileSeg grad_fwd_seg(const nf_handle *h, int s)
 {
@@ -1991,7 +2015,7 @@ static size_t grad_img_bytes(const nf_handle *h, int64_t B) { return (((size_t)B
 // scratch of one call: the forward launches' tile sums, the S - 1 tensors between two segments, two gradient tensors (ping-pong)
 static size_t grad_workspace_bytes(const nf_handle *h, int64_t B)
 {
-    if (h->grad_rc != NF_OK || h->grad_path != NF_GRAD_PATH_TILED || B <= 0) return 0;
+    if (h->grad_rc != NF_OK || !grad_path_is_tiled(h->grad_path) || B <= 0) return 0;
     const int S = (int)h->grad_segs.size();
     size_t part4 = 0;
     for (int s = 0; s < S; ++s) {
@@ -2002,7 +2026,8 @@ static size_t grad_workspace_bytes(const nf_handle *h, int64_t B)
 }
 
 // Forward: the tiled launches of nf_nll cut at the gradient plan's boundaries, every tensor between two segments kept, and
-// nf_tile_combine for nll_out.  Backward: one launch of nf_grad_kernel<.., TILED> per segment, last to first; segment s reads the
+// nf_tile_combine for nll_out.  Backward: one launch of nf_grad_kernel<.., TILED> (NF_GRAD_PATH_TILED_WIDE32: of
+// nf_grad_wide_kernel<.., TILED>, over the same h->d_grad in its NFGW_* layout) per segment, last to first; segment s reads the
 // tensor in front of it and the gradient segment s + 1 stored, and stores core windows — to gx_out (s = 0) or to the other of two
 // scratch tensors.  gy_out: the first launch (in this order) whose segment has an SDN-kind op stores it, later ones add to it.
 // Everything is enqueued on `st`.
@@ -2063,7 +2088,8 @@ static int grad_tiled(nf_handle *h, const float *x, const float *y, int64_t B, c
         a.W = W < NF_GRAD_TILE ? W : NF_GRAD_TILE;
         a.img_H = H;
         a.img_W = W;
-        a.gate_words = nf_grad_gate_words(h->grad_seg_cpl, h->gprog.width);
+        const bool wide = h->grad_path == NF_GRAD_PATH_TILED_WIDE32;
+        a.gate_words = wide ? nfgw_tpw(a.H) * h->grad_seg_cpl : nf_grad_gate_words(h->grad_seg_cpl, h->gprog.width);
         bool gy_written = false;
         for (int s = S - 1; s >= 0 && e == hipSuccess; --s) {
             const Built::TileSeg &g = h->grad_segs[s];
@@ -2091,7 +2117,7 @@ static int grad_tiled(nf_handle *h, const float *x, const float *y, int64_t B, c
             t.gy_out = wr ? gy_out : nullptr;
             t.tflags = wr && gy_written ? NF_GT_GY_ACC : 0u;
             gy_written = gy_written || wr;
-            e = nf_launch_grad_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st);
+            e = wide ? nf_launch_grad_wide_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st) : nf_launch_grad_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st);
         }
     }
     ws_release(h, wsp, st);
@@ -2107,7 +2133,7 @@ int nf_grad_tile_segments(const nf_config *cfg, const nf_layer_desc *layers, con
     int path = NF_GRAD_PATH_SCALAR;
     std::vector<Built::TileSeg> segs;
     if ((rc = grad_support(cfg, b, &path, &segs)) != NF_OK) return rc;
-    if (path != NF_GRAD_PATH_TILED) return 0;
+    if (!grad_path_is_tiled(path)) return 0;
     for (int i = 0; i < (int)segs.size() && i < cap && out5; ++i) {
         const Built::TileSeg &g = segs[i];
         const int32_t v[5] = {g.op0, g.op1, g.halo, g.ny, g.nx};
@@ -2144,7 +2170,7 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
         if (rc != NF_OK) return rc;
     }
     if (B == 0) return NF_OK;
-    if (h->grad_path == NF_GRAD_PATH_TILED) {
+    if (grad_path_is_tiled(h->grad_path)) {
         NfDeviceGuard guard;
         int rc = guard.enter(h->device);
         if (rc != NF_OK) return rc;

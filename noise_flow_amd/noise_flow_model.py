@@ -202,6 +202,7 @@ class FlowHandle:
         flags = {"fp32": 0, "fp16": _lib.NF_CFG_FP16_CNN, "fp32_exact": _lib.NF_CFG_EXACT_FP32}[cnn_dtype]
         flags |= _lib.NF_CFG_GRAD_MFMA if grad_kernel == "mfma" else 0
         flags |= _lib.NF_CFG_GRAD_TILED if grad_tiles else 0
+        flags |= _lib.NF_CFG_GRAD_TILED_WIDE if (grad_tiles and grad_kernel == "mfma") else 0   # width 32: tiles of the matrix-core kernel
         cfg = _lib.nf_config(H, W, Cc, len(self.layers), -1 if device is None else int(device), flags)
         self._model_args = (cfg, descs, flat)   # what nf_cond_rows takes (kept alive with the handle)
         h = C.c_void_p()
@@ -266,7 +267,8 @@ class NoiseFlow(object):
           Also selectable as ``hps.grad_kernel``; not with cnn_dtype='fp16'.
     grad_tiles : ``True`` lets ``nll_and_grad`` / ``nll_torch`` take every H, W up to 4096 at coupling widths up to 16: a shape
           the whole-patch gradient kernel does not hold is evaluated as overlapping 32-pixel tiles (``NF_CFG_GRAD_TILED``); a
-          shape it holds is untouched.  Default ``False``; also selectable as ``hps.grad_tiles``.
+          shape it holds is untouched.  Together with grad_kernel='mfma' the same holds at coupling widths 17 .. 32, on tiles of
+          the matrix-core gradient kernel (``NF_CFG_GRAD_TILED_WIDE``).  Default ``False``; also selectable as ``hps.grad_tiles``.
     binding : 'loss_first' | 'sample_first' — template→layer binding (quirk Q1).
     """
 

@@ -1,7 +1,7 @@
 """nf_nll_grad next to nf_nll: the shipped model at 32x32 and 64x64, and the paper-scale model (width 32, 8 couplings) on the
 matrix-core gradient kernel, B = 1 024, same box, same process.
 
-    python tools/time_nll_grad.py [--launches 200] [--legs shipped,wide,tiled] [--out FILE.json]
+    python tools/time_nll_grad.py [--launches 200] [--legs shipped,wide,tiled,tiled_wide] [--out FILE.json]
 
 Every figure is the mean over a window of `--launches` (at least 200) back-to-back launches between two device events, after
 a warm-up of a quarter of that; three windows per entry, their median is reported.  The yardstick is nf_nll (the forward
@@ -21,6 +21,12 @@ the arms alternated `--reps` times in one process, same window protocol; per arm
 pixels/s, and the ratio to nf_nll of the same images (median of as many repetitions).  Beside every arm the terms of the
 planner's cost model (csrc/nf_host.hip, plan_tile_segments): sum over segments of tiles x couplings, of tiles, and the segment
 boundaries x image pixels — what the planner's constants are fitted to.
+
+Leg `tiled_wide` (not in the default set): the same at coupling width 32 (grad_kernel="mfma", grad_tiles=True: NF_CFG_GRAD_TILED_WIDE,
+tiles of csrc/nf_grad_wide.hip), FULL_ARCH / paper_like_variables on 64x64 x 1 024 and 256x256 x 16 (`--tw-shapes`).  Arms: the
+planner's own choice and S = 8 / 4 / 3, alternated; beside them nf_nll of the same handle and the whole-patch matrix-core kernel at
+32x32 x 1 024, per pixel.  Tile-couplings, tiles and boundary pixels are those of the whole launch here (x images).  At the end the least-squares fit of (ms) over (tile-couplings, tiles) of the forced arms of all shapes:
+ns per tile-coupling, ns per tile, and their ratio — the per-tile constant of the planner's rule (csrc/nf_host.hip, kGradWideSegs).
 """
 import argparse
 import ctypes as C
@@ -38,6 +44,7 @@ def main():
     ap.add_argument("--legs", default="shipped,wide")
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--ab-sides", default="24", help="patch sides of the A/B legs (both gradient kernels must hold them)")
+    ap.add_argument("--tw-shapes", default="64x1024,256x16", help="side x images of the tiled_wide leg")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     legs = a.legs.split(",")
@@ -88,6 +95,8 @@ def main():
         res["wide32"] = wide_legs(a, timed, B)
     if "tiled" in legs:
         res["tiled"] = tiled_legs(a, timed, v)
+    if "tiled_wide" in legs:
+        res["tiled_wide"] = tiled_wide_legs(a, timed)
     print("RESULT " + json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -238,6 +247,101 @@ def tiled_legs(a, timed, v):
                      arms[S]["plan"]["tiles"], arms[S]["plan"]["boundary_pixels"]), flush=True)
         out["%dx%d" % (side, side)] = r
         del arms
+    return out
+
+
+def tiled_wide_legs(a, timed):
+    import numpy as np
+    import torch
+    from noise_flow_amd import NoiseFlow, _lib, default_hps
+    v = paper_like_variables(FULL_ARCH, 32)
+    cond = _lib.nf_cond(800.0, 2.0, 0.0, 0.0)
+    med = lambda t: float(np.median(t))   # noqa: E731
+    out = {}
+
+    def with_forced(S, fn):
+        if S:
+            os.environ["NF_GRAD_TILE_SEGMENTS"] = str(S)
+        try:
+            return fn()
+        finally:
+            os.environ.pop("NF_GRAD_TILE_SEGMENTS", None)
+
+    def tensors(B, side):
+        rng = np.random.RandomState(0)
+        y = torch.as_tensor(rng.rand(B, side, side, 4).astype(np.float32)).cuda()
+        x = torch.as_tensor((rng.randn(B, side, side, 4) * 0.02).astype(np.float32)).cuda()
+        return x, y, torch.empty((B,), device="cuda"), torch.empty_like(x), torch.empty_like(y)
+
+    # the whole-patch matrix-core kernel at 32x32, per pixel
+    B32 = 1024
+    m32 = NoiseFlow([32, 32, 4], False, default_hps(arch=FULL_ARCH, width=32), variables=v, device=0, grad_kernel="mfma", grad_tiles=True)
+    x, y, nll, gx, gy = tensors(B32, 32)
+    lib, h, st = m32._flow.lib, m32._flow.ptr, m32._dev.stream_ptr()
+    assert lib.nf_grad_path(h) == _lib.NF_GRAD_PATH_WIDE32
+    t32 = timed(lambda: _lib.check(lib.nf_nll_grad(h, x.data_ptr(), y.data_ptr(), B32, C.byref(cond), None, nll.data_ptr(), gx.data_ptr(),
+                                                   gy.data_ptr(), st)))
+    whole_pps = B32 * 1024.0 / t32 * 1e3
+    out["32x32"] = {"B": B32, "grad_ms": t32, "pixels_per_s": whole_pps}
+    print("width 32, 32x32 x %d whole-patch matrix-core kernel  %.4f ms  %.3e pixels/s" % (B32, t32, whole_pps), flush=True)
+    del m32, x, y, nll, gx, gy
+
+    fit_rows = []
+    for side, B in [tuple(int(q) for q in w.split("x")) for w in a.tw_shapes.split(",") if w]:
+        x, y, nll, gx, gy = tensors(B, side)
+        sd, ld = torch.empty((B,), device="cuda"), torch.empty((B,), device="cuda")
+        arms = {}
+        for S in (0, 8, 4, 3):     # 0: the planner's choice
+            m = with_forced(S, lambda: NoiseFlow([side, side, 4], False, default_hps(arch=FULL_ARCH, width=32), variables=v, device=0,
+                                                 grad_kernel="mfma", grad_tiles=True))
+            lib, h, st = m._flow.lib, m._flow.ptr, m._dev.stream_ptr()
+            assert lib.nf_grad_path(h) == _lib.NF_GRAD_PATH_TILED_WIDE32
+            _lib.check(lib.nf_reserve_grad_workspace(h, B, 1))
+            cfg, descs, flat = m._flow._model_args
+            seg = (C.c_int32 * 80)()
+            n = with_forced(S, lambda: lib.nf_grad_tile_segments(C.byref(cfg), descs, flat.ctypes.data_as(C.POINTER(C.c_float)), flat.size, seg, 16))
+            assert n > 0 and (not S or n == S)
+            rows = [tuple(seg[5 * i:5 * i + 5]) for i in range(n)]
+            plan = {"segments": n, "tile_couplings": B * sum(r[3] * r[4] * (r[2] // 4) for r in rows), "tiles": B * sum(r[3] * r[4] for r in rows),
+                    "boundary_pixels": (n - 1) * B * side * side}
+            grad = (lambda lib=lib, h=h, st=st: _lib.check(lib.nf_nll_grad(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), None, nll.data_ptr(),
+                                                                          gx.data_ptr(), gy.data_ptr(), st)))
+            fwd = (lambda lib=lib, h=h, st=st: _lib.check(lib.nf_nll(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), nll.data_ptr(), sd.data_ptr(),
+                                                                    ld.data_ptr(), None, None, 0, st)))
+            arms[S] = {"model": m, "grad": grad, "fwd": fwd, "plan": plan, "ms": []}
+        t_nll = []
+        for rep in range(a.reps):
+            t_nll.append(timed(arms[0]["fwd"]))
+            for S in (0, 8, 4, 3):
+                arms[S]["ms"].append(timed(arms[S]["grad"]))
+            print("%dx%d x %d rep %d  nf_nll %.4f ms   nf_nll_grad unforced (S=%d) %.4f  S=8 %.4f  S=4 %.4f  S=3 %.4f ms"
+                  % (side, side, B, rep, t_nll[-1], arms[0]["plan"]["segments"], arms[0]["ms"][-1], arms[8]["ms"][-1], arms[4]["ms"][-1],
+                     arms[3]["ms"][-1]), flush=True)
+        px = float(B) * side * side
+        r = {"B": B, "nll_ms": t_nll, "nll_median_ms": med(t_nll), "nll_pixels_per_s": px / med(t_nll) * 1e3, "arms": {}}
+        for S in (0, 8, 4, 3):
+            t = arms[S]["ms"]
+            name = "S=%d" % S if S else "unforced"
+            r["arms"][name] = dict(arms[S]["plan"], ms=t, median_ms=med(t), spread_ms=max(t) - min(t), pixels_per_s=px / med(t) * 1e3,
+                                   grad_over_nll=med(t) / med(t_nll), whole_patch_over_this=whole_pps / (px / med(t) * 1e3))
+            print("%dx%d x %d  %-8s (S=%d)  %.4f ms (spread %.4f)  %.3e pixels/s  grad / nll %.2f  32x32 whole-patch pixels/s over this %.2f   "
+                  "tile-couplings %d  tiles %d  boundary pixels %d"
+                  % (side, side, B, name, arms[S]["plan"]["segments"], med(t), max(t) - min(t), px / med(t) * 1e3, med(t) / med(t_nll),
+                     whole_pps / (px / med(t) * 1e3), arms[S]["plan"]["tile_couplings"], arms[S]["plan"]["tiles"], arms[S]["plan"]["boundary_pixels"]),
+                  flush=True)
+            if S:
+                fit_rows.append((arms[S]["plan"]["tile_couplings"], arms[S]["plan"]["tiles"], med(t)))
+        out["%dx%d" % (side, side)] = r
+        del arms
+    if len(fit_rows) >= 2:
+        A = np.array([[r[0], r[1]] for r in fit_rows], np.float64)
+        t = np.array([r[2] for r in fit_rows], np.float64) * 1e6      # ns
+        coef = np.linalg.lstsq(A, t, rcond=None)[0]
+        resid = (A @ coef - t) / t
+        out["fit"] = {"ns_per_tile_coupling": float(coef[0]), "ns_per_tile": float(coef[1]), "per_tile_in_tile_couplings": float(coef[1] / coef[0]),
+                      "largest_relative_residual": float(np.abs(resid).max()), "rows": len(fit_rows)}
+        print("fit over %d forced arms: %.1f ns per tile-coupling, %.1f ns per tile: a tile costs its couplings + %.2f (largest residual %.1f %%)"
+              % (len(fit_rows), coef[0], coef[1], coef[1] / coef[0], 100.0 * np.abs(resid).max()), flush=True)
     return out
 
 
