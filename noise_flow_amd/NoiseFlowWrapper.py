@@ -53,7 +53,7 @@ class NoiseFlowWrapper:
         self.patch_shape = (32, 32) if patch_shape is None else (int(patch_shape[0]), int(patch_shape[1]))
         self.binding = binding
         self.device = device
-        self.grad_kernel = grad_kernel   # 'scalar' | 'mfma' (NoiseFlow); None: hps.grad_kernel, else 'scalar'
+        self.grad_kernel = grad_kernel   # 'scalar' | 'mfma' | 'gemm' (NoiseFlow); None: hps.grad_kernel, else 'scalar'
         self.grad_tiles = grad_tiles     # True: input gradients of images beyond 64x64 (NoiseFlow; with grad_kernel='mfma' also at widths 17 .. 32); None: hps.grad_tiles, else False
         self.hps = self.hps_loader(os.path.join(self.nf_path, "hps.txt"))
         if seed is not None:

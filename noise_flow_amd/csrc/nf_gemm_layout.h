@@ -58,3 +58,41 @@ __host__ __device__ constexpr int nf10_slab_B2(int wp) { return 32 * wp + 1024 +
 __host__ __device__ constexpr int nf10_img_SLAB(int wp) { return (wp / 32) * 832; }
 __host__ __device__ constexpr int nf10_img_size(int wp) { return (wp / 32) * 832 + (wp / 32) * nf10_slab_floats(wp); }
 __host__ __device__ constexpr int nf10_cpl_size(int wp) { return 68 + nf10_img_size(wp); }
+
+// ---- input gradients at coupling widths 33 .. 512 (nf_grad_gemm.hip, NF_CFG_GRAD_GEMM) ---------------------------------------------
+// Same launch record (NfGradLaunch) and op list as the other gradient kernels; MIX and SCALE as the scalar gradient block.  Per
+// coupling the block carries, in the tile / lane / register conventions of NF7_* (nf_device.h) and with nothing pre-scaled (tanh / exp
+// are nf_tanh / nf_exp as in nf_grad.hip), every weight in the fetch order of v_mfma_f32_32x32x2_f32 — for the forward chain and for
+// the three transposed products.  WP = the width zero-padded to 64 / 128 / 256 / 512, MT = WP / 32; a padded channel is zero in all:
+//   COUPLING  E [16][4] @0 (generic values), S [4] @64 (rescaling_scale, 0, 0, 0),
+//             FWD @68: the NF7 image (nf7_img_*: A1, B1, B2, A2, A3, A3C) without the 2 log2(e) factor
+//             BWD @68 + nf7_img_size(WP):
+//               A3T [MT][5][64][4]      l_last^T of output tile m, K = 9 taps x 4 = 36 in 18 steps (20 stored): step s, lane l:
+//                                       W3[tap = s>>1][c = 32 m + (l&31)][j = 2 (s&1) + (l>>5)]; the B operand is d(shift, raw)[j] at
+//                                       pixel - (tap - centre)
+//               A2T [MT][WP/8][64][4]   l_2^T of output tile m: K step kk = 4 kc + s consumes tile kk / 16, register kk % 16 of d h2:
+//                                       lane l: W2[in = 32 m + (l&31)][out = 32 (kk/16) + c(kk%16, l>>5)]
+//               A1T [MT][4][64][4]      l_1^T as D18 = W1 d h1: row i = l&31 = 2 tap + ch (18 used), step v of input tile mi:
+//                                       W1[tap][ch][32 mi + c(v, l>>5)]
+// Geometry of nf_gemm_kernel: bands of NB = 32768 / WP pixels, 512 threads, the band's activations ([WP][NB], 128 KiB) in LDS in
+// B-operand order — h1 in the forward chain, the gated d h2 in the transposed one.  The partial D18 records of the WM = WP / 64
+// wavefronts along the channel axis meet in the same region: NFGG_D_STRIDE floats per pixel, [2 tap + ch].
+// Gate record: the sign of every D register of h1 (layer 0) and h2 (layer 1), 16 bits per lane and tile, in DEVICE SCRATCH per
+// workgroup: uint16 [coupling][band][layer][tile = 32 of (m, nt)][lane] = 8 KiB per coupling and band — 2 WP bits per pixel.
+#define NFGG_CPL_E 0
+#define NFGG_CPL_S 64
+#define NFGG_CPL_FWD 68
+#define NFGG_D_STRIDE 20
+#define NFGG_MAX_COUPLINGS 32   // couplings per model on this path: the scratch of a 32x32 patch at width 512 stays at 4 MiB per workgroup
+__host__ __device__ constexpr int nfgg_cpl_bwd(int wp) { return 68 + (wp / 32) * 832 + wp * wp + (wp / 32) * (1024 + 128); }
+__host__ __device__ constexpr int nfgg_bwd_A3T(int) { return 0; }
+__host__ __device__ constexpr int nfgg_bwd_A2T(int wp) { return (wp / 32) * 1280; }
+__host__ __device__ constexpr int nfgg_bwd_A1T(int wp) { return (wp / 32) * 1280 + wp * wp; }
+__host__ __device__ constexpr int nfgg_bwd_size(int wp) { return (wp / 32) * (1280 + 1024) + wp * wp; }
+__host__ __device__ constexpr int nfgg_cpl_size(int wp) { return nfgg_cpl_bwd(wp) + nfgg_bwd_size(wp); }
+__host__ __device__ constexpr int nfgg_bands(int hw, int wp) { return (hw + 32768 / wp - 1) / (32768 / wp); }
+// uint16 words of gate record per workgroup (one patch at a time): [coupling][band][2][32][64]
+__host__ __device__ constexpr size_t nfgg_gate_halves(int hw, int wp, int n_cpl) { return (size_t)n_cpl * (size_t)nfgg_bands(hw, wp) * 4096; }
+// LDS: the band, the zero-bordered tiles of z0 (2 planes) and d(shift, raw) (4 planes) at pitch W + 2, the reduction scratch
+__host__ __device__ constexpr int nfgg_plane(int H, int W) { return ((H + 2) * (W + 2) + 3) & ~3; }
+__host__ __device__ constexpr size_t nfgg_lds_floats(int H, int W) { return 32768 + 6 * (size_t)nfgg_plane(H, W) + 32; }

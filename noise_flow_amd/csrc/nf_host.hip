@@ -51,6 +51,8 @@ hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cp
 hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 hipError_t nf_launch_grad_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 hipError_t nf_launch_grad_wide_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
+hipError_t nf_launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes, hipStream_t stream);
+int nf_grad_gemm_groups(int64_t B, int n_cu);
 
 namespace {
 
@@ -384,12 +386,11 @@ void relayout_coupling_wide32(const float *v1, int w, float *out)
 
 // GEMM re-layout (nf_device.h, NF7_*; widths 33 .. 512 zero-padded to wp = 64 / 128 / 256 / 512): every weight in the order the
 // wavefront that consumes it fetches it from L2 (nf_gemm.hip).
-void relayout_coupling_gemm(const float *v1, int w, int wp, float *out)
+// the NF7 image (A1, B1, B2, A2, A3, A3C) with the raw columns of l_last scaled by k2: 2 log2(e) for the flow kernels, 1 for the
+// gradient kernel (nf_gemm_layout.h, NFGG_*), which takes tanh / exp of unscaled values
+void relayout_gemm_image(const float *v1, int w, int wp, double k2, float *img)
 {
-    const double k2 = k2Log2e;
     const int MT = wp / 32, KC = wp / 8;
-    relayout_ES(v1, w, out + NF7_CPL_E, out + NF7_CPL_S);
-    float *img = out + NF7_CPL_IMG;
     const float *W1 = v1 + nf_cpl_off_W1(w), *B1 = v1 + nf_cpl_off_B1(w), *W2 = v1 + nf_cpl_off_W2(w);
     const float *B2 = v1 + nf_cpl_off_B2(w), *W3 = v1 + nf_cpl_off_W3(w);
     for (int m = 0; m < MT; ++m) {
@@ -428,6 +429,11 @@ void relayout_coupling_gemm(const float *v1, int w, int wp, float *out)
                     if (j >= 2) wv *= k2;
                     img[nf7_img_A3C(wp) + (((size_t)mi * 4 + (v >> 2)) * 8 + g * 4 + j) * 4 + (v & 3)] = (float)wv;
                 }
+}
+void relayout_coupling_gemm(const float *v1, int w, int wp, float *out)
+{
+    relayout_ES(v1, w, out + NF7_CPL_E, out + NF7_CPL_S);
+    relayout_gemm_image(v1, w, wp, k2Log2e, out + NF7_CPL_IMG);
 }
 
 // Variant B of the GEMM layout (NF10_*, widths <= 128): the NF7 values, one contiguous slab per channel tile.
@@ -773,7 +779,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     out.tile_w = tw;
     out.segs.clear();
     if (cfg->n_layers < 1) return fail(NF_EINVAL, "n_layers must be >= 1");
-    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
+    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE | NF_CFG_GRAD_GEMM)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
     const double HW = (double)cfg->height * cfg->width;
 
     // intermediate list in NLL order
@@ -1027,6 +1033,23 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
 {
     if (path) *path = NF_GRAD_PATH_SCALAR;
     if (tiles) tiles->clear();
+    // NF_CFG_GRAD_GEMM: coupling widths beyond 32 — and nothing else — on the GEMM gradient kernel (nf_grad_gemm.hip): whole patches of
+    // up to 32x32, fp32 handles, no tile mode whatever the tile flags say
+    if ((cfg->flags & NF_CFG_GRAD_GEMM) && fwd.lay[NF_PATH_SCALAR].prog.width > 32) {
+        const NfProgram &gprog = fwd.lay[NF_PATH_SCALAR].prog;
+        if (cfg->flags & NF_CFG_FP16_CNN)
+            return fail(NF_EINVAL, "nf_nll_grad: coupling width %d under NF_CFG_GRAD_GEMM takes fp32 handles only (NF_CFG_FP16_CNN is set)", fwd.raw_width);
+        if (cfg->height > 32 || cfg->width > 32)
+            return fail(NF_EINVAL, "nf_nll_grad: coupling width %d under NF_CFG_GRAD_GEMM covers whole patches of up to 32x32 (%dx%d given; no tile mode at "
+                                   "widths beyond 32, with or without NF_CFG_GRAD_TILED / NF_CFG_GRAD_TILED_WIDE)", fwd.raw_width, cfg->height, cfg->width);
+        int n_gc = 0;
+        for (int i = 0; i < gprog.n_ops; ++i) n_gc += gprog.ops[i].type == NF_OP_COUPLING_FWD ? 1 : 0;
+        if (n_gc > NFGG_MAX_COUPLINGS)
+            return fail(NF_EINVAL, "nf_nll_grad: at most %d couplings at coupling width %d under NF_CFG_GRAD_GEMM (%d given): the gate record in device "
+                                   "scratch", NFGG_MAX_COUPLINGS, fwd.raw_width, n_gc);
+        if (path) *path = NF_GRAD_PATH_GEMM;
+        return NF_OK;
+    }
     if (cfg->flags & NF_CFG_FP16_CNN) return fail(NF_EINVAL, "nf_nll_grad: fp32 handles only (NF_CFG_FP16_CNN is set)");
     const bool whole = cfg->height <= 64 && cfg->width <= 64;   // one workgroup's patch
     const bool tile_flag = (cfg->flags & NF_CFG_GRAD_TILED) != 0;
@@ -1132,13 +1155,48 @@ void relayout_coupling_grad_wide(const float *v1, float *out)
             }
 }
 
+// One coupling of the GEMM gradient block (nf_gemm_layout.h, NFGG_*) from its generic block at width w (33 .. 512), padded to wp:
+// the NF7 image of the forward chain without the 2 log2(e) factor, and the fetch-order images of the three transposed products.
+void relayout_coupling_grad_gemm(const float *v1, int w, int wp, float *out)
+{
+    const int MT = wp / 32, KC = wp / 8;
+    memcpy(out + NFGG_CPL_E, v1 + nf_cpl_off_E(w), 64 * sizeof(float));
+    out[NFGG_CPL_S] = v1[nf_cpl_off_S(w)];
+    out[NFGG_CPL_S + 1] = out[NFGG_CPL_S + 2] = out[NFGG_CPL_S + 3] = 0.0f;
+    relayout_gemm_image(v1, w, wp, 1.0, out + NFGG_CPL_FWD);
+    const float *W1 = v1 + nf_cpl_off_W1(w), *W2 = v1 + nf_cpl_off_W2(w), *W3 = v1 + nf_cpl_off_W3(w);
+    float *bwd = out + nfgg_cpl_bwd(wp);
+    for (int m = 0; m < MT; ++m) {
+        for (int s = 0; s < 20; ++s)   // l_last^T: K step s = (tap s >> 1, elements j = 2 (s & 1) + K slice)
+            for (int l = 0; l < 64; ++l) {
+                const int c = 32 * m + (l & 31);
+                bwd[nfgg_bwd_A3T(wp) + ((m * 5 + (s >> 2)) * 64 + l) * 4 + (s & 3)] =
+                    (s < 18 && c < w) ? W3[((size_t)(s >> 1) * w + c) * 4 + 2 * (s & 1) + (l >> 5)] : 0.0f;
+            }
+        for (int kc = 0; kc < KC; ++kc)   // l_2^T: the output tile is an INPUT tile of W2, K runs over its output channels
+            for (int l = 0; l < 64; ++l)
+                for (int s2 = 0; s2 < 4; ++s2) {
+                    const int kk = 4 * kc + s2, oc = 32 * (kk / 16) + nf4_chan(kk % 16, l >> 5), cin = 32 * m + (l & 31);
+                    bwd[nfgg_bwd_A2T(wp) + (((size_t)m * KC + kc) * 64 + l) * 4 + s2] = (cin < w && oc < w) ? W2[(size_t)cin * w + oc] : 0.0f;
+                }
+        for (int v = 0; v < 16; ++v)      // l_1^T: row i = 2 tap + ch of D18, K = the channels of input tile m
+            for (int l = 0; l < 64; ++l) {
+                const int row = l & 31, cin = 32 * m + nf4_chan(v, l >> 5);
+                bwd[nfgg_bwd_A1T(wp) + (((size_t)m * 4 + (v >> 2)) * 64 + l) * 4 + (v & 3)] = (row < 18 && cin < w) ? W1[(size_t)row * w + cin] : 0.0f;
+            }
+    }
+}
+
 // The gradient block (nf_device.h, NfGradLaunch): the NLL-order generic block with A^-1 beside every 1x1 matrix — op i of
 // the NLL program is op n - 1 - i of the sampling program, whose block holds the inverse — and 1/s beside every scale.
-// (`fwd`, `rev` = the generic layouts of the two directions).  `wide`: couplings in the NFGW_* layout (nf_grad_wide.hip).
-void build_grad_block(const Layout &fwd, const Layout &rev, bool wide, NfProgram &gp, std::vector<float> &blk, int &n_cpl, int &first_cpl)
+// (`fwd`, `rev` = the generic layouts of the two directions).  `path` (NF_GRAD_PATH_*, grad_support) decides the couplings' layout:
+// NFGW_* on the matrix-core paths at width 32 (nf_grad_wide.hip), NFGG_* at the padded width on NF_GRAD_PATH_GEMM (nf_grad_gemm.hip;
+// the program's width is then the padded one), the generic block otherwise.
+void build_grad_block(const Layout &fwd, const Layout &rev, int path, NfProgram &gp, std::vector<float> &blk, int &n_cpl, int &first_cpl)
 {
+    const bool wide = grad_path_is_wide(path), gemm = path == NF_GRAD_PATH_GEMM;
     memset(&gp, 0, sizeof(gp));
-    gp.width = fwd.prog.width;
+    gp.width = gemm ? nf7_pad_width(fwd.prog.width) : fwd.prog.width;
     gp.n_ops = fwd.prog.n_ops;
     blk.clear();
     n_cpl = 0;
@@ -1156,6 +1214,9 @@ void build_grad_block(const Layout &fwd, const Layout &rev, bool wide, NfProgram
             if (wide) {
                 blk.resize(blk.size() + NFGW_CPL_SIZE);
                 relayout_coupling_grad_wide(v, blk.data() + gp.ops[i].off);
+            } else if (gemm) {
+                blk.resize(blk.size() + nfgg_cpl_size(gp.width));
+                relayout_coupling_grad_gemm(v, fwd.prog.width, gp.width, blk.data() + gp.ops[i].off);
             } else {
                 blk.insert(blk.end(), v, v + nf_cpl_size(gp.width));
             }
@@ -1437,7 +1498,7 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
         g_last_error = keep;
         if (h->grad_rc == NF_OK) {
             std::vector<float> gb;
-            build_grad_block(h->fwd.lay[NF_PATH_SCALAR], h->rev.lay[NF_PATH_SCALAR], grad_path_is_wide(h->grad_path), h->gprog, gb,
+            build_grad_block(h->fwd.lay[NF_PATH_SCALAR], h->rev.lay[NF_PATH_SCALAR], h->grad_path, h->gprog, gb,
                              h->grad_n_cpl, h->grad_first_cpl);
             if ((e = hipMalloc((void **)&h->d_grad, gb.size() * sizeof(float))) != hipSuccess ||
                 (e = hipMemcpy(h->d_grad, gb.data(), gb.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) {
@@ -1994,7 +2055,7 @@ int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float 
     if ((rc = grad_support(cfg, f, &gpath)) != NF_OK) return rc;
     Layout l;
     int n_cpl = 0, first_cpl = 0;
-    build_grad_block(f.lay[NF_PATH_SCALAR], r.lay[NF_PATH_SCALAR], grad_path_is_wide(gpath), l.prog, l.block, n_cpl, first_cpl);
+    build_grad_block(f.lay[NF_PATH_SCALAR], r.lay[NF_PATH_SCALAR], gpath, l.prog, l.block, n_cpl, first_cpl);
     if (path) *path = gpath;
     return export_layout(l, ops_out, ops_cap, n_ops, folded, folded_cap, n_folded);
 }
@@ -2012,10 +2073,15 @@ static Built::TileSeg grad_fwd_seg(const nf_handle *h, int s)
 
 static size_t grad_img_bytes(const nf_handle *h, int64_t B) { return (((size_t)B * h->cfg.height * h->cfg.width * kC * sizeof(float)) + 255) & ~(size_t)255; }
 
-// scratch of one call: the forward launches' tile sums, the S - 1 tensors between two segments, two gradient tensors (ping-pong)
+// scratch of one call: the forward launches' tile sums, the S - 1 tensors between two segments, two gradient tensors (ping-pong);
+// NF_GRAD_PATH_GEMM: the gate records of the launch's workgroups (nf_gemm_layout.h, NFGG_*)
 static size_t grad_workspace_bytes(const nf_handle *h, int64_t B)
 {
-    if (h->grad_rc != NF_OK || !grad_path_is_tiled(h->grad_path) || B <= 0) return 0;
+    if (h->grad_rc != NF_OK || B <= 0) return 0;
+    if (h->grad_path == NF_GRAD_PATH_GEMM)   // the gate records: one per WORKGROUP of the launch, not per patch
+        return ((size_t)nf_grad_gemm_groups(B, h->n_cu) * nfgg_gate_halves(h->cfg.height * h->cfg.width, h->gprog.width, h->grad_n_cpl) * sizeof(uint16_t) + 255) &
+               ~(size_t)255;
+    if (!grad_path_is_tiled(h->grad_path)) return 0;
     const int S = (int)h->grad_segs.size();
     size_t part4 = 0;
     for (int s = 0; s < S; ++s) {
@@ -2197,6 +2263,18 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
     NfDeviceGuard guard;
     int rc = guard.enter(h->device);
     if (rc != NF_OK) return rc;
+    if (h->grad_path == NF_GRAD_PATH_GEMM) {
+        // the gate records live in a buffer of the handle's workspace set: one per call in flight, grown only by a call that needs
+        // more than any earlier one (nf_reserve_grad_workspace sizes it up front); everything else is enqueued
+        a.gate_words = 0;
+        const size_t need = grad_workspace_bytes(h, B);
+        nf_handle::Workspace *wsp = nullptr;
+        if ((rc = ws_acquire(h, need, (hipStream_t)stream, &wsp)) != NF_OK) return rc;
+        const hipError_t eg = nf_launch_grad_gemm(h->gprog, a, h->grad_n_cpl, h->n_cu, wsp ? wsp->p : nullptr, wsp ? wsp->bytes : 0, (hipStream_t)stream);
+        ws_release(h, wsp, (hipStream_t)stream);
+        if (eg != hipSuccess) return fail_hip(eg, "nf_nll_grad launch (GEMM)");
+        return NF_OK;
+    }
     hipError_t e = wide ? nf_launch_grad_wide(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream)
                         : nf_launch_grad(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "nf_nll_grad launch");

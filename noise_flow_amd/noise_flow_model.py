@@ -195,12 +195,13 @@ class FlowHandle:
         self.x_shape = (H, W, Cc)
         if cnn_dtype not in ("fp32", "fp16", "fp32_exact"):
             raise ValueError("cnn_dtype must be 'fp32', 'fp16' or 'fp32_exact'")
-        if grad_kernel not in ("scalar", "mfma"):
-            raise ValueError("grad_kernel must be 'scalar' or 'mfma'")
-        if grad_kernel == "mfma" and cnn_dtype == "fp16":
-            raise ValueError("grad_kernel='mfma' needs an fp32 handle (cnn_dtype='fp16' has no gradient kernel)")
+        if grad_kernel not in ("scalar", "mfma", "gemm"):
+            raise ValueError("grad_kernel must be 'scalar', 'mfma' or 'gemm'")
+        if grad_kernel in ("mfma", "gemm") and cnn_dtype == "fp16":
+            raise ValueError("grad_kernel='%s' needs an fp32 handle (cnn_dtype='fp16' has no gradient kernel)" % grad_kernel)
         flags = {"fp32": 0, "fp16": _lib.NF_CFG_FP16_CNN, "fp32_exact": _lib.NF_CFG_EXACT_FP32}[cnn_dtype]
         flags |= _lib.NF_CFG_GRAD_MFMA if grad_kernel == "mfma" else 0
+        flags |= _lib.NF_CFG_GRAD_GEMM if grad_kernel == "gemm" else 0   # widths 33 .. 512: the GEMM gradient kernel
         flags |= _lib.NF_CFG_GRAD_TILED if grad_tiles else 0
         flags |= _lib.NF_CFG_GRAD_TILED_WIDE if (grad_tiles and grad_kernel == "mfma") else 0   # width 32: tiles of the matrix-core kernel
         cfg = _lib.nf_config(H, W, Cc, len(self.layers), -1 if device is None else int(device), flags)
@@ -262,9 +263,11 @@ class NoiseFlow(object):
           names; default = fresh initialisation with the reference initialisers.
     cnn_dtype : 'fp32' (default) | 'fp16' — precision of the coupling-CNN convolutions; 'fp32_exact' keeps every conv of the
           width-4 model on the fp32 matrix instruction where 'fp32' would use the fp32-accurate split-bf16 kernel (32x32 patches).
-    grad_kernel : 'scalar' (default) | 'mfma' — which kernel ``nll_and_grad`` / ``nll_torch`` run at coupling widths 17 .. 32:
-          'mfma' is the matrix-core gradient kernel (patches up to 32x32, ``NF_CFG_GRAD_MFMA``); no effect on narrower models.
-          Also selectable as ``hps.grad_kernel``; not with cnn_dtype='fp16'.
+    grad_kernel : 'scalar' (default) | 'mfma' | 'gemm' — which kernel ``nll_and_grad`` / ``nll_torch`` run beyond coupling width 16:
+          'mfma' is the matrix-core gradient kernel of widths 17 .. 32 (patches up to 32x32, ``NF_CFG_GRAD_MFMA``); no effect on
+          narrower models.  'gemm' is the GEMM gradient kernel of widths 33 .. 512 (whole patches up to 32x32,
+          ``NF_CFG_GRAD_GEMM``), which have no gradient without it; no effect at widths up to 32.
+          Also selectable as ``hps.grad_kernel``; neither with cnn_dtype='fp16'.
     grad_tiles : ``True`` lets ``nll_and_grad`` / ``nll_torch`` take every H, W up to 4096 at coupling widths up to 16: a shape
           the whole-patch gradient kernel does not hold is evaluated as overlapping 32-pixel tiles (``NF_CFG_GRAD_TILED``); a
           shape it holds is untouched.  Together with grad_kernel='mfma' the same holds at coupling widths 17 .. 32, on tiles of

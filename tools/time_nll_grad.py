@@ -1,7 +1,7 @@
 """nf_nll_grad next to nf_nll: the shipped model at 32x32 and 64x64, and the paper-scale model (width 32, 8 couplings) on the
 matrix-core gradient kernel, B = 1 024, same box, same process.
 
-    python tools/time_nll_grad.py [--launches 200] [--legs shipped,wide,tiled,tiled_wide] [--out FILE.json]
+    python tools/time_nll_grad.py [--launches 200] [--legs shipped,wide,tiled,tiled_wide,gemm] [--out FILE.json]
 
 Every figure is the mean over a window of `--launches` (at least 200) back-to-back launches between two device events, after
 a warm-up of a quarter of that; three windows per entry, their median is reported.  The yardstick is nf_nll (the forward
@@ -27,6 +27,12 @@ tiles of csrc/nf_grad_wide.hip), FULL_ARCH / paper_like_variables on 64x64 x 1 0
 planner's own choice and S = 8 / 4 / 3, alternated; beside them nf_nll of the same handle and the whole-patch matrix-core kernel at
 32x32 x 1 024, per pixel.  Tile-couplings, tiles and boundary pixels are those of the whole launch here (x images).  At the end the least-squares fit of (ms) over (tile-couplings, tiles) of the forced arms of all shapes:
 ns per tile-coupling, ns per tile, and their ratio — the per-tile constant of the planner's rule (csrc/nf_host.hip, kGradWideSegs).
+
+Leg `gemm` (not in the default set): the GEMM gradient kernel (grad_kernel="gemm", NF_CFG_GRAD_GEMM, csrc/nf_grad_gemm.hip) at coupling
+widths 64, 128 and 512, FULL_ARCH / paper_like_variables on 32x32; width 512 at B = 512, the others at B = 1 024.  Same window
+protocol; per width nf_nll of the same handle, the gradient's three window means (median and spread), patches/s, the ratio to nf_nll
+and the fraction of the fp32 matrix peak (157.3 TFLOP/s), counting THREE coupling-CNN evaluations per coupling — forward sweep,
+recomputation, transposed products: the gates are stored, not recomputed.
 """
 import argparse
 import ctypes as C
@@ -97,6 +103,8 @@ def main():
         res["tiled"] = tiled_legs(a, timed, v)
     if "tiled_wide" in legs:
         res["tiled_wide"] = tiled_wide_legs(a, timed)
+    if "gemm" in legs:
+        res["gemm"] = gemm_legs(a)
     print("RESULT " + json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -342,6 +350,58 @@ def tiled_wide_legs(a, timed):
                       "largest_relative_residual": float(np.abs(resid).max()), "rows": len(fit_rows)}
         print("fit over %d forced arms: %.1f ns per tile-coupling, %.1f ns per tile: a tile costs its couplings + %.2f (largest residual %.1f %%)"
               % (len(fit_rows), coef[0], coef[1], coef[1] / coef[0], 100.0 * np.abs(resid).max()), flush=True)
+    return out
+
+
+def gemm_legs(a):
+    import numpy as np
+    import torch
+    from noise_flow_amd import NoiseFlow, _lib, default_hps
+    cond = _lib.nf_cond(800.0, 2.0, 0.0, 0.0)
+    PEAK = 157.3e12   # fp32 matrix peak of an MI355X, FLOP/s
+    EVALS = 3         # coupling-CNN evaluations per coupling: forward sweep, recomputation, transposed products
+    out = {}
+
+    def windows(fn):   # the window protocol of `timed`, all three window means kept
+        def window(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) / n
+        window(max(a.launches // 4, 10))
+        return sorted(window(a.launches) for _ in range(3))
+
+    for width, B in ((64, 1024), (128, 1024), (512, 512)):
+        v = paper_like_variables(FULL_ARCH, width)
+        m = NoiseFlow([32, 32, 4], False, default_hps(arch=FULL_ARCH, width=width), variables=v, device=0, grad_kernel="gemm")
+        rng = np.random.RandomState(0)
+        y = torch.as_tensor(rng.rand(B, 32, 32, 4).astype(np.float32)).cuda()
+        x = torch.as_tensor((rng.randn(B, 32, 32, 4) * 0.02).astype(np.float32)).cuda()
+        nll, sd, ld = (torch.empty((B,), device="cuda") for _ in range(3))
+        gx, gy = torch.empty_like(x), torch.empty_like(y)
+        lib, h, st = m._flow.lib, m._flow.ptr, m._dev.stream_ptr()
+        assert lib.nf_grad_path(h) == _lib.NF_GRAD_PATH_GEMM and lib.nf_kernel_path(h, 0) == _lib.NF_PATH_GEMM
+        _lib.check(lib.nf_reserve_grad_workspace(h, B, 1))
+        t_nll = windows(lambda: _lib.check(lib.nf_nll(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), nll.data_ptr(), sd.data_ptr(),
+                                                      ld.data_ptr(), None, None, 0, st)))
+        t_grad = windows(lambda: _lib.check(lib.nf_nll_grad(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), None, nll.data_ptr(),
+                                                            gx.data_ptr(), gy.data_ptr(), st)))
+        n_cpl = FULL_ARCH.split("|").count("unc")
+        flop = 2.0 * (18 * width + width * width + 36 * width) * 1024 * n_cpl * B   # one coupling-CNN evaluation of every coupling and patch
+        r = {"B": B, "nll_ms": t_nll, "grad_ms": t_grad, "nll_median_ms": t_nll[1], "grad_median_ms": t_grad[1],
+             "grad_spread_ms": t_grad[2] - t_grad[0], "nll_spread_ms": t_nll[2] - t_nll[0], "grad_patches_per_s": B / t_grad[1] * 1e3,
+             "nll_patches_per_s": B / t_nll[1] * 1e3, "grad_over_nll": t_grad[1] / t_nll[1],
+             "grad_fraction_of_fp32_matrix_peak": EVALS * flop / (t_grad[1] * 1e-3) / PEAK, "nll_fraction_of_fp32_matrix_peak": flop / (t_nll[1] * 1e-3) / PEAK,
+             "workspace_bytes": int(lib.nf_workspace_bytes(h, 2, B))}
+        out["w%d" % width] = r
+        print("width %d, 32x32 x %d  nf_nll %.4f ms (spread %.4f, %.3f of peak)   nf_nll_grad (GEMM) %.4f ms (spread %.4f)  %.3e patches/s   "
+              "ratio %.2f   %.3f of the fp32 matrix peak at %d evaluations per coupling   gate scratch %.1f MiB"
+              % (width, B, t_nll[1], r["nll_spread_ms"], r["nll_fraction_of_fp32_matrix_peak"], t_grad[1], r["grad_spread_ms"], r["grad_patches_per_s"],
+                 r["grad_over_nll"], r["grad_fraction_of_fp32_matrix_peak"], EVALS, r["workspace_bytes"] / 2.0 ** 20), flush=True)
+        del m, x, y, gx, gy
     return out
 
 
