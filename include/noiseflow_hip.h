@@ -154,6 +154,11 @@ typedef struct nf_config {
                               every H, W <= 32: the GEMM gradient kernel (csrc/nf_grad_gemm.hip, NF_GRAD_PATH_GEMM) and its weight
                               image, uploaded by nf_create.  fp32 handles only.  No effect on nf_nll, nf_sample, nf_kernel_path,
                               nor on widths up to 32 (the other gradient flags keep their meaning there).  (Bit 8 is not assigned.) */
+#define NF_CFG_GRAD_TILED_GEMM 128 /* nf_nll_grad at coupling widths 33 .. 512 on every H, W up to NF_MAX_IMAGE_SIDE: everything
+                              NF_CFG_GRAD_GEMM does (shapes up to 32x32 held whole by the GEMM gradient kernel, bit for bit), and every
+                              other shape on overlapping 32-pixel tiles of that kernel, the program cut into segments
+                              (NF_GRAD_PATH_TILED_GEMM).  No effect at widths up to 32; NF_CFG_FP16_CNN handles stay refused;
+                              NF_CFG_GRAD_GEMM with NF_CFG_GRAD_TILED / _TILED_WIDE but without this bit stays refused beyond 32x32. */
 
 /* Per-call conditioning: ONE value per call, not per patch — the reference
  * feeds length-1 lists (MiniBatchSampler.py:61-64, NoiseFlowWrapper.py:85-86).
@@ -301,14 +306,20 @@ int nf_sample_percond(nf_handle *h, const float *y, const float *eps, uint64_t s
  * those of NF_GRAD_PATH_TILED.
  * With NF_CFG_GRAD_GEMM, coupling widths 33 .. 512 run the same contract as GEMMs on v_mfma_f32_32x32x2_f32 (csrc/nf_grad_gemm.hip,
  * NF_GRAD_PATH_GEMM): whole patches of every H, W <= 32, at most 32 couplings, the whole layer vocabulary, cond or rows, any subset
- * of the outputs.  There is no tile mode at these widths: H or W > 32 is NF_EINVAL with or without NF_CFG_GRAD_TILED /
- * NF_CFG_GRAD_TILED_WIDE, and so is NF_CFG_FP16_CNN.  The ReLU gates of a patch (2 x the padded width bits per pixel and coupling:
+ * of the outputs.  Under this flag alone there is no tile mode at these widths: H or W > 32 is NF_EINVAL with or without
+ * NF_CFG_GRAD_TILED / NF_CFG_GRAD_TILED_WIDE, and so is NF_CFG_FP16_CNN.  The ReLU gates of a patch (2 x the padded width bits per pixel and coupling:
  * 128 KiB per coupling on a 32x32 patch at width 512) do not fit the LDS; they are stored in device scratch, one record per
  * WORKGROUP of the launch (one workgroup per CU, never more than B), taken from the handle's workspace set like the scratch of the
  * tiled paths: one buffer per call in flight, allocated only when a call needs more than any earlier one
  * (nf_workspace_bytes(h, 2, B), nf_reserve_grad_workspace make it allocation-free); everything else is enqueued.  Without the
  * flag these widths stay refused.
- * Not covered: tiles beyond 32x32 at widths beyond 32, NF_CFG_FP16_CNN, batch-statistics mode, and host-fed variants. */
+ * With NF_CFG_GRAD_TILED_GEMM, widths 33 .. 512 have the tile mode of the other widths on the GEMM kernel (NF_GRAD_PATH_TILED_GEMM): a
+ * shape of up to 32x32 stays NF_GRAD_PATH_GEMM, program, block and output bits unchanged; every other shape up to NF_MAX_IMAGE_SIDE
+ * per side runs segment by segment (at most 3 couplings each) on min(H,32) x min(W,32) tiles of csrc/nf_grad_gemm.hip.  Plan,
+ * outputs and conditioning are those of NF_GRAD_PATH_TILED; the workspace buffer of a call holds, behind the tile sums, the kept
+ * tensors and the two gradient tensors, one gate record per workgroup of the largest backward launch, sized for the couplings of
+ * the largest SEGMENT on one tile, not for the model.
+ * Not covered: NF_CFG_FP16_CNN, batch-statistics mode, and host-fed variants. */
 int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const nf_cond *cond,
                 const nf_cond_row *rows, float *nll_out, float *gx_out, float *gy_out, void *stream);
 
@@ -325,9 +336,10 @@ int nf_grad_supported(const nf_config *cfg, const nf_layer_desc *layers, const f
 #define NF_GRAD_PATH_TILED 2    /* NF_CFG_GRAD_TILED: nf_grad_kernel on 32-pixel tiles, one launch per segment */
 #define NF_GRAD_PATH_TILED_WIDE32 3   /* NF_CFG_GRAD_TILED_WIDE: nf_grad_wide_kernel on 32-pixel tiles, one launch per segment */
 #define NF_GRAD_PATH_GEMM 4     /* NF_CFG_GRAD_GEMM: nf_grad_gemm_kernel (csrc/nf_grad_gemm.hip), coupling widths 33 .. 512 */
+#define NF_GRAD_PATH_TILED_GEMM 5   /* NF_CFG_GRAD_TILED_GEMM: nf_grad_gemm_kernel on 32-pixel tiles, one launch per segment */
 int nf_grad_path(const nf_handle *h);
 
-/* How nf_nll_grad cuts a model under NF_CFG_GRAD_TILED (or, at widths 17 .. 32, NF_CFG_GRAD_TILED_WIDE), in the format of nf_tile_segments: returns the number of segments (0:
+/* How nf_nll_grad cuts a model under NF_CFG_GRAD_TILED (or, at widths 17 .. 32, NF_CFG_GRAD_TILED_WIDE; at widths 33 .. 512, NF_CFG_GRAD_TILED_GEMM), in the format of nf_tile_segments: returns the number of segments (0:
  * the shape is held whole by a whole-patch kernel; negative: NF_E*, e.g. what nf_grad_supported refuses) and for i < cap
  * out5[5 i ..] = first op, one-past-last op, GRADIENT halo (4 x the segment's couplings), tiles along H, tiles along W of the
  * backward launch (tiles of min(H,32) x min(W,32)).  Host arithmetic only.  NF_GRAD_TILE_SEGMENTS=<n> in the environment, read
@@ -337,7 +349,7 @@ int nf_grad_tile_segments(const nf_config *cfg, const nf_layer_desc *layers, con
 
 /* Host-only: the program and parameter block nf_nll_grad would run for this model ("gradient block": A^-1 beside every 1x1
  * matrix, 1/s beside every scale; couplings in the generic layout or, *path == NF_GRAD_PATH_WIDE32 / _TILED_WIDE32, in the fetch-order layout of
- * csrc/nf_device.h, NFGW_*; *path == NF_GRAD_PATH_GEMM: in that of csrc/nf_gemm_layout.h, NFGG_*, the program's width being the padded
+ * csrc/nf_device.h, NFGW_*; *path == NF_GRAD_PATH_GEMM / _TILED_GEMM: in that of csrc/nf_gemm_layout.h, NFGG_*, the program's width being the padded
  * one).  Argument style and sizing protocol of nf_fold_layout. */
 int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params, int32_t *path,
                  int32_t *ops_out, int32_t ops_cap, int32_t *n_ops, float *folded, size_t folded_cap, size_t *n_folded);
@@ -579,8 +591,8 @@ int nf_batchstats_route(const nf_handle *h);
  * images allocates anything.  No reference counterpart (TF sizes its arena inside sess.run). */
 int64_t nf_workspace_bytes(const nf_handle *h, int32_t direction, int64_t B);   /* direction 2: one tiled nf_nll_grad call */
 int nf_reserve_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
-/* the same for nf_nll_grad under NF_CFG_GRAD_TILED / NF_CFG_GRAD_TILED_WIDE (nothing to do for a handle whose shape is held whole)
- * and for the gate records of NF_GRAD_PATH_GEMM */
+/* the same for nf_nll_grad under NF_CFG_GRAD_TILED / NF_CFG_GRAD_TILED_WIDE / NF_CFG_GRAD_TILED_GEMM (nothing to do for a handle whose
+ * shape is held whole) and for the gate records of NF_GRAD_PATH_GEMM; NF_GRAD_PATH_TILED_GEMM keeps both in the one buffer */
 int nf_reserve_grad_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
 
 /* Host-only: the SDN5 scalars the kernels receive for a given (iso, cam):

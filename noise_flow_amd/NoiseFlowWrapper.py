@@ -54,7 +54,7 @@ class NoiseFlowWrapper:
         self.binding = binding
         self.device = device
         self.grad_kernel = grad_kernel   # 'scalar' | 'mfma' | 'gemm' (NoiseFlow); None: hps.grad_kernel, else 'scalar'
-        self.grad_tiles = grad_tiles     # True: input gradients of images beyond 64x64 (NoiseFlow; with grad_kernel='mfma' also at widths 17 .. 32); None: hps.grad_tiles, else False
+        self.grad_tiles = grad_tiles     # True: input gradients of images beyond 64x64 (NoiseFlow; with grad_kernel='mfma' also at widths 17 .. 32, with grad_kernel='gemm' beyond 32x32 at widths 33 .. 512); None: hps.grad_tiles, else False
         self.hps = self.hps_loader(os.path.join(self.nf_path, "hps.txt"))
         if seed is not None:
             self.hps.seed = seed

@@ -28,6 +28,7 @@ NF_CFG_GRAD_MFMA = 4
 NF_CFG_GRAD_TILED = 16   # (bit 8 is not assigned)
 NF_CFG_GRAD_TILED_WIDE = 32   # widths 17 .. 32: everything NF_CFG_GRAD_MFMA does, plus tiles of its kernel beyond 32x32
 NF_CFG_GRAD_GEMM = 64   # widths 33 .. 512: the GEMM gradient kernel, whole patches up to 32x32
+NF_CFG_GRAD_TILED_GEMM = 128   # widths 33 .. 512: everything NF_CFG_GRAD_GEMM does, plus tiles of its kernel beyond 32x32
 
 NF_ACCUMULATE = 1
 NF_NO_PRIOR = 2
@@ -213,6 +214,7 @@ EXPORTED_SYMBOLS = (
     "nf_nll_grad", "nf_grad_supported", "nf_grad_path", "nf_grad_fold", "nf_grad_tile_segments", "nf_reserve_grad_workspace",
 )
 NF_GRAD_PATH_SCALAR, NF_GRAD_PATH_WIDE32, NF_GRAD_PATH_TILED, NF_GRAD_PATH_TILED_WIDE32, NF_GRAD_PATH_GEMM = 0, 1, 2, 3, 4
+NF_GRAD_PATH_TILED_GEMM = 5
 NF_PATH_SCALAR, NF_PATH_MFMA4, NF_PATH_FP16, NF_PATH_WIDE32, NF_PATH_WIDE16, NF_PATH_WIDE32_FP16, NF_PATH_GEMM, NF_PATH_GEMM_FP16 = 0, 1, 2, 3, 4, 5, 6, 7
 NF_PATH_SPLIT_BF16 = 8
 NF_BS_ROUTE_MFMA4, NF_BS_ROUTE_SCALAR, NF_BS_ROUTE_TRAINER = 0, 1, 2

@@ -79,6 +79,8 @@ __host__ __device__ constexpr int nf10_cpl_size(int wp) { return 68 + nf10_img_s
 // wavefronts along the channel axis meet in the same region: NFGG_D_STRIDE floats per pixel, [2 tap + ch].
 // Gate record: the sign of every D register of h1 (layer 0) and h2 (layer 1), 16 bits per lane and tile, in DEVICE SCRATCH per
 // workgroup: uint16 [coupling][band][layer][tile = 32 of (m, nt)][lane] = 8 KiB per coupling and band — 2 WP bits per pixel.
+// On gradient tiles (NF_CFG_GRAD_TILED_GEMM, the TILED instantiations) a launch is one segment on min(H,32) x min(W,32) tiles: the
+// record of a workgroup then holds the couplings of the call's largest SEGMENT on one tile, the same function below sizing it.
 #define NFGG_CPL_E 0
 #define NFGG_CPL_S 64
 #define NFGG_CPL_FWD 68

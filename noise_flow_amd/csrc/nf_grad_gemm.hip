@@ -17,6 +17,8 @@
 //                   records are summed by the scatter-gather of the nine taps into g0.
 // 'SAME' padding: the zero borders of the two tiles and the bounds checks of the two gathers.  The border table E is constant and has
 // no gradient.  Everything in front of the first coupling is computed forward from the loaded x.
+// Beyond 32x32 (NF_CFG_GRAD_TILED_GEMM) the TILED instantiations run the same sweeps on one tile of an image and one segment of the
+// program per launch patch, as nf_grad_wide_kernel<.., TILED> does at width 32.
 // Weights are not staged in LDS at any width: the band takes 128 KiB of the CU's 160, every weight is consumed by exactly one
 // wavefront of the workgroup, and at widths 64 / 128 a coupling's block (66 / 195 KiB) is L2-resident like the 2.3 MiB at 512.
 #include <hip/hip_runtime.h>
@@ -84,7 +86,12 @@ __device__ __forceinline__ void gg_l2(v16f (&acc)[2][2], const float *ap0, const
 
 //   WP       padded coupling width: 64, 128, 256, 512
 //   scratch  the gate records of the launch, `scratch_halves` uint16 per workgroup (nfgg_gate_halves)
-template <int WP>
+//   TILED    NF_CFG_GRAD_TILED_GEMM (nf_device.h, "gradient tiles"), the contract of nf_grad_wide_kernel<.., TILED>: a "patch" of the
+//            launch is one H x W tile of an img_H x img_W image and `prog` one segment.  Addresses and the index into the border table
+//            E follow the IMAGE (recomputed from the tile's origin where they are used); the zero borders of the two LDS tiles and
+//            the bounds checks of the gathers stay the TILE's — a tile is evaluated on its own, the wrong terms stay inside the
+//            halo — and only the core window is stored.  nll_b is not formed here.  The gate record is one segment's.
+template <int WP, bool TILED = false>
 __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, const NfGradLaunch a, uint16_t *const scratch, const size_t scratch_halves)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -131,12 +138,43 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
 
     const int n_ops = prog.n_ops;
     const int first_cpl = a.first_cpl;
+    // TILED: where the tile of the current launch patch sits in its image (wave-uniform), and what follows from it per owned pixel
+    [[maybe_unused]] int oy = 0, ox = 0, cy0 = 0, cy1 = 0, cx0 = 0, cx1 = 0;
+    auto gidx_of = [&](int m) {   // the pixel's index in the patch's / image's tensors (act[m] pixels only)
+        if constexpr (TILED) return (oy + pr[m]) * a.img_W + ox + pc[m];
+        else return t + GT * m;
+    };
+    auto bmask_of = [&](int m) {
+        if constexpr (TILED) {
+            const int R = oy + pr[m], C = ox + pc[m];
+            return act[m] ? ((R == 0 ? 1 : 0) | (R == a.img_H - 1 ? 2 : 0) | (C == 0 ? 4 : 0) | (C == a.img_W - 1 ? 8 : 0)) : 0;
+        } else {
+            return bmask[m];
+        }
+    };
+    [[maybe_unused]] auto own_of = [&](int m) {   // TILED: the pixel is in the tile's core window
+        const int R = oy + pr[m], C = ox + pc[m];
+        return act[m] && R >= cy0 && R < cy1 && C >= cx0 && C < cx1;
+    };
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const size_t patch_off = (size_t)b * (size_t)HW;
-        const float4 *const x4 = reinterpret_cast<const float4 *>(a.x) + patch_off;
+        int64_t img = b;
+        if constexpr (TILED) {   // tile b % tiles of image b / tiles (nf_device.h, "overlapping tiles")
+            const int nt = a.tile_ny * a.tile_nx;
+            img = b / nt;
+            const int ti = (int)(b - img * nt);
+            const int ty = ti / a.tile_nx, tx = ti - ty * a.tile_nx;
+            oy = nf_tile_origin(ty, a.img_H, H, a.tile_halo);
+            ox = nf_tile_origin(tx, a.img_W, W, a.tile_halo);
+            cy0 = nf_tile_core0(ty, a.img_H, H, a.tile_halo);
+            cy1 = nf_tile_core1(ty, a.tile_ny, a.img_H, H, a.tile_halo);
+            cx0 = nf_tile_core0(tx, a.img_W, W, a.tile_halo);
+            cx1 = nf_tile_core1(tx, a.tile_nx, a.img_W, W, a.tile_halo);
+        }
+        const size_t patch_off = TILED ? (size_t)img * (size_t)a.img_H * (size_t)a.img_W : (size_t)b * (size_t)HW;
+        const float4 *const x4 = reinterpret_cast<const float4 *>(TILED ? a.z_in : a.x) + patch_off;
         const float4 *const y4 = reinterpret_cast<const float4 *>(a.y) + patch_off;   // (not dereferenced when a.y is null)
-        const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + b;
+        const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + img;
         auto cond_a = [&](int slot) { return a.cond_rows ? crow->a[slot & 3] : a.cond_a[slot & 3]; };
         auto cond_b = [&](int slot) { return a.cond_rows ? crow->b[slot & 3] : a.cond_b[slot & 3]; };
 
@@ -144,7 +182,7 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
 #pragma unroll
             for (int m = 0; m < OWN; ++m) {
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (act[m]) v = x4[t + GT * m];
+                if (act[m]) v = x4[gidx_of(m)];
                 z[m][0] = v.x; z[m][1] = v.y; z[m][2] = v.z; z[m][3] = v.w;
             }
         };
@@ -152,7 +190,7 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
 #pragma unroll
             for (int m = 0; m < OWN; ++m) {
                 float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
-                if (act[m]) v = y4[t + GT * m];
+                if (act[m]) v = y4[gidx_of(m)];
                 yy[m][0] = v.x; yy[m][1] = v.y; yy[m][2] = v.z; yy[m][3] = v.w;
             }
         };
@@ -350,7 +388,7 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
             }
 #pragma unroll
             for (int m = 0; m < OWN; ++m) {
-                const float4 eb = *reinterpret_cast<const float4 *>(a.params + off + NFGG_CPL_E + 4 * bmask[m]);
+                const float4 eb = *reinterpret_cast<const float4 *>(a.params + off + NFGG_CPL_E + 4 * bmask_of(m));
                 o[m][0] += eb.x; o[m][1] += eb.y; o[m][2] += eb.z; o[m][3] += eb.w;
             }
         };
@@ -499,7 +537,7 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
             }
         }
         // nll_b = -(log-det) + prior, as nf_flow_kernel forms it
-        if (a.nll_out) {
+        if (!TILED && a.nll_out) {
             float s2 = 0.f;
 #pragma unroll
             for (int m = 0; m < OWN; ++m)
@@ -537,6 +575,17 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
                 gz[m][q] = z[m][q];
                 gy[m][q] = 0.0f;
             }
+        if constexpr (TILED) {
+            if (a.g_in) {   // not the last segment: the gradient the segment behind this one stored, whole tile
+                const float4 *const g4 = reinterpret_cast<const float4 *>(a.g_in) + patch_off;
+#pragma unroll
+                for (int m = 0; m < OWN; ++m) {
+                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (act[m]) v = g4[gidx_of(m)];
+                    gz[m][0] = v.x; gz[m][1] = v.y; gz[m][2] = v.z; gz[m][3] = v.w;
+                }
+            }
+        }
         int cidx = 0;
         for (int op = 0; op < n_ops; ++op) cidx += prog.ops[op].type == NF_OP_COUPLING_FWD ? 1 : 0;
         for (int op = n_ops - 1; op >= 0; --op) {
@@ -640,22 +689,47 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
             }
         }
 
-        if (a.gx_out) {
-            float4 *const o4 = reinterpret_cast<float4 *>(a.gx_out) + patch_off;
+        if constexpr (TILED) {
+            // the core window only; every pixel of the image is in exactly one tile's core, so an accumulating launch adds to gy
+            // without atomics (the launch that wrote it is ahead of this one in the stream)
+            if (a.g_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.g_out) + patch_off;
 #pragma unroll
-            for (int m = 0; m < OWN; ++m)
-                if (act[m]) o4[t + GT * m] = make_float4(gz[m][0], gz[m][1], gz[m][2], gz[m][3]);
-        }
-        if (a.gy_out) {
-            float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+                for (int m = 0; m < OWN; ++m)
+                    if (own_of(m)) o4[gidx_of(m)] = make_float4(gz[m][0], gz[m][1], gz[m][2], gz[m][3]);
+            }
+            if (a.gy_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+                const bool acc = (a.tflags & NF_GT_GY_ACC) != 0;
 #pragma unroll
-            for (int m = 0; m < OWN; ++m)
-                if (act[m]) o4[t + GT * m] = make_float4(gy[m][0], gy[m][1], gy[m][2], gy[m][3]);
+                for (int m = 0; m < OWN; ++m)
+                    if (own_of(m)) {
+                        float4 v = make_float4(gy[m][0], gy[m][1], gy[m][2], gy[m][3]);
+                        if (acc) {
+                            const float4 p = o4[gidx_of(m)];
+                            v = make_float4(p.x + v.x, p.y + v.y, p.z + v.z, p.w + v.w);
+                        }
+                        o4[gidx_of(m)] = v;
+                    }
+            }
+        } else {
+            if (a.gx_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gx_out) + patch_off;
+#pragma unroll
+                for (int m = 0; m < OWN; ++m)
+                    if (act[m]) o4[t + GT * m] = make_float4(gz[m][0], gz[m][1], gz[m][2], gz[m][3]);
+            }
+            if (a.gy_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+#pragma unroll
+                for (int m = 0; m < OWN; ++m)
+                    if (act[m]) o4[t + GT * m] = make_float4(gy[m][0], gy[m][1], gy[m][2], gy[m][3]);
+            }
         }
     }
 }
 
-template <int WP>
+template <int WP, bool TILED = false>
 hipError_t launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, int groups, size_t lds, uint16_t *scratch, size_t scratch_halves, hipStream_t stream)
 {
     // dynamic LDS beyond 64 KiB is a per-device function attribute: always the CU's whole 160 KiB, set once per device
@@ -664,11 +738,11 @@ hipError_t launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, int gr
     (void)hipGetDevice(&dev);
     const uint32_t bit = 1u << (dev & 31);
     if (!(done.load(std::memory_order_relaxed) & bit) || dev > 31) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&nf_grad_gemm_kernel<WP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLOW_LDS_MAX);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&nf_grad_gemm_kernel<WP, TILED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLOW_LDS_MAX);
         if (e != hipSuccess) return e;
         done.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(nf_grad_gemm_kernel<WP>, dim3((unsigned)groups), dim3(GT), lds, stream, prog, a, scratch, scratch_halves);
+    hipLaunchKernelGGL((nf_grad_gemm_kernel<WP, TILED>), dim3((unsigned)groups), dim3(GT), lds, stream, prog, a, scratch, scratch_halves);
     return hipGetLastError();
 }
 
@@ -700,5 +774,31 @@ hipError_t nf_launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, int
     case 128: return launch_grad_gemm<128>(prog, a, groups, lds, s, halves, stream);
     case 256: return launch_grad_gemm<256>(prog, a, groups, lds, s, halves, stream);
     default: return launch_grad_gemm<512>(prog, a, groups, lds, s, halves, stream);
+    }
+}
+
+// one segment of a tiled call (NF_CFG_GRAD_TILED_GEMM): `prog` = the segment's ops, a.H x a.W = the tile, a.B = images x tiles,
+// n_cpl = the couplings of the call's largest segment: `scratch` holds nf_grad_gemm_groups(a.B, n_cu) x nfgg_gate_halves(H W, width,
+// n_cpl) uint16.  A segment with more couplings than that, or a buffer too small, is refused before anything is enqueued.
+hipError_t nf_launch_grad_gemm_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes, hipStream_t stream)
+{
+    const int wp = prog.width;
+    if ((wp != 64 && wp != 128 && wp != 256 && wp != 512) || a.H < 1 || a.W < 1 || a.H > NF_GRAD_TILE || a.W > NF_GRAD_TILE || a.H > a.img_H ||
+        a.W > a.img_W || a.tile_ny < 1 || a.tile_nx < 1 || a.tile_halo < 0 || !a.z_in || n_cpl < 0 || n_cpl > NFGG_MAX_COUPLINGS)
+        return hipErrorInvalidValue;
+    int seg_cpl = 0;
+    for (int i = 0; i < prog.n_ops; ++i) seg_cpl += prog.ops[i].type == NF_OP_COUPLING_FWD ? 1 : 0;
+    if (seg_cpl > n_cpl) return hipErrorInvalidValue;
+    const int groups = nf_grad_gemm_groups(a.B, n_cu);
+    const size_t halves = nfgg_gate_halves(a.H * a.W, wp, n_cpl);
+    if (halves && (!scratch || scratch_bytes < (size_t)groups * halves * sizeof(uint16_t))) return hipErrorInvalidValue;
+    const size_t lds = sizeof(float) * nfgg_lds_floats(a.H, a.W);
+    if (lds > FLOW_LDS_MAX) return hipErrorInvalidValue;
+    uint16_t *const s = static_cast<uint16_t *>(scratch);
+    switch (wp) {
+    case 64: return launch_grad_gemm<64, true>(prog, a, groups, lds, s, halves, stream);
+    case 128: return launch_grad_gemm<128, true>(prog, a, groups, lds, s, halves, stream);
+    case 256: return launch_grad_gemm<256, true>(prog, a, groups, lds, s, halves, stream);
+    default: return launch_grad_gemm<512, true>(prog, a, groups, lds, s, halves, stream);
     }
 }

@@ -52,6 +52,7 @@ hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int
 hipError_t nf_launch_grad_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 hipError_t nf_launch_grad_wide_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
 hipError_t nf_launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t nf_launch_grad_gemm_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes, hipStream_t stream);
 int nf_grad_gemm_groups(int64_t B, int n_cu);
 
 namespace {
@@ -680,6 +681,13 @@ struct Built {
 // x 8 couplings at 256^2 x 16 and 64^2 x 1 024, unforced and S = 8 / 4 / 3), which is what keeps it.  Least squares over the six forced
 // arms gives 199.6 ns per tile-coupling and -6.3 ns per tile with residuals up to 21 %: a tile of a 3-coupling segment costs more than
 // three one-coupling tiles (80.6 KiB of LDS: one workgroup per CU instead of two), which two terms cannot say.
+// Widths 33 .. 512 on tiles (NF_CFG_GRAD_TILED_GEMM, nf_grad_gemm_kernel<.., TILED>): kGradGemmSegs, the same tiles, halo, switch and
+// limit of 3 couplings per segment.  Its per-tile constant is measured (tools/time_nll_grad.py --legs tiled_gemm,
+// profiles/nll_grad_tiled_gemm.txt: 8 couplings at widths 64 / 128 / 512 on 64^2 x 256 and 256^2 x 16, unforced and S = 8 .. 3): least
+// squares over the twelve forced arms of a width gives 558 / 1 369 / 13 420 ns per tile-coupling and 205 / 544 / 5 103 ns per tile — a
+// tile costs its couplings + 0.37 / 0.40 / 0.38 at the three widths (residuals up to 16 %: the launches of 256^2 x 16 fill the 256
+// CUs less evenly than those of 64^2 x 256, which two terms cannot say), no boundary cost these runs resolve.  With 0.38 the unforced
+// plan is the fastest measured arm, or within the spread of the repeated timings of it, at every width and on both workloads.
 struct SegRule {
     const char *env;       // forces S
     int tile;              // tile side the core must fit
@@ -692,6 +700,7 @@ struct SegRule {
 static const SegRule kFwdSegs = {"NF_TILE_SEGMENTS", 64, 2, 0.75, 1.0 / 4096.0, "patches beyond 64x64"};
 static const SegRule kGradSegs = {"NF_GRAD_TILE_SEGMENTS", NF_GRAD_TILE, 4, 1.57, 0.0, "nf_nll_grad on tiles"};
 static const SegRule kGradWideSegs = {"NF_GRAD_TILE_SEGMENTS", NF_GRAD_TILE, 4, 1.57, 0.0, "nf_nll_grad on tiles at coupling width 32", 3};   // 3: the gate record of a 32x32 tile beside the rest, and 32 - 2 x 12 = 8 core pixels
+static const SegRule kGradGemmSegs = {"NF_GRAD_TILE_SEGMENTS", NF_GRAD_TILE, 4, 0.38, 0.0, "nf_nll_grad on tiles at coupling widths beyond 32", 3};   // 3: 32 - 2 x 12 = 8 core pixels
 static int plan_tile_segments(const NfProgram &prog, int H, int W, int th, int tw, std::vector<Built::TileSeg> &segs, const SegRule &rule = kFwdSegs)
 {
     std::vector<int> cpl;
@@ -779,7 +788,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     out.tile_w = tw;
     out.segs.clear();
     if (cfg->n_layers < 1) return fail(NF_EINVAL, "n_layers must be >= 1");
-    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE | NF_CFG_GRAD_GEMM)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
+    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE | NF_CFG_GRAD_GEMM | NF_CFG_GRAD_TILED_GEMM)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
     const double HW = (double)cfg->height * cfg->width;
 
     // intermediate list in NLL order
@@ -1027,19 +1036,21 @@ bool grad_force_scalar()
 
 // THE place that decides what nf_nll_grad supports and which kernel runs it (`path`: NF_GRAD_PATH_*): `fwd` = the NLL-direction
 // program of the model.
-// `tiles` (NF_GRAD_PATH_TILED and NF_GRAD_PATH_TILED_WIDE32 only): the segments of the tiled route, gradient halos and the backward
+// `tiles` (NF_GRAD_PATH_TILED, NF_GRAD_PATH_TILED_WIDE32 and NF_GRAD_PATH_TILED_GEMM only): the segments of the tiled route, gradient halos and the backward
 // launches' tile counts.
 int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, std::vector<Built::TileSeg> *tiles = nullptr)
 {
     if (path) *path = NF_GRAD_PATH_SCALAR;
     if (tiles) tiles->clear();
     // NF_CFG_GRAD_GEMM: coupling widths beyond 32 — and nothing else — on the GEMM gradient kernel (nf_grad_gemm.hip): whole patches of
-    // up to 32x32, fp32 handles, no tile mode whatever the tile flags say
-    if ((cfg->flags & NF_CFG_GRAD_GEMM) && fwd.lay[NF_PATH_SCALAR].prog.width > 32) {
+    // up to 32x32, fp32 handles, no tile mode whatever the other tile flags say.  NF_CFG_GRAD_TILED_GEMM: all of that, and every other
+    // shape on 32-pixel tiles of the same kernel, one launch per segment (kGradGemmSegs)
+    if ((cfg->flags & (NF_CFG_GRAD_GEMM | NF_CFG_GRAD_TILED_GEMM)) && fwd.lay[NF_PATH_SCALAR].prog.width > 32) {
         const NfProgram &gprog = fwd.lay[NF_PATH_SCALAR].prog;
+        const bool gemm_tiles = (cfg->flags & NF_CFG_GRAD_TILED_GEMM) != 0;
         if (cfg->flags & NF_CFG_FP16_CNN)
             return fail(NF_EINVAL, "nf_nll_grad: coupling width %d under NF_CFG_GRAD_GEMM takes fp32 handles only (NF_CFG_FP16_CNN is set)", fwd.raw_width);
-        if (cfg->height > 32 || cfg->width > 32)
+        if ((cfg->height > 32 || cfg->width > 32) && !gemm_tiles)
             return fail(NF_EINVAL, "nf_nll_grad: coupling width %d under NF_CFG_GRAD_GEMM covers whole patches of up to 32x32 (%dx%d given; no tile mode at "
                                    "widths beyond 32, with or without NF_CFG_GRAD_TILED / NF_CFG_GRAD_TILED_WIDE)", fwd.raw_width, cfg->height, cfg->width);
         int n_gc = 0;
@@ -1047,6 +1058,15 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
         if (n_gc > NFGG_MAX_COUPLINGS)
             return fail(NF_EINVAL, "nf_nll_grad: at most %d couplings at coupling width %d under NF_CFG_GRAD_GEMM (%d given): the gate record in device "
                                    "scratch", NFGG_MAX_COUPLINGS, fwd.raw_width, n_gc);
+        if (cfg->height > 32 || cfg->width > 32) {
+            std::vector<Built::TileSeg> segs;
+            const int th = cfg->height < NF_GRAD_TILE ? cfg->height : NF_GRAD_TILE, tw = cfg->width < NF_GRAD_TILE ? cfg->width : NF_GRAD_TILE;
+            const int rc = plan_tile_segments(gprog, cfg->height, cfg->width, th, tw, segs, kGradGemmSegs);
+            if (rc != NF_OK) return rc;
+            if (path) *path = NF_GRAD_PATH_TILED_GEMM;
+            if (tiles) tiles->swap(segs);
+            return NF_OK;
+        }
         if (path) *path = NF_GRAD_PATH_GEMM;
         return NF_OK;
     }
@@ -1113,9 +1133,11 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
     return NF_OK;
 }
 
-// the paths whose couplings are in the NFGW_* layout (the matrix-core kernel, whole patches or tiles); the tiled paths
+// the paths whose couplings are in the NFGW_* layout (the matrix-core kernel, whole patches or tiles); those in the NFGG_* layout
+// (the GEMM kernel, likewise); the tiled paths
 static bool grad_path_is_wide(int path) { return path == NF_GRAD_PATH_WIDE32 || path == NF_GRAD_PATH_TILED_WIDE32; }
-static bool grad_path_is_tiled(int path) { return path == NF_GRAD_PATH_TILED || path == NF_GRAD_PATH_TILED_WIDE32; }
+static bool grad_path_is_gemm(int path) { return path == NF_GRAD_PATH_GEMM || path == NF_GRAD_PATH_TILED_GEMM; }
+static bool grad_path_is_tiled(int path) { return path == NF_GRAD_PATH_TILED || path == NF_GRAD_PATH_TILED_WIDE32 || path == NF_GRAD_PATH_TILED_GEMM; }
 
 // One coupling of the wide gradient block (nf_device.h, NFGW_*) from its generic block at width 32: the NF4_IMG_* image of the
 // forward chain without the 2 log2(e) factor, and the fetch-order images of the three transposed products.
@@ -1190,11 +1212,11 @@ void relayout_coupling_grad_gemm(const float *v1, int w, int wp, float *out)
 // The gradient block (nf_device.h, NfGradLaunch): the NLL-order generic block with A^-1 beside every 1x1 matrix — op i of
 // the NLL program is op n - 1 - i of the sampling program, whose block holds the inverse — and 1/s beside every scale.
 // (`fwd`, `rev` = the generic layouts of the two directions).  `path` (NF_GRAD_PATH_*, grad_support) decides the couplings' layout:
-// NFGW_* on the matrix-core paths at width 32 (nf_grad_wide.hip), NFGG_* at the padded width on NF_GRAD_PATH_GEMM (nf_grad_gemm.hip;
+// NFGW_* on the matrix-core paths at width 32 (nf_grad_wide.hip), NFGG_* at the padded width on NF_GRAD_PATH_GEMM / _TILED_GEMM (nf_grad_gemm.hip;
 // the program's width is then the padded one), the generic block otherwise.
 void build_grad_block(const Layout &fwd, const Layout &rev, int path, NfProgram &gp, std::vector<float> &blk, int &n_cpl, int &first_cpl)
 {
-    const bool wide = grad_path_is_wide(path), gemm = path == NF_GRAD_PATH_GEMM;
+    const bool wide = grad_path_is_wide(path), gemm = grad_path_is_gemm(path);
     memset(&gp, 0, sizeof(gp));
     gp.width = gemm ? nf7_pad_width(fwd.prog.width) : fwd.prog.width;
     gp.n_ops = fwd.prog.n_ops;
@@ -1321,7 +1343,7 @@ struct nf_handle {
     int grad_rc = NF_EINVAL;
     int grad_path = NF_GRAD_PATH_SCALAR;   // NF_GRAD_PATH_*: which kernel nf_nll_grad launches (grad_support)
     std::string grad_why;
-    std::vector<Built::TileSeg> grad_segs;   // NF_GRAD_PATH_TILED / _TILED_WIDE32: the segments (gradient halo, tiles of the backward launches)
+    std::vector<Built::TileSeg> grad_segs;   // NF_GRAD_PATH_TILED / _TILED_WIDE32 / _TILED_GEMM: the segments (gradient halo, tiles of the backward launches)
     int grad_seg_cpl = 0;                    // ... and the couplings of the largest one (sizes the gate record)
     // scratch of the tiled calls (images beyond 64x64): the per-tile sums and the tensors between two segments.  A small set of
     // device buffers owned by the handle, one per call in flight; a call takes a free one (waiting, on ITS stream, for the work
@@ -2060,7 +2082,7 @@ int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float 
     return export_layout(l, ops_out, ops_cap, n_ops, folded, folded_cap, n_folded);
 }
 
-// ---- nf_nll_grad on tiles (NF_CFG_GRAD_TILED, NF_CFG_GRAD_TILED_WIDE; nf_device.h, "gradient tiles") ----
+// ---- nf_nll_grad on tiles (NF_CFG_GRAD_TILED, NF_CFG_GRAD_TILED_WIDE, NF_CFG_GRAD_TILED_GEMM; nf_device.h, "gradient tiles") ----
 // The forward launch of segment s runs on the forward direction's own tiles (tile_h x tile_w, halo 2 per coupling)
 static Built::TileSeg grad_fwd_seg(const nf_handle *h, int s)
 {
@@ -2073,7 +2095,19 @@ static Built::TileSeg grad_fwd_seg(const nf_handle *h, int s)
 
 static size_t grad_img_bytes(const nf_handle *h, int64_t B) { return (((size_t)B * h->cfg.height * h->cfg.width * kC * sizeof(float)) + 255) & ~(size_t)255; }
 
-// scratch of one call: the forward launches' tile sums, the S - 1 tensors between two segments, two gradient tensors (ping-pong);
+// NF_GRAD_PATH_TILED_GEMM: the gate records of a call, one per WORKGROUP of its largest backward launch, each sized for the couplings
+// of the largest segment on one tile (nf_gemm_layout.h, nfgg_gate_halves: the function the kernel indexes by)
+static size_t grad_tiled_gate_bytes(const nf_handle *h, int64_t B)
+{
+    if (h->grad_path != NF_GRAD_PATH_TILED_GEMM) return 0;
+    int64_t most = 0;
+    for (const Built::TileSeg &g : h->grad_segs) most = std::max<int64_t>(most, B * g.ny * g.nx);
+    const int th = std::min(h->cfg.height, NF_GRAD_TILE), tw = std::min(h->cfg.width, NF_GRAD_TILE);
+    return ((size_t)nf_grad_gemm_groups(most, h->n_cu) * nfgg_gate_halves(th * tw, h->gprog.width, h->grad_seg_cpl) * sizeof(uint16_t) + 255) & ~(size_t)255;
+}
+
+// scratch of one call: the forward launches' tile sums, the S - 1 tensors between two segments, two gradient tensors (ping-pong),
+// NF_GRAD_PATH_TILED_GEMM: and the gate records behind them;
 // NF_GRAD_PATH_GEMM: the gate records of the launch's workgroups (nf_gemm_layout.h, NFGG_*)
 static size_t grad_workspace_bytes(const nf_handle *h, int64_t B)
 {
@@ -2088,12 +2122,13 @@ static size_t grad_workspace_bytes(const nf_handle *h, int64_t B)
         const Built::TileSeg f = grad_fwd_seg(h, s);
         part4 += (size_t)B * f.ny * f.nx;
     }
-    return ((part4 * 4 * sizeof(float) + 255) & ~(size_t)255) + grad_img_bytes(h, B) * (size_t)(S - 1 + (S - 1 < 2 ? S - 1 : 2));
+    return ((part4 * 4 * sizeof(float) + 255) & ~(size_t)255) + grad_img_bytes(h, B) * (size_t)(S - 1 + (S - 1 < 2 ? S - 1 : 2)) + grad_tiled_gate_bytes(h, B);
 }
 
 // Forward: the tiled launches of nf_nll cut at the gradient plan's boundaries, every tensor between two segments kept, and
 // nf_tile_combine for nll_out.  Backward: one launch of nf_grad_kernel<.., TILED> (NF_GRAD_PATH_TILED_WIDE32: of
-// nf_grad_wide_kernel<.., TILED>, over the same h->d_grad in its NFGW_* layout) per segment, last to first; segment s reads the
+// nf_grad_wide_kernel<.., TILED>, over the same h->d_grad in its NFGW_* layout; NF_GRAD_PATH_TILED_GEMM: of nf_grad_gemm_kernel<.., TILED>
+// over the NFGG_* layout, its gate records behind the tensors in the call's workspace buffer) per segment, last to first; segment s reads the
 // tensor in front of it and the gradient segment s + 1 stored, and stores core windows — to gx_out (s = 0) or to the other of two
 // scratch tensors.  gy_out: the first launch (in this order) whose segment has an SDN-kind op stores it, later ones add to it.
 // Everything is enqueued on `st`.
@@ -2124,6 +2159,12 @@ static int grad_tiled(nf_handle *h, const float *x, const float *y, int64_t B, c
     float *inter[NF_MAX_TILE_SEGS] = {}, *gbuf[2] = {nullptr, nullptr};
     for (int s = 0; s < S - 1; ++s, q += img_bytes) inter[s] = reinterpret_cast<float *>(q);
     for (int i = 0; i < 2 && i < S - 1; ++i, q += img_bytes) gbuf[i] = reinterpret_cast<float *>(q);
+    char *const gate_rec = q;   // NF_GRAD_PATH_TILED_GEMM: the gate records, the rest of the buffer
+    const size_t gate_room = wsp->bytes - (size_t)(q - wsp->p);
+    if (gate_room < grad_tiled_gate_bytes(h, B)) {   // refused before anything is enqueued (the launcher checks its own launch once more)
+        ws_release(h, wsp, st, false);
+        return fail(NF_EINVAL, "nf_nll_grad: the workspace buffer holds %zu bytes of gate records, the call needs %zu", gate_room, grad_tiled_gate_bytes(h, B));
+    }
 
     hipError_t e = hipSuccess;
     const int n_fwd = nll_out ? S : S - 1;   // the last segment's forward launch only leaves its tile sums
@@ -2154,8 +2195,8 @@ static int grad_tiled(nf_handle *h, const float *x, const float *y, int64_t B, c
         a.W = W < NF_GRAD_TILE ? W : NF_GRAD_TILE;
         a.img_H = H;
         a.img_W = W;
-        const bool wide = h->grad_path == NF_GRAD_PATH_TILED_WIDE32;
-        a.gate_words = wide ? nfgw_tpw(a.H) * h->grad_seg_cpl : nf_grad_gate_words(h->grad_seg_cpl, h->gprog.width);
+        const bool wide = h->grad_path == NF_GRAD_PATH_TILED_WIDE32, gemm = h->grad_path == NF_GRAD_PATH_TILED_GEMM;
+        a.gate_words = gemm ? 0 : wide ? nfgw_tpw(a.H) * h->grad_seg_cpl : nf_grad_gate_words(h->grad_seg_cpl, h->gprog.width);
         bool gy_written = false;
         for (int s = S - 1; s >= 0 && e == hipSuccess; --s) {
             const Built::TileSeg &g = h->grad_segs[s];
@@ -2183,7 +2224,9 @@ static int grad_tiled(nf_handle *h, const float *x, const float *y, int64_t B, c
             t.gy_out = wr ? gy_out : nullptr;
             t.tflags = wr && gy_written ? NF_GT_GY_ACC : 0u;
             gy_written = gy_written || wr;
-            e = wide ? nf_launch_grad_wide_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st) : nf_launch_grad_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st);
+            e = gemm   ? nf_launch_grad_gemm_tiled(sp, t, h->grad_seg_cpl, h->n_cu, gate_rec, gate_room, st)
+                : wide ? nf_launch_grad_wide_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st)
+                       : nf_launch_grad_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st);
         }
     }
     ws_release(h, wsp, st);

@@ -204,6 +204,7 @@ class FlowHandle:
         flags |= _lib.NF_CFG_GRAD_GEMM if grad_kernel == "gemm" else 0   # widths 33 .. 512: the GEMM gradient kernel
         flags |= _lib.NF_CFG_GRAD_TILED if grad_tiles else 0
         flags |= _lib.NF_CFG_GRAD_TILED_WIDE if (grad_tiles and grad_kernel == "mfma") else 0   # width 32: tiles of the matrix-core kernel
+        flags |= _lib.NF_CFG_GRAD_TILED_GEMM if (grad_tiles and grad_kernel == "gemm") else 0   # widths 33 .. 512: tiles of the GEMM kernel
         cfg = _lib.nf_config(H, W, Cc, len(self.layers), -1 if device is None else int(device), flags)
         self._model_args = (cfg, descs, flat)   # what nf_cond_rows takes (kept alive with the handle)
         h = C.c_void_p()
@@ -271,7 +272,9 @@ class NoiseFlow(object):
     grad_tiles : ``True`` lets ``nll_and_grad`` / ``nll_torch`` take every H, W up to 4096 at coupling widths up to 16: a shape
           the whole-patch gradient kernel does not hold is evaluated as overlapping 32-pixel tiles (``NF_CFG_GRAD_TILED``); a
           shape it holds is untouched.  Together with grad_kernel='mfma' the same holds at coupling widths 17 .. 32, on tiles of
-          the matrix-core gradient kernel (``NF_CFG_GRAD_TILED_WIDE``).  Default ``False``; also selectable as ``hps.grad_tiles``.
+          the matrix-core gradient kernel (``NF_CFG_GRAD_TILED_WIDE``), and together with grad_kernel='gemm' at coupling widths
+          33 .. 512, on tiles of the GEMM gradient kernel (``NF_CFG_GRAD_TILED_GEMM``; without grad_tiles those widths stay at
+          patches of up to 32x32).  Default ``False``; also selectable as ``hps.grad_tiles``.
     binding : 'loss_first' | 'sample_first' — template→layer binding (quirk Q1).
     """
 

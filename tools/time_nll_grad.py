@@ -1,7 +1,7 @@
 """nf_nll_grad next to nf_nll: the shipped model at 32x32 and 64x64, and the paper-scale model (width 32, 8 couplings) on the
 matrix-core gradient kernel, B = 1 024, same box, same process.
 
-    python tools/time_nll_grad.py [--launches 200] [--legs shipped,wide,tiled,tiled_wide,gemm] [--out FILE.json]
+    python tools/time_nll_grad.py [--launches 200] [--legs shipped,wide,tiled,tiled_wide,gemm,tiled_gemm] [--out FILE.json]
 
 Every figure is the mean over a window of `--launches` (at least 200) back-to-back launches between two device events, after
 a warm-up of a quarter of that; three windows per entry, their median is reported.  The yardstick is nf_nll (the forward
@@ -33,6 +33,16 @@ widths 64, 128 and 512, FULL_ARCH / paper_like_variables on 32x32; width 512 at 
 protocol; per width nf_nll of the same handle, the gradient's three window means (median and spread), patches/s, the ratio to nf_nll
 and the fraction of the fp32 matrix peak (157.3 TFLOP/s), counting THREE coupling-CNN evaluations per coupling — forward sweep,
 recomputation, transposed products: the gates are stored, not recomputed.
+
+Leg `tiled_gemm` (not in the default set): whole images at coupling widths 64, 128 and 512 (`--tg-widths`) through tiles of the GEMM
+gradient kernel (grad_kernel="gemm", grad_tiles=True: NF_CFG_GRAD_TILED_GEMM), FULL_ARCH / paper_like_variables on 64x64 x 256 and
+256x256 x 16 (`--tg-shapes`).  Arms: the planner's own choice and every feasible forced count S = 8 .. 3, alternated `--reps` times;
+beside them nf_nll of the same handle and the whole-patch GEMM gradient kernel at 32x32, per pixel.  A call takes 10 ms .. 1 s here,
+so a window is as many back-to-back calls as fill `--tg-window-ms` (at least 3) behind one warm-up call, one window per repetition:
+per arm the median and the spread (max - min) of its repetitions.  Beside every arm the planner's terms (tile-couplings, tiles,
+boundary pixels of the whole launch; at the end of a width the least-squares fits of the forced arms over them, tiled_gemm_fit: the
+per-tile constant of csrc/nf_host.hip, kGradGemmSegs) and the halo recomputation factor it implies, tile pixels evaluated per image pixel and
+coupling: sum over segments of couplings x tiles x 1024 / (all couplings x image pixels).
 """
 import argparse
 import ctypes as C
@@ -51,6 +61,9 @@ def main():
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--ab-sides", default="24", help="patch sides of the A/B legs (both gradient kernels must hold them)")
     ap.add_argument("--tw-shapes", default="64x1024,256x16", help="side x images of the tiled_wide leg")
+    ap.add_argument("--tg-widths", default="64,128,512", help="coupling widths of the tiled_gemm leg")
+    ap.add_argument("--tg-shapes", default="64x256,256x16", help="side x images of the tiled_gemm leg")
+    ap.add_argument("--tg-window-ms", type=float, default=300.0, help="least duration of a timing window of the tiled_gemm leg")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     legs = a.legs.split(",")
@@ -105,6 +118,8 @@ def main():
         res["tiled_wide"] = tiled_wide_legs(a, timed)
     if "gemm" in legs:
         res["gemm"] = gemm_legs(a)
+    if "tiled_gemm" in legs:
+        res["tiled_gemm"] = tiled_gemm_legs(a)
     print("RESULT " + json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -402,6 +417,147 @@ def gemm_legs(a):
               % (width, B, t_nll[1], r["nll_spread_ms"], r["nll_fraction_of_fp32_matrix_peak"], t_grad[1], r["grad_spread_ms"], r["grad_patches_per_s"],
                  r["grad_over_nll"], r["grad_fraction_of_fp32_matrix_peak"], EVALS, r["workspace_bytes"] / 2.0 ** 20), flush=True)
         del m, x, y, gx, gy
+    return out
+
+
+def tiled_gemm_fit(width, res, n_cpl):
+    """Least squares of the forced arms' medians (ns) of one width, all shapes of `res` together, over (tile-couplings, tiles) and over
+    (tile-couplings, tiles, boundary pixels): the per-tile constant of the planner's rule (csrc/nf_host.hip, kGradGemmSegs) is the ratio
+    of the first fit's two coefficients.  Beside them the whole-patch kernel's time per 32x32 patch and coupling."""
+    import numpy as np
+    rows = [(arm["tile_couplings"], arm["tiles"], arm["boundary_pixels"], arm["median_ms"])
+            for shape, r in res.items() if shape != "32x32" for name, arm in r["arms"].items() if name != "unforced"]
+    fit = {"rows": len(rows), "whole_patch_ns_per_tile_coupling": res["32x32"]["grad_ms"][1] * 1e6 / (res["32x32"]["B"] * n_cpl)}
+    if len(rows) >= 3:
+        t = np.array([r[3] for r in rows], np.float64) * 1e6      # ns
+        for terms in (2, 3):
+            A = np.array([r[:terms] for r in rows], np.float64)
+            coef = np.linalg.lstsq(A, t, rcond=None)[0]
+            fit["%d_terms" % terms] = {"ns_per_tile_coupling": float(coef[0]), "ns_per_tile": float(coef[1]),
+                                       "ns_per_boundary_pixel": float(coef[2]) if terms == 3 else None,
+                                       "per_tile_in_tile_couplings": float(coef[1] / coef[0]),
+                                       "largest_relative_residual": float(np.abs((A @ coef - t) / t).max())}
+        f2, f3 = fit["2_terms"], fit["3_terms"]
+        print("width %d  fit over %d forced arms: %.1f ns per tile-coupling, %.1f ns per tile: a tile costs its couplings + %.2f (largest residual %.1f %%)"
+              % (width, len(rows), f2["ns_per_tile_coupling"], f2["ns_per_tile"], f2["per_tile_in_tile_couplings"], 100.0 * f2["largest_relative_residual"]),
+              flush=True)
+        print("width %d  fit with a third term: %.1f ns per tile-coupling, %.1f ns per tile, %.4f ns per boundary pixel (largest residual %.1f %%)"
+              % (width, f3["ns_per_tile_coupling"], f3["ns_per_tile"], f3["ns_per_boundary_pixel"], 100.0 * f3["largest_relative_residual"]), flush=True)
+    print("width %d  whole-patch kernel: %.1f ns per 32x32 patch and coupling" % (width, fit["whole_patch_ns_per_tile_coupling"]), flush=True)
+    return fit
+
+
+def tiled_gemm_legs(a):
+    import numpy as np
+    import torch
+    from noise_flow_amd import NoiseFlow, _lib, default_hps
+    cond = _lib.nf_cond(800.0, 2.0, 0.0, 0.0)
+    med = lambda t: float(np.median(t))   # noqa: E731
+    n_cpl = FULL_ARCH.split("|").count("unc")
+    out = {}
+
+    def window(fn):
+        """ms per call over one window: a warm-up call (timed, to size the window), then max(3, window / call) calls between two events."""
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        n = max(3, int(np.ceil(a.tg_window_ms / max(e0.elapsed_time(e1), 1e-3))))
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def with_forced(S, fn):
+        if S:
+            os.environ["NF_GRAD_TILE_SEGMENTS"] = str(S)
+        try:
+            return fn()
+        finally:
+            os.environ.pop("NF_GRAD_TILE_SEGMENTS", None)
+
+    def tensors(B, side):
+        rng = np.random.RandomState(0)
+        y = torch.as_tensor(rng.rand(B, side, side, 4).astype(np.float32)).cuda()
+        x = torch.as_tensor((rng.randn(B, side, side, 4) * 0.02).astype(np.float32)).cuda()
+        return x, y, torch.empty((B,), device="cuda"), torch.empty_like(x), torch.empty_like(y)
+
+    forced = [S for S in range(n_cpl, 0, -1) if -(-n_cpl // S) <= 3]     # at most 3 couplings per segment: 8 .. 3
+    for width in [int(w) for w in a.tg_widths.split(",") if w]:
+        v = paper_like_variables(FULL_ARCH, width)
+        hps = lambda: default_hps(arch=FULL_ARCH, width=width)   # noqa: E731
+        res = {}
+        # the whole-patch GEMM gradient kernel at 32x32, per pixel
+        B32 = 512 if width > 128 else 1024
+        m32 = NoiseFlow([32, 32, 4], False, hps(), variables=v, device=0, grad_kernel="gemm", grad_tiles=True)
+        x, y, nll, gx, gy = tensors(B32, 32)
+        lib, h, st = m32._flow.lib, m32._flow.ptr, m32._dev.stream_ptr()
+        assert lib.nf_grad_path(h) == _lib.NF_GRAD_PATH_GEMM
+        _lib.check(lib.nf_reserve_grad_workspace(h, B32, 1))
+        t32 = sorted(window(lambda: _lib.check(lib.nf_nll_grad(h, x.data_ptr(), y.data_ptr(), B32, C.byref(cond), None, nll.data_ptr(), gx.data_ptr(),
+                                                               gy.data_ptr(), st))) for _ in range(3))
+        whole_pps = B32 * 1024.0 / t32[1] * 1e3
+        res["32x32"] = {"B": B32, "grad_ms": t32, "pixels_per_s": whole_pps, "patches_per_s": B32 / t32[1] * 1e3}
+        print("width %d, 32x32 x %d whole-patch GEMM gradient kernel  %.4f ms (spread %.4f)  %.3e patches/s  %.3e pixels/s"
+              % (width, B32, t32[1], t32[2] - t32[0], B32 / t32[1] * 1e3, whole_pps), flush=True)
+        del m32, x, y, nll, gx, gy
+        for side, B in [tuple(int(q) for q in w.split("x")) for w in a.tg_shapes.split(",") if w]:
+            x, y, nll, gx, gy = tensors(B, side)
+            sd, ld = torch.empty((B,), device="cuda"), torch.empty((B,), device="cuda")
+            arms = {}
+            for S in [0] + forced:     # 0: the planner's choice
+                m = with_forced(S, lambda: NoiseFlow([side, side, 4], False, hps(), variables=v, device=0, grad_kernel="gemm", grad_tiles=True))
+                lib, h, st = m._flow.lib, m._flow.ptr, m._dev.stream_ptr()
+                assert lib.nf_grad_path(h) == _lib.NF_GRAD_PATH_TILED_GEMM
+                _lib.check(lib.nf_reserve_grad_workspace(h, B, 1))
+                cfg, descs, flat = m._flow._model_args
+                seg = (C.c_int32 * 80)()
+                n = with_forced(S, lambda: lib.nf_grad_tile_segments(C.byref(cfg), descs, flat.ctypes.data_as(C.POINTER(C.c_float)), flat.size, seg, 16))
+                assert n > 0 and (not S or n == S)
+                rows = [tuple(seg[5 * i:5 * i + 5]) for i in range(n)]
+                tc = sum(r[3] * r[4] * (r[2] // 4) for r in rows)
+                plan = {"segments": n, "couplings_per_segment": [r[2] // 4 for r in rows], "tile_couplings": B * tc, "tiles": B * sum(r[3] * r[4] for r in rows),
+                        "boundary_pixels": (n - 1) * B * side * side, "halo_recomputation": tc * 1024.0 / (n_cpl * side * side),
+                        "workspace_bytes": int(lib.nf_workspace_bytes(h, 2, B))}
+                grad = (lambda lib=lib, h=h, st=st: _lib.check(lib.nf_nll_grad(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), None, nll.data_ptr(),
+                                                                              gx.data_ptr(), gy.data_ptr(), st)))
+                fwd = (lambda lib=lib, h=h, st=st: _lib.check(lib.nf_nll(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), nll.data_ptr(), sd.data_ptr(),
+                                                                        ld.data_ptr(), None, None, 0, st)))
+                arms[S] = {"model": m, "grad": grad, "fwd": fwd, "plan": plan, "ms": []}
+            t_nll = []
+            for r_ in range(a.reps):
+                t_nll.append(window(arms[0]["fwd"]))
+                for S in arms:
+                    arms[S]["ms"].append(window(arms[S]["grad"]))
+                print("width %d  %dx%d x %d rep %d  nf_nll %.4f ms   nf_nll_grad unforced (S=%d) %.4f  %s ms"
+                      % (width, side, side, B, r_, t_nll[-1], arms[0]["plan"]["segments"], arms[0]["ms"][-1],
+                         "  ".join("S=%d %.4f" % (S, arms[S]["ms"][-1]) for S in forced)), flush=True)
+            px = float(B) * side * side
+            r = {"B": B, "nll_ms": t_nll, "nll_median_ms": med(t_nll), "nll_spread_ms": max(t_nll) - min(t_nll), "nll_pixels_per_s": px / med(t_nll) * 1e3,
+                 "arms": {}}
+            for S in arms:
+                t = arms[S]["ms"]
+                name = "S=%d" % S if S else "unforced"
+                r["arms"][name] = dict(arms[S]["plan"], ms=t, median_ms=med(t), spread_ms=max(t) - min(t), pixels_per_s=px / med(t) * 1e3,
+                                       grad_over_nll=med(t) / med(t_nll), fraction_of_whole_patch_pixel_rate=(px / med(t) * 1e3) / whole_pps)
+                print("width %d  %dx%d x %d  %-8s (S=%d %r)  %.4f ms (spread %.4f)  %.3e pixels/s  grad / nll %.2f  %.3f of the 32x32 whole-patch pixel rate   "
+                      "halo recomputation %.2f   tile-couplings %d  tiles %d  boundary pixels %d  workspace %.1f MiB"
+                      % (width, side, side, B, name, arms[S]["plan"]["segments"], arms[S]["plan"]["couplings_per_segment"], med(t), max(t) - min(t),
+                         px / med(t) * 1e3, med(t) / med(t_nll), (px / med(t) * 1e3) / whole_pps, arms[S]["plan"]["halo_recomputation"],
+                         arms[S]["plan"]["tile_couplings"], arms[S]["plan"]["tiles"], arms[S]["plan"]["boundary_pixels"],
+                         arms[S]["plan"]["workspace_bytes"] / 2.0 ** 20), flush=True)
+            best = min((k for k in r["arms"] if k != "unforced"), key=lambda k: r["arms"][k]["median_ms"])
+            r["fastest_forced_arm"] = best
+            r["unforced_over_fastest"] = r["arms"]["unforced"]["median_ms"] / r["arms"][best]["median_ms"]
+            print("width %d  %dx%d x %d  nf_nll %.4f ms (spread %.4f)   fastest forced arm %s; unforced / fastest %.4f"
+                  % (width, side, side, B, med(t_nll), max(t_nll) - min(t_nll), best, r["unforced_over_fastest"]), flush=True)
+            res["%dx%d" % (side, side)] = r
+            del arms, x, y, nll, gx, gy
+        res["fit"] = tiled_gemm_fit(width, res, n_cpl)
+        out["w%d" % width] = res
     return out
 
 
