@@ -354,6 +354,37 @@ int nf_grad_tile_segments(const nf_config *cfg, const nf_layer_desc *layers, con
 int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params, int32_t *path,
                  int32_t *ops_out, int32_t ops_cap, int32_t *n_ops, float *folded, size_t folded_cap, size_t *n_folded);
 
+/* Vector-Jacobian product of sampling: with x = nf_sample(y, eps, temp) (evaluation mode, fp32) and gx_in = d L / d x of any
+ * scalar L, returns d L / d y, d L / d eps and, per patch, d L / d temp — the piece that makes the sampling direction
+ * differentiable (re-noising a network's clean estimate, pathwise gradients in the latent draw, fitting the temperature).
+ * Exactly one of cond / rows is non-NULL: cond = one nf_cond for the call, rows = DEVICE nf_cond_row[B] made by
+ * nf_cond_rows(direction 1), as for nf_sample_percond.
+ *   y         [B,H,W,4] device, 16-byte aligned (NULL only for models without an SDN-kind layer)
+ *   eps       [B,H,W,4] or NULL: the in-kernel Philox draw nf_sample makes for (seed, patch_index_base) — the draw nf_sample_eps
+ *             returns — regenerated where the backward sweep needs it
+ *   gx_in     [B,H,W,4], required
+ *   x_out     [B,H,W,4] or NULL (the sample itself)      gy_out [B,H,W,4] or NULL (must be NULL when y is)
+ *   geps_out  [B,H,W,4] or NULL                          gtemp_out [B] or NULL: sum over the patch of (d L / d z) eps, z = eps temp
+ * Like nf_nll_grad: any subset of the outputs, re-entrant, no synchronisation, no allocation, any B >= 0, only enqueues on
+ * `stream`.  gtemp is reduced in a fixed order inside the workgroup (no atomics): the same bits on every run.
+ * One fused kernel (csrc/nf_sample_grad.hip) in the design of nf_nll_grad's scalar kernel: a forward sweep (nf_sample's
+ * arithmetic) that records the ReLU gates, then a backward sweep over the ops in NLL order that rebuilds every op's input from
+ * its output; no activation is stored, HBM traffic is y, eps, gx_in in and the gradients out.  It interprets the handle's scalar
+ * gradient block.  Supported set (nf_sample_vjp_supported decides, everything else is NF_EINVAL): fp32 handles, the whole layer
+ * vocabulary, padded coupling widths 4 / 8 / 16 / 32, and the shapes nf_nll_grad's scalar kernel holds whole — patches up to
+ * 64x64 at width 4, up to 3072 pixels at width 8 (768 threads x 4 pixels; the LDS budget ends near 55x55 there anyway), up to 1024
+ * pixels at widths 16 and 32, as far as 160 KiB of LDS hold the tiles and the gate record.
+ * A handle with NF_CFG_GRAD_TILED is supported on the shapes held whole; handles whose gradient block is in the matrix-core or
+ * GEMM layout (NF_CFG_GRAD_MFMA, NF_CFG_GRAD_TILED_WIDE at padded width 32; NF_CFG_GRAD_GEMM, NF_CFG_GRAD_TILED_GEMM beyond) are
+ * refused.  Not covered: tiles, NF_CFG_FP16_CNN, batch-statistics mode, host-fed variants, parameter gradients. */
+int nf_sample_vjp(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp, int64_t B,
+                  const nf_cond *cond, const nf_cond_row *rows, const float *gx_in, float *x_out, float *gy_out,
+                  float *geps_out, float *gtemp_out, void *stream);
+
+/* Host-only, as nf_grad_supported: 0 when nf_sample_vjp supports this model, patch size and flags, NF_EINVAL otherwise, with
+ * nf_last_error() naming the limit that was hit. */
+int nf_sample_vjp_supported(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params);
+
 /* The tile plan of one image axis (see "Patch sizes"): `size` pixels, tiles of `tile` = min(size, 64) pixels, `halo` =
  * 2 x the number of coupling layers.  Returns the number of tiles n (or a negative NF_E* code) and, for i < min(n, cap),
  * the tile's first pixel origin[i] and the window [core0[i], core1[i]) it reports — a partition of [0, size) with

@@ -192,6 +192,11 @@ def load() -> C.CDLL:
                                           C.POINTER(i32), i32]
     lib.nf_reserve_grad_workspace.restype = C.c_int
     lib.nf_reserve_grad_workspace.argtypes = [vp, i64, i32]
+    if hasattr(lib, "nf_sample_vjp"):   # (as above: libraries of earlier commits through NF_TOOL_LIB lack it)
+        lib.nf_sample_vjp.restype = C.c_int
+        lib.nf_sample_vjp.argtypes = [vp, vp, vp, u64, i64, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.nf_sample_vjp_supported.restype = C.c_int
+        lib.nf_sample_vjp_supported.argtypes = [C.POINTER(nf_config), C.POINTER(nf_layer_desc), C.POINTER(C.c_float), C.c_size_t]
     if lib.nf_abi_version() != 1:
         raise ImportError("noiseflow_hip ABI version mismatch")
     _lib = lib
@@ -212,6 +217,7 @@ EXPORTED_SYMBOLS = (
     "nf_trainer_get_params", "nf_trainer_set_params", "nf_trainer_steps", "nf_trainer_set_sync",
     "nf_cond_rows", "nf_nll_percond", "nf_sample_percond",
     "nf_nll_grad", "nf_grad_supported", "nf_grad_path", "nf_grad_fold", "nf_grad_tile_segments", "nf_reserve_grad_workspace",
+    "nf_sample_vjp", "nf_sample_vjp_supported",
 )
 NF_GRAD_PATH_SCALAR, NF_GRAD_PATH_WIDE32, NF_GRAD_PATH_TILED, NF_GRAD_PATH_TILED_WIDE32, NF_GRAD_PATH_GEMM = 0, 1, 2, 3, 4
 NF_GRAD_PATH_TILED_GEMM = 5

@@ -456,6 +456,34 @@ __host__ __device__ constexpr size_t nf_grad_lds_floats(int H, int W, int width,
            (size_t)nf_grad_gate_words(n_cpl, width) * (size_t)(nf_grad_threads(H * W, width) * nf_grad_px(H * W, width)) + 32;
 }
 
+// ---- vector-Jacobian product of sampling (nf_sample_grad.hip, nf_sample_vjp) -------------------------------------------------
+// The same gradient block (scalar layout), pixel slots, tiles, gate record and LDS budget as nf_grad_kernel, in the other
+// direction: x = f(y, eps, temp) is evaluated from z = eps * temp through the NLL-order ops last to first, each inverted (MIX by
+// Ainv, SCALE by 1/s, SDN multiplied, couplings reversed), and the cotangent gx_in = d L / d x walks the ops first to last.
+// cond_a / cond_b or cond_rows are those of direction 1 (nf_cond_rows): a gain kind's `a` is the factor sampling multiplies by.
+struct NfSampleGradLaunch {
+    const float *params;   // gradient block (device), scalar layout
+    const float *y;        // [B,H,W,4] or null
+    const float *eps;      // [B,H,W,4], or null: the Philox draw of nf_sample (seed, patch_base + b, pixel, NF_STREAM_SAMP)
+    const float *gx_in;    // [B,H,W,4] d L / d x
+    float *x_out;          // [B,H,W,4] or null
+    float *gy_out;         // [B,H,W,4] or null
+    float *geps_out;       // [B,H,W,4] or null
+    float *gtemp_out;      // [B] or null: sum over the patch of d L / d z * eps, reduced in a fixed order
+    int64_t B;
+    int64_t patch_base;
+    uint64_t seed;
+    float temp;
+    float cond_a[4];
+    float cond_b[4];
+    const nf_cond_row *cond_rows;   // [B] or null
+    int32_t H, W;
+    int32_t last_cpl;      // index of the last coupling op in NLL order (-1 when the model has none)
+    int32_t n_cpl;
+    int32_t gate_words;    // nf_grad_gate_words
+};
+#define NF_SVJP_W8_MAX_PIXELS 3072   // padded width 8 beyond 1 024 pixels: 768 threads x 4 pixels (nf_sample_grad.hip, dispatch_sgrad)
+
 // ---- input gradients at coupling width 32 on the f32 matrix cores (nf_grad_wide.hip, NF_CFG_GRAD_MFMA) --------------------
 // Same launch record (NfGradLaunch), same op list; the gradient block carries per coupling, instead of the generic block, every
 // weight in the fetch order of v_mfma_f32_32x32x2_f32 (tile / lane / register conventions of NF4_*), for the forward chain and

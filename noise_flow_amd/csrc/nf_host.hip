@@ -54,6 +54,7 @@ hipError_t nf_launch_grad_wide_tiled(const NfProgram &prog, const NfGradLaunch &
 hipError_t nf_launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes, hipStream_t stream);
 hipError_t nf_launch_grad_gemm_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes, hipStream_t stream);
 int nf_grad_gemm_groups(int64_t B, int n_cu);
+hipError_t nf_launch_sample_grad(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, hipStream_t stream);
 
 namespace {
 
@@ -1133,6 +1134,33 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
     return NF_OK;
 }
 
+// What nf_sample_vjp supports (nf_sample_grad.hip interprets the SCALAR gradient block on whole patches): whatever grad_support sends
+// to NF_GRAD_PATH_SCALAR for this model, shape and flags — the same width, register and LDS limits, no arithmetic of its own.
+int sample_vjp_support(const nf_config *cfg, const Built &fwd)
+{
+    int path = NF_GRAD_PATH_SCALAR;
+    const int rc = grad_support(cfg, fwd, &path);
+    if (rc != NF_OK) {   // the limit grad_support named, under this call's name
+        std::string why = g_last_error;
+        const size_t at = why.find("nf_nll_grad");
+        if (at != std::string::npos) why.replace(at, strlen("nf_nll_grad"), "nf_sample_vjp");
+        return fail(rc, "%s", why.c_str());
+    }
+    if (path == NF_GRAD_PATH_SCALAR) {
+        if (fwd.lay[NF_PATH_SCALAR].prog.width == 8 && cfg->height * cfg->width > NF_SVJP_W8_MAX_PIXELS)
+            return fail(NF_EINVAL, "nf_sample_vjp: coupling width %d covers patches of up to %d pixels (%dx%d given): registers", fwd.raw_width,
+                        NF_SVJP_W8_MAX_PIXELS, cfg->height, cfg->width);
+        return NF_OK;
+    }
+    if (path == NF_GRAD_PATH_TILED)
+        return fail(NF_EINVAL, "nf_sample_vjp: shapes the scalar gradient kernel holds whole (a %dx%d patch at coupling width %d is cut into "
+                               "tiles under NF_CFG_GRAD_TILED; no tile mode yet)", cfg->height, cfg->width, fwd.raw_width);
+    const bool gemm = path == NF_GRAD_PATH_GEMM || path == NF_GRAD_PATH_TILED_GEMM;
+    return fail(NF_EINVAL, "nf_sample_vjp: the handle's gradient block is in the %s layout (%s at coupling width %d); the scalar layout only: "
+                           "no matrix-core or GEMM variant yet", gemm ? "GEMM" : "matrix-core",
+                gemm ? "NF_CFG_GRAD_GEMM / NF_CFG_GRAD_TILED_GEMM" : "NF_CFG_GRAD_MFMA / NF_CFG_GRAD_TILED_WIDE", fwd.raw_width);
+}
+
 // the paths whose couplings are in the NFGW_* layout (the matrix-core kernel, whole patches or tiles); those in the NFGG_* layout
 // (the GEMM kernel, likewise); the tiled paths
 static bool grad_path_is_wide(int path) { return path == NF_GRAD_PATH_WIDE32 || path == NF_GRAD_PATH_TILED_WIDE32; }
@@ -1343,6 +1371,10 @@ struct nf_handle {
     int grad_rc = NF_EINVAL;
     int grad_path = NF_GRAD_PATH_SCALAR;   // NF_GRAD_PATH_*: which kernel nf_nll_grad launches (grad_support)
     std::string grad_why;
+    // nf_sample_vjp (nf_sample_grad.hip) runs on gprog / d_grad where sample_vjp_support says so
+    int svjp_rc = NF_EINVAL;
+    int svjp_last_cpl = -1;
+    std::string svjp_why;
     std::vector<Built::TileSeg> grad_segs;   // NF_GRAD_PATH_TILED / _TILED_WIDE32 / _TILED_GEMM: the segments (gradient halo, tiles of the backward launches)
     int grad_seg_cpl = 0;                    // ... and the couplings of the largest one (sizes the gate record)
     // scratch of the tiled calls (images beyond 64x64): the per-tile sums and the tensors between two segments.  A small set of
@@ -1528,6 +1560,12 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
                 return fail_hip(e, "hipMalloc/hipMemcpy(gradient params)");
             }
         }
+        const std::string keep2 = g_last_error;
+        h->svjp_rc = sample_vjp_support(cfg, h->fwd);
+        h->svjp_why = g_last_error;
+        g_last_error = keep2;
+        for (int i = 0; h->svjp_rc == NF_OK && i < h->gprog.n_ops; ++i)
+            if (h->gprog.ops[i].type == NF_OP_COUPLING_FWD) h->svjp_last_cpl = i;
     }
     *out = h;
     return NF_OK;
@@ -2321,6 +2359,68 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
     hipError_t e = wide ? nf_launch_grad_wide(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream)
                         : nf_launch_grad(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "nf_nll_grad launch");
+    return NF_OK;
+}
+
+// ---- vector-Jacobian product of sampling: d L / d y, d L / d eps, d L / d temp (nf_sample_grad.hip) ----
+int nf_sample_vjp_supported(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params)
+{
+    Built b;
+    int rc = build_program(cfg, layers, params, n_params, 0, b);
+    if (rc != NF_OK) return rc;
+    return sample_vjp_support(cfg, b);
+}
+
+int nf_sample_vjp(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp, int64_t B,
+                  const nf_cond *cond, const nf_cond_row *rows, const float *gx_in, float *x_out, float *gy_out, float *geps_out,
+                  float *gtemp_out, void *stream)
+{
+    if (!h) return fail(NF_EINVAL, "handle is NULL");
+    if (h->svjp_rc != NF_OK) return fail(h->svjp_rc, "%s", h->svjp_why.c_str());
+    if (B < 0) return fail(NF_EINVAL, "B must be >= 0");
+    if ((cond != nullptr) == (rows != nullptr)) return fail(NF_EINVAL, "nf_sample_vjp: exactly one of cond / rows must be given");
+    if (B > 0 && !gx_in) return fail(NF_EINVAL, "gx_in is NULL");
+    if (h->rev.has_sdn && B > 0 && !y) return fail(NF_EINVAL, "model has a signal-dependent layer but y is NULL");
+    if (!y && gy_out) return fail(NF_EINVAL, "gy_out must be NULL when y is");
+    if (!aligned16(y) || !aligned16(eps) || !aligned16(gx_in) || !aligned16(x_out) || !aligned16(gy_out) || !aligned16(geps_out))
+        return fail(NF_EINVAL, "y, eps, gx_in, x_out, gy_out and geps_out must be 16-byte aligned (every pixel is one float4 access)");
+    nf_cond_row r;
+    memset(&r, 0, sizeof(r));
+    if (rows) {
+        int rc = check_rows(h, rows, B);
+        if (rc != NF_OK) return rc;
+    } else {
+        int rc = cond_row_of(h->rev, h->cfg.height, h->cfg.width, 1, cond, r);
+        if (rc != NF_OK) return rc;
+    }
+    if (B == 0) return NF_OK;
+    NfSampleGradLaunch a;
+    memset(&a, 0, sizeof(a));
+    a.params = h->d_grad;
+    a.y = y;
+    a.eps = eps;
+    a.gx_in = gx_in;
+    a.x_out = x_out;
+    a.gy_out = gy_out;
+    a.geps_out = geps_out;
+    a.gtemp_out = gtemp_out;
+    a.B = B;
+    a.patch_base = patch_index_base;
+    a.seed = seed;
+    a.temp = temp;
+    memcpy(a.cond_a, r.a, sizeof(r.a));
+    memcpy(a.cond_b, r.b, sizeof(r.b));
+    a.cond_rows = rows;
+    a.H = h->cfg.height;
+    a.W = h->cfg.width;
+    a.last_cpl = h->svjp_last_cpl;
+    a.n_cpl = h->grad_n_cpl;
+    a.gate_words = nf_grad_gate_words(h->grad_n_cpl, h->gprog.width);
+    NfDeviceGuard guard;
+    int rc = guard.enter(h->device);
+    if (rc != NF_OK) return rc;
+    const hipError_t e = nf_launch_sample_grad(h->gprog, a, h->n_cu, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "nf_sample_vjp launch");
     return NF_OK;
 }
 

@@ -1,0 +1,556 @@
+// Vector-Jacobian product of sampling (nf_sample_vjp): given g = d L / d x of x = sample(y, eps, temp), one fused kernel returns
+// d L / d y, d L / d eps and d L / d temp (per patch) — and x itself, if asked.
+//
+// The design is nf_grad_kernel's (nf_grad.hip) run in the other direction: one workgroup per patch, grid-stride over patches, the
+// handle's scalar gradient block with scalar (SGPR) weights, the same pixel slots (nf_grad_threads, nf_grad_px; one exception:
+// width 8 beyond 1 024 pixels, dispatch_sgrad below), the same two zero-bordered LDS tiles, gate record (nf_grad_gate_words) and
+// LDS budget (nf_grad_lds_floats).  Per patch:
+//   forward sweep   z = eps * temp (the caller's eps or nf_sample's Philox draw), then the NLL-order ops LAST TO FIRST, each inverted
+//                   (nf_sample's arithmetic): x — and every ReLU gate recorded as one bit;
+//   backward sweep  g = gx_in, then the ops FIRST TO LAST.  With v the output of an op's inverse and u its input, every op first
+//                   transforms g (and adds to gy) from v, then rebuilds u — the NLL-direction op applied to v: no activation is
+//                   stored, HBM traffic is y, eps, g in and the gradients out.
+//     MIX       v = u Ainv            g <- g Ainv^T                                     u = v A
+//     COUPLING  v1 = (u1 - shift(u0)) exp(-ls(u0)), ls = S tanh(raw)
+//               d shift = -g1 exp(-ls), d ls = -g1 v1, d raw = S (1 - tanh^2) d ls, g1 <- g1 exp(-ls),
+//               g0 <- g0 + CNN^T(d shift, d raw) through the RECORDED gates         u1 = v1 exp(ls) + shift
+//     SDN       v = u s, s^2 = a y + b   gy += g v a / (2 s^2), g <- g s                 u = v / s
+//     SCALE     v = u c                  g <- g c                                        u = v / c
+//   end             geps = temp g, gtemp_b = sum over the patch of g eps (per thread, wavefront, then the wavefronts in order: no
+//                   atomics, the same bits on every run).
+// The gates come from the forward sweep, not from the rebuilt values: the result is the derivative of the function the forward
+// sweep evaluated.  The ops behind the last coupling in NLL order (the first ones sampling runs) take their values forward from
+// eps * temp instead of the rebuilt ones, as nf_grad_kernel does for the ops behind x.
+// The coupling CNN, its transposed pass and the gate record restate nf_grad_kernel's; a change to one is made in both files.
+#include <hip/hip_runtime.h>
+#include <atomic>
+#include <stdint.h>
+#include <type_traits>
+
+#include "nf_device.h"
+#include "nf_dev_util.h"
+#include "nf_internal.h"
+#include "nf_flow_common.h"   // flow_launch: the persistent-grid launcher
+
+namespace {
+
+template <int WIDTH, int THREADS, int PX>
+__global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram prog, const NfSampleGradLaunch a)
+{
+    static_assert(WIDTH == 4 || WIDTH == 8 || WIDTH == 16 || WIDTH == 32, "gate sets of WIDTH bits must tile a 32-bit word");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int NPIX = THREADS * PX;
+    constexpr int NW = THREADS / 64;
+    constexpr int SPW = 32 / WIDTH;   // gate sets per word
+    const int H = a.H, W = a.W, HW = H * W, Wp = W + 2;
+    const int tile_px = ((H + 2) * Wp + 1) & ~1;
+    float2 *const t0 = reinterpret_cast<float2 *>(smem);   // z0 tile [tile_px] float2
+    float *const th = smem + 2 * tile_px;                   // relu(h2) / d(shift, raw) / d h1 tile [tile_px][WIDTH]
+    uint32_t *const gates = reinterpret_cast<uint32_t *>(th + (size_t)tile_px * WIDTH);   // [gate_words][NPIX]
+    float *const red = reinterpret_cast<float *>(gates + (size_t)a.gate_words * NPIX);    // [NW]
+
+    const int t = threadIdx.x;
+    int lidx[PX], gidx[PX], bmask[PX];
+    bool act[PX];
+#pragma unroll
+    for (int k = 0; k < PX; ++k) {
+        const int p = t + THREADS * k;
+        act[k] = p < HW;
+        const int pp = act[k] ? p : 0;
+        const int r = pp / W, c = pp - r * W;
+        gidx[k] = pp;
+        lidx[k] = (r + 1) * Wp + (c + 1);
+        bmask[k] = (r == 0 ? 1 : 0) | (r == H - 1 ? 2 : 0) | (c == 0 ? 4 : 0) | (c == W - 1 ? 8 : 0);
+    }
+    // zero both tiles once: the 1-pixel border is never written again
+    for (int i = t; i < tile_px * (2 + WIDTH); i += THREADS) smem[i] = 0.0f;
+    __syncthreads();
+
+    const int n_ops = prog.n_ops;
+    const int last_cpl = a.last_cpl;
+
+    for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const size_t patch_off = (size_t)b * (size_t)HW;
+        const float4 *const y4 = reinterpret_cast<const float4 *>(a.y) + patch_off;   // (not dereferenced when a.y is null)
+        const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + b;
+        auto cond_a = [&](int slot) { return a.cond_rows ? crow->a[slot & 3] : a.cond_a[slot & 3]; };
+        auto cond_b = [&](int slot) { return a.cond_rows ? crow->b[slot & 3] : a.cond_b[slot & 3]; };
+
+        auto load4 = [&](const float *src, float fill, float (&v)[PX][4]) {
+            const float4 *const s4 = reinterpret_cast<const float4 *>(src) + patch_off;
+#pragma unroll
+            for (int k = 0; k < PX; ++k) {
+                float4 q = make_float4(fill, fill, fill, fill);
+                if (act[k]) q = s4[gidx[k]];
+                v[k][0] = q.x; v[k][1] = q.y; v[k][2] = q.z; v[k][3] = q.w;
+            }
+        };
+        // eps: the caller's, or nf_sample's draw (the same key), regenerated wherever it is needed
+        auto load_eps = [&](float (&e)[PX][4]) {
+            if (a.eps) {
+                load4(a.eps, 0.0f, e);
+            } else {
+#pragma unroll
+                for (int k = 0; k < PX; ++k) {
+                    philox_normal4(a.seed, a.patch_base + b, (uint32_t)gidx[k], NF_STREAM_SAMP, e[k]);
+                    if (!act[k]) e[k][0] = e[k][1] = e[k][2] = e[k][3] = 0.0f;
+                }
+            }
+        };
+        auto load_y = [&](float (&yy)[PX][4]) {
+#pragma unroll
+            for (int k = 0; k < PX; ++k) {
+                float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
+                if (act[k]) v = y4[gidx[k]];
+                yy[k][0] = v.x; yy[k][1] = v.y; yy[k][2] = v.z; yy[k][3] = v.w;
+            }
+        };
+        // z <- z M, M row-major [c][k] at P
+        auto mat4 = [&](const cfloat_p P, float (&z)[PX][4]) {
+            float m[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) m[i] = P[i];
+#pragma unroll
+            for (int k = 0; k < PX; ++k) {
+                float o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float s = z[k][0] * m[j];
+                    s = fmaf(z[k][1], m[4 + j], s);
+                    s = fmaf(z[k][2], m[8 + j], s);
+                    s = fmaf(z[k][3], m[12 + j], s);
+                    o[j] = s;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) z[k][j] = o[j];
+            }
+        };
+
+        // the pointwise ops in the sampling direction (nf_sample's arithmetic): the inverse of NLL-order op `op`
+        auto pointwise_inv = [&](int op, float (&z)[PX][4]) {
+            const int type = prog.ops[op].type;
+            const int off = prog.ops[op].off;
+            if (type == NF_OP_MIX) {
+                mat4((cfloat_p)(a.params + off) + 16, z);
+            } else if (type == NF_OP_SDN_DIV) {
+                const float ck1 = cond_a(off), cb2 = cond_b(off);
+                float yy[PX][4];
+                load_y(yy);
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) z[k][c] *= __builtin_amdgcn_sqrtf(fmaf(yy[k][c], ck1, cb2));
+            } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
+                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[1] : cond_a(off);
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) z[k][c] *= s;
+            }
+        };
+
+        // gate set s of pixel slot k (nf_device.h)
+        auto gate_put = [&](int s, int k, uint32_t bits) {
+            uint32_t *const p = gates + (size_t)(s / SPW) * NPIX + t + THREADS * k;
+            const int sh = (s % SPW) * WIDTH;
+            *p = sh == 0 ? bits : (*p | (bits << sh));
+        };
+        auto gate_get = [&](int s, int k) { return gates[(size_t)(s / SPW) * NPIX + t + THREADS * k] >> ((s % SPW) * WIDTH); };
+
+        // The coupling CNN on z0 = z[.][0:2]: o = (shift, raw log-scale), as nf_grad_kernel's.  RECORD: the forward sweep — ReLU by
+        // sign, gates written to the record; otherwise the backward sweep's recomputation on the same z0 — ReLU by the recorded gates.
+        // The forward sweep reaches the couplings LAST TO FIRST: coupling cidx (NLL order) owns the gate sets 2 (n_cpl - 1 - cidx) + layer,
+        // so that the sets of a word are written in rising order and the one with shift 0 clears it (gate_put).
+        auto coupling_cnn = [&](int off, int cidx, auto record, const float (&z)[PX][4], float (&o)[PX][4]) {
+            constexpr bool RECORD = decltype(record)::value;
+            const int gs = 2 * (a.n_cpl - 1 - cidx);
+            const cfloat_p P = (cfloat_p)(a.params + off);
+#pragma unroll
+            for (int k = 0; k < PX; ++k)
+                if (act[k]) t0[lidx[k]] = make_float2(z[k][0], z[k][1]);
+            __syncthreads();
+            {
+                const cfloat_p W1 = P + nf_cpl_off_W1(WIDTH);
+                const cfloat_p B1 = P + nf_cpl_off_B1(WIDTH);
+                const cfloat_p W2 = P + nf_cpl_off_W2(WIDTH);
+                const cfloat_p B2 = P + nf_cpl_off_B2(WIDTH);
+                float h1[PX][WIDTH];
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+#pragma unroll
+                    for (int j = 0; j < WIDTH; ++j) h1[k][j] = B1[j];
+#pragma unroll 1
+                for (int di = 0; di < 3; ++di) {
+                    const cfloat_p W1r = W1 + di * (3 * 2 * WIDTH);
+                    const int roff = (di - 1) * Wp - 1;
+#pragma unroll
+                    for (int dj = 0; dj < 3; ++dj) {
+#pragma unroll
+                        for (int k = 0; k < PX; ++k) {
+                            const float2 v = t0[lidx[k] + roff + dj];
+#pragma unroll
+                            for (int j = 0; j < WIDTH; ++j) {
+                                h1[k][j] = fmaf(v.x, W1r[(dj * 2 + 0) * WIDTH + j], h1[k][j]);
+                                h1[k][j] = fmaf(v.y, W1r[(dj * 2 + 1) * WIDTH + j], h1[k][j]);
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < PX; ++k) {
+                    uint32_t g1 = 0u, g2 = 0u;
+                    if constexpr (RECORD) {
+#pragma unroll
+                        for (int i = 0; i < WIDTH; ++i) g1 |= (__float_as_int(h1[k][i]) > 0 ? 1u : 0u) << i;
+                        gate_put(gs, k, g1);
+                    } else {
+                        g1 = gate_get(gs, k);
+                        g2 = gate_get(gs + 1, k);
+                    }
+                    float h2[WIDTH];
+#pragma unroll
+                    for (int j = 0; j < WIDTH; ++j) h2[j] = B2[j];
+#pragma unroll
+                    for (int i = 0; i < WIDTH; ++i) {
+                        const float hi = RECORD ? nf_relu(h1[k][i]) : ((g1 >> i) & 1u) ? h1[k][i] : 0.0f;
+#pragma unroll
+                        for (int j = 0; j < WIDTH; ++j) h2[j] = fmaf(hi, W2[i * WIDTH + j], h2[j]);
+                    }
+                    if constexpr (RECORD) {
+#pragma unroll
+                        for (int i = 0; i < WIDTH; ++i) g2 |= (__float_as_int(h2[i]) > 0 ? 1u : 0u) << i;
+                        gate_put(gs + 1, k, g2);
+                    }
+                    if (act[k]) {
+                        float4 *const dst = reinterpret_cast<float4 *>(th + (size_t)lidx[k] * WIDTH);
+#pragma unroll
+                        for (int q = 0; q < WIDTH / 4; ++q) {
+                            float v[4];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                v[e] = RECORD ? nf_relu(h2[4 * q + e]) : ((g2 >> (4 * q + e)) & 1u) ? h2[4 * q + e] : 0.0f;
+                            dst[q] = make_float4(v[0], v[1], v[2], v[3]);
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            {
+                const cfloat_p W3 = P + nf_cpl_off_W3(WIDTH);
+#pragma unroll
+                for (int k = 0; k < PX; ++k) {
+                    const float4 e = *reinterpret_cast<const float4 *>(a.params + off + nf_cpl_off_E(WIDTH) + 4 * bmask[k]);
+                    o[k][0] = e.x; o[k][1] = e.y; o[k][2] = e.z; o[k][3] = e.w;
+                }
+#pragma unroll 1
+                for (int di = 0; di < 3; ++di) {
+                    const cfloat_p W3r = W3 + di * (3 * WIDTH * 4);
+                    const int roff = (di - 1) * Wp - 1;
+#pragma unroll
+                    for (int dj = 0; dj < 3; ++dj) {
+#pragma unroll
+                        for (int q = 0; q < WIDTH / 4; ++q) {
+#pragma unroll
+                            for (int k = 0; k < PX; ++k) {
+                                const float4 hv = *reinterpret_cast<const float4 *>(th + (size_t)(lidx[k] + roff + dj) * WIDTH + 4 * q);
+                                const float hh[4] = {hv.x, hv.y, hv.z, hv.w};
+#pragma unroll
+                                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                                    for (int j = 0; j < 4; ++j) o[k][j] = fmaf(hh[i], W3r[(dj * WIDTH + 4 * q + i) * 4 + j], o[k][j]);
+                            }
+                        }
+                    }
+                }
+            }
+        };
+
+        // ---- forward sweep: x = f(y, eps, temp) ----
+        float z[PX][4];
+        load_eps(z);
+#pragma unroll
+        for (int k = 0; k < PX; ++k)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) z[k][c] *= a.temp;
+        {
+            int cidx = a.n_cpl;
+            for (int op = n_ops - 1; op >= 0; --op) {
+                if (prog.ops[op].type != NF_OP_COUPLING_FWD) {
+                    pointwise_inv(op, z);
+                    continue;
+                }
+                --cidx;
+                const cfloat_p P = (cfloat_p)(a.params + prog.ops[op].off);
+                float o[PX][4];
+                coupling_cnn(prog.ops[op].off, cidx, std::true_type{}, z, o);
+                const float sc = P[nf_cpl_off_S(WIDTH)];
+#pragma unroll
+                for (int k = 0; k < PX; ++k) {
+                    const float ls0 = sc * nf_tanh(o[k][2]);
+                    const float ls1 = sc * nf_tanh(o[k][3]);
+                    z[k][2] = (z[k][2] - o[k][0]) * nf_exp(-ls0);
+                    z[k][3] = (z[k][3] - o[k][1]) * nf_exp(-ls1);
+                }
+            }
+        }
+        if (a.x_out) {
+            float4 *const o4 = reinterpret_cast<float4 *>(a.x_out) + patch_off;
+#pragma unroll
+            for (int k = 0; k < PX; ++k)
+                if (act[k]) o4[gidx[k]] = make_float4(z[k][0], z[k][1], z[k][2], z[k][3]);
+        }
+
+        // ---- backward sweep ----
+        float g[PX][4];    // d L / d (the tensor in front of the NLL-order op being reached): gx_in at the start
+        float gy[PX][4];
+        load4(a.gx_in, 0.0f, g);
+#pragma unroll
+        for (int k = 0; k < PX; ++k)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) gy[k][c] = 0.0f;
+        int cidx = 0;
+        for (int op = 0; op < n_ops; ++op) {
+            const int type = prog.ops[op].type;
+            const int off = prog.ops[op].off;
+            if (type == NF_OP_COUPLING_FWD) {
+                const cfloat_p P = (cfloat_p)(a.params + off);
+                float o[PX][4];
+                coupling_cnn(off, cidx, std::false_type{}, z, o);
+                const float sc = P[nf_cpl_off_S(WIDTH)];
+                float d[PX][4];   // d L / d (shift, raw)
+#pragma unroll
+                for (int k = 0; k < PX; ++k) {
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const float th_ = nf_tanh(o[k][2 + c]);
+                        const float ls = sc * th_;
+                        const float gu = g[k][2 + c] * nf_exp(-ls);
+                        const float dls = -g[k][2 + c] * z[k][2 + c];
+                        d[k][c] = -gu;
+                        d[k][2 + c] = sc * fmaf(-th_, th_, 1.0f) * dls;
+                        g[k][2 + c] = gu;
+                        z[k][2 + c] = fmaf(z[k][2 + c], nf_exp(ls), o[k][c]);   // the sampling op's input
+                    }
+                }
+                __syncthreads();   // relu(h2) consumed: d(shift, raw) overlays it
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+                    if (act[k]) *reinterpret_cast<float4 *>(th + (size_t)lidx[k] * WIDTH) = make_float4(d[k][0], d[k][1], d[k][2], d[k][3]);
+                __syncthreads();
+                // W3^T over the zero-bordered tile: d relu(h2)[q][i] = sum_taps sum_j d[q - tap][j] W3[tap][i][j]
+                float dh[PX][WIDTH];
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+#pragma unroll
+                    for (int i = 0; i < WIDTH; ++i) dh[k][i] = 0.0f;
+                {
+                    const cfloat_p W3 = P + nf_cpl_off_W3(WIDTH);
+#pragma unroll 1
+                    for (int di = 0; di < 3; ++di) {
+                        const cfloat_p W3r = W3 + di * (3 * WIDTH * 4);
+                        const int roff = -(di - 1) * Wp + 1;
+#pragma unroll
+                        for (int dj = 0; dj < 3; ++dj) {
+#pragma unroll
+                            for (int k = 0; k < PX; ++k) {
+                                const float4 dv = *reinterpret_cast<const float4 *>(th + (size_t)(lidx[k] + roff - dj) * WIDTH);
+                                const float dd[4] = {dv.x, dv.y, dv.z, dv.w};
+#pragma unroll
+                                for (int i = 0; i < WIDTH; ++i)
+#pragma unroll
+                                    for (int j = 0; j < 4; ++j) dh[k][i] = fmaf(dd[j], W3r[(dj * WIDTH + i) * 4 + j], dh[k][i]);
+                            }
+                        }
+                    }
+                }
+                // through the recorded gates and W2^T: d h1
+                {
+                    const cfloat_p W2 = P + nf_cpl_off_W2(WIDTH);
+#pragma unroll
+                    for (int k = 0; k < PX; ++k) {
+                        const int gs = 2 * (a.n_cpl - 1 - cidx);
+                        const uint32_t g1 = gate_get(gs, k), g2 = gate_get(gs + 1, k);
+                        float d2[WIDTH];
+#pragma unroll
+                        for (int j = 0; j < WIDTH; ++j) d2[j] = ((g2 >> j) & 1u) ? dh[k][j] : 0.0f;
+#pragma unroll
+                        for (int i = 0; i < WIDTH; ++i) {
+                            float s = 0.0f;
+#pragma unroll
+                            for (int j = 0; j < WIDTH; ++j) s = fmaf(d2[j], W2[i * WIDTH + j], s);
+                            dh[k][i] = ((g1 >> i) & 1u) ? s : 0.0f;
+                        }
+                    }
+                }
+                __syncthreads();   // d(shift, raw) consumed: d h1 overlays it
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+                    if (act[k]) {
+                        float4 *const dst = reinterpret_cast<float4 *>(th + (size_t)lidx[k] * WIDTH);
+#pragma unroll
+                        for (int q = 0; q < WIDTH / 4; ++q) dst[q] = make_float4(dh[k][4 * q], dh[k][4 * q + 1], dh[k][4 * q + 2], dh[k][4 * q + 3]);
+                    }
+                __syncthreads();
+                // W1^T over the zero-bordered tile, added to the pass-through half's gradient
+                {
+                    const cfloat_p W1 = P + nf_cpl_off_W1(WIDTH);
+#pragma unroll 1
+                    for (int di = 0; di < 3; ++di) {
+                        const cfloat_p W1r = W1 + di * (3 * 2 * WIDTH);
+                        const int roff = -(di - 1) * Wp + 1;
+#pragma unroll
+                        for (int dj = 0; dj < 3; ++dj) {
+#pragma unroll
+                            for (int q = 0; q < WIDTH / 4; ++q) {
+#pragma unroll
+                                for (int k = 0; k < PX; ++k) {
+                                    const float4 hv = *reinterpret_cast<const float4 *>(th + (size_t)(lidx[k] + roff - dj) * WIDTH + 4 * q);
+                                    const float hh[4] = {hv.x, hv.y, hv.z, hv.w};
+#pragma unroll
+                                    for (int i = 0; i < 4; ++i) {
+                                        g[k][0] = fmaf(hh[i], W1r[(dj * 2 + 0) * WIDTH + 4 * q + i], g[k][0]);
+                                        g[k][1] = fmaf(hh[i], W1r[(dj * 2 + 1) * WIDTH + 4 * q + i], g[k][1]);
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+                ++cidx;
+            } else if (type == NF_OP_MIX) {
+                const cfloat_p P = (cfloat_p)(a.params + off);
+                float mi[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) mi[i] = P[16 + i];
+#pragma unroll
+                for (int k = 0; k < PX; ++k) {
+                    float gi[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {   // g Ainv^T
+                        float q = g[k][0] * mi[4 * j];
+                        q = fmaf(g[k][1], mi[4 * j + 1], q);
+                        q = fmaf(g[k][2], mi[4 * j + 2], q);
+                        q = fmaf(g[k][3], mi[4 * j + 3], q);
+                        gi[j] = q;
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) g[k][j] = gi[j];
+                }
+                mat4(P, z);   // u = v A
+            } else if (type == NF_OP_SDN_DIV) {
+                const float ck1 = cond_a(off), cb2 = cond_b(off);
+                if (op > last_cpl) {   // the first ops sampling runs: the op's output, forward from eps * temp
+                    load_eps(z);
+#pragma unroll
+                    for (int k = 0; k < PX; ++k)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) z[k][c] *= a.temp;
+                    for (int q = n_ops - 1; q >= op; --q) pointwise_inv(q, z);
+                }
+                float yy[PX][4];
+                load_y(yy);
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const float v = fmaf(yy[k][c], ck1, cb2);
+                        const float r = __builtin_amdgcn_rsqf(v);
+                        gy[k][c] = fmaf(0.5f * ck1 * (r * r), g[k][c] * z[k][c], gy[k][c]);
+                        g[k][c] *= __builtin_amdgcn_sqrtf(v);
+                        z[k][c] *= r;
+                    }
+            } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
+                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[1] : cond_a(off);
+                const float si = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : 1.0f / s;
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        g[k][c] *= s;
+                        z[k][c] *= si;
+                    }
+            }
+        }
+
+        if (a.gy_out) {
+            float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+#pragma unroll
+            for (int k = 0; k < PX; ++k)
+                if (act[k]) o4[gidx[k]] = make_float4(gy[k][0], gy[k][1], gy[k][2], gy[k][3]);
+        }
+        if (a.geps_out) {
+            float4 *const o4 = reinterpret_cast<float4 *>(a.geps_out) + patch_off;
+#pragma unroll
+            for (int k = 0; k < PX; ++k)
+                if (act[k]) o4[gidx[k]] = make_float4(a.temp * g[k][0], a.temp * g[k][1], a.temp * g[k][2], a.temp * g[k][3]);
+        }
+        if (a.gtemp_out) {   // wave-uniform
+            load_eps(z);
+            float s = 0.0f;
+#pragma unroll
+            for (int k = 0; k < PX; ++k)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) s = act[k] ? fmaf(g[k][c], z[k][c], s) : s;
+            float r = wave_sum(s);
+            if constexpr (NW > 1) {
+                __syncthreads();   // the previous patch's reader is done
+                if ((t & 63) == 0) red[t >> 6] = r;
+                __syncthreads();
+                if (t == 0) {
+                    r = 0.f;
+                    for (int wv = 0; wv < NW; ++wv) r += red[wv];
+                }
+            }
+            if (t == 0) a.gtemp_out[b] = r;
+        }
+    }
+}
+
+template <int WIDTH, int THREADS, int PX>
+hipError_t launch_sgrad(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return flow_launch<&nf_sample_grad_kernel<WIDTH, THREADS, PX>>(THREADS, lds, prog, a, n_cu, dev, stream);
+}
+
+// the geometries of nf_grad.hip's dispatch_grad (nf_grad_threads, nf_grad_px), but for width 8 beyond 1 024 pixels: 768 x 4 pixel slots,
+// fewer than nf_grad_lds_floats budgets the gate record for (the kernel sizes its record by ITS slots: the budget is never exceeded)
+template <int WIDTH>
+hipError_t dispatch_sgrad(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
+{
+    const int hw = a.H * a.W;
+    if (hw <= 64) return launch_sgrad<WIDTH, 64, 1>(prog, a, n_cu, lds, stream);
+    if (hw <= 256) return launch_sgrad<WIDTH, 256, 1>(prog, a, n_cu, lds, stream);
+    if constexpr (WIDTH >= 32) {
+        if (hw <= 1024) return launch_sgrad<WIDTH, 1024, 1>(prog, a, n_cu, lds, stream);
+    } else {
+        if (hw <= 1024) return launch_sgrad<WIDTH, 256, 4>(prog, a, n_cu, lds, stream);
+        // beyond 1 024 pixels a lane holds 4 pixels.  Width 4 does inside the 128 VGPRs of a 1 024-thread workgroup (155 spilled);
+        // width 8 runs 768 threads (168 VGPRs: up to 3 072 pixels, nearly all that the LDS budget leaves it) — its 1 024-thread
+        // build returned wrong gradients on the GPU and is not instantiated
+        if constexpr (WIDTH == 4) {
+            if (hw <= 4096) return launch_sgrad<WIDTH, 1024, 4>(prog, a, n_cu, lds, stream);
+        } else if constexpr (WIDTH == 8) {
+            if (hw <= NF_SVJP_W8_MAX_PIXELS) return launch_sgrad<WIDTH, 768, 4>(prog, a, n_cu, lds, stream);
+        }
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+// entry point used by nf_host.hip (which has checked the supported set: sample_vjp_support)
+hipError_t nf_launch_sample_grad(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, hipStream_t stream)
+{
+    if (a.H < 1 || a.W < 1 || a.H > 64 || a.W > 64) return hipErrorInvalidValue;
+    const size_t lds = sizeof(float) * nf_grad_lds_floats(a.H, a.W, prog.width, a.n_cpl);
+    if (lds > 160 * 1024 || a.gate_words != nf_grad_gate_words(a.n_cpl, prog.width)) return hipErrorInvalidValue;
+    switch (prog.width) {
+    case 4: return dispatch_sgrad<4>(prog, a, n_cu, lds, stream);
+    case 8: return dispatch_sgrad<8>(prog, a, n_cu, lds, stream);
+    case 16: return dispatch_sgrad<16>(prog, a, n_cu, lds, stream);
+    case 32: return dispatch_sgrad<32>(prog, a, n_cu, lds, stream);
+    default: return hipErrorInvalidValue;
+    }
+}

@@ -740,6 +740,70 @@ class NoiseFlow(object):
                 _lib.check(self._flow.lib.nf_sample(*args, dev.stream_ptr()))
         return dev.back(out, was_np)
 
+    # ------------------------------------------------------------------ sampling direction: vector-Jacobian product
+    def _run_sample_vjp(self, yt, epst, seed, base, temp, cond, gt, want_x=True, want_gy=True, want_geps=True, want_gtemp=True):
+        """One ``nf_sample_vjp`` call on device tensors, on the current stream → (x, gy, geps, gtemp), ``None`` where not asked
+        (``epst`` None: the in-kernel draw of ``nf_sample`` for ``(seed, base)``)."""
+        dev = self._dev
+        B = int(gt.shape[0])
+        x = dev.empty(gt.shape) if want_x else None
+        gy = dev.empty(gt.shape) if (want_gy and yt is not None) else None
+        geps = dev.empty(gt.shape) if want_geps else None
+        gtemp = dev.empty((B,)) if want_gtemp else None
+        per_patch = isinstance(cond, PatchCond)
+        rows = self._rows_to_dev(cond, 1) if per_patch else None
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        with dev.torch.cuda.device(dev.device):
+            _lib.check(self._flow.lib.nf_sample_vjp(self._flow.ptr, ptr(yt), ptr(epst), int(seed) & _U64, int(base), float(temp), B,
+                                                    None if per_patch else C.byref(cond), ptr(rows), gt.data_ptr(), ptr(x), ptr(gy),
+                                                    ptr(geps), ptr(gtemp), dev.stream_ptr()))
+        return x, gy, geps, gtemp
+
+    def _sample_vjp_inputs(self, y_shape_src, yy, eps, seed):
+        """Device tensors and the Philox key of a differentiable sampling call → (yt | None, epst | None, seed, base, B, was_np)."""
+        if self._is_training:
+            raise NotImplementedError("the sampling direction is differentiable in evaluation mode only (is_training=False): batch "
+                                      "statistics couple the patches of a call")
+        tail = tuple(self.x_shape)
+        if yy is None and self._flow.has_sdn:
+            raise ValueError("this architecture has a signal-dependent layer: the clean image yy is required")
+        src = eps if eps is not None else y_shape_src
+        B = _batch_of(src)
+        was_np = not isinstance(src, self._dev.torch.Tensor)
+        yt = self._dev.to_dev(yy, tail)[0] if (yy is not None and self._flow.has_sdn) else None
+        if yt is not None and int(yt.shape[0]) != B:
+            raise ValueError("batch sizes differ")
+        if eps is not None:
+            return yt, self._dev.to_dev(eps, tail)[0], 0, 0, B, was_np
+        with self._lock:
+            base = self._draws
+            self._draws += B
+        return yt, None, (self._seed if seed is None else int(seed)), base, B, was_np
+
+    def sample_and_vjp(self, y_shape_src, g, eps_std=None, yy=None, nlf0=None, nlf1=None, iso=None, cam=None, eps=None, seed=None):
+        """``(x, gy, geps, gtemp)``: the sample ``x`` that :meth:`sample` returns for the same arguments, and for the cotangent
+        ``g`` = d L / d x the gradients d L / d yy (``None`` for a model without a signal-dependent layer), d L / d eps and, per
+        patch, d L / d eps_std — one fused ``nf_sample_vjp`` kernel (evaluation mode, fp32).  numpy in → numpy out, CUDA tensors
+        in → CUDA tensors out; ``eps_std`` is one temperature for the call (default 1); without ``eps`` the draw is the in-kernel
+        one of :meth:`sample` (``y_shape_src`` then only supplies the batch size, as there); length-B ``iso`` / ``cam`` lists
+        condition per patch."""
+        yt, epst, sd, base, B, was_np = self._sample_vjp_inputs(y_shape_src, yy, eps, seed)
+        gt, g_np = self._dev.to_dev(g, tuple(self.x_shape))
+        if int(gt.shape[0]) != B:
+            raise ValueError("batch sizes differ")
+        temp = 1.0 if eps_std is None else _first(eps_std)
+        out = self._run_sample_vjp(yt, epst, sd, base, temp, self._cond(nlf0, nlf1, iso, cam, B), gt)
+        back = self._dev.back
+        return tuple(back(t, was_np and g_np) if t is not None else None for t in out)
+
+    def sample_torch(self, yy, eps=None, seed=None, eps_std=None, nlf0=None, nlf1=None, iso=None, cam=None):
+        """The sample ``x`` [B, H, W, 4] as a differentiable function (``torch.autograd``) of the clean image ``yy``, of ``eps``
+        when that is a tensor requiring grad, and of ``eps_std`` when that is a 0-d tensor requiring grad: re-noising a
+        network's estimate is ``est + nf.sample_torch(est, iso=..., cam=...)``.  The forward pass is plain ``nf_sample``, the
+        backward pass one ``nf_sample_vjp`` launch; issued on the current stream, no host synchronisation."""
+        from .autograd import sample_torch
+        return sample_torch(self, yy, eps, seed, eps_std, nlf0, nlf1, iso, cam)
+
 
 def default_hps(**kw) -> SimpleNamespace:
     """The hyper-parameters the hot path reads, with the shipped values
