@@ -12,6 +12,8 @@
 // (the fp32 round trip through the stack loses ~1e-4 of x, which the leading sdn layer's gy term would inherit).
 // LDS: the forward kernel's two zero-bordered tiles (z0: 2 words, relu(h2): w words per tile pixel); in the backward sweep the
 // relu(h2) tile is overlaid, once consumed, by d(shift, raw) (4 words of a pixel's w) and then by d h1 (w words).
+// The frame (conditioning, loads, the pointwise layers in the NLL direction) and the gate record with the coupling CNN are
+// nf_grad_common.h's: the frame is shared with all gradient kernels, the coupling CNN with nf_sample_grad_kernel.
 //
 // TILED (NF_CFG_GRAD_TILED, nf_device.h "gradient tiles"): a "patch" of the launch is one H x W tile of an img_H x img_W image and
 // `prog` one SEGMENT of the program.  The tile loads the tensor in front of the segment (z_in), runs the same forward sweep over
@@ -27,17 +29,16 @@
 #include "nf_dev_util.h"
 #include "nf_internal.h"
 #include "nf_flow_common.h"   // flow_launch: the persistent-grid launcher
+#include "nf_grad_common.h"   // GradFrame, GradCoupling
 
 namespace {
 
 template <int WIDTH, int THREADS, int PX, bool TILED = false>
 __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, const NfGradLaunch a)
 {
-    static_assert(WIDTH == 4 || WIDTH == 8 || WIDTH == 16 || WIDTH == 32, "gate sets of WIDTH bits must tile a 32-bit word");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NPIX = THREADS * PX;
     constexpr int NW = THREADS / 64;
-    constexpr int SPW = 32 / WIDTH;   // gate sets per word
     const int H = a.H, W = a.W, HW = H * W, Wp = W + 2;
     const int tile_px = ((H + 2) * Wp + 1) & ~1;
     float2 *const t0 = reinterpret_cast<float2 *>(smem);   // z0 tile [tile_px] float2
@@ -45,6 +46,7 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
     uint32_t *const gates = reinterpret_cast<uint32_t *>(th + (size_t)tile_px * WIDTH);   // [gate_words][NPIX]
     float *const red = reinterpret_cast<float *>(gates + (size_t)a.gate_words * NPIX);    // [2][NW]
 
+    // (slot set-up and carve-up stand inline here and in nf_sample_grad_kernel: as a shared helper they moved instructions)
     const int t = threadIdx.x;
     int lidx[PX], gidx[PX], bmask[PX];
     bool act[PX];
@@ -93,202 +95,24 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
         const float4 *const x4 = reinterpret_cast<const float4 *>(TILED ? a.z_in : a.x) + patch_off;
         const float4 *const y4 = reinterpret_cast<const float4 *>(a.y) + patch_off;   // (not dereferenced when a.y is null)
         const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + img;
-        auto cond_a = [&](int slot) { return a.cond_rows ? crow->a[slot & 3] : a.cond_a[slot & 3]; };
-        auto cond_b = [&](int slot) { return a.cond_rows ? crow->b[slot & 3] : a.cond_b[slot & 3]; };
-
-        auto load_x = [&](float (&z)[PX][4]) {
-#pragma unroll
-            for (int k = 0; k < PX; ++k) {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (act[k]) v = x4[gidx[k]];
-                z[k][0] = v.x; z[k][1] = v.y; z[k][2] = v.z; z[k][3] = v.w;
-            }
-        };
-        auto load_y = [&](float (&yy)[PX][4]) {
-#pragma unroll
-            for (int k = 0; k < PX; ++k) {
-                float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
-                if (act[k]) v = y4[gidx[k]];
-                yy[k][0] = v.x; yy[k][1] = v.y; yy[k][2] = v.z; yy[k][3] = v.w;
-            }
-        };
-
-        // the pointwise ops in the NLL direction (nf_flow_kernel's scalar path); ld: this thread's share of the log-det
-        auto pointwise_fwd = [&](int op, float (&z)[PX][4], float &ld) {
-            const int type = prog.ops[op].type;
-            const int off = prog.ops[op].off;
-            if (type == NF_OP_MIX) {
-                const cfloat_p P = (cfloat_p)(a.params + off);
-                float m[16];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) m[i] = P[i];
-#pragma unroll
-                for (int k = 0; k < PX; ++k) {
-                    float o[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float s = z[k][0] * m[j];
-                        s = fmaf(z[k][1], m[4 + j], s);
-                        s = fmaf(z[k][2], m[8 + j], s);
-                        s = fmaf(z[k][3], m[12 + j], s);
-                        o[j] = s;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) z[k][j] = o[j];
-                }
-            } else if (type == NF_OP_SDN_DIV) {
-                const float ck1 = cond_a(off), cb2 = cond_b(off);
-                float yy[PX][4];
-                load_y(yy);
-#pragma unroll
-                for (int k = 0; k < PX; ++k) {
-                    float rp = 1.0f;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const float r = __builtin_amdgcn_rsqf(fmaf(yy[k][c], ck1, cb2));
-                        z[k][c] *= r;
-                        rp = c == 0 ? r : rp * r;
-                    }
-                    if (act[k]) ld = fmaf(0.6931471805599453f, __builtin_amdgcn_logf(rp), ld);   // -sum_c log scale_c
-                }
-            } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : cond_a(off);
-#pragma unroll
-                for (int k = 0; k < PX; ++k)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) z[k][c] *= s;
-            }
-        };
-
-        // gate set s of pixel slot k (nf_device.h)
-        auto gate_put = [&](int s, int k, uint32_t bits) {
-            uint32_t *const p = gates + (size_t)(s / SPW) * NPIX + t + THREADS * k;
-            const int sh = (s % SPW) * WIDTH;
-            *p = sh == 0 ? bits : (*p | (bits << sh));
-        };
-        auto gate_get = [&](int s, int k) { return gates[(size_t)(s / SPW) * NPIX + t + THREADS * k] >> ((s % SPW) * WIDTH); };
-
-        // The coupling CNN on z0 = z[.][0:2]: o = (shift, raw log-scale).  RECORD: the forward sweep — ReLU by sign, gates written
-        // to the record; otherwise the backward sweep's recomputation on the rebuilt z0 — ReLU by the recorded gates.
-        // Barriers: the z0 tile is free on entry (its readers passed the barrier in here), and the barrier behind its
-        // publication also separates the previous readers of the h2 tile from this call's writes to it.
-        auto coupling_cnn = [&](int off, int cidx, auto record, const float (&z)[PX][4], float (&o)[PX][4]) {
-            constexpr bool RECORD = decltype(record)::value;
-            const cfloat_p P = (cfloat_p)(a.params + off);
-#pragma unroll
-            for (int k = 0; k < PX; ++k)
-                if (act[k]) t0[lidx[k]] = make_float2(z[k][0], z[k][1]);
-            __syncthreads();
-            {
-                const cfloat_p W1 = P + nf_cpl_off_W1(WIDTH);
-                const cfloat_p B1 = P + nf_cpl_off_B1(WIDTH);
-                const cfloat_p W2 = P + nf_cpl_off_W2(WIDTH);
-                const cfloat_p B2 = P + nf_cpl_off_B2(WIDTH);
-                float h1[PX][WIDTH];
-#pragma unroll
-                for (int k = 0; k < PX; ++k)
-#pragma unroll
-                    for (int j = 0; j < WIDTH; ++j) h1[k][j] = B1[j];
-#pragma unroll 1
-                for (int di = 0; di < 3; ++di) {
-                    const cfloat_p W1r = W1 + di * (3 * 2 * WIDTH);
-                    const int roff = (di - 1) * Wp - 1;
-#pragma unroll
-                    for (int dj = 0; dj < 3; ++dj) {
-#pragma unroll
-                        for (int k = 0; k < PX; ++k) {
-                            const float2 v = t0[lidx[k] + roff + dj];
-#pragma unroll
-                            for (int j = 0; j < WIDTH; ++j) {
-                                h1[k][j] = fmaf(v.x, W1r[(dj * 2 + 0) * WIDTH + j], h1[k][j]);
-                                h1[k][j] = fmaf(v.y, W1r[(dj * 2 + 1) * WIDTH + j], h1[k][j]);
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < PX; ++k) {
-                    uint32_t g1 = 0u, g2 = 0u;
-                    if constexpr (RECORD) {
-#pragma unroll
-                        for (int i = 0; i < WIDTH; ++i) g1 |= (__float_as_int(h1[k][i]) > 0 ? 1u : 0u) << i;
-                        gate_put(2 * cidx, k, g1);
-                    } else {
-                        g1 = gate_get(2 * cidx, k);
-                        g2 = gate_get(2 * cidx + 1, k);
-                    }
-                    float h2[WIDTH];
-#pragma unroll
-                    for (int j = 0; j < WIDTH; ++j) h2[j] = B2[j];
-#pragma unroll
-                    for (int i = 0; i < WIDTH; ++i) {
-                        const float hi = RECORD ? nf_relu(h1[k][i]) : ((g1 >> i) & 1u) ? h1[k][i] : 0.0f;
-#pragma unroll
-                        for (int j = 0; j < WIDTH; ++j) h2[j] = fmaf(hi, W2[i * WIDTH + j], h2[j]);
-                    }
-                    if constexpr (RECORD) {
-#pragma unroll
-                        for (int i = 0; i < WIDTH; ++i) g2 |= (__float_as_int(h2[i]) > 0 ? 1u : 0u) << i;
-                        gate_put(2 * cidx + 1, k, g2);
-                    }
-                    if (act[k]) {
-                        float4 *const dst = reinterpret_cast<float4 *>(th + (size_t)lidx[k] * WIDTH);
-#pragma unroll
-                        for (int q = 0; q < WIDTH / 4; ++q) {
-                            float v[4];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                v[e] = RECORD ? nf_relu(h2[4 * q + e]) : ((g2 >> (4 * q + e)) & 1u) ? h2[4 * q + e] : 0.0f;
-                            dst[q] = make_float4(v[0], v[1], v[2], v[3]);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            {
-                const cfloat_p W3 = P + nf_cpl_off_W3(WIDTH);
-#pragma unroll
-                for (int k = 0; k < PX; ++k) {
-                    const float4 e = *reinterpret_cast<const float4 *>(a.params + off + nf_cpl_off_E(WIDTH) + 4 * bmask[k]);
-                    o[k][0] = e.x; o[k][1] = e.y; o[k][2] = e.z; o[k][3] = e.w;
-                }
-#pragma unroll 1
-                for (int di = 0; di < 3; ++di) {
-                    const cfloat_p W3r = W3 + di * (3 * WIDTH * 4);
-                    const int roff = (di - 1) * Wp - 1;
-#pragma unroll
-                    for (int dj = 0; dj < 3; ++dj) {
-#pragma unroll
-                        for (int q = 0; q < WIDTH / 4; ++q) {
-#pragma unroll
-                            for (int k = 0; k < PX; ++k) {
-                                const float4 hv = *reinterpret_cast<const float4 *>(th + (size_t)(lidx[k] + roff + dj) * WIDTH + 4 * q);
-                                const float hh[4] = {hv.x, hv.y, hv.z, hv.w};
-#pragma unroll
-                                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                                    for (int j = 0; j < 4; ++j) o[k][j] = fmaf(hh[i], W3r[(dj * WIDTH + 4 * q + i) * 4 + j], o[k][j]);
-                            }
-                        }
-                    }
-                }
-            }
-        };
+        const GradSlotPix<PX> pix = {act, gidx};
+        const GradFrame<PX, NfGradLaunch, GradSlotPix<PX>> F = {prog, a, pix, crow, patch_off, x4, y4};
+        const GradCoupling<WIDTH, THREADS, PX, NfGradLaunch, false> cpl = {a, act, t0, lidx, Wp, gates, t, th, bmask};
 
         // ---- forward sweep ----
         float z[PX][4];
-        load_x(z);
+        F.load_x(z);
         float ld = 0.0f;
         {
             int cidx = 0;
             for (int op = 0; op < n_ops; ++op) {
                 if (prog.ops[op].type != NF_OP_COUPLING_FWD) {
-                    pointwise_fwd(op, z, ld);
+                    F.pointwise_fwd(op, z, ld);
                     continue;
                 }
                 const cfloat_p P = (cfloat_p)(a.params + prog.ops[op].off);
                 float o[PX][4];
-                coupling_cnn(prog.ops[op].off, cidx, std::true_type{}, z, o);
+                cpl.template cnn<true>(prog.ops[op].off, cidx, z, o);
                 const float sc = P[nf_cpl_off_S(WIDTH)];
 #pragma unroll
                 for (int k = 0; k < PX; ++k) {
@@ -364,7 +188,7 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
                 --cidx;
                 const cfloat_p P = (cfloat_p)(a.params + off);
                 float o[PX][4];
-                coupling_cnn(off, cidx, std::false_type{}, z, o);
+                cpl.template cnn<false>(off, cidx, z, o);
                 const float sc = P[nf_cpl_off_S(WIDTH)];
                 float d[PX][4];   // d nll / d (shift, raw)
 #pragma unroll
@@ -382,6 +206,7 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
                         z[k][2 + c] = z1;
                     }
                 }
+                // (the transposed pass stands inline here and in nf_sample_grad_kernel: as a shared helper it moved instructions)
                 __syncthreads();   // relu(h2) consumed: d(shift, raw) overlays it
 #pragma unroll
                 for (int k = 0; k < PX; ++k)
@@ -418,7 +243,7 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
                     const cfloat_p W2 = P + nf_cpl_off_W2(WIDTH);
 #pragma unroll
                     for (int k = 0; k < PX; ++k) {
-                        const uint32_t g1 = gate_get(2 * cidx, k), g2 = gate_get(2 * cidx + 1, k);
+                        const uint32_t g1 = cpl.gate_get(2 * cidx, k), g2 = cpl.gate_get(2 * cidx + 1, k);
                         float d2[WIDTH];
 #pragma unroll
                         for (int j = 0; j < WIDTH; ++j) d2[j] = ((g2 >> j) & 1u) ? dh[k][j] : 0.0f;
@@ -497,14 +322,14 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
                 }
             } else if (type == NF_OP_SDN_DIV) {
                 // scale s = sqrt(v), v = a y + b:  z_in = z s,  g_in = g / s,  gy += (a / 2 v) (1 - g_out z_out)
-                const float ck1 = cond_a(off), cb2 = cond_b(off);
+                const float ck1 = F.cond_a(off), cb2 = F.cond_b(off);
                 if (op < first_cpl) {   // in front of the first coupling: the op's output, forward from the loaded x
                     float dummy = 0.0f;
-                    load_x(z);
-                    for (int q = 0; q <= op; ++q) pointwise_fwd(q, z, dummy);
+                    F.load_x(z);
+                    for (int q = 0; q <= op; ++q) F.pointwise_fwd(q, z, dummy);
                 }
                 float yy[PX][4];
-                load_y(yy);
+                F.load_y(yy);
 #pragma unroll
                 for (int k = 0; k < PX; ++k)
 #pragma unroll
@@ -516,7 +341,7 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
                         z[k][c] *= __builtin_amdgcn_sqrtf(v);
                     }
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : cond_a(off);
+                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : F.cond_a(off);
                 const float si = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[1] : 1.0f / s;
 #pragma unroll
                 for (int k = 0; k < PX; ++k)
@@ -568,7 +393,7 @@ __global__ __launch_bounds__(THREADS) void nf_grad_kernel(const NfProgram prog, 
     }
 }
 
-template <int WIDTH, int THREADS, int PX, bool TILED = false>
+template <int WIDTH, int THREADS, int PX, bool TILED>
 hipError_t launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
 {
     int dev = 0;
@@ -576,62 +401,46 @@ hipError_t launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cu, s
     return flow_launch<&nf_grad_kernel<WIDTH, THREADS, PX, TILED>>(THREADS, lds, prog, a, n_cu, dev, stream);
 }
 
-template <int WIDTH>
+// TILED: tiles are at most 32x32 (nf_device.h, NF_GRAD_TILE) — the three geometries that hold them without scratch, widths 4 / 8 / 16
+template <int WIDTH, bool TILED>
 hipError_t dispatch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
 {
     const int hw = a.H * a.W;
-    if (hw <= 64) return launch_grad<WIDTH, 64, 1>(prog, a, n_cu, lds, stream);
-    if (hw <= 256) return launch_grad<WIDTH, 256, 1>(prog, a, n_cu, lds, stream);
-    if constexpr (WIDTH >= 32) {
-        if (hw <= 1024) return launch_grad<WIDTH, 1024, 1>(prog, a, n_cu, lds, stream);
-    } else {
-        if (hw <= 1024) return launch_grad<WIDTH, 256, 4>(prog, a, n_cu, lds, stream);
-        if constexpr (WIDTH <= 8) {
-            if (hw <= 4096) return launch_grad<WIDTH, 1024, 4>(prog, a, n_cu, lds, stream);
+    if constexpr (!TILED || WIDTH <= 16) {
+        if (hw <= 64) return launch_grad<WIDTH, 64, 1, TILED>(prog, a, n_cu, lds, stream);
+        if (hw <= 256) return launch_grad<WIDTH, 256, 1, TILED>(prog, a, n_cu, lds, stream);
+        if constexpr (WIDTH >= 32) {
+            if (hw <= 1024) return launch_grad<WIDTH, 1024, 1, TILED>(prog, a, n_cu, lds, stream);
+        } else {
+            if (hw <= 1024) return launch_grad<WIDTH, 256, 4, TILED>(prog, a, n_cu, lds, stream);
+            if constexpr (WIDTH <= 8 && !TILED) {
+                if (hw <= 4096) return launch_grad<WIDTH, 1024, 4, TILED>(prog, a, n_cu, lds, stream);
+            }
         }
     }
     return hipErrorInvalidValue;
 }
 
-// tiles are at most 32x32 (nf_device.h, NF_GRAD_TILE): the three geometries that hold them without scratch, widths 4 / 8 / 16
-template <int WIDTH>
-hipError_t dispatch_grad_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
+template <bool TILED>
+hipError_t dispatch_grad_width(const NfProgram &prog, const NfGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
 {
-    const int hw = a.H * a.W;
-    if (hw <= 64) return launch_grad<WIDTH, 64, 1, true>(prog, a, n_cu, lds, stream);
-    if (hw <= 256) return launch_grad<WIDTH, 256, 1, true>(prog, a, n_cu, lds, stream);
-    if (hw <= 1024) return launch_grad<WIDTH, 256, 4, true>(prog, a, n_cu, lds, stream);
-    return hipErrorInvalidValue;
+    switch (prog.width) {
+    case 4: return dispatch_grad<4, TILED>(prog, a, n_cu, lds, stream);
+    case 8: return dispatch_grad<8, TILED>(prog, a, n_cu, lds, stream);
+    case 16: return dispatch_grad<16, TILED>(prog, a, n_cu, lds, stream);
+    case 32: return dispatch_grad<32, TILED>(prog, a, n_cu, lds, stream);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace
 
-// entry point used by nf_host.hip (which has checked the supported set: nf_grad_supported)
-hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream)
+hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, bool tiled, int n_cpl, int n_cu, hipStream_t stream)
 {
-    const size_t lds = sizeof(float) * nf_grad_lds_floats(a.H, a.W, prog.width, n_cpl);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    switch (prog.width) {
-    case 4: return dispatch_grad<4>(prog, a, n_cu, lds, stream);
-    case 8: return dispatch_grad<8>(prog, a, n_cu, lds, stream);
-    case 16: return dispatch_grad<16>(prog, a, n_cu, lds, stream);
-    case 32: return dispatch_grad<32>(prog, a, n_cu, lds, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-// one segment of a tiled call (NF_CFG_GRAD_TILED): `prog` = the segment's ops, a.H x a.W = the tile, a.B = images x tiles,
-// n_cpl = the couplings of the call's largest segment (what a.gate_words was sized by)
-hipError_t nf_launch_grad_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream)
-{
-    if (a.H > NF_GRAD_TILE || a.W > NF_GRAD_TILE || a.H > a.img_H || a.W > a.img_W || a.tile_ny < 1 || a.tile_nx < 1 || !a.z_in)
+    if (tiled && (a.H > NF_GRAD_TILE || a.W > NF_GRAD_TILE || a.H > a.img_H || a.W > a.img_W || a.tile_ny < 1 || a.tile_nx < 1 || !a.z_in))
         return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * nf_grad_lds_floats(a.H, a.W, prog.width, n_cpl);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    switch (prog.width) {
-    case 4: return dispatch_grad_tiled<4>(prog, a, n_cu, lds, stream);
-    case 8: return dispatch_grad_tiled<8>(prog, a, n_cu, lds, stream);
-    case 16: return dispatch_grad_tiled<16>(prog, a, n_cu, lds, stream);
-    default: return hipErrorInvalidValue;
-    }
+    // (whole-patch instantiations first: the module keeps the kernels in the order profiles/grad_common_asm.txt was compared in)
+    return !tiled ? dispatch_grad_width<false>(prog, a, n_cu, lds, stream) : dispatch_grad_width<true>(prog, a, n_cu, lds, stream);
 }

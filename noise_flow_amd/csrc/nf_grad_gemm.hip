@@ -19,6 +19,7 @@
 // no gradient.  Everything in front of the first coupling is computed forward from the loaded x.
 // Beyond 32x32 (NF_CFG_GRAD_TILED_GEMM) the TILED instantiations run the same sweeps on one tile of an image and one segment of the
 // program per launch patch, as nf_grad_wide_kernel<.., TILED> does at width 32.
+// Conditioning, loads and the pointwise layers in the NLL direction are nf_grad_common.h's GradFrame, as in every gradient kernel.
 // Weights are not staged in LDS at any width: the band takes 128 KiB of the CU's 160, every weight is consumed by exactly one
 // wavefront of the workgroup, and at widths 64 / 128 a coupling's block (66 / 195 KiB) is L2-resident like the 2.3 MiB at 512.
 #include <hip/hip_runtime.h>
@@ -30,6 +31,7 @@
 #include "nf_dev_util.h"
 #include "nf_internal.h"
 #include "nf_gemm_common.h"   // GT, GW, v16f, ldg4, gemm_acc_bias
+#include "nf_grad_common.h"   // GradFrame
 
 namespace {
 
@@ -175,72 +177,8 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
         const float4 *const x4 = reinterpret_cast<const float4 *>(TILED ? a.z_in : a.x) + patch_off;
         const float4 *const y4 = reinterpret_cast<const float4 *>(a.y) + patch_off;   // (not dereferenced when a.y is null)
         const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + img;
-        auto cond_a = [&](int slot) { return a.cond_rows ? crow->a[slot & 3] : a.cond_a[slot & 3]; };
-        auto cond_b = [&](int slot) { return a.cond_rows ? crow->b[slot & 3] : a.cond_b[slot & 3]; };
-
-        auto load_x = [&](float (&z)[OWN][4]) {
-#pragma unroll
-            for (int m = 0; m < OWN; ++m) {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (act[m]) v = x4[gidx_of(m)];
-                z[m][0] = v.x; z[m][1] = v.y; z[m][2] = v.z; z[m][3] = v.w;
-            }
-        };
-        auto load_y = [&](float (&yy)[OWN][4]) {
-#pragma unroll
-            for (int m = 0; m < OWN; ++m) {
-                float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
-                if (act[m]) v = y4[gidx_of(m)];
-                yy[m][0] = v.x; yy[m][1] = v.y; yy[m][2] = v.z; yy[m][3] = v.w;
-            }
-        };
-
-        // the pointwise ops in the NLL direction, as nf_grad_kernel / nf_grad_wide_kernel; ld: this thread's share of the log-det
-        auto pointwise_fwd = [&](int op, float (&z)[OWN][4], float &ld) {
-            const int type = prog.ops[op].type;
-            const int off = prog.ops[op].off;
-            if (type == NF_OP_MIX) {
-                const cfloat_p P = (cfloat_p)(a.params + off);
-                float mm[16];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) mm[i] = P[i];
-#pragma unroll
-                for (int m = 0; m < OWN; ++m) {
-                    float o[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float s = z[m][0] * mm[j];
-                        s = fmaf(z[m][1], mm[4 + j], s);
-                        s = fmaf(z[m][2], mm[8 + j], s);
-                        s = fmaf(z[m][3], mm[12 + j], s);
-                        o[j] = s;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) z[m][j] = o[j];
-                }
-            } else if (type == NF_OP_SDN_DIV) {
-                const float ck1 = cond_a(off), cb2 = cond_b(off);
-                float yy[OWN][4];
-                load_y(yy);
-#pragma unroll
-                for (int m = 0; m < OWN; ++m) {
-                    float rp = 1.0f;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float r = __builtin_amdgcn_rsqf(fmaf(yy[m][q], ck1, cb2));
-                        z[m][q] *= r;
-                        rp = q == 0 ? r : rp * r;
-                    }
-                    if (act[m]) ld = fmaf(0.6931471805599453f, __builtin_amdgcn_logf(rp), ld);   // -sum_c log scale_c
-                }
-            } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : cond_a(off);
-#pragma unroll
-                for (int m = 0; m < OWN; ++m)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) z[m][q] *= s;
-            }
-        };
+        const GradPix<OWN, decltype(gidx_of)> pix = {act, gidx_of};
+        const GradFrame<OWN, NfGradLaunch, GradPix<OWN, decltype(gidx_of)>> F = {prog, a, pix, crow, patch_off, x4, y4};
 
         // The coupling CNN on z0 = z[.][0:2]: o = (shift, raw log-scale) of the owned pixels.  RECORD: the forward sweep — ReLU by
         // sign, gate bits written; otherwise the backward sweep's recomputation on the rebuilt z0 — ReLU by the recorded bits.
@@ -512,13 +450,13 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
 
         // ---- forward sweep ----
         float z[OWN][4];
-        load_x(z);
+        F.load_x(z);
         float ld = 0.0f;
         {
             int cidx = 0;
             for (int op = 0; op < n_ops; ++op) {
                 if (prog.ops[op].type != NF_OP_COUPLING_FWD) {
-                    pointwise_fwd(op, z, ld);
+                    F.pointwise_fwd(op, z, ld);
                     continue;
                 }
                 const cfloat_p P = (cfloat_p)(a.params + prog.ops[op].off);
@@ -658,14 +596,14 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
                 }
             } else if (type == NF_OP_SDN_DIV) {
                 // scale s = sqrt(v), v = a y + b:  z_in = z s,  g_in = g / s,  gy += (a / 2 v) (1 - g_out z_out)
-                const float ck1 = cond_a(off), cb2 = cond_b(off);
+                const float ck1 = F.cond_a(off), cb2 = F.cond_b(off);
                 if (op < first_cpl) {   // in front of the first coupling: the op's output, forward from the loaded x
                     float dummy = 0.0f;
-                    load_x(z);
-                    for (int q = 0; q <= op; ++q) pointwise_fwd(q, z, dummy);
+                    F.load_x(z);
+                    for (int q = 0; q <= op; ++q) F.pointwise_fwd(q, z, dummy);
                 }
                 float yy[OWN][4];
-                load_y(yy);
+                F.load_y(yy);
 #pragma unroll
                 for (int m = 0; m < OWN; ++m)
 #pragma unroll
@@ -677,7 +615,7 @@ __global__ __launch_bounds__(GT) void nf_grad_gemm_kernel(const NfProgram prog, 
                         z[m][q] *= __builtin_amdgcn_sqrtf(v);
                     }
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : cond_a(off);
+                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : F.cond_a(off);
                 const float si = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[1] : 1.0f / s;
 #pragma unroll
                 for (int m = 0; m < OWN; ++m)
@@ -746,6 +684,14 @@ hipError_t launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, int gr
     return hipGetLastError();
 }
 
+template <int WP>
+hipError_t launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, bool tiled, int groups, size_t lds, uint16_t *scratch, size_t scratch_halves,
+                            hipStream_t stream)
+{
+    return tiled ? launch_grad_gemm<WP, true>(prog, a, groups, lds, scratch, scratch_halves, stream)
+                 : launch_grad_gemm<WP, false>(prog, a, groups, lds, scratch, scratch_halves, stream);
+}
+
 }  // namespace
 
 // the persistent grid of the kernel: one workgroup per CU (the band takes most of a CU's LDS), never more than patches
@@ -756,39 +702,21 @@ int nf_grad_gemm_groups(int64_t B, int n_cu)
     return groups < 1 ? 1 : (int)groups;
 }
 
-// entry point used by nf_host.hip (which has checked the supported set: grad_support): programs over the GEMM gradient block
-// (nf_gemm_layout.h, NFGG_*); `scratch` holds nf_grad_gemm_groups(B, n_cu) x nfgg_gate_halves(H W, width, n_cpl) uint16
-hipError_t nf_launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes, hipStream_t stream)
+// programs over the GEMM gradient block (nf_gemm_layout.h, NFGG_*).  A tiled segment with more couplings than n_cpl, or a buffer too
+// small, is refused before anything is enqueued.
+hipError_t nf_launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, bool tiled, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes,
+                               hipStream_t stream)
 {
+    static_assert(NF_GRAD_TILE == 32, "a tile is a patch the whole-patch geometry holds");
     const int wp = prog.width;
     if ((wp != 64 && wp != 128 && wp != 256 && wp != 512) || a.H < 1 || a.W < 1 || a.H > 32 || a.W > 32 || n_cpl < 0 || n_cpl > NFGG_MAX_COUPLINGS)
         return hipErrorInvalidValue;
-    const int groups = nf_grad_gemm_groups(a.B, n_cu);
-    const size_t halves = nfgg_gate_halves(a.H * a.W, wp, n_cpl);
-    if (halves && (!scratch || scratch_bytes < (size_t)groups * halves * sizeof(uint16_t))) return hipErrorInvalidValue;
-    const size_t lds = sizeof(float) * nfgg_lds_floats(a.H, a.W);
-    if (lds > FLOW_LDS_MAX) return hipErrorInvalidValue;
-    uint16_t *const s = static_cast<uint16_t *>(scratch);
-    switch (wp) {
-    case 64: return launch_grad_gemm<64>(prog, a, groups, lds, s, halves, stream);
-    case 128: return launch_grad_gemm<128>(prog, a, groups, lds, s, halves, stream);
-    case 256: return launch_grad_gemm<256>(prog, a, groups, lds, s, halves, stream);
-    default: return launch_grad_gemm<512>(prog, a, groups, lds, s, halves, stream);
+    if (tiled) {
+        if (a.H > a.img_H || a.W > a.img_W || a.tile_ny < 1 || a.tile_nx < 1 || a.tile_halo < 0 || !a.z_in) return hipErrorInvalidValue;
+        int seg_cpl = 0;
+        for (int i = 0; i < prog.n_ops; ++i) seg_cpl += prog.ops[i].type == NF_OP_COUPLING_FWD ? 1 : 0;
+        if (seg_cpl > n_cpl) return hipErrorInvalidValue;
     }
-}
-
-// one segment of a tiled call (NF_CFG_GRAD_TILED_GEMM): `prog` = the segment's ops, a.H x a.W = the tile, a.B = images x tiles,
-// n_cpl = the couplings of the call's largest segment: `scratch` holds nf_grad_gemm_groups(a.B, n_cu) x nfgg_gate_halves(H W, width,
-// n_cpl) uint16.  A segment with more couplings than that, or a buffer too small, is refused before anything is enqueued.
-hipError_t nf_launch_grad_gemm_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes, hipStream_t stream)
-{
-    const int wp = prog.width;
-    if ((wp != 64 && wp != 128 && wp != 256 && wp != 512) || a.H < 1 || a.W < 1 || a.H > NF_GRAD_TILE || a.W > NF_GRAD_TILE || a.H > a.img_H ||
-        a.W > a.img_W || a.tile_ny < 1 || a.tile_nx < 1 || a.tile_halo < 0 || !a.z_in || n_cpl < 0 || n_cpl > NFGG_MAX_COUPLINGS)
-        return hipErrorInvalidValue;
-    int seg_cpl = 0;
-    for (int i = 0; i < prog.n_ops; ++i) seg_cpl += prog.ops[i].type == NF_OP_COUPLING_FWD ? 1 : 0;
-    if (seg_cpl > n_cpl) return hipErrorInvalidValue;
     const int groups = nf_grad_gemm_groups(a.B, n_cu);
     const size_t halves = nfgg_gate_halves(a.H * a.W, wp, n_cpl);
     if (halves && (!scratch || scratch_bytes < (size_t)groups * halves * sizeof(uint16_t))) return hipErrorInvalidValue;
@@ -796,9 +724,9 @@ hipError_t nf_launch_grad_gemm_tiled(const NfProgram &prog, const NfGradLaunch &
     if (lds > FLOW_LDS_MAX) return hipErrorInvalidValue;
     uint16_t *const s = static_cast<uint16_t *>(scratch);
     switch (wp) {
-    case 64: return launch_grad_gemm<64, true>(prog, a, groups, lds, s, halves, stream);
-    case 128: return launch_grad_gemm<128, true>(prog, a, groups, lds, s, halves, stream);
-    case 256: return launch_grad_gemm<256, true>(prog, a, groups, lds, s, halves, stream);
-    default: return launch_grad_gemm<512, true>(prog, a, groups, lds, s, halves, stream);
+    case 64: return launch_grad_gemm<64>(prog, a, tiled, groups, lds, s, halves, stream);
+    case 128: return launch_grad_gemm<128>(prog, a, tiled, groups, lds, s, halves, stream);
+    case 256: return launch_grad_gemm<256>(prog, a, tiled, groups, lds, s, halves, stream);
+    default: return launch_grad_gemm<512>(prog, a, tiled, groups, lds, s, halves, stream);
     }
 }

@@ -17,6 +17,7 @@
 // table E is constant and has no gradient.  Everything in front of the first coupling is computed forward from the loaded x.
 // Beyond 32x32 (NF_CFG_GRAD_TILED_WIDE) the TILED instantiations run the same sweeps on one tile of an image and one segment of the
 // program per launch patch, as nf_grad_kernel<.., TILED> does at the narrower widths.
+// Conditioning, loads and the pointwise layers in the NLL direction are nf_grad_common.h's GradFrame, as in every gradient kernel.
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stdint.h>
@@ -26,6 +27,7 @@
 #include "nf_dev_util.h"
 #include "nf_internal.h"
 #include "nf_flow_common.h"   // flow_launch: the persistent-grid launcher
+#include "nf_grad_common.h"   // GradFrame
 
 namespace {
 
@@ -166,72 +168,8 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
         const float4 *const x4 = reinterpret_cast<const float4 *>(TILED ? a.z_in : a.x) + patch_off;
         const float4 *const y4 = reinterpret_cast<const float4 *>(a.y) + patch_off;   // (not dereferenced when a.y is null)
         const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + img;
-        auto cond_a = [&](int slot) { return a.cond_rows ? crow->a[slot & 3] : a.cond_a[slot & 3]; };
-        auto cond_b = [&](int slot) { return a.cond_rows ? crow->b[slot & 3] : a.cond_b[slot & 3]; };
-
-        auto load_x = [&](float (&z)[OWN][4]) {
-#pragma unroll
-            for (int m = 0; m < OWN; ++m) {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (act[m]) v = x4[gidx_of(m)];
-                z[m][0] = v.x; z[m][1] = v.y; z[m][2] = v.z; z[m][3] = v.w;
-            }
-        };
-        auto load_y = [&](float (&yy)[OWN][4]) {
-#pragma unroll
-            for (int m = 0; m < OWN; ++m) {
-                float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
-                if (act[m]) v = y4[gidx_of(m)];
-                yy[m][0] = v.x; yy[m][1] = v.y; yy[m][2] = v.z; yy[m][3] = v.w;
-            }
-        };
-
-        // the pointwise ops in the NLL direction, as nf_grad_kernel; ld: this lane's share of the log-det
-        auto pointwise_fwd = [&](int op, float (&z)[OWN][4], float &ld) {
-            const int type = prog.ops[op].type;
-            const int off = prog.ops[op].off;
-            if (type == NF_OP_MIX) {
-                const cfloat_p P = (cfloat_p)(a.params + off);
-                float mm[16];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) mm[i] = P[i];
-#pragma unroll
-                for (int m = 0; m < OWN; ++m) {
-                    float o[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float s = z[m][0] * mm[j];
-                        s = fmaf(z[m][1], mm[4 + j], s);
-                        s = fmaf(z[m][2], mm[8 + j], s);
-                        s = fmaf(z[m][3], mm[12 + j], s);
-                        o[j] = s;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) z[m][j] = o[j];
-                }
-            } else if (type == NF_OP_SDN_DIV) {
-                const float ck1 = cond_a(off), cb2 = cond_b(off);
-                float yy[OWN][4];
-                load_y(yy);
-#pragma unroll
-                for (int m = 0; m < OWN; ++m) {
-                    float rp = 1.0f;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float r = __builtin_amdgcn_rsqf(fmaf(yy[m][q], ck1, cb2));
-                        z[m][q] *= r;
-                        rp = q == 0 ? r : rp * r;
-                    }
-                    if (act[m]) ld = fmaf(0.6931471805599453f, __builtin_amdgcn_logf(rp), ld);   // -sum_c log scale_c
-                }
-            } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : cond_a(off);
-#pragma unroll
-                for (int m = 0; m < OWN; ++m)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) z[m][q] *= s;
-            }
-        };
+        const GradPix<OWN, decltype(gidx_of)> pix = {act, gidx_of};
+        const GradFrame<OWN, NfGradLaunch, GradPix<OWN, decltype(gidx_of)>> F = {prog, a, pix, crow, patch_off, x4, y4};
 
         // The coupling CNN on z0 = z[.][0:2]: o = (shift, raw log-scale) of the owned pixels.  RECORD: the forward sweep — ReLU by
         // sign, gate word written; otherwise the backward sweep's recomputation on the rebuilt z0 — ReLU by the recorded word.
@@ -335,13 +273,13 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
 
         // ---- forward sweep ----
         float z[OWN][4];
-        load_x(z);
+        F.load_x(z);
         float ld = 0.0f;
         {
             int cidx = 0;
             for (int op = 0; op < n_ops; ++op) {
                 if (prog.ops[op].type != NF_OP_COUPLING_FWD) {
-                    pointwise_fwd(op, z, ld);
+                    F.pointwise_fwd(op, z, ld);
                     continue;
                 }
                 const cfloat_p P = (cfloat_p)(a.params + prog.ops[op].off);
@@ -549,14 +487,14 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
                 }
             } else if (type == NF_OP_SDN_DIV) {
                 // scale s = sqrt(v), v = a y + b:  z_in = z s,  g_in = g / s,  gy += (a / 2 v) (1 - g_out z_out)
-                const float ck1 = cond_a(off), cb2 = cond_b(off);
+                const float ck1 = F.cond_a(off), cb2 = F.cond_b(off);
                 if (op < first_cpl) {   // in front of the first coupling: the op's output, forward from the loaded x
                     float dummy = 0.0f;
-                    load_x(z);
-                    for (int q = 0; q <= op; ++q) pointwise_fwd(q, z, dummy);
+                    F.load_x(z);
+                    for (int q = 0; q <= op; ++q) F.pointwise_fwd(q, z, dummy);
                 }
                 float yy[OWN][4];
-                load_y(yy);
+                F.load_y(yy);
 #pragma unroll
                 for (int m = 0; m < OWN; ++m)
 #pragma unroll
@@ -568,7 +506,7 @@ __global__ __launch_bounds__(64 * NW) void nf_grad_wide_kernel(const NfProgram p
                         z[m][q] *= __builtin_amdgcn_sqrtf(v);
                     }
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : cond_a(off);
+                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : F.cond_a(off);
                 const float si = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[1] : 1.0f / s;
 #pragma unroll
                 for (int m = 0; m < OWN; ++m)
@@ -643,24 +581,14 @@ hipError_t dispatch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int 
 
 }  // namespace
 
-// entry point used by nf_host.hip (which has checked the supported set: nf_grad_supported): programs over the wide gradient block
-// (nf_device.h, NFGW_*), a.gate_words = nfgw_tpw(H) words per coupling
-hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream)
+// programs over the wide gradient block (nf_device.h, NFGW_*), a.gate_words = nfgw_tpw(H) words per coupling; tiled: n_cpl is at most 3
+// (LDS <= 81 KiB)
+hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, bool tiled, int n_cpl, int n_cu, hipStream_t stream)
 {
+    static_assert(NF_GRAD_TILE == 32, "a tile is a patch the whole-patch geometry holds");
     if (prog.width != 32 || a.H < 1 || a.W < 1 || a.H > 32 || a.W > 32 || a.gate_words != nfgw_tpw(a.H) * n_cpl) return hipErrorInvalidValue;
+    if (tiled && (a.H > a.img_H || a.W > a.img_W || a.tile_ny < 1 || a.tile_nx < 1 || !a.z_in)) return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * nfgw_lds_floats(a.H, n_cpl);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    return dispatch_grad_wide<false>(prog, a, n_cu, lds, stream);
-}
-
-// one segment of a tiled call (NF_CFG_GRAD_TILED_WIDE): `prog` = the segment's ops, a.H x a.W = the tile, a.B = images x tiles,
-// n_cpl = the couplings of the call's largest segment (what a.gate_words was sized by; at most 3: LDS <= 81 KiB)
-hipError_t nf_launch_grad_wide_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream)
-{
-    if (prog.width != 32 || a.H < 1 || a.W < 1 || a.H > NF_GRAD_TILE || a.W > NF_GRAD_TILE || a.H > a.img_H || a.W > a.img_W || a.tile_ny < 1 ||
-        a.tile_nx < 1 || !a.z_in || a.gate_words != nfgw_tpw(a.H) * n_cpl)
-        return hipErrorInvalidValue;
-    const size_t lds = sizeof(float) * nfgw_lds_floats(a.H, n_cpl);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    return dispatch_grad_wide<true>(prog, a, n_cu, lds, stream);
+    return tiled ? dispatch_grad_wide<true>(prog, a, n_cu, lds, stream) : dispatch_grad_wide<false>(prog, a, n_cu, lds, stream);
 }

@@ -47,14 +47,7 @@ hipError_t nf_launch_bs_finalize(double *stats, int w, double n, float *Wm, int 
 hipError_t nf_launch_tile_combine(const float *part, const NfTileParts &tp, int64_t B, double n, double ld_const, const nf_cond_row *cond_rows,
                                   uint32_t flags,
                                   float *nll_out, float *sd_out, float *ld_out, double *sums, hipStream_t stream);
-hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
-hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
-hipError_t nf_launch_grad_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
-hipError_t nf_launch_grad_wide_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
-hipError_t nf_launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes, hipStream_t stream);
-hipError_t nf_launch_grad_gemm_tiled(const NfProgram &prog, const NfGradLaunch &a, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes, hipStream_t stream);
-int nf_grad_gemm_groups(int64_t B, int n_cu);
-hipError_t nf_launch_sample_grad(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, hipStream_t stream);
+// (the gradient kernels' launchers: nf_internal.h)
 
 namespace {
 
@@ -1167,6 +1160,15 @@ static bool grad_path_is_wide(int path) { return path == NF_GRAD_PATH_WIDE32 || 
 static bool grad_path_is_gemm(int path) { return path == NF_GRAD_PATH_GEMM || path == NF_GRAD_PATH_TILED_GEMM; }
 static bool grad_path_is_tiled(int path) { return path == NF_GRAD_PATH_TILED || path == NF_GRAD_PATH_TILED_WIDE32 || path == NF_GRAD_PATH_TILED_GEMM; }
 
+// a.gate_words of a launch on `path`: the words of LDS gate record per pixel slot (scalar kernel) or per lane (matrix-core kernel) for
+// n_cpl couplings on patches / tiles of height H; the GEMM kernel keeps its record in device scratch
+static int grad_gate_words(int path, int H, int n_cpl, int width)
+{
+    return grad_path_is_gemm(path) ? 0 : grad_path_is_wide(path) ? nfgw_tpw(H) * n_cpl : nf_grad_gate_words(n_cpl, width);
+}
+
+static size_t round_up_256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
 // One coupling of the wide gradient block (nf_device.h, NFGW_*) from its generic block at width 32: the NF4_IMG_* image of the
 // forward chain without the 2 log2(e) factor, and the fetch-order images of the three transposed products.
 void relayout_coupling_grad_wide(const float *v1, float *out)
@@ -1726,8 +1728,8 @@ static size_t tiled_workspace_bytes(const nf_handle *h, int direction, int64_t B
     const int S = (int)b.segs.size();
     size_t part4 = 0;
     for (int s = 0; s < S; ++s) part4 += (size_t)B * b.segs[s].ny * b.segs[s].nx;
-    const size_t img = (((size_t)B * h->cfg.height * h->cfg.width * kC * sizeof(float)) + 255) & ~(size_t)255;
-    const size_t part = want_sums ? ((part4 * 4 * sizeof(float) + 255) & ~(size_t)255) : 0;
+    const size_t img = round_up_256((size_t)B * h->cfg.height * h->cfg.width * kC * sizeof(float));
+    const size_t part = want_sums ? round_up_256(part4 * 4 * sizeof(float)) : 0;
     return part + img * (size_t)(S - 1 < 2 ? (S - 1 < 0 ? 0 : S - 1) : 2);
 }
 
@@ -1905,7 +1907,7 @@ static int launch_tiled(nf_handle *h, int direction, NfLaunch &a, hipStream_t st
         if (B > (INT64_MAX / 64) / tp.nt[s]) return fail(NF_EINVAL, "B too large");
         part4 += B * tp.nt[s];
     }
-    const size_t img_bytes = (((size_t)B * h->cfg.height * h->cfg.width * kC * sizeof(float)) + 255) & ~(size_t)255;
+    const size_t img_bytes = round_up_256((size_t)B * h->cfg.height * h->cfg.width * kC * sizeof(float));
     float *part = nullptr, *scratch[2] = {nullptr, nullptr};
     hipError_t e = hipSuccess;
     nf_handle::Workspace *wsp = nullptr;
@@ -1915,7 +1917,7 @@ static int launch_tiled(nf_handle *h, int direction, NfLaunch &a, hipStream_t st
         char *q = wsp ? wsp->p : nullptr;
         if (want) {
             part = reinterpret_cast<float *>(q);
-            q += ((size_t)part4 * 4 * sizeof(float) + 255) & ~(size_t)255;
+            q += round_up_256((size_t)part4 * 4 * sizeof(float));
         }
         for (int i = 0; i < 2 && i < S - 1; ++i, q += img_bytes) scratch[i] = reinterpret_cast<float *>(q);
     }
@@ -2121,6 +2123,16 @@ int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float 
 }
 
 // ---- nf_nll_grad on tiles (NF_CFG_GRAD_TILED, NF_CFG_GRAD_TILED_WIDE, NF_CFG_GRAD_TILED_GEMM; nf_device.h, "gradient tiles") ----
+// One launch of the handle's gradient kernel: whole patches, or one segment of a tiled call (`prog` = the segment, n_cpl = the
+// couplings of the call's largest segment).  scratch / bytes: the GEMM kernel's gate records.
+static hipError_t grad_launch(const nf_handle *h, const NfProgram &prog, const NfGradLaunch &a, int n_cpl, void *scratch, size_t bytes, hipStream_t stream)
+{
+    const bool tiled = grad_path_is_tiled(h->grad_path);
+    if (grad_path_is_gemm(h->grad_path)) return nf_launch_grad_gemm(prog, a, tiled, n_cpl, h->n_cu, scratch, bytes, stream);
+    if (grad_path_is_wide(h->grad_path)) return nf_launch_grad_wide(prog, a, tiled, n_cpl, h->n_cu, stream);
+    return nf_launch_grad(prog, a, tiled, n_cpl, h->n_cu, stream);
+}
+
 // The forward launch of segment s runs on the forward direction's own tiles (tile_h x tile_w, halo 2 per coupling)
 static Built::TileSeg grad_fwd_seg(const nf_handle *h, int s)
 {
@@ -2131,7 +2143,7 @@ static Built::TileSeg grad_fwd_seg(const nf_handle *h, int s)
     return g;
 }
 
-static size_t grad_img_bytes(const nf_handle *h, int64_t B) { return (((size_t)B * h->cfg.height * h->cfg.width * kC * sizeof(float)) + 255) & ~(size_t)255; }
+static size_t grad_img_bytes(const nf_handle *h, int64_t B) { return round_up_256((size_t)B * h->cfg.height * h->cfg.width * kC * sizeof(float)); }
 
 // NF_GRAD_PATH_TILED_GEMM: the gate records of a call, one per WORKGROUP of its largest backward launch, each sized for the couplings
 // of the largest segment on one tile (nf_gemm_layout.h, nfgg_gate_halves: the function the kernel indexes by)
@@ -2141,7 +2153,7 @@ static size_t grad_tiled_gate_bytes(const nf_handle *h, int64_t B)
     int64_t most = 0;
     for (const Built::TileSeg &g : h->grad_segs) most = std::max<int64_t>(most, B * g.ny * g.nx);
     const int th = std::min(h->cfg.height, NF_GRAD_TILE), tw = std::min(h->cfg.width, NF_GRAD_TILE);
-    return ((size_t)nf_grad_gemm_groups(most, h->n_cu) * nfgg_gate_halves(th * tw, h->gprog.width, h->grad_seg_cpl) * sizeof(uint16_t) + 255) & ~(size_t)255;
+    return round_up_256((size_t)nf_grad_gemm_groups(most, h->n_cu) * nfgg_gate_halves(th * tw, h->gprog.width, h->grad_seg_cpl) * sizeof(uint16_t));
 }
 
 // scratch of one call: the forward launches' tile sums, the S - 1 tensors between two segments, two gradient tensors (ping-pong),
@@ -2151,8 +2163,7 @@ static size_t grad_workspace_bytes(const nf_handle *h, int64_t B)
 {
     if (h->grad_rc != NF_OK || B <= 0) return 0;
     if (h->grad_path == NF_GRAD_PATH_GEMM)   // the gate records: one per WORKGROUP of the launch, not per patch
-        return ((size_t)nf_grad_gemm_groups(B, h->n_cu) * nfgg_gate_halves(h->cfg.height * h->cfg.width, h->gprog.width, h->grad_n_cpl) * sizeof(uint16_t) + 255) &
-               ~(size_t)255;
+        return round_up_256((size_t)nf_grad_gemm_groups(B, h->n_cu) * nfgg_gate_halves(h->cfg.height * h->cfg.width, h->gprog.width, h->grad_n_cpl) * sizeof(uint16_t));
     if (!grad_path_is_tiled(h->grad_path)) return 0;
     const int S = (int)h->grad_segs.size();
     size_t part4 = 0;
@@ -2160,7 +2171,7 @@ static size_t grad_workspace_bytes(const nf_handle *h, int64_t B)
         const Built::TileSeg f = grad_fwd_seg(h, s);
         part4 += (size_t)B * f.ny * f.nx;
     }
-    return ((part4 * 4 * sizeof(float) + 255) & ~(size_t)255) + grad_img_bytes(h, B) * (size_t)(S - 1 + (S - 1 < 2 ? S - 1 : 2)) + grad_tiled_gate_bytes(h, B);
+    return round_up_256(part4 * 4 * sizeof(float)) + grad_img_bytes(h, B) * (size_t)(S - 1 + (S - 1 < 2 ? S - 1 : 2)) + grad_tiled_gate_bytes(h, B);
 }
 
 // Forward: the tiled launches of nf_nll cut at the gradient plan's boundaries, every tensor between two segments kept, and
@@ -2193,7 +2204,7 @@ static int grad_tiled(nf_handle *h, const float *x, const float *y, int64_t B, c
     const size_t img_bytes = grad_img_bytes(h, B);
     char *q = wsp->p;
     float *const part = reinterpret_cast<float *>(q);
-    q += ((size_t)part4 * 4 * sizeof(float) + 255) & ~(size_t)255;
+    q += round_up_256((size_t)part4 * 4 * sizeof(float));
     float *inter[NF_MAX_TILE_SEGS] = {}, *gbuf[2] = {nullptr, nullptr};
     for (int s = 0; s < S - 1; ++s, q += img_bytes) inter[s] = reinterpret_cast<float *>(q);
     for (int i = 0; i < 2 && i < S - 1; ++i, q += img_bytes) gbuf[i] = reinterpret_cast<float *>(q);
@@ -2233,8 +2244,7 @@ static int grad_tiled(nf_handle *h, const float *x, const float *y, int64_t B, c
         a.W = W < NF_GRAD_TILE ? W : NF_GRAD_TILE;
         a.img_H = H;
         a.img_W = W;
-        const bool wide = h->grad_path == NF_GRAD_PATH_TILED_WIDE32, gemm = h->grad_path == NF_GRAD_PATH_TILED_GEMM;
-        a.gate_words = gemm ? 0 : wide ? nfgw_tpw(a.H) * h->grad_seg_cpl : nf_grad_gate_words(h->grad_seg_cpl, h->gprog.width);
+        a.gate_words = grad_gate_words(h->grad_path, a.H, h->grad_seg_cpl, h->gprog.width);
         bool gy_written = false;
         for (int s = S - 1; s >= 0 && e == hipSuccess; --s) {
             const Built::TileSeg &g = h->grad_segs[s];
@@ -2262,9 +2272,7 @@ static int grad_tiled(nf_handle *h, const float *x, const float *y, int64_t B, c
             t.gy_out = wr ? gy_out : nullptr;
             t.tflags = wr && gy_written ? NF_GT_GY_ACC : 0u;
             gy_written = gy_written || wr;
-            e = gemm   ? nf_launch_grad_gemm_tiled(sp, t, h->grad_seg_cpl, h->n_cu, gate_rec, gate_room, st)
-                : wide ? nf_launch_grad_wide_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st)
-                       : nf_launch_grad_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st);
+            e = grad_launch(h, sp, t, h->grad_seg_cpl, gate_rec, gate_room, st);
         }
     }
     ws_release(h, wsp, st);
@@ -2339,26 +2347,18 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
     a.H = h->cfg.height;
     a.W = h->cfg.width;
     a.first_cpl = h->grad_first_cpl;
-    const bool wide = h->grad_path == NF_GRAD_PATH_WIDE32;
-    a.gate_words = wide ? nfgw_tpw(h->cfg.height) * h->grad_n_cpl : nf_grad_gate_words(h->grad_n_cpl, h->gprog.width);
+    a.gate_words = grad_gate_words(h->grad_path, h->cfg.height, h->grad_n_cpl, h->gprog.width);
     NfDeviceGuard guard;
     int rc = guard.enter(h->device);
     if (rc != NF_OK) return rc;
-    if (h->grad_path == NF_GRAD_PATH_GEMM) {
-        // the gate records live in a buffer of the handle's workspace set: one per call in flight, grown only by a call that needs
-        // more than any earlier one (nf_reserve_grad_workspace sizes it up front); everything else is enqueued
-        a.gate_words = 0;
-        const size_t need = grad_workspace_bytes(h, B);
-        nf_handle::Workspace *wsp = nullptr;
-        if ((rc = ws_acquire(h, need, (hipStream_t)stream, &wsp)) != NF_OK) return rc;
-        const hipError_t eg = nf_launch_grad_gemm(h->gprog, a, h->grad_n_cpl, h->n_cu, wsp ? wsp->p : nullptr, wsp ? wsp->bytes : 0, (hipStream_t)stream);
-        ws_release(h, wsp, (hipStream_t)stream);
-        if (eg != hipSuccess) return fail_hip(eg, "nf_nll_grad launch (GEMM)");
-        return NF_OK;
-    }
-    hipError_t e = wide ? nf_launch_grad_wide(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream)
-                        : nf_launch_grad(h->gprog, a, h->grad_n_cpl, h->n_cu, (hipStream_t)stream);
-    if (e != hipSuccess) return fail_hip(e, "nf_nll_grad launch");
+    // NF_GRAD_PATH_GEMM: the gate records live in a buffer of the handle's workspace set: one per call in flight, grown only by a call
+    // that needs more than any earlier one (nf_reserve_grad_workspace sizes it up front); everything else is enqueued
+    const bool gemm = h->grad_path == NF_GRAD_PATH_GEMM;
+    nf_handle::Workspace *wsp = nullptr;
+    if (gemm && (rc = ws_acquire(h, grad_workspace_bytes(h, B), (hipStream_t)stream, &wsp)) != NF_OK) return rc;
+    const hipError_t e = grad_launch(h, h->gprog, a, h->grad_n_cpl, wsp ? wsp->p : nullptr, wsp ? wsp->bytes : 0, (hipStream_t)stream);
+    if (gemm) ws_release(h, wsp, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, gemm ? "nf_nll_grad launch (GEMM)" : "nf_nll_grad launch");
     return NF_OK;
 }
 

@@ -21,7 +21,8 @@
 // The gates come from the forward sweep, not from the rebuilt values: the result is the derivative of the function the forward
 // sweep evaluated.  The ops behind the last coupling in NLL order (the first ones sampling runs) take their values forward from
 // eps * temp instead of the rebuilt ones, as nf_grad_kernel does for the ops behind x.
-// The coupling CNN, its transposed pass and the gate record restate nf_grad_kernel's; a change to one is made in both files.
+// The frame (conditioning, loads, the 4x4 product) and the gate record with the coupling CNN are nf_grad_common.h's, shared with
+// nf_grad_kernel; slot set-up and the transposed pass stand inline in both kernels (nf_grad_common.h says why).
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stdint.h>
@@ -31,17 +32,16 @@
 #include "nf_dev_util.h"
 #include "nf_internal.h"
 #include "nf_flow_common.h"   // flow_launch: the persistent-grid launcher
+#include "nf_grad_common.h"   // GradFrame, GradCoupling
 
 namespace {
 
 template <int WIDTH, int THREADS, int PX>
 __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram prog, const NfSampleGradLaunch a)
 {
-    static_assert(WIDTH == 4 || WIDTH == 8 || WIDTH == 16 || WIDTH == 32, "gate sets of WIDTH bits must tile a 32-bit word");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NPIX = THREADS * PX;
     constexpr int NW = THREADS / 64;
-    constexpr int SPW = 32 / WIDTH;   // gate sets per word
     const int H = a.H, W = a.W, HW = H * W, Wp = W + 2;
     const int tile_px = ((H + 2) * Wp + 1) & ~1;
     float2 *const t0 = reinterpret_cast<float2 *>(smem);   // z0 tile [tile_px] float2
@@ -73,22 +73,16 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
         const size_t patch_off = (size_t)b * (size_t)HW;
         const float4 *const y4 = reinterpret_cast<const float4 *>(a.y) + patch_off;   // (not dereferenced when a.y is null)
         const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + b;
-        auto cond_a = [&](int slot) { return a.cond_rows ? crow->a[slot & 3] : a.cond_a[slot & 3]; };
-        auto cond_b = [&](int slot) { return a.cond_rows ? crow->b[slot & 3] : a.cond_b[slot & 3]; };
+        const float4 *const no_in4 = nullptr;   // (the sweep starts from eps: GradFrame::load_x is not used)
+        const GradSlotPix<PX> pix = {act, gidx};
+        const GradFrame<PX, NfSampleGradLaunch, GradSlotPix<PX>> F = {prog, a, pix, crow, patch_off, no_in4, y4};
+        // the sampling sweep reaches the couplings LAST TO FIRST: GradCoupling's LAST_FIRST numbering of the gate sets
+        const GradCoupling<WIDTH, THREADS, PX, NfSampleGradLaunch, true> cpl = {a, act, t0, lidx, Wp, gates, t, th, bmask};
 
-        auto load4 = [&](const float *src, float fill, float (&v)[PX][4]) {
-            const float4 *const s4 = reinterpret_cast<const float4 *>(src) + patch_off;
-#pragma unroll
-            for (int k = 0; k < PX; ++k) {
-                float4 q = make_float4(fill, fill, fill, fill);
-                if (act[k]) q = s4[gidx[k]];
-                v[k][0] = q.x; v[k][1] = q.y; v[k][2] = q.z; v[k][3] = q.w;
-            }
-        };
         // eps: the caller's, or nf_sample's draw (the same key), regenerated wherever it is needed
         auto load_eps = [&](float (&e)[PX][4]) {
             if (a.eps) {
-                load4(a.eps, 0.0f, e);
+                F.load4(a.eps, 0.0f, e);
             } else {
 #pragma unroll
                 for (int k = 0; k < PX; ++k) {
@@ -97,171 +91,26 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
                 }
             }
         };
-        auto load_y = [&](float (&yy)[PX][4]) {
-#pragma unroll
-            for (int k = 0; k < PX; ++k) {
-                float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
-                if (act[k]) v = y4[gidx[k]];
-                yy[k][0] = v.x; yy[k][1] = v.y; yy[k][2] = v.z; yy[k][3] = v.w;
-            }
-        };
-        // z <- z M, M row-major [c][k] at P
-        auto mat4 = [&](const cfloat_p P, float (&z)[PX][4]) {
-            float m[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) m[i] = P[i];
-#pragma unroll
-            for (int k = 0; k < PX; ++k) {
-                float o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float s = z[k][0] * m[j];
-                    s = fmaf(z[k][1], m[4 + j], s);
-                    s = fmaf(z[k][2], m[8 + j], s);
-                    s = fmaf(z[k][3], m[12 + j], s);
-                    o[j] = s;
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) z[k][j] = o[j];
-            }
-        };
-
         // the pointwise ops in the sampling direction (nf_sample's arithmetic): the inverse of NLL-order op `op`
         auto pointwise_inv = [&](int op, float (&z)[PX][4]) {
             const int type = prog.ops[op].type;
             const int off = prog.ops[op].off;
             if (type == NF_OP_MIX) {
-                mat4((cfloat_p)(a.params + off) + 16, z);
+                F.mat4((cfloat_p)(a.params + off) + 16, z);
             } else if (type == NF_OP_SDN_DIV) {
-                const float ck1 = cond_a(off), cb2 = cond_b(off);
+                const float ck1 = F.cond_a(off), cb2 = F.cond_b(off);
                 float yy[PX][4];
-                load_y(yy);
+                F.load_y(yy);
 #pragma unroll
                 for (int k = 0; k < PX; ++k)
 #pragma unroll
                     for (int c = 0; c < 4; ++c) z[k][c] *= __builtin_amdgcn_sqrtf(fmaf(yy[k][c], ck1, cb2));
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[1] : cond_a(off);
+                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[1] : F.cond_a(off);
 #pragma unroll
                 for (int k = 0; k < PX; ++k)
 #pragma unroll
                     for (int c = 0; c < 4; ++c) z[k][c] *= s;
-            }
-        };
-
-        // gate set s of pixel slot k (nf_device.h)
-        auto gate_put = [&](int s, int k, uint32_t bits) {
-            uint32_t *const p = gates + (size_t)(s / SPW) * NPIX + t + THREADS * k;
-            const int sh = (s % SPW) * WIDTH;
-            *p = sh == 0 ? bits : (*p | (bits << sh));
-        };
-        auto gate_get = [&](int s, int k) { return gates[(size_t)(s / SPW) * NPIX + t + THREADS * k] >> ((s % SPW) * WIDTH); };
-
-        // The coupling CNN on z0 = z[.][0:2]: o = (shift, raw log-scale), as nf_grad_kernel's.  RECORD: the forward sweep — ReLU by
-        // sign, gates written to the record; otherwise the backward sweep's recomputation on the same z0 — ReLU by the recorded gates.
-        // The forward sweep reaches the couplings LAST TO FIRST: coupling cidx (NLL order) owns the gate sets 2 (n_cpl - 1 - cidx) + layer,
-        // so that the sets of a word are written in rising order and the one with shift 0 clears it (gate_put).
-        auto coupling_cnn = [&](int off, int cidx, auto record, const float (&z)[PX][4], float (&o)[PX][4]) {
-            constexpr bool RECORD = decltype(record)::value;
-            const int gs = 2 * (a.n_cpl - 1 - cidx);
-            const cfloat_p P = (cfloat_p)(a.params + off);
-#pragma unroll
-            for (int k = 0; k < PX; ++k)
-                if (act[k]) t0[lidx[k]] = make_float2(z[k][0], z[k][1]);
-            __syncthreads();
-            {
-                const cfloat_p W1 = P + nf_cpl_off_W1(WIDTH);
-                const cfloat_p B1 = P + nf_cpl_off_B1(WIDTH);
-                const cfloat_p W2 = P + nf_cpl_off_W2(WIDTH);
-                const cfloat_p B2 = P + nf_cpl_off_B2(WIDTH);
-                float h1[PX][WIDTH];
-#pragma unroll
-                for (int k = 0; k < PX; ++k)
-#pragma unroll
-                    for (int j = 0; j < WIDTH; ++j) h1[k][j] = B1[j];
-#pragma unroll 1
-                for (int di = 0; di < 3; ++di) {
-                    const cfloat_p W1r = W1 + di * (3 * 2 * WIDTH);
-                    const int roff = (di - 1) * Wp - 1;
-#pragma unroll
-                    for (int dj = 0; dj < 3; ++dj) {
-#pragma unroll
-                        for (int k = 0; k < PX; ++k) {
-                            const float2 v = t0[lidx[k] + roff + dj];
-#pragma unroll
-                            for (int j = 0; j < WIDTH; ++j) {
-                                h1[k][j] = fmaf(v.x, W1r[(dj * 2 + 0) * WIDTH + j], h1[k][j]);
-                                h1[k][j] = fmaf(v.y, W1r[(dj * 2 + 1) * WIDTH + j], h1[k][j]);
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < PX; ++k) {
-                    uint32_t g1 = 0u, g2 = 0u;
-                    if constexpr (RECORD) {
-#pragma unroll
-                        for (int i = 0; i < WIDTH; ++i) g1 |= (__float_as_int(h1[k][i]) > 0 ? 1u : 0u) << i;
-                        gate_put(gs, k, g1);
-                    } else {
-                        g1 = gate_get(gs, k);
-                        g2 = gate_get(gs + 1, k);
-                    }
-                    float h2[WIDTH];
-#pragma unroll
-                    for (int j = 0; j < WIDTH; ++j) h2[j] = B2[j];
-#pragma unroll
-                    for (int i = 0; i < WIDTH; ++i) {
-                        const float hi = RECORD ? nf_relu(h1[k][i]) : ((g1 >> i) & 1u) ? h1[k][i] : 0.0f;
-#pragma unroll
-                        for (int j = 0; j < WIDTH; ++j) h2[j] = fmaf(hi, W2[i * WIDTH + j], h2[j]);
-                    }
-                    if constexpr (RECORD) {
-#pragma unroll
-                        for (int i = 0; i < WIDTH; ++i) g2 |= (__float_as_int(h2[i]) > 0 ? 1u : 0u) << i;
-                        gate_put(gs + 1, k, g2);
-                    }
-                    if (act[k]) {
-                        float4 *const dst = reinterpret_cast<float4 *>(th + (size_t)lidx[k] * WIDTH);
-#pragma unroll
-                        for (int q = 0; q < WIDTH / 4; ++q) {
-                            float v[4];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                v[e] = RECORD ? nf_relu(h2[4 * q + e]) : ((g2 >> (4 * q + e)) & 1u) ? h2[4 * q + e] : 0.0f;
-                            dst[q] = make_float4(v[0], v[1], v[2], v[3]);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            {
-                const cfloat_p W3 = P + nf_cpl_off_W3(WIDTH);
-#pragma unroll
-                for (int k = 0; k < PX; ++k) {
-                    const float4 e = *reinterpret_cast<const float4 *>(a.params + off + nf_cpl_off_E(WIDTH) + 4 * bmask[k]);
-                    o[k][0] = e.x; o[k][1] = e.y; o[k][2] = e.z; o[k][3] = e.w;
-                }
-#pragma unroll 1
-                for (int di = 0; di < 3; ++di) {
-                    const cfloat_p W3r = W3 + di * (3 * WIDTH * 4);
-                    const int roff = (di - 1) * Wp - 1;
-#pragma unroll
-                    for (int dj = 0; dj < 3; ++dj) {
-#pragma unroll
-                        for (int q = 0; q < WIDTH / 4; ++q) {
-#pragma unroll
-                            for (int k = 0; k < PX; ++k) {
-                                const float4 hv = *reinterpret_cast<const float4 *>(th + (size_t)(lidx[k] + roff + dj) * WIDTH + 4 * q);
-                                const float hh[4] = {hv.x, hv.y, hv.z, hv.w};
-#pragma unroll
-                                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                                    for (int j = 0; j < 4; ++j) o[k][j] = fmaf(hh[i], W3r[(dj * WIDTH + 4 * q + i) * 4 + j], o[k][j]);
-                            }
-                        }
-                    }
-                }
             }
         };
 
@@ -282,7 +131,7 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
                 --cidx;
                 const cfloat_p P = (cfloat_p)(a.params + prog.ops[op].off);
                 float o[PX][4];
-                coupling_cnn(prog.ops[op].off, cidx, std::true_type{}, z, o);
+                cpl.template cnn<true>(prog.ops[op].off, cidx, z, o);
                 const float sc = P[nf_cpl_off_S(WIDTH)];
 #pragma unroll
                 for (int k = 0; k < PX; ++k) {
@@ -303,7 +152,7 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
         // ---- backward sweep ----
         float g[PX][4];    // d L / d (the tensor in front of the NLL-order op being reached): gx_in at the start
         float gy[PX][4];
-        load4(a.gx_in, 0.0f, g);
+        F.load4(a.gx_in, 0.0f, g);
 #pragma unroll
         for (int k = 0; k < PX; ++k)
 #pragma unroll
@@ -315,7 +164,7 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
             if (type == NF_OP_COUPLING_FWD) {
                 const cfloat_p P = (cfloat_p)(a.params + off);
                 float o[PX][4];
-                coupling_cnn(off, cidx, std::false_type{}, z, o);
+                cpl.template cnn<false>(off, cidx, z, o);
                 const float sc = P[nf_cpl_off_S(WIDTH)];
                 float d[PX][4];   // d L / d (shift, raw)
 #pragma unroll
@@ -369,7 +218,7 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
 #pragma unroll
                     for (int k = 0; k < PX; ++k) {
                         const int gs = 2 * (a.n_cpl - 1 - cidx);
-                        const uint32_t g1 = gate_get(gs, k), g2 = gate_get(gs + 1, k);
+                        const uint32_t g1 = cpl.gate_get(gs, k), g2 = cpl.gate_get(gs + 1, k);
                         float d2[WIDTH];
 #pragma unroll
                         for (int j = 0; j < WIDTH; ++j) d2[j] = ((g2 >> j) & 1u) ? dh[k][j] : 0.0f;
@@ -436,9 +285,9 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
 #pragma unroll
                     for (int j = 0; j < 4; ++j) g[k][j] = gi[j];
                 }
-                mat4(P, z);   // u = v A
+                F.mat4(P, z);   // u = v A
             } else if (type == NF_OP_SDN_DIV) {
-                const float ck1 = cond_a(off), cb2 = cond_b(off);
+                const float ck1 = F.cond_a(off), cb2 = F.cond_b(off);
                 if (op > last_cpl) {   // the first ops sampling runs: the op's output, forward from eps * temp
                     load_eps(z);
 #pragma unroll
@@ -448,7 +297,7 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
                     for (int q = n_ops - 1; q >= op; --q) pointwise_inv(q, z);
                 }
                 float yy[PX][4];
-                load_y(yy);
+                F.load_y(yy);
 #pragma unroll
                 for (int k = 0; k < PX; ++k)
 #pragma unroll
@@ -460,7 +309,7 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
                         z[k][c] *= r;
                     }
             } else if (type == NF_OP_SCALE || type == NF_OP_SCALE_COND) {
-                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[1] : cond_a(off);
+                const float s = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[1] : F.cond_a(off);
                 const float si = type == NF_OP_SCALE ? ((cfloat_p)(a.params + off))[0] : 1.0f / s;
 #pragma unroll
                 for (int k = 0; k < PX; ++k)

@@ -18,6 +18,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+if os.environ.get("NF_TOOL_LIB"):   # A/B a differently-built library (this tool only)
+    from noise_flow_amd import _lib as _nf_lib
+    _nf_lib.LIB_PATH = os.path.abspath(os.environ["NF_TOOL_LIB"])
 
 
 def main():
