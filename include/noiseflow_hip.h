@@ -140,6 +140,12 @@ typedef struct nf_config {
 #define NF_CFG_GRAD_MFMA 4  /* nf_nll_grad at coupling widths 17 .. 32: the matrix-core gradient kernel
                               (csrc/nf_grad_wide.hip, patches up to 32x32) and its weight image, uploaded by
                               nf_create.  No effect on any other call, nor on widths up to 16. */
+#define NF_CFG_SVJP_MFMA 256 /* nf_sample_vjp at coupling widths 17 .. 32: the matrix-core kernel (csrc/nf_sample_grad_wide.hip,
+                              patches up to 32x32, NF_SVJP_PATH_WIDE32).  Includes NF_CFG_GRAD_MFMA: the handle is treated exactly
+                              as if that bit were set, one gradient block serves nf_nll_grad and nf_sample_vjp, and nf_nll_grad
+                              returns the bits of a handle built with NF_CFG_GRAD_MFMA alone.  The flag only adds: wherever
+                              nf_nll_grad stays on the scalar kernel (widths up to 16, a 16x48 patch, NF_GRAD=scalar),
+                              nf_sample_vjp runs its scalar kernel, bit for bit.  fp32 handles only.  (Bit 8 stays unassigned.) */
 #define NF_CFG_GRAD_TILED 16 /* nf_nll_grad at padded coupling widths 4 / 8 / 16 on every H, W up to NF_MAX_IMAGE_SIDE: a
                               shape the whole-patch kernel does not hold is evaluated as overlapping 32-pixel tiles, the
                               program cut into segments (see nf_nll_grad, nf_grad_tile_segments).  The flag only adds: a
@@ -374,9 +380,14 @@ int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float 
  * vocabulary, padded coupling widths 4 / 8 / 16 / 32, and the shapes nf_nll_grad's scalar kernel holds whole — patches up to
  * 64x64 at width 4, up to 3072 pixels at width 8 (768 threads x 4 pixels; the LDS budget ends near 55x55 there anyway), up to 1024
  * pixels at widths 16 and 32, as far as 160 KiB of LDS hold the tiles and the gate record.
- * A handle with NF_CFG_GRAD_TILED is supported on the shapes held whole; handles whose gradient block is in the matrix-core or
- * GEMM layout (NF_CFG_GRAD_MFMA, NF_CFG_GRAD_TILED_WIDE at padded width 32; NF_CFG_GRAD_GEMM, NF_CFG_GRAD_TILED_GEMM beyond) are
- * refused.  Not covered: tiles, NF_CFG_FP16_CNN, batch-statistics mode, host-fed variants, parameter gradients. */
+ * With NF_CFG_SVJP_MFMA, coupling widths 17 .. 32 run the same contract on v_mfma_f32_32x32x2_f32 (csrc/nf_sample_grad_wide.hip) over
+ * the handle's matrix-core gradient block, on every shape nf_nll_grad sends to NF_GRAD_PATH_WIDE32: H, W <= 32 and as many
+ * couplings as the gate record fits (12 at 32x32).  This is the paper's configuration, width 32 on 32x32 patches, which the scalar
+ * kernel's LDS tile does not hold (it ends near 24x24 there).  nf_sample_vjp_path reports which kernel a handle launches.
+ * A handle with NF_CFG_GRAD_TILED is supported on the shapes held whole; without NF_CFG_SVJP_MFMA, handles whose gradient block is in
+ * the matrix-core layout (NF_CFG_GRAD_MFMA, NF_CFG_GRAD_TILED_WIDE at padded width 32) are refused, and those in the GEMM layout
+ * (NF_CFG_GRAD_GEMM, NF_CFG_GRAD_TILED_GEMM beyond width 32) always are.
+ * Not covered: tiles, NF_CFG_FP16_CNN, batch-statistics mode, host-fed variants, parameter gradients. */
 int nf_sample_vjp(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp, int64_t B,
                   const nf_cond *cond, const nf_cond_row *rows, const float *gx_in, float *x_out, float *gy_out,
                   float *geps_out, float *gtemp_out, void *stream);
@@ -384,6 +395,12 @@ int nf_sample_vjp(nf_handle *h, const float *y, const float *eps, uint64_t seed,
 /* Host-only, as nf_grad_supported: 0 when nf_sample_vjp supports this model, patch size and flags, NF_EINVAL otherwise, with
  * nf_last_error() naming the limit that was hit. */
 int nf_sample_vjp_supported(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params);
+
+/* Which kernel nf_sample_vjp launches for this handle, or NF_EINVAL when the handle does not support the call
+ * (nf_sample_vjp_supported), next to nf_grad_path. */
+#define NF_SVJP_PATH_SCALAR 0   /* nf_sample_grad_kernel (csrc/nf_sample_grad.hip) */
+#define NF_SVJP_PATH_WIDE32 1   /* NF_CFG_SVJP_MFMA: nf_sample_grad_wide_kernel (csrc/nf_sample_grad_wide.hip), v_mfma_f32_32x32x2_f32 */
+int nf_sample_vjp_path(const nf_handle *h);
 
 /* The tile plan of one image axis (see "Patch sizes"): `size` pixels, tiles of `tile` = min(size, 64) pixels, `halo` =
  * 2 x the number of coupling layers.  Returns the number of tiles n (or a negative NF_E* code) and, for i < min(n, cap),

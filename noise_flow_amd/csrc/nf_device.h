@@ -462,7 +462,7 @@ __host__ __device__ constexpr size_t nf_grad_lds_floats(int H, int W, int width,
 // Ainv, SCALE by 1/s, SDN multiplied, couplings reversed), and the cotangent gx_in = d L / d x walks the ops first to last.
 // cond_a / cond_b or cond_rows are those of direction 1 (nf_cond_rows): a gain kind's `a` is the factor sampling multiplies by.
 struct NfSampleGradLaunch {
-    const float *params;   // gradient block (device), scalar layout
+    const float *params;   // gradient block (device): scalar layout, or NFGW_* for nf_sample_grad_wide_kernel
     const float *y;        // [B,H,W,4] or null
     const float *eps;      // [B,H,W,4], or null: the Philox draw of nf_sample (seed, patch_base + b, pixel, NF_STREAM_SAMP)
     const float *gx_in;    // [B,H,W,4] d L / d x
@@ -480,7 +480,7 @@ struct NfSampleGradLaunch {
     int32_t H, W;
     int32_t last_cpl;      // index of the last coupling op in NLL order (-1 when the model has none)
     int32_t n_cpl;
-    int32_t gate_words;    // nf_grad_gate_words
+    int32_t gate_words;    // nf_grad_gate_words; nf_sample_grad_wide_kernel: nfgw_tpw(H) x n_cpl
 };
 #define NF_SVJP_W8_MAX_PIXELS 3072   // padded width 8 beyond 1 024 pixels: 768 threads x 4 pixels (nf_sample_grad.hip, dispatch_sgrad)
 

@@ -1,6 +1,6 @@
-// What the four gradient kernels share: nf_grad_kernel (nf_grad.hip), nf_grad_wide_kernel (nf_grad_wide.hip), nf_grad_gemm_kernel
-// (nf_grad_gemm.hip) and nf_sample_grad_kernel (nf_sample_grad.hip).  Two layers:
-//   (a) GradFrame, for all four: one launch patch's view of its tensors — conditioning access, the float4 load with a fill value
+// What the gradient kernels share: nf_grad_kernel (nf_grad.hip), nf_grad_wide_kernel (nf_grad_wide.hip), nf_grad_gemm_kernel
+// (nf_grad_gemm.hip), nf_sample_grad_kernel (nf_sample_grad.hip) and nf_sample_grad_wide_kernel (nf_sample_grad_wide.hip).  Two layers:
+//   (a) GradFrame, for all of them: one launch patch's view of its tensors — conditioning access, the float4 load with a fill value
 //       (x, y, g_in, eps and gx_in all go through it), the 4x4 product and the pointwise layers in the NLL direction (MIX, SDN_DIV,
 //       SCALE, SCALE_COND);
 //   (b) GradCoupling, for nf_grad_kernel and nf_sample_grad_kernel: the gate record and the coupling CNN with scalar (SGPR) weights,

@@ -782,7 +782,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     out.tile_w = tw;
     out.segs.clear();
     if (cfg->n_layers < 1) return fail(NF_EINVAL, "n_layers must be >= 1");
-    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE | NF_CFG_GRAD_GEMM | NF_CFG_GRAD_TILED_GEMM)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
+    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE | NF_CFG_GRAD_GEMM | NF_CFG_GRAD_TILED_GEMM | NF_CFG_SVJP_MFMA)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
     const double HW = (double)cfg->height * cfg->width;
 
     // intermediate list in NLL order
@@ -1099,7 +1099,8 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
         if (tiles) tiles->swap(segs);
         return NF_OK;
     }
-    if (((cfg->flags & NF_CFG_GRAD_MFMA) || wide_tiles) && w == 32) {
+    // NF_CFG_SVJP_MFMA includes NF_CFG_GRAD_MFMA: one gradient block serves nf_nll_grad and nf_sample_vjp
+    if (((cfg->flags & (NF_CFG_GRAD_MFMA | NF_CFG_SVJP_MFMA)) || wide_tiles) && w == 32) {
         // The flag only adds: the matrix-core kernel (nf_grad_wide.hip) takes every shape up to 32x32 — unless NF_GRAD=scalar asks for
         // the other arm where that one holds the shape — and a shape beyond it (16x48, 8x64) stays with the scalar kernel as far as
         // that kernel holds it
@@ -1127,10 +1128,13 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
     return NF_OK;
 }
 
-// What nf_sample_vjp supports (nf_sample_grad.hip interprets the SCALAR gradient block on whole patches): whatever grad_support sends
-// to NF_GRAD_PATH_SCALAR for this model, shape and flags — the same width, register and LDS limits, no arithmetic of its own.
-int sample_vjp_support(const nf_config *cfg, const Built &fwd)
+// What nf_sample_vjp supports and which kernel runs it (`svjp_path`: NF_SVJP_PATH_*).  nf_sample_grad.hip interprets the SCALAR
+// gradient block on whole patches: whatever grad_support sends to NF_GRAD_PATH_SCALAR for this model, shape and flags.  With
+// NF_CFG_SVJP_MFMA, nf_sample_grad_wide.hip interprets the matrix-core block: whatever grad_support sends to NF_GRAD_PATH_WIDE32
+// (that kernel keeps inside nfgw_lds_floats).  Either way the width, register and LDS limits are nf_nll_grad's: no arithmetic here.
+int sample_vjp_support(const nf_config *cfg, const Built &fwd, int *svjp_path = nullptr)
 {
+    if (svjp_path) *svjp_path = NF_SVJP_PATH_SCALAR;
     int path = NF_GRAD_PATH_SCALAR;
     const int rc = grad_support(cfg, fwd, &path);
     if (rc != NF_OK) {   // the limit grad_support named, under this call's name
@@ -1145,13 +1149,21 @@ int sample_vjp_support(const nf_config *cfg, const Built &fwd)
                         NF_SVJP_W8_MAX_PIXELS, cfg->height, cfg->width);
         return NF_OK;
     }
+    if (path == NF_GRAD_PATH_WIDE32 && (cfg->flags & NF_CFG_SVJP_MFMA)) {
+        if (svjp_path) *svjp_path = NF_SVJP_PATH_WIDE32;
+        return NF_OK;
+    }
     if (path == NF_GRAD_PATH_TILED)
         return fail(NF_EINVAL, "nf_sample_vjp: shapes the scalar gradient kernel holds whole (a %dx%d patch at coupling width %d is cut into "
                                "tiles under NF_CFG_GRAD_TILED; no tile mode yet)", cfg->height, cfg->width, fwd.raw_width);
+    if (path == NF_GRAD_PATH_TILED_WIDE32 && (cfg->flags & NF_CFG_SVJP_MFMA))
+        return fail(NF_EINVAL, "nf_sample_vjp: shapes the matrix-core gradient kernel holds whole (a %dx%d patch at coupling width %d is cut "
+                               "into tiles under NF_CFG_GRAD_TILED_WIDE; no tile mode yet)", cfg->height, cfg->width, fwd.raw_width);
     const bool gemm = path == NF_GRAD_PATH_GEMM || path == NF_GRAD_PATH_TILED_GEMM;
     return fail(NF_EINVAL, "nf_sample_vjp: the handle's gradient block is in the %s layout (%s at coupling width %d); the scalar layout only: "
-                           "no matrix-core or GEMM variant yet", gemm ? "GEMM" : "matrix-core",
-                gemm ? "NF_CFG_GRAD_GEMM / NF_CFG_GRAD_TILED_GEMM" : "NF_CFG_GRAD_MFMA / NF_CFG_GRAD_TILED_WIDE", fwd.raw_width);
+                           "no matrix-core or GEMM variant yet%s", gemm ? "GEMM" : "matrix-core",
+                gemm ? "NF_CFG_GRAD_GEMM / NF_CFG_GRAD_TILED_GEMM" : "NF_CFG_GRAD_MFMA / NF_CFG_GRAD_TILED_WIDE", fwd.raw_width,
+                path == NF_GRAD_PATH_WIDE32 ? " (set NF_CFG_SVJP_MFMA for the matrix-core kernel)" : "");
 }
 
 // the paths whose couplings are in the NFGW_* layout (the matrix-core kernel, whole patches or tiles); those in the NFGG_* layout
@@ -1375,6 +1387,7 @@ struct nf_handle {
     std::string grad_why;
     // nf_sample_vjp (nf_sample_grad.hip) runs on gprog / d_grad where sample_vjp_support says so
     int svjp_rc = NF_EINVAL;
+    int svjp_path = NF_SVJP_PATH_SCALAR;   // NF_SVJP_PATH_*: which kernel nf_sample_vjp launches (sample_vjp_support)
     int svjp_last_cpl = -1;
     std::string svjp_why;
     std::vector<Built::TileSeg> grad_segs;   // NF_GRAD_PATH_TILED / _TILED_WIDE32 / _TILED_GEMM: the segments (gradient halo, tiles of the backward launches)
@@ -1563,7 +1576,7 @@ int nf_create(const nf_config *cfg, const nf_layer_desc *layers, const float *pa
             }
         }
         const std::string keep2 = g_last_error;
-        h->svjp_rc = sample_vjp_support(cfg, h->fwd);
+        h->svjp_rc = sample_vjp_support(cfg, h->fwd, &h->svjp_path);
         h->svjp_why = g_last_error;
         g_last_error = keep2;
         for (int i = 0; h->svjp_rc == NF_OK && i < h->gprog.n_ops; ++i)
@@ -2362,13 +2375,20 @@ int nf_nll_grad(nf_handle *h, const float *x, const float *y, int64_t B, const n
     return NF_OK;
 }
 
-// ---- vector-Jacobian product of sampling: d L / d y, d L / d eps, d L / d temp (nf_sample_grad.hip) ----
+// ---- vector-Jacobian product of sampling: d L / d y, d L / d eps, d L / d temp (nf_sample_grad.hip, nf_sample_grad_wide.hip) ----
 int nf_sample_vjp_supported(const nf_config *cfg, const nf_layer_desc *layers, const float *params, size_t n_params)
 {
     Built b;
     int rc = build_program(cfg, layers, params, n_params, 0, b);
     if (rc != NF_OK) return rc;
     return sample_vjp_support(cfg, b);
+}
+
+int nf_sample_vjp_path(const nf_handle *h)
+{
+    if (!h) return fail(NF_EINVAL, "handle is NULL");
+    if (h->svjp_rc != NF_OK) return fail(h->svjp_rc, "%s", h->svjp_why.c_str());
+    return h->svjp_path;
 }
 
 int nf_sample_vjp(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp, int64_t B,
@@ -2415,11 +2435,13 @@ int nf_sample_vjp(nf_handle *h, const float *y, const float *eps, uint64_t seed,
     a.W = h->cfg.width;
     a.last_cpl = h->svjp_last_cpl;
     a.n_cpl = h->grad_n_cpl;
-    a.gate_words = nf_grad_gate_words(h->grad_n_cpl, h->gprog.width);
+    const bool wide = h->svjp_path == NF_SVJP_PATH_WIDE32;
+    a.gate_words = wide ? nfgw_tpw(a.H) * h->grad_n_cpl : nf_grad_gate_words(h->grad_n_cpl, h->gprog.width);
     NfDeviceGuard guard;
     int rc = guard.enter(h->device);
     if (rc != NF_OK) return rc;
-    const hipError_t e = nf_launch_sample_grad(h->gprog, a, h->n_cu, (hipStream_t)stream);
+    const hipError_t e = wide ? nf_launch_sample_grad_wide(h->gprog, a, h->n_cu, (hipStream_t)stream)
+                              : nf_launch_sample_grad(h->gprog, a, h->n_cu, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "nf_sample_vjp launch");
     return NF_OK;
 }

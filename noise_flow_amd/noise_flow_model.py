@@ -185,7 +185,7 @@ class FlowHandle:
     def __init__(self, arch, variables: Dict[str, np.ndarray], x_shape, width: int,
                  binding: str = "loss_first", device: Optional[int] = None, layers=None, tmpl=None,
                  cnn_dtype: str = "fp32", flow_permutation: int = 1, decomp: str = "LU", grad_kernel: str = "scalar",
-                 grad_tiles: bool = False):
+                 grad_tiles: bool = False, sample_vjp_kernel: str = "scalar"):
         self.lib = _lib.load()
         if layers is None:
             self.layers, descs, flat = _params.pack(arch, variables, width, binding, flow_permutation, decomp)
@@ -199,11 +199,17 @@ class FlowHandle:
             raise ValueError("grad_kernel must be 'scalar', 'mfma' or 'gemm'")
         if grad_kernel in ("mfma", "gemm") and cnn_dtype == "fp16":
             raise ValueError("grad_kernel='%s' needs an fp32 handle (cnn_dtype='fp16' has no gradient kernel)" % grad_kernel)
+        if sample_vjp_kernel not in ("scalar", "mfma"):
+            raise ValueError("sample_vjp_kernel must be 'scalar' or 'mfma'")
+        if sample_vjp_kernel == "mfma" and cnn_dtype == "fp16":
+            raise ValueError("sample_vjp_kernel='mfma' needs an fp32 handle (cnn_dtype='fp16' has no gradient kernel)")
         flags = {"fp32": 0, "fp16": _lib.NF_CFG_FP16_CNN, "fp32_exact": _lib.NF_CFG_EXACT_FP32}[cnn_dtype]
+        flags |= _lib.NF_CFG_SVJP_MFMA if sample_vjp_kernel == "mfma" else 0   # includes NF_CFG_GRAD_MFMA
         flags |= _lib.NF_CFG_GRAD_MFMA if grad_kernel == "mfma" else 0
         flags |= _lib.NF_CFG_GRAD_GEMM if grad_kernel == "gemm" else 0   # widths 33 .. 512: the GEMM gradient kernel
         flags |= _lib.NF_CFG_GRAD_TILED if grad_tiles else 0
-        flags |= _lib.NF_CFG_GRAD_TILED_WIDE if (grad_tiles and grad_kernel == "mfma") else 0   # width 32: tiles of the matrix-core kernel
+        wide = grad_kernel == "mfma" or (sample_vjp_kernel == "mfma" and grad_kernel == "scalar")   # NF_CFG_SVJP_MFMA includes NF_CFG_GRAD_MFMA
+        flags |= _lib.NF_CFG_GRAD_TILED_WIDE if (grad_tiles and wide) else 0   # width 32: tiles of the matrix-core kernel
         flags |= _lib.NF_CFG_GRAD_TILED_GEMM if (grad_tiles and grad_kernel == "gemm") else 0   # widths 33 .. 512: tiles of the GEMM kernel
         cfg = _lib.nf_config(H, W, Cc, len(self.layers), -1 if device is None else int(device), flags)
         self._model_args = (cfg, descs, flat)   # what nf_cond_rows takes (kept alive with the handle)
@@ -275,11 +281,18 @@ class NoiseFlow(object):
           the matrix-core gradient kernel (``NF_CFG_GRAD_TILED_WIDE``), and together with grad_kernel='gemm' at coupling widths
           33 .. 512, on tiles of the GEMM gradient kernel (``NF_CFG_GRAD_TILED_GEMM``; without grad_tiles those widths stay at
           patches of up to 32x32).  Default ``False``; also selectable as ``hps.grad_tiles``.
+    sample_vjp_kernel : 'scalar' (default) | 'mfma' — which kernel ``sample_and_vjp`` / ``sample_torch`` run at coupling widths
+          17 .. 32: 'mfma' is the matrix-core kernel (patches up to 32x32, ``NF_CFG_SVJP_MFMA``), the only one that holds the
+          paper's width 32 on 32x32 patches (the scalar kernel's LDS tile ends near 24x24 there).  It includes
+          grad_kernel='mfma': one gradient block serves ``nll_torch`` and ``sample_torch``.  No effect on narrower models.
+          Where both kernels hold the shape the matrix-core one was the faster (1.36 x at 24x24, 1.10 x at 16x16, width 32 x 8
+          couplings; smaller shapes were not measured).
+          Also selectable as ``hps.sample_vjp_kernel``; not with cnn_dtype='fp16'.
     binding : 'loss_first' | 'sample_first' — template→layer binding (quirk Q1).
     """
 
     def __init__(self, x_shape, is_training=False, hps=None, variables=None, binding="loss_first", device=None,
-                 cnn_dtype=None, grad_kernel=None, grad_tiles=None):
+                 cnn_dtype=None, grad_kernel=None, grad_tiles=None, sample_vjp_kernel=None):
         if hps is None:
             raise ValueError("hps is required (arch, width, ...)")
         self.x_shape = [int(v) for v in x_shape]
@@ -311,9 +324,10 @@ class NoiseFlow(object):
         self.cnn_dtype = cnn_dtype or str(getattr(hps, "cnn_dtype", "fp32"))
         self.grad_kernel = grad_kernel or str(getattr(hps, "grad_kernel", "scalar"))
         self.grad_tiles = bool(getattr(hps, "grad_tiles", False) if grad_tiles is None else grad_tiles)
+        self.sample_vjp_kernel = sample_vjp_kernel or str(getattr(hps, "sample_vjp_kernel", "scalar"))
         self._flow = FlowHandle(self.arch, self._variables, self.x_shape, self.width, binding, self._dev.device.index,
                                 cnn_dtype=self.cnn_dtype, flow_permutation=self.flow_permutation, decomp=self.decomp,
-                                grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles)
+                                grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles, sample_vjp_kernel=self.sample_vjp_kernel)
 
     # ------------------------------------------------------------------ variables
     @property
@@ -331,7 +345,8 @@ class NoiseFlow(object):
         old = self._flow
         self._flow = FlowHandle(self.arch, self._variables, self.x_shape, self.width, self.binding,
                                 self._dev.device.index, cnn_dtype=self.cnn_dtype, flow_permutation=self.flow_permutation,
-                                decomp=self.decomp, grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles)
+                                decomp=self.decomp, grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles,
+                                sample_vjp_kernel=self.sample_vjp_kernel)
         old.close()
         if getattr(self, "_sync", None) is not None:
             self._install_sync()

@@ -9,6 +9,14 @@ reported.  nf_sample is the forward direction alone (one coupling-CNN evaluation
 nf_sample_vjp does in the other direction — three CNN evaluations per coupling: forward sweep, recomputation, transposed products —
 on the same scalar gradient block.  nf_sample_vjp is timed with all four outputs and with x_out = NULL (the backward pass of
 sample_torch).  ms per launch, patches/s and the ratios.
+
+    python tools/time_sample_vjp.py --width 32 --kernel mfma [--reps 4] [--ab-sides 24,16]
+
+The matrix-core kernel (csrc/nf_sample_grad_wide.hip, sample_vjp_kernel="mfma") on the deep model at width 32 (deep_variables below),
+B = 1 024, temp 0.6, the same windows.  32x32: nf_sample_vjp (all outputs, and x_out = NULL) against nf_nll_grad (NF_GRAD_PATH_WIDE32:
+the same three CNN evaluations per coupling) and nf_sample of the same handle.  `--ab-sides`: the new kernel against the scalar
+nf_sample_vjp of a handle without the flag, arms alternated `--reps` times; per arm the median and the spread (max - min) of its
+`--reps` medians, and the difference read against twice the larger spread.
 """
 import argparse
 import ctypes as C
@@ -27,7 +35,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--width", type=int, default=4, help="4: the shipped model (default); 32: the deep model at width 32")
+    ap.add_argument("--kernel", default="scalar", help="with --width 32: 'mfma' = sample_vjp_kernel='mfma'")
+    ap.add_argument("--reps", type=int, default=4)
+    ap.add_argument("--ab-sides", default="24,16")
     a = ap.parse_args()
+    if (a.width, a.kernel) not in ((4, "scalar"), (32, "mfma")):
+        raise SystemExit("--width 4 [--kernel scalar] or --width 32 --kernel mfma")
     if a.launches < 200:
         raise SystemExit("--launches must be at least 200")
     import numpy as np
@@ -53,8 +67,18 @@ def main():
         return w[1], w
 
     res = {"B": B, "temp": temp, "launches_per_window": a.launches, "shapes": {}}
-    for side in (32, 64):
-        m = NoiseFlow([side, side, 4], False, default_hps(), variables=v, device=0)
+    wide = a.width == 32
+    if wide:
+        v = deep_variables(32)
+        cond = _lib.nf_cond(800.0, 2.0, 0.0, 0.0)
+        res["model"] = "deep_variables(32)"
+    for side in ((32,) if wide else (32, 64)):
+        if wide:
+            m = NoiseFlow([side, side, 4], False, default_hps(arch=FULL_ARCH, width=32), variables=v, device=0, sample_vjp_kernel="mfma")
+            assert m._flow.lib.nf_sample_vjp_path(m._flow.ptr) == _lib.NF_SVJP_PATH_WIDE32
+            assert m._flow.lib.nf_grad_path(m._flow.ptr) == _lib.NF_GRAD_PATH_WIDE32
+        else:
+            m = NoiseFlow([side, side, 4], False, default_hps(), variables=v, device=0)
         rng = np.random.RandomState(0)
         y = torch.as_tensor(rng.rand(B, side, side, 4).astype(np.float32)).cuda()
         eps, g = (torch.as_tensor(rng.randn(B, side, side, 4).astype(np.float32)).cuda() for _ in range(2))
@@ -79,9 +103,71 @@ def main():
               "       nf_sample_vjp %.4f ms [%s] (%.3e patches/s), x_out = NULL %.4f ms [%s]   vjp / sample %.2f   vjp / nll_grad %.2f"
               % (side, side, t_s, fmt(w_s), r["sample_patches_per_s"], t_g, fmt(w_g), r["nll_grad_patches_per_s"], t_v, fmt(w_v),
                  r["vjp_patches_per_s"], t_b, fmt(w_b), r["vjp_over_sample"], r["vjp_over_nll_grad"]), flush=True)
+    # the matrix-core kernel against the scalar one where both hold the shape: arms alternated, differences against the spread
+    for side in ([int(q) for q in a.ab_sides.split(",") if q] if wide else []):
+        rng = np.random.RandomState(0)
+        y = torch.as_tensor(rng.rand(B, side, side, 4).astype(np.float32)).cuda()
+        eps, g = (torch.as_tensor(rng.randn(B, side, side, 4).astype(np.float32)).cuda() for _ in range(2))
+        gt = torch.empty((B,), device="cuda")
+        o1, o2, o3 = (torch.empty_like(y) for _ in range(3))
+        arms = {}
+        for name in ("mfma", "scalar"):
+            m = NoiseFlow([side, side, 4], False, default_hps(arch=FULL_ARCH, width=32), variables=v, device=0, sample_vjp_kernel=name)
+            assert m._flow.lib.nf_sample_vjp_path(m._flow.ptr) == (_lib.NF_SVJP_PATH_WIDE32 if name == "mfma" else _lib.NF_SVJP_PATH_SCALAR)
+            arms[name] = m
+        med = {name: [] for name in arms}
+        for _ in range(a.reps):
+            for name, m in arms.items():
+                lib, h, st = m._flow.lib, m._flow.ptr, m._dev.stream_ptr()
+                med[name].append(timed(lambda: _lib.check(lib.nf_sample_vjp(h, y.data_ptr(), eps.data_ptr(), 0, 0, temp, B, C.byref(cond), None,
+                                                                            g.data_ptr(), o1.data_ptr(), o2.data_ptr(), o3.data_ptr(),
+                                                                            gt.data_ptr(), st)))[0])
+        mid = {name: sorted(w)[len(w) // 2] for name, w in med.items()}
+        spread = {name: max(w) - min(w) for name, w in med.items()}
+        diff, noise = mid["mfma"] - mid["scalar"], 2.0 * max(spread.values())
+        res["shapes"]["ab %dx%d" % (side, side)] = {"medians_ms": med, "median_ms": mid, "spread_ms": spread, "mfma_minus_scalar_ms": diff,
+                                                    "twice_spread_ms": noise, "mfma_over_scalar": mid["mfma"] / mid["scalar"]}
+        print("%dx%d  nf_sample_vjp  mfma %.4f ms [%s]   scalar %.4f ms [%s]   mfma - scalar %+.4f ms (2 x spread %.4f: %s)   mfma / scalar %.3f"
+              % (side, side, mid["mfma"], "/".join("%.4f" % q for q in med["mfma"]), mid["scalar"], "/".join("%.4f" % q for q in med["scalar"]),
+                 diff, noise, "a difference" if abs(diff) > noise else "inside the noise", mid["mfma"] / mid["scalar"]), flush=True)
     if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
+
+
+FULL_ARCH = "sdn5|unc|unc|unc|unc|gain4|unc|unc|unc|unc"
+
+
+def deep_variables(width, seed=0):
+    """The deep model of tests/sample_vjp_wide_cases.py, value for value (conftest.trained_like_variables with l_2/W and l_last/W
+    multiplied by sqrt(4 / width), then by 0.5), restated here so that the tool stands without the test modules."""
+    import numpy as np
+    from noise_flow_amd import params
+    rng = np.random.RandomState(seed + 1000)
+    v = params.init_variables(FULL_ARCH, width, 4, seed)
+    f = np.float32(np.sqrt(4.0 / width))
+    for k in list(v):
+        a = v[k]
+        if k.endswith("l_1/W"):
+            v[k] = (rng.randn(*a.shape) * 0.4).astype(np.float32)
+        elif k.endswith("l_2/W"):
+            v[k] = (((rng.randn(*a.shape) * 0.4).astype(np.float32) * f).astype(np.float32) * np.float32(0.5)).astype(np.float32)
+        elif k.endswith("l_last/W"):
+            v[k] = (((rng.randn(*a.shape) * 0.15).astype(np.float32) * f).astype(np.float32) * np.float32(0.5)).astype(np.float32)
+        elif k.endswith("/b") or k.endswith("l_last/logs"):
+            v[k] = (rng.randn(*a.shape) * 0.1).astype(np.float32)
+        elif k.endswith("/mean"):
+            v[k] = (rng.randn(*a.shape) * 0.2).astype(np.float32)
+        elif k.endswith("/var"):
+            v[k] = (0.5 + rng.rand(*a.shape)).astype(np.float32)
+        elif "rescaling_scale" in k:
+            v[k] = np.float32(0.3 + 0.6 * rng.rand())
+        elif "log_S" in k or "L_vec" in k or "U_vec" in k:
+            v[k] = (a + rng.randn(*a.shape).astype(np.float32) * 0.1).astype(np.float32)
+        elif k.endswith("gain_val"):
+            v[k] = np.asarray([1.3], np.float32)
+    return v
 
 
 if __name__ == "__main__":
