@@ -146,6 +146,13 @@ typedef struct nf_config {
                               returns the bits of a handle built with NF_CFG_GRAD_MFMA alone.  The flag only adds: wherever
                               nf_nll_grad stays on the scalar kernel (widths up to 16, a 16x48 patch, NF_GRAD=scalar),
                               nf_sample_vjp runs its scalar kernel, bit for bit.  fp32 handles only.  (Bit 8 stays unassigned.) */
+#define NF_CFG_SVJP_TILED 512 /* nf_sample_vjp at padded coupling widths 4 / 8 / 16 on every H, W up to NF_MAX_IMAGE_SIDE: a shape
+                              the whole-patch kernel does not hold runs on the tiles and segments of nf_nll_grad's plan
+                              (NF_SVJP_PATH_TILED, csrc/nf_sample_grad.hip).  Includes NF_CFG_GRAD_TILED: the handle is treated
+                              exactly as if that bit were set, one gradient block and one plan (nf_grad_tile_segments,
+                              NF_GRAD_TILE_SEGMENTS) serve both calls, and nf_nll_grad returns the bits of a handle built with
+                              NF_CFG_GRAD_TILED alone.  The flag only adds: a shape held whole runs the whole-patch kernel, bit
+                              for bit.  Widths 17 and beyond keep their refusals; fp32 handles only. */
 #define NF_CFG_GRAD_TILED 16 /* nf_nll_grad at padded coupling widths 4 / 8 / 16 on every H, W up to NF_MAX_IMAGE_SIDE: a
                               shape the whole-patch kernel does not hold is evaluated as overlapping 32-pixel tiles, the
                               program cut into segments (see nf_nll_grad, nf_grad_tile_segments).  The flag only adds: a
@@ -384,10 +391,20 @@ int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float 
  * the handle's matrix-core gradient block, on every shape nf_nll_grad sends to NF_GRAD_PATH_WIDE32: H, W <= 32 and as many
  * couplings as the gate record fits (12 at 32x32).  This is the paper's configuration, width 32 on 32x32 patches, which the scalar
  * kernel's LDS tile does not hold (it ends near 24x24 there).  nf_sample_vjp_path reports which kernel a handle launches.
- * A handle with NF_CFG_GRAD_TILED is supported on the shapes held whole; without NF_CFG_SVJP_MFMA, handles whose gradient block is in
+ * With NF_CFG_SVJP_TILED, padded coupling widths 4 / 8 / 16 take every H, W up to NF_MAX_IMAGE_SIDE (NF_SVJP_PATH_TILED): a shape the
+ * whole-patch kernel does not hold runs on nf_nll_grad's tiles and segments (nf_grad_tile_segments, NF_GRAD_TILE_SEGMENTS: 32-pixel
+ * tiles, a halo of 4 pixels per coupling of a segment).  Forward, the tiled launches of nf_sample cut at that plan's boundaries, every
+ * tensor between two segments kept (the last one runs only for x_out); backward, one launch of the same kernel per segment in NLL
+ * order over images x tiles workgroups, each tile storing its core window only; gy_out is stored by the first segment with an SDN-kind
+ * op and added to by later ones; gtemp is one sum per tile of the last launch, over the tile's core, added per image in tile order by a
+ * small kernel (no atomics: the same bits on every run).  The whole contract above holds.  Scratch — segments - 1 tensors, two gradient
+ * tensors, the tile sums — is a buffer of the handle's workspace set per call in flight: a call allocates only when it needs more than
+ * any earlier one (nf_workspace_bytes(h, 3, B), nf_reserve_sample_vjp_workspace make it allocation-free).  A shape held whole runs the
+ * whole-patch kernel, bit for bit; widths 17 and beyond keep their refusals.
+ * A handle with NF_CFG_GRAD_TILED alone is supported on the shapes held whole; without NF_CFG_SVJP_MFMA, handles whose gradient block is in
  * the matrix-core layout (NF_CFG_GRAD_MFMA, NF_CFG_GRAD_TILED_WIDE at padded width 32) are refused, and those in the GEMM layout
  * (NF_CFG_GRAD_GEMM, NF_CFG_GRAD_TILED_GEMM beyond width 32) always are.
- * Not covered: tiles, NF_CFG_FP16_CNN, batch-statistics mode, host-fed variants, parameter gradients. */
+ * Not covered: tiles at widths 17 and beyond, NF_CFG_FP16_CNN, batch-statistics mode, host-fed variants, parameter gradients. */
 int nf_sample_vjp(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp, int64_t B,
                   const nf_cond *cond, const nf_cond_row *rows, const float *gx_in, float *x_out, float *gy_out,
                   float *geps_out, float *gtemp_out, void *stream);
@@ -400,6 +417,7 @@ int nf_sample_vjp_supported(const nf_config *cfg, const nf_layer_desc *layers, c
  * (nf_sample_vjp_supported), next to nf_grad_path. */
 #define NF_SVJP_PATH_SCALAR 0   /* nf_sample_grad_kernel (csrc/nf_sample_grad.hip) */
 #define NF_SVJP_PATH_WIDE32 1   /* NF_CFG_SVJP_MFMA: nf_sample_grad_wide_kernel (csrc/nf_sample_grad_wide.hip), v_mfma_f32_32x32x2_f32 */
+#define NF_SVJP_PATH_TILED 2    /* NF_CFG_SVJP_TILED: nf_sample_grad_kernel on 32-pixel tiles, one launch per segment */
 int nf_sample_vjp_path(const nf_handle *h);
 
 /* The tile plan of one image axis (see "Patch sizes"): `size` pixels, tiles of `tile` = min(size, 64) pixels, `halo` =
@@ -637,11 +655,14 @@ int nf_batchstats_route(const nf_handle *h);
  * what one call of B images needs (0 for patches of up to 64x64: they need none); nf_reserve_workspace allocates that for
  * `calls_in_flight` concurrent calls up front (synchronous; at nf_create time, so to speak), after which no call of up to B
  * images allocates anything.  No reference counterpart (TF sizes its arena inside sess.run). */
-int64_t nf_workspace_bytes(const nf_handle *h, int32_t direction, int64_t B);   /* direction 2: one tiled nf_nll_grad call */
+int64_t nf_workspace_bytes(const nf_handle *h, int32_t direction, int64_t B);   /* direction 2: one tiled nf_nll_grad call; 3: one tiled nf_sample_vjp call */
 int nf_reserve_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
 /* the same for nf_nll_grad under NF_CFG_GRAD_TILED / NF_CFG_GRAD_TILED_WIDE / NF_CFG_GRAD_TILED_GEMM (nothing to do for a handle whose
  * shape is held whole) and for the gate records of NF_GRAD_PATH_GEMM; NF_GRAD_PATH_TILED_GEMM keeps both in the one buffer */
 int nf_reserve_grad_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
+/* the same for nf_sample_vjp under NF_CFG_SVJP_TILED (nf_workspace_bytes(h, 3, B): what one tiled call of B images needs; 0 for a
+ * shape held whole or a handle without the flag, and then there is nothing to do) */
+int nf_reserve_sample_vjp_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
 
 /* Host-only: the SDN5 scalars the kernels receive for a given (iso, cam):
  * out[0] = beta1/gain, out[1] = beta2 (cond_utils.py:205-239). */

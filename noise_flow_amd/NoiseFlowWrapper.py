@@ -32,7 +32,7 @@ from .noise_flow_model import NoiseFlow
 
 class NoiseFlowWrapper:
     def __init__(self, path, sampling_temperature=0.6, binding="loss_first", device=None, seed=None,
-                 bn_mode="running", compat=None, patch_shape=None, grad_kernel=None, grad_tiles=None, sample_vjp_kernel=None):
+                 bn_mode="running", compat=None, patch_shape=None, grad_kernel=None, grad_tiles=None, sample_vjp_kernel=None, sample_vjp_tiles=None):
         if compat not in (None, "reference"):
             raise ValueError("compat must be None or 'reference'")
         if compat == "reference":
@@ -55,6 +55,7 @@ class NoiseFlowWrapper:
         self.device = device
         self.grad_kernel = grad_kernel   # 'scalar' | 'mfma' | 'gemm' (NoiseFlow); None: hps.grad_kernel, else 'scalar'
         self.grad_tiles = grad_tiles     # True: input gradients of images beyond 64x64 (NoiseFlow; with grad_kernel='mfma' also at widths 17 .. 32, with grad_kernel='gemm' beyond 32x32 at widths 33 .. 512); None: hps.grad_tiles, else False
+        self.sample_vjp_tiles = sample_vjp_tiles   # True: differentiable sampling on every H x W at widths up to 16 (NoiseFlow; includes grad_tiles); None: hps.sample_vjp_tiles, else False
         self.sample_vjp_kernel = sample_vjp_kernel   # 'scalar' | 'mfma' (NoiseFlow: differentiable sampling at widths 17 .. 32); None: hps.sample_vjp_kernel, else 'scalar'
         self.hps = self.hps_loader(os.path.join(self.nf_path, "hps.txt"))
         if seed is not None:
@@ -69,7 +70,8 @@ class NoiseFlowWrapper:
             setattr(self.hps, "x_shape", self.x_shape)
         self.logger.info("Building Noise Flow")
         self.nf_model = NoiseFlow(self.x_shape[1:], self.bn_mode == "batch", self.hps, binding=self.binding, device=self.device,
-                                  grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles, sample_vjp_kernel=self.sample_vjp_kernel)
+                                  grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles, sample_vjp_kernel=self.sample_vjp_kernel,
+                                  sample_vjp_tiles=self.sample_vjp_tiles)
         self.logger.info("Restoring best model")
         self.nf_model.restore(self.model_checkpoint_path)
 

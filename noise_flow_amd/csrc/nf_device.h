@@ -440,6 +440,8 @@ struct NfGradLaunch {
 // into segments as the forward direction's (at most 3 couplings each: 32 - 2 x 12 = 8 core pixels), with every tensor between two
 // segments in HBM.  Width 32 runs the same scheme on nf_grad_wide_kernel (NF_CFG_GRAD_TILED_WIDE): the same tiles, halo and
 // segments, a.gate_words = nfgw_tpw(tile H) x (couplings of the largest segment), LDS = nfgw_lds_floats of those (<= 81 KiB).
+// nf_sample_vjp runs the same scheme in the sampling direction (NF_CFG_SVJP_TILED, nf_sample_grad_kernel<.., TILED>): the same
+// tiles, halo, plan and segments (tests/test_sample_vjp_tiles_cpu.py pins the halo in fp64), NfSampleGradTileLaunch below.
 #define NF_GRAD_TILE 32
 enum : uint32_t {
     NF_GT_GY_ACC = 1u,     // gy_out += instead of gy_out = (a segment behind this one has written it)
@@ -483,6 +485,24 @@ struct NfSampleGradLaunch {
     int32_t gate_words;    // nf_grad_gate_words; nf_sample_grad_wide_kernel: nfgw_tpw(H) x n_cpl
 };
 #define NF_SVJP_W8_MAX_PIXELS 3072   // padded width 8 beyond 1 024 pixels: 768 threads x 4 pixels (nf_sample_grad.hip, dispatch_sgrad)
+// The record of a tiled launch: the whole-patch record and the tile / image fields behind it — a record of its own, so that the
+// whole-patch kernels keep their kernel-argument layout (and with it every instruction: profiles/sample_vjp_tiled_asm.txt).
+struct NfSampleGradTileLaunch : NfSampleGradLaunch {
+    // Tiles (NF_CFG_SVJP_TILED, nf_sample_grad_kernel<.., TILED>; "gradient tiles" above, the same tiles, halo and plan): patch b of the
+    // launch is tile b % (tile_ny tile_nx) of image b / (tile_ny tile_nx), H x W pixels at the nf_tile_origin of `tile_halo`; every
+    // tensor is [images][img_H][img_W][4], cond_rows and the Philox key are per image, `prog` is one segment of the NLL-order program,
+    // last_cpl / n_cpl count inside it, gate_words is sized for the call's largest segment; gx_in / x_out / gtemp_out are not used
+    const float *z_in;     // the tensor at the segment's sampling-side input (behind it in NLL order), or null for the NLL-last
+                           // segment: eps * temp, from `eps` or the regenerated draw
+    const float *g_in;     // d L / d (the tensor in front of the segment in NLL order): the caller's gx_in for the NLL-first segment
+    float *g_out;          // d L / d z_in, core windows only, or null (the NLL-last segment stores geps_out = temp g instead)
+    float *tile_sum;       // [launch patches] or null: sum over the tile's core of g eps, in the kernel's fixed order (NLL-last segment;
+                           // nf_tile_sum_kernel adds an image's tiles up in tile order)
+    int32_t img_H, img_W;
+    int32_t tile_ny, tile_nx;
+    int32_t tile_halo;
+    uint32_t tflags;       // NF_GT_*
+};
 
 // ---- input gradients at coupling width 32 on the f32 matrix cores (nf_grad_wide.hip, NF_CFG_GRAD_MFMA) --------------------
 // Same launch record (NfGradLaunch), same op list; the gradient block carries per coupling, instead of the generic block, every

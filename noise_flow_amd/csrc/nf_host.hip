@@ -782,7 +782,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     out.tile_w = tw;
     out.segs.clear();
     if (cfg->n_layers < 1) return fail(NF_EINVAL, "n_layers must be >= 1");
-    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE | NF_CFG_GRAD_GEMM | NF_CFG_GRAD_TILED_GEMM | NF_CFG_SVJP_MFMA)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
+    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE | NF_CFG_GRAD_GEMM | NF_CFG_GRAD_TILED_GEMM | NF_CFG_SVJP_MFMA | NF_CFG_SVJP_TILED)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
     const double HW = (double)cfg->height * cfg->width;
 
     // intermediate list in NLL order
@@ -1066,7 +1066,8 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
     }
     if (cfg->flags & NF_CFG_FP16_CNN) return fail(NF_EINVAL, "nf_nll_grad: fp32 handles only (NF_CFG_FP16_CNN is set)");
     const bool whole = cfg->height <= 64 && cfg->width <= 64;   // one workgroup's patch
-    const bool tile_flag = (cfg->flags & NF_CFG_GRAD_TILED) != 0;
+    // NF_CFG_SVJP_TILED includes NF_CFG_GRAD_TILED: one gradient block and one plan serve nf_nll_grad and nf_sample_vjp
+    const bool tile_flag = (cfg->flags & (NF_CFG_GRAD_TILED | NF_CFG_SVJP_TILED)) != 0;
     const bool wide_flag = (cfg->flags & NF_CFG_GRAD_TILED_WIDE) != 0;
     if (!whole && !tile_flag && !wide_flag)
         return fail(NF_EINVAL, "nf_nll_grad: patches of up to 64x64 (%dx%d given; no tiled evaluation)", cfg->height, cfg->width);
@@ -1131,8 +1132,10 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
 // What nf_sample_vjp supports and which kernel runs it (`svjp_path`: NF_SVJP_PATH_*).  nf_sample_grad.hip interprets the SCALAR
 // gradient block on whole patches: whatever grad_support sends to NF_GRAD_PATH_SCALAR for this model, shape and flags.  With
 // NF_CFG_SVJP_MFMA, nf_sample_grad_wide.hip interprets the matrix-core block: whatever grad_support sends to NF_GRAD_PATH_WIDE32
-// (that kernel keeps inside nfgw_lds_floats).  Either way the width, register and LDS limits are nf_nll_grad's: no arithmetic here.
-int sample_vjp_support(const nf_config *cfg, const Built &fwd, int *svjp_path = nullptr)
+// (that kernel keeps inside nfgw_lds_floats).  With NF_CFG_SVJP_TILED, whatever grad_support sends to NF_GRAD_PATH_TILED (padded widths
+// 4 / 8 / 16) runs nf_sample_grad_kernel<.., TILED> on the gradient plan's tiles and segments (sample_vjp_tiled).  Either way the
+// width, register and LDS limits are nf_nll_grad's: no arithmetic here.
+static int sample_vjp_support_(const nf_config *cfg, const Built &fwd, int *svjp_path)
 {
     if (svjp_path) *svjp_path = NF_SVJP_PATH_SCALAR;
     int path = NF_GRAD_PATH_SCALAR;
@@ -1142,6 +1145,10 @@ int sample_vjp_support(const nf_config *cfg, const Built &fwd, int *svjp_path = 
         const size_t at = why.find("nf_nll_grad");
         if (at != std::string::npos) why.replace(at, strlen("nf_nll_grad"), "nf_sample_vjp");
         return fail(rc, "%s", why.c_str());
+    }
+    if (path == NF_GRAD_PATH_TILED && (cfg->flags & NF_CFG_SVJP_TILED)) {
+        if (svjp_path) *svjp_path = NF_SVJP_PATH_TILED;
+        return NF_OK;
     }
     if (path == NF_GRAD_PATH_SCALAR) {
         if (fwd.lay[NF_PATH_SCALAR].prog.width == 8 && cfg->height * cfg->width > NF_SVJP_W8_MAX_PIXELS)
@@ -1164,6 +1171,17 @@ int sample_vjp_support(const nf_config *cfg, const Built &fwd, int *svjp_path = 
                            "no matrix-core or GEMM variant yet%s", gemm ? "GEMM" : "matrix-core",
                 gemm ? "NF_CFG_GRAD_GEMM / NF_CFG_GRAD_TILED_GEMM" : "NF_CFG_GRAD_MFMA / NF_CFG_GRAD_TILED_WIDE", fwd.raw_width,
                 path == NF_GRAD_PATH_WIDE32 ? " (set NF_CFG_SVJP_MFMA for the matrix-core kernel)" : "");
+}
+
+int sample_vjp_support(const nf_config *cfg, const Built &fwd, int *svjp_path = nullptr)
+{
+    const int rc = sample_vjp_support_(cfg, fwd, svjp_path);
+    // a refusal at a width the tile mode does not cover says so beside its present words
+    if (rc != NF_OK && (cfg->flags & NF_CFG_SVJP_TILED) && !(cfg->flags & NF_CFG_FP16_CNN) && fwd.lay[NF_PATH_SCALAR].prog.width > 16) {
+        const std::string why = g_last_error;
+        return fail(rc, "%s (NF_CFG_SVJP_TILED: tiles at coupling widths up to 16)", why.c_str());
+    }
+    return rc;
 }
 
 // the paths whose couplings are in the NFGW_* layout (the matrix-core kernel, whole patches or tiles); those in the NFGG_* layout
@@ -1959,10 +1977,13 @@ static int launch_resident(nf_handle *h, int direction, NfLaunch &a, hipStream_t
 
 static size_t grad_workspace_bytes(const nf_handle *h, int64_t B);
 
+static size_t svjp_workspace_bytes(const nf_handle *h, int64_t B);
+
 int64_t nf_workspace_bytes(const nf_handle *h, int32_t direction, int64_t B)
 {
-    if (!h || direction < 0 || direction > 2 || B < 0) return fail(NF_EINVAL, "bad argument");
+    if (!h || direction < 0 || direction > 3 || B < 0) return fail(NF_EINVAL, "bad argument");
     if (direction == 2) return (int64_t)grad_workspace_bytes(h, B);   // one tiled nf_nll_grad call
+    if (direction == 3) return (int64_t)svjp_workspace_bytes(h, B);   // one tiled nf_sample_vjp call
     return (int64_t)tiled_workspace_bytes(h, direction, B, direction == 0);
 }
 
@@ -2384,6 +2405,154 @@ int nf_sample_vjp_supported(const nf_config *cfg, const nf_layer_desc *layers, c
     return sample_vjp_support(cfg, b);
 }
 
+// ---- nf_sample_vjp on tiles (NF_CFG_SVJP_TILED; nf_device.h, "gradient tiles", NfSampleGradTileLaunch) ----
+// Sampling-order segment j of a tiled call is segment S - 1 - j of the gradient plan: op i of the NLL program is op n - 1 - i of the
+// sampling program.  Its forward launch runs on the sampling direction's own tiles (tile_h x tile_w, halo 2 per coupling), as
+// grad_fwd_seg's.
+static Built::TileSeg svjp_fwd_seg(const nf_handle *h, int j)
+{
+    const int S = (int)h->grad_segs.size(), n = h->gprog.n_ops;
+    const Built::TileSeg &g = h->grad_segs[S - 1 - j];
+    Built::TileSeg f;
+    f.op0 = n - g.op1;
+    f.op1 = n - g.op0;
+    f.halo = g.halo / kGradSegs.halo_per_cpl * kFwdSegs.halo_per_cpl;
+    f.ny = nf_tile_count(h->cfg.height, h->rev.tile_h, f.halo);
+    f.nx = nf_tile_count(h->cfg.width, h->rev.tile_w, f.halo);
+    return f;
+}
+
+// scratch of one call: the tile sums of the NLL-last segment's launch (gtemp), the S - 1 tensors between two segments, two gradient
+// tensors (ping-pong)
+static size_t svjp_workspace_bytes(const nf_handle *h, int64_t B)
+{
+    if (h->svjp_rc != NF_OK || h->svjp_path != NF_SVJP_PATH_TILED || B <= 0) return 0;
+    const int S = (int)h->grad_segs.size();
+    const Built::TileSeg &last = h->grad_segs[S - 1];
+    return round_up_256((size_t)B * last.ny * last.nx * sizeof(float)) + grad_img_bytes(h, B) * (size_t)(S - 1 + (S - 1 < 2 ? S - 1 : 2));
+}
+
+// Forward: the tiled launches of nf_sample cut at the gradient plan's boundaries, every tensor between two segments kept; the
+// sampling-last one runs only for x_out.  Backward: one launch of nf_sample_grad_kernel<.., TILED> per segment in NLL order, first to
+// last; segment s starts from the tensor kept behind it (the NLL-last one from eps * temp), takes the gradient segment s - 1 stored
+// (the first one gx_in) and stores core windows — to the other of two scratch tensors, or (the NLL-last one) geps_out = temp g and
+// its tile sums of g eps, which nf_tile_sum_kernel adds up per image.  gy_out: the first launch whose segment has an SDN-kind op
+// stores it, later ones add to it.  Everything is enqueued on `st`.
+static int sample_vjp_tiled(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp, int64_t B,
+                            const nf_cond_row &r, const nf_cond_row *rows, const float *gx_in, float *x_out, float *gy_out, float *geps_out,
+                            float *gtemp_out, hipStream_t st)
+{
+    const int S = (int)h->grad_segs.size(), H = h->cfg.height, W = h->cfg.width;
+    const int fpath = select_path(h, 1);
+    if (h->rev.lay[fpath].prog.n_ops != h->gprog.n_ops) return fail(NF_EINVAL, "nf_sample_vjp: the sampling program does not mirror the gradient program");
+    NfTileParts tp;
+    memset(&tp, 0, sizeof(tp));
+    tp.n_seg = S;
+    Built::TileSeg fseg[NF_MAX_TILE_SEGS];
+    for (int j = 0; j < S; ++j) {
+        fseg[j] = svjp_fwd_seg(h, j);
+        tp.nt[j] = fseg[j].ny * fseg[j].nx;
+        const int64_t most = std::max<int64_t>(tp.nt[j], (int64_t)h->grad_segs[j].ny * h->grad_segs[j].nx);
+        if (B > (INT64_MAX / 64) / most) return fail(NF_EINVAL, "B too large");
+    }
+    const bool back = gy_out || geps_out || gtemp_out;
+    nf_handle::Workspace *wsp = nullptr;
+    const int rc = ws_acquire(h, svjp_workspace_bytes(h, B), st, &wsp);
+    if (rc != NF_OK) return rc;
+    const size_t img_bytes = grad_img_bytes(h, B);
+    const int nt_last = h->grad_segs[S - 1].ny * h->grad_segs[S - 1].nx;
+    char *q = wsp->p;
+    float *const sums = reinterpret_cast<float *>(q);
+    q += round_up_256((size_t)B * nt_last * sizeof(float));
+    float *kept[NF_MAX_TILE_SEGS + 1] = {}, *gbuf[2] = {nullptr, nullptr};   // kept[s]: the tensor in front of NLL segment s (s = 1 .. S - 1)
+    for (int s = 1; s < S; ++s, q += img_bytes) kept[s] = reinterpret_cast<float *>(q);
+    for (int i = 0; i < 2 && i < S - 1; ++i, q += img_bytes) gbuf[i] = reinterpret_cast<float *>(q);
+
+    hipError_t e = hipSuccess;
+    const int n_fwd = x_out ? S : S - 1;   // the sampling-last segment's forward launch only forms x
+    if (n_fwd > 0) {
+        NfLaunch a;
+        memset(&a, 0, sizeof(a));
+        a.in = eps;
+        a.y = y;
+        a.B = B;
+        a.patch_base = patch_index_base;
+        a.seed = seed;
+        a.in_scale = temp;
+        memcpy(a.cond_a, r.a, sizeof(r.a));
+        memcpy(a.cond_b, r.b, sizeof(r.b));
+        a.cond_rows = rows;
+        a.flags = eps ? 0u : NF_K_PHILOX_IN;
+        float *outs[NF_MAX_TILE_SEGS];
+        for (int j = 0; j < S; ++j) outs[j] = j == S - 1 ? x_out : kept[S - 1 - j];
+        e = launch_segments(h, 1, a, fseg, n_fwd, tp, nullptr, outs, st);
+    }
+    if (e == hipSuccess && back) {
+        NfSampleGradTileLaunch a;
+        memset(&a, 0, sizeof(a));
+        a.params = h->d_grad;
+        a.y = y;
+        a.eps = eps;
+        a.patch_base = patch_index_base;
+        a.seed = seed;
+        a.temp = temp;
+        memcpy(a.cond_a, r.a, sizeof(r.a));
+        memcpy(a.cond_b, r.b, sizeof(r.b));
+        a.cond_rows = rows;
+        a.H = H < NF_GRAD_TILE ? H : NF_GRAD_TILE;
+        a.W = W < NF_GRAD_TILE ? W : NF_GRAD_TILE;
+        a.img_H = H;
+        a.img_W = W;
+        a.gate_words = nf_grad_gate_words(h->grad_seg_cpl, h->gprog.width);
+        bool gy_written = false;
+        for (int s = 0; s < S && e == hipSuccess; ++s) {
+            const Built::TileSeg &g = h->grad_segs[s];
+            NfProgram sp;
+            memset(&sp, 0, sizeof(sp));
+            sp.width = h->gprog.width;
+            sp.n_ops = g.op1 - g.op0;
+            memcpy(sp.ops, h->gprog.ops + g.op0, sizeof(NfOp) * (size_t)sp.n_ops);
+            NfSampleGradTileLaunch t = a;
+            t.last_cpl = -1;
+            bool sdn = false;
+            for (int i = 0; i < sp.n_ops; ++i) {
+                if (sp.ops[i].type == NF_OP_COUPLING_FWD) {
+                    t.last_cpl = i;
+                    ++t.n_cpl;
+                }
+                sdn = sdn || sp.ops[i].type == NF_OP_SDN_DIV;
+            }
+            const bool last = s == S - 1;
+            t.B = B * g.ny * g.nx;
+            t.tile_ny = g.ny;
+            t.tile_nx = g.nx;
+            t.tile_halo = g.halo;
+            t.z_in = last ? nullptr : kept[s + 1];
+            t.g_in = s == 0 ? gx_in : gbuf[(s - 1) & 1];
+            t.g_out = last ? nullptr : gbuf[s & 1];
+            t.geps_out = last ? geps_out : nullptr;
+            t.tile_sum = last && gtemp_out ? sums : nullptr;
+            // a model without an SDN-kind op: the last launch stores the zeros
+            const bool wr = gy_out && (sdn || (last && !gy_written));
+            t.gy_out = wr ? gy_out : nullptr;
+            t.tflags = wr && gy_written ? NF_GT_GY_ACC : 0u;
+            gy_written = gy_written || wr;
+            if (last && !t.geps_out && !t.tile_sum && !t.gy_out) break;   // nothing left to store
+            e = nf_launch_sample_grad_tiled(sp, t, h->grad_seg_cpl, h->n_cu, st);
+        }
+        if (e == hipSuccess && gtemp_out) e = nf_launch_tile_sum(sums, nt_last, B, gtemp_out, st);
+    }
+    ws_release(h, wsp, st);
+    if (e != hipSuccess) return fail_hip(e, "nf_sample_vjp launch (tiles)");
+    return NF_OK;
+}
+
+int nf_reserve_sample_vjp_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight)
+{
+    if (!h || B < 0 || calls_in_flight < 1 || calls_in_flight > 64) return fail(NF_EINVAL, "bad argument");
+    return reserve_workspace(h, svjp_workspace_bytes(h, B), calls_in_flight);
+}
+
 int nf_sample_vjp_path(const nf_handle *h)
 {
     if (!h) return fail(NF_EINVAL, "handle is NULL");
@@ -2414,6 +2583,12 @@ int nf_sample_vjp(nf_handle *h, const float *y, const float *eps, uint64_t seed,
         if (rc != NF_OK) return rc;
     }
     if (B == 0) return NF_OK;
+    if (h->svjp_path == NF_SVJP_PATH_TILED) {
+        NfDeviceGuard guard;
+        int rc = guard.enter(h->device);
+        if (rc != NF_OK) return rc;
+        return sample_vjp_tiled(h, y, eps, seed, patch_index_base, temp, B, r, rows, gx_in, x_out, gy_out, geps_out, gtemp_out, (hipStream_t)stream);
+    }
     NfSampleGradLaunch a;
     memset(&a, 0, sizeof(a));
     a.params = h->d_grad;

@@ -70,11 +70,16 @@ int nf_bs_wide_run(nf_trainer *t, const nf_bs_wide_args &a, hipStream_t st);
 struct NfProgram;
 struct NfGradLaunch;
 struct NfSampleGradLaunch;
+struct NfSampleGradTileLaunch;
 hipError_t nf_launch_grad(const NfProgram &prog, const NfGradLaunch &a, bool tiled, int n_cpl, int n_cu, hipStream_t stream);
 hipError_t nf_launch_grad_wide(const NfProgram &prog, const NfGradLaunch &a, bool tiled, int n_cpl, int n_cu, hipStream_t stream);
 hipError_t nf_launch_grad_gemm(const NfProgram &prog, const NfGradLaunch &a, bool tiled, int n_cpl, int n_cu, void *scratch, size_t scratch_bytes,
                                hipStream_t stream);
 int nf_grad_gemm_groups(int64_t B, int n_cu);   // the persistent grid of the GEMM kernel: one workgroup per CU, never more than patches
 hipError_t nf_launch_sample_grad(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, hipStream_t stream);
+// NF_SVJP_PATH_TILED: one segment of a tiled call, as `tiled` above (a.n_cpl = the segment's own couplings)
+hipError_t nf_launch_sample_grad_tiled(const NfProgram &prog, const NfSampleGradTileLaunch &a, int n_cpl, int n_cu, hipStream_t stream);
+// gtemp of a tiled nf_sample_vjp: out[b] = the nt tile sums of image b at part + b nt, added in tile order
+hipError_t nf_launch_tile_sum(const float *part, int nt, int64_t B, float *out, hipStream_t stream);
 // NF_SVJP_PATH_WIDE32: programs over the NFGW_* block, a.gate_words = nfgw_tpw(a.H) x a.n_cpl
 hipError_t nf_launch_sample_grad_wide(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, hipStream_t stream);

@@ -23,6 +23,16 @@
 // eps * temp instead of the rebuilt ones, as nf_grad_kernel does for the ops behind x.
 // The frame (conditioning, loads, the 4x4 product) and the gate record with the coupling CNN are nf_grad_common.h's, shared with
 // nf_grad_kernel; slot set-up and the transposed pass stand inline in both kernels (nf_grad_common.h says why).
+//
+// TILED (NF_CFG_SVJP_TILED, nf_device.h "gradient tiles", NfSampleGradTileLaunch): a "patch" of the launch is one H x W tile of an
+// img_H x img_W image and `prog` one SEGMENT of the NLL-order program.  The tile starts from the tensor kept at the segment's
+// sampling-side input (z_in; the NLL-last segment from eps * temp, the draw keyed by image and image pixel), runs the same forward
+// sweep over the segment's ops, takes g from g_in (the caller's gx_in, or what the segment in front of it stored), runs the same
+// backward sweep and stores its CORE window only: g_out, or (NLL-last) geps_out = temp g and the tile's sum of g eps over its core
+// (tile_sum; nf_tile_sum_kernel adds an image's tiles up in tile order); gy_out stored or added to.  Border masks follow the image
+// border, conditioning rows are per image, and x is not formed here (the tiled nf_sample launches in front of this one form it).
+// The whole-patch instantiations keep the parent's instructions (profiles/sample_vjp_tiled_asm.txt): what TILED changes stands in
+// `if constexpr` arms, and its fields in a launch record of its own.
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stdint.h>
@@ -36,9 +46,14 @@
 
 namespace {
 
-template <int WIDTH, int THREADS, int PX>
-__global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram prog, const NfSampleGradLaunch a)
+// the launch record: a tiled launch's carries the tile / image fields behind the whole-patch record (nf_device.h)
+template <bool TILED>
+using SGradArgs = std::conditional_t<TILED, NfSampleGradTileLaunch, NfSampleGradLaunch>;
+
+template <int WIDTH, int THREADS, int PX, bool TILED = false>
+__global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram prog, const SGradArgs<TILED> a)
 {
+    using ARGS = SGradArgs<TILED>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NPIX = THREADS * PX;
     constexpr int NW = THREADS / 64;
@@ -52,6 +67,7 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
     const int t = threadIdx.x;
     int lidx[PX], gidx[PX], bmask[PX];
     bool act[PX];
+    [[maybe_unused]] int prow[PX], pcol[PX];   // TILED: row / column of the slot's pixel inside the tile
 #pragma unroll
     for (int k = 0; k < PX; ++k) {
         const int p = t + THREADS * k;
@@ -59,6 +75,8 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
         const int pp = act[k] ? p : 0;
         const int r = pp / W, c = pp - r * W;
         gidx[k] = pp;
+        prow[k] = r;
+        pcol[k] = c;
         lidx[k] = (r + 1) * Wp + (c + 1);
         bmask[k] = (r == 0 ? 1 : 0) | (r == H - 1 ? 2 : 0) | (c == 0 ? 4 : 0) | (c == W - 1 ? 8 : 0);
     }
@@ -70,14 +88,37 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
     const int last_cpl = a.last_cpl;
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-        const size_t patch_off = (size_t)b * (size_t)HW;
+        // Where this "patch" sits: on its own, or — TILED — as tile b % tiles of image b / tiles (nf_device.h, "overlapping tiles"):
+        // addresses, border masks and the Philox key follow the image, own[] is the tile's core window
+        int64_t img = b;
+        [[maybe_unused]] bool own[PX];
+        if constexpr (TILED) {
+            const int nt = a.tile_ny * a.tile_nx;
+            img = b / nt;
+            const int ti = (int)(b - img * nt);
+            const int ty = ti / a.tile_nx, tx = ti - ty * a.tile_nx;
+            const int oy = nf_tile_origin(ty, a.img_H, H, a.tile_halo), ox = nf_tile_origin(tx, a.img_W, W, a.tile_halo);
+            const int cy0 = nf_tile_core0(ty, a.img_H, H, a.tile_halo), cy1 = nf_tile_core1(ty, a.tile_ny, a.img_H, H, a.tile_halo);
+            const int cx0 = nf_tile_core0(tx, a.img_W, W, a.tile_halo), cx1 = nf_tile_core1(tx, a.tile_nx, a.img_W, W, a.tile_halo);
+#pragma unroll
+            for (int k = 0; k < PX; ++k) {
+                const int R = oy + prow[k], C = ox + pcol[k];
+                gidx[k] = R * a.img_W + C;
+                bmask[k] = (R == 0 ? 1 : 0) | (R == a.img_H - 1 ? 2 : 0) | (C == 0 ? 4 : 0) | (C == a.img_W - 1 ? 8 : 0);
+                own[k] = act[k] && R >= cy0 && R < cy1 && C >= cx0 && C < cx1;
+            }
+        }
+        const size_t patch_off = [&] {
+            if constexpr (TILED) return (size_t)img * (size_t)a.img_H * (size_t)a.img_W;
+            else return (size_t)b * (size_t)HW;
+        }();
         const float4 *const y4 = reinterpret_cast<const float4 *>(a.y) + patch_off;   // (not dereferenced when a.y is null)
-        const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + b;
+        const nf_crow_p crow = (nf_crow_p)(a.cond_rows) + img;
         const float4 *const no_in4 = nullptr;   // (the sweep starts from eps: GradFrame::load_x is not used)
         const GradSlotPix<PX> pix = {act, gidx};
-        const GradFrame<PX, NfSampleGradLaunch, GradSlotPix<PX>> F = {prog, a, pix, crow, patch_off, no_in4, y4};
+        const GradFrame<PX, ARGS, GradSlotPix<PX>> F = {prog, a, pix, crow, patch_off, no_in4, y4};
         // the sampling sweep reaches the couplings LAST TO FIRST: GradCoupling's LAST_FIRST numbering of the gate sets
-        const GradCoupling<WIDTH, THREADS, PX, NfSampleGradLaunch, true> cpl = {a, act, t0, lidx, Wp, gates, t, th, bmask};
+        const GradCoupling<WIDTH, THREADS, PX, ARGS, true> cpl = {a, act, t0, lidx, Wp, gates, t, th, bmask};
 
         // eps: the caller's, or nf_sample's draw (the same key), regenerated wherever it is needed
         auto load_eps = [&](float (&e)[PX][4]) {
@@ -86,7 +127,7 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
             } else {
 #pragma unroll
                 for (int k = 0; k < PX; ++k) {
-                    philox_normal4(a.seed, a.patch_base + b, (uint32_t)gidx[k], NF_STREAM_SAMP, e[k]);
+                    philox_normal4(a.seed, a.patch_base + img, (uint32_t)gidx[k], NF_STREAM_SAMP, e[k]);
                     if (!act[k]) e[k][0] = e[k][1] = e[k][2] = e[k][3] = 0.0f;
                 }
             }
@@ -114,13 +155,32 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
             }
         };
 
+        // the tensor the sweep starts from: eps * temp — TILED: or the tensor kept at the segment's sampling-side input
+        auto load_start = [&](float (&v)[PX][4]) {
+            if constexpr (TILED) {
+                if (a.z_in) {
+                    F.load4(a.z_in, 0.0f, v);
+                    return;
+                }
+            }
+            load_eps(v);
+#pragma unroll
+            for (int k = 0; k < PX; ++k)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) v[k][c] *= a.temp;
+        };
+
         // ---- forward sweep: x = f(y, eps, temp) ----
         float z[PX][4];
-        load_eps(z);
+        if constexpr (TILED) {
+            load_start(z);
+        } else {
+            load_eps(z);
 #pragma unroll
-        for (int k = 0; k < PX; ++k)
+            for (int k = 0; k < PX; ++k)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) z[k][c] *= a.temp;
+                for (int c = 0; c < 4; ++c) z[k][c] *= a.temp;
+        }
         {
             int cidx = a.n_cpl;
             for (int op = n_ops - 1; op >= 0; --op) {
@@ -142,7 +202,7 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
                 }
             }
         }
-        if (a.x_out) {
+        if (!TILED && a.x_out) {   // (TILED: the tiled nf_sample launches in front of this one form x)
             float4 *const o4 = reinterpret_cast<float4 *>(a.x_out) + patch_off;
 #pragma unroll
             for (int k = 0; k < PX; ++k)
@@ -152,7 +212,8 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
         // ---- backward sweep ----
         float g[PX][4];    // d L / d (the tensor in front of the NLL-order op being reached): gx_in at the start
         float gy[PX][4];
-        F.load4(a.gx_in, 0.0f, g);
+        if constexpr (TILED) F.load4(a.g_in, 0.0f, g);
+        else F.load4(a.gx_in, 0.0f, g);
 #pragma unroll
         for (int k = 0; k < PX; ++k)
 #pragma unroll
@@ -289,11 +350,15 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
             } else if (type == NF_OP_SDN_DIV) {
                 const float ck1 = F.cond_a(off), cb2 = F.cond_b(off);
                 if (op > last_cpl) {   // the first ops sampling runs: the op's output, forward from eps * temp
-                    load_eps(z);
+                    if constexpr (TILED) {
+                        load_start(z);
+                    } else {
+                        load_eps(z);
 #pragma unroll
-                    for (int k = 0; k < PX; ++k)
+                        for (int k = 0; k < PX; ++k)
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) z[k][c] *= a.temp;
+                            for (int c = 0; c < 4; ++c) z[k][c] *= a.temp;
+                    }
                     for (int q = n_ops - 1; q >= op; --q) pointwise_inv(q, z);
                 }
                 float yy[PX][4];
@@ -321,46 +386,96 @@ __global__ __launch_bounds__(THREADS) void nf_sample_grad_kernel(const NfProgram
             }
         }
 
-        if (a.gy_out) {
-            float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+        if constexpr (TILED) {
+            // the core window only; every pixel of the image is in exactly one tile's core, so an accumulating launch adds to gy
+            // without atomics (the launch that wrote it is ahead of this one in the stream)
+            if (a.g_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.g_out) + patch_off;
 #pragma unroll
-            for (int k = 0; k < PX; ++k)
-                if (act[k]) o4[gidx[k]] = make_float4(gy[k][0], gy[k][1], gy[k][2], gy[k][3]);
-        }
-        if (a.geps_out) {
-            float4 *const o4 = reinterpret_cast<float4 *>(a.geps_out) + patch_off;
-#pragma unroll
-            for (int k = 0; k < PX; ++k)
-                if (act[k]) o4[gidx[k]] = make_float4(a.temp * g[k][0], a.temp * g[k][1], a.temp * g[k][2], a.temp * g[k][3]);
-        }
-        if (a.gtemp_out) {   // wave-uniform
-            load_eps(z);
-            float s = 0.0f;
-#pragma unroll
-            for (int k = 0; k < PX; ++k)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) s = act[k] ? fmaf(g[k][c], z[k][c], s) : s;
-            float r = wave_sum(s);
-            if constexpr (NW > 1) {
-                __syncthreads();   // the previous patch's reader is done
-                if ((t & 63) == 0) red[t >> 6] = r;
-                __syncthreads();
-                if (t == 0) {
-                    r = 0.f;
-                    for (int wv = 0; wv < NW; ++wv) r += red[wv];
-                }
+                for (int k = 0; k < PX; ++k)
+                    if (own[k]) o4[gidx[k]] = make_float4(g[k][0], g[k][1], g[k][2], g[k][3]);
             }
-            if (t == 0) a.gtemp_out[b] = r;
+            if (a.gy_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+                const bool acc = (a.tflags & NF_GT_GY_ACC) != 0;
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+                    if (own[k]) {
+                        float4 v = make_float4(gy[k][0], gy[k][1], gy[k][2], gy[k][3]);
+                        if (acc) {
+                            const float4 p = o4[gidx[k]];
+                            v = make_float4(p.x + v.x, p.y + v.y, p.z + v.z, p.w + v.w);
+                        }
+                        o4[gidx[k]] = v;
+                    }
+            }
+            if (a.geps_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.geps_out) + patch_off;
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+                    if (own[k]) o4[gidx[k]] = make_float4(a.temp * g[k][0], a.temp * g[k][1], a.temp * g[k][2], a.temp * g[k][3]);
+            }
+            if (a.tile_sum) {   // wave-uniform: the tile's share of gtemp, its core only
+                load_eps(z);
+                float s = 0.0f;
+#pragma unroll
+                for (int k = 0; k < PX; ++k)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) s = own[k] ? fmaf(g[k][c], z[k][c], s) : s;
+                float r = wave_sum(s);
+                if constexpr (NW > 1) {
+                    __syncthreads();   // the previous tile's reader is done
+                    if ((t & 63) == 0) red[t >> 6] = r;
+                    __syncthreads();
+                    if (t == 0) {
+                        r = 0.f;
+                        for (int wv = 0; wv < NW; ++wv) r += red[wv];
+                    }
+                }
+                if (t == 0) a.tile_sum[b] = r;
+            }
+        } else {
+            if (a.gy_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.gy_out) + patch_off;
+    #pragma unroll
+                for (int k = 0; k < PX; ++k)
+                    if (act[k]) o4[gidx[k]] = make_float4(gy[k][0], gy[k][1], gy[k][2], gy[k][3]);
+            }
+            if (a.geps_out) {
+                float4 *const o4 = reinterpret_cast<float4 *>(a.geps_out) + patch_off;
+    #pragma unroll
+                for (int k = 0; k < PX; ++k)
+                    if (act[k]) o4[gidx[k]] = make_float4(a.temp * g[k][0], a.temp * g[k][1], a.temp * g[k][2], a.temp * g[k][3]);
+            }
+            if (a.gtemp_out) {   // wave-uniform
+                load_eps(z);
+                float s = 0.0f;
+    #pragma unroll
+                for (int k = 0; k < PX; ++k)
+    #pragma unroll
+                    for (int c = 0; c < 4; ++c) s = act[k] ? fmaf(g[k][c], z[k][c], s) : s;
+                float r = wave_sum(s);
+                if constexpr (NW > 1) {
+                    __syncthreads();   // the previous patch's reader is done
+                    if ((t & 63) == 0) red[t >> 6] = r;
+                    __syncthreads();
+                    if (t == 0) {
+                        r = 0.f;
+                        for (int wv = 0; wv < NW; ++wv) r += red[wv];
+                    }
+                }
+                if (t == 0) a.gtemp_out[b] = r;
+            }
         }
     }
 }
 
-template <int WIDTH, int THREADS, int PX>
-hipError_t launch_sgrad(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, size_t lds, hipStream_t stream)
+template <int WIDTH, int THREADS, int PX, bool TILED = false>
+hipError_t launch_sgrad(const NfProgram &prog, const SGradArgs<TILED> &a, int n_cu, size_t lds, hipStream_t stream)
 {
     int dev = 0;
     (void)hipGetDevice(&dev);
-    return flow_launch<&nf_sample_grad_kernel<WIDTH, THREADS, PX>>(THREADS, lds, prog, a, n_cu, dev, stream);
+    return flow_launch<&nf_sample_grad_kernel<WIDTH, THREADS, PX, TILED>>(THREADS, lds, prog, a, n_cu, dev, stream);
 }
 
 // the geometries of nf_grad.hip's dispatch_grad (nf_grad_threads, nf_grad_px), but for width 8 beyond 1 024 pixels: 768 x 4 pixel slots,
@@ -387,9 +502,40 @@ hipError_t dispatch_sgrad(const NfProgram &prog, const NfSampleGradLaunch &a, in
     return hipErrorInvalidValue;
 }
 
+// TILED: tiles are at most 32x32 (nf_device.h, NF_GRAD_TILE) — the three geometries nf_grad.hip tiles with, widths 4 / 8 / 16 (no
+// 1 024-thread or 768-thread build, and none at width 32)
+template <int WIDTH>
+hipError_t dispatch_sgrad_tiled(const NfProgram &prog, const NfSampleGradTileLaunch &a, int n_cu, size_t lds, hipStream_t stream)
+{
+    const int hw = a.H * a.W;
+    if (hw <= 64) return launch_sgrad<WIDTH, 64, 1, true>(prog, a, n_cu, lds, stream);
+    if (hw <= 256) return launch_sgrad<WIDTH, 256, 1, true>(prog, a, n_cu, lds, stream);
+    if (hw <= 1024) return launch_sgrad<WIDTH, 256, 4, true>(prog, a, n_cu, lds, stream);
+    return hipErrorInvalidValue;
+}
+
+// gtemp of a tiled call: image b's tile sums (what the NLL-last segment's launch left, [image][tile]) added in tile order by one
+// thread — no atomics, the same bits on every run
+__global__ __launch_bounds__(64) void nf_tile_sum_kernel(const float *__restrict__ part, int nt, int64_t B, float *__restrict__ out)
+{
+    const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const float *const p = part + b * nt;
+    float s = 0.0f;
+    for (int i = 0; i < nt; ++i) s += p[i];
+    out[b] = s;
+}
+
 }  // namespace
 
-// entry point used by nf_host.hip (which has checked the supported set: sample_vjp_support)
+hipError_t nf_launch_tile_sum(const float *part, int nt, int64_t B, float *out, hipStream_t stream)
+{
+    if (!part || !out || nt < 1 || B < 1 || (B + 63) / 64 > INT32_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nf_tile_sum_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, part, nt, B, out);
+    return hipGetLastError();
+}
+
+// entry points used by nf_host.hip (which has checked the supported set: sample_vjp_support): whole patches ...
 hipError_t nf_launch_sample_grad(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, hipStream_t stream)
 {
     if (a.H < 1 || a.W < 1 || a.H > 64 || a.W > 64) return hipErrorInvalidValue;
@@ -400,6 +546,23 @@ hipError_t nf_launch_sample_grad(const NfProgram &prog, const NfSampleGradLaunch
     case 8: return dispatch_sgrad<8>(prog, a, n_cu, lds, stream);
     case 16: return dispatch_sgrad<16>(prog, a, n_cu, lds, stream);
     case 32: return dispatch_sgrad<32>(prog, a, n_cu, lds, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// ... and one segment of a tiled call: `prog` = the segment's ops, a.H x a.W = the tile, a.B = images x tiles, n_cpl = the couplings
+// of the call's largest segment (what a.gate_words and the LDS are sized by; a.n_cpl = the segment's own)
+hipError_t nf_launch_sample_grad_tiled(const NfProgram &prog, const NfSampleGradTileLaunch &a, int n_cpl, int n_cu, hipStream_t stream)
+{
+    if (a.H < 1 || a.W < 1 || a.H > NF_GRAD_TILE || a.W > NF_GRAD_TILE || a.H > a.img_H || a.W > a.img_W || a.tile_ny < 1 || a.tile_nx < 1 ||
+        a.tile_halo < 0 || !a.g_in || a.n_cpl > n_cpl)
+        return hipErrorInvalidValue;
+    const size_t lds = sizeof(float) * nf_grad_lds_floats(a.H, a.W, prog.width, n_cpl);
+    if (lds > 160 * 1024 || a.gate_words != nf_grad_gate_words(n_cpl, prog.width)) return hipErrorInvalidValue;
+    switch (prog.width) {
+    case 4: return dispatch_sgrad_tiled<4>(prog, a, n_cu, lds, stream);
+    case 8: return dispatch_sgrad_tiled<8>(prog, a, n_cu, lds, stream);
+    case 16: return dispatch_sgrad_tiled<16>(prog, a, n_cu, lds, stream);
     default: return hipErrorInvalidValue;
     }
 }

@@ -185,7 +185,7 @@ class FlowHandle:
     def __init__(self, arch, variables: Dict[str, np.ndarray], x_shape, width: int,
                  binding: str = "loss_first", device: Optional[int] = None, layers=None, tmpl=None,
                  cnn_dtype: str = "fp32", flow_permutation: int = 1, decomp: str = "LU", grad_kernel: str = "scalar",
-                 grad_tiles: bool = False, sample_vjp_kernel: str = "scalar"):
+                 grad_tiles: bool = False, sample_vjp_kernel: str = "scalar", sample_vjp_tiles: bool = False):
         self.lib = _lib.load()
         if layers is None:
             self.layers, descs, flat = _params.pack(arch, variables, width, binding, flow_permutation, decomp)
@@ -208,6 +208,7 @@ class FlowHandle:
         flags |= _lib.NF_CFG_GRAD_MFMA if grad_kernel == "mfma" else 0
         flags |= _lib.NF_CFG_GRAD_GEMM if grad_kernel == "gemm" else 0   # widths 33 .. 512: the GEMM gradient kernel
         flags |= _lib.NF_CFG_GRAD_TILED if grad_tiles else 0
+        flags |= _lib.NF_CFG_SVJP_TILED if sample_vjp_tiles else 0   # includes NF_CFG_GRAD_TILED
         wide = grad_kernel == "mfma" or (sample_vjp_kernel == "mfma" and grad_kernel == "scalar")   # NF_CFG_SVJP_MFMA includes NF_CFG_GRAD_MFMA
         flags |= _lib.NF_CFG_GRAD_TILED_WIDE if (grad_tiles and wide) else 0   # width 32: tiles of the matrix-core kernel
         flags |= _lib.NF_CFG_GRAD_TILED_GEMM if (grad_tiles and grad_kernel == "gemm") else 0   # widths 33 .. 512: tiles of the GEMM kernel
@@ -288,11 +289,16 @@ class NoiseFlow(object):
           Where both kernels hold the shape the matrix-core one was the faster (1.36 x at 24x24, 1.10 x at 16x16, width 32 x 8
           couplings; smaller shapes were not measured).
           Also selectable as ``hps.sample_vjp_kernel``; not with cnn_dtype='fp16'.
+    sample_vjp_tiles : ``True`` lets ``sample_and_vjp`` / ``sample_torch`` take every H, W up to 4096 at coupling widths up to 16:
+          a shape the whole-patch kernel does not hold runs on the tiles and segments of ``nll_and_grad``'s plan
+          (``NF_CFG_SVJP_TILED``); a shape it holds is untouched.  It includes grad_tiles=True: one gradient block and one plan
+          serve ``nll_torch`` and ``sample_torch`` (grad_tiles=True alone keeps refusing ``sample_and_vjp`` beyond the shapes held
+          whole).  Widths 17 and beyond keep their refusals.  Default ``False``; also selectable as ``hps.sample_vjp_tiles``.
     binding : 'loss_first' | 'sample_first' — template→layer binding (quirk Q1).
     """
 
     def __init__(self, x_shape, is_training=False, hps=None, variables=None, binding="loss_first", device=None,
-                 cnn_dtype=None, grad_kernel=None, grad_tiles=None, sample_vjp_kernel=None):
+                 cnn_dtype=None, grad_kernel=None, grad_tiles=None, sample_vjp_kernel=None, sample_vjp_tiles=None):
         if hps is None:
             raise ValueError("hps is required (arch, width, ...)")
         self.x_shape = [int(v) for v in x_shape]
@@ -325,9 +331,11 @@ class NoiseFlow(object):
         self.grad_kernel = grad_kernel or str(getattr(hps, "grad_kernel", "scalar"))
         self.grad_tiles = bool(getattr(hps, "grad_tiles", False) if grad_tiles is None else grad_tiles)
         self.sample_vjp_kernel = sample_vjp_kernel or str(getattr(hps, "sample_vjp_kernel", "scalar"))
+        self.sample_vjp_tiles = bool(getattr(hps, "sample_vjp_tiles", False) if sample_vjp_tiles is None else sample_vjp_tiles)
         self._flow = FlowHandle(self.arch, self._variables, self.x_shape, self.width, binding, self._dev.device.index,
                                 cnn_dtype=self.cnn_dtype, flow_permutation=self.flow_permutation, decomp=self.decomp,
-                                grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles, sample_vjp_kernel=self.sample_vjp_kernel)
+                                grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles, sample_vjp_kernel=self.sample_vjp_kernel,
+                                sample_vjp_tiles=self.sample_vjp_tiles)
 
     # ------------------------------------------------------------------ variables
     @property
@@ -346,7 +354,7 @@ class NoiseFlow(object):
         self._flow = FlowHandle(self.arch, self._variables, self.x_shape, self.width, self.binding,
                                 self._dev.device.index, cnn_dtype=self.cnn_dtype, flow_permutation=self.flow_permutation,
                                 decomp=self.decomp, grad_kernel=self.grad_kernel, grad_tiles=self.grad_tiles,
-                                sample_vjp_kernel=self.sample_vjp_kernel)
+                                sample_vjp_kernel=self.sample_vjp_kernel, sample_vjp_tiles=self.sample_vjp_tiles)
         old.close()
         if getattr(self, "_sync", None) is not None:
             self._install_sync()

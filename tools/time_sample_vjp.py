@@ -17,6 +17,14 @@ B = 1 024, temp 0.6, the same windows.  32x32: nf_sample_vjp (all outputs, and x
 the same three CNN evaluations per coupling) and nf_sample of the same handle.  `--ab-sides`: the new kernel against the scalar
 nf_sample_vjp of a handle without the flag, arms alternated `--reps` times; per arm the median and the spread (max - min) of its
 `--reps` medians, and the difference read against twice the larger spread.
+
+    python tools/time_sample_vjp.py --legs tiled [--reps 3]
+
+The tile mode (sample_vjp_tiles=True, NF_SVJP_PATH_TILED) on the shipped model at 256x256 x 16 and 1024x1024 x 1, temp 0.6, under the
+plans NF_GRAD_TILE_SEGMENTS = 8 / 4 / 3 (one handle per plan; the switch is read when a handle is made).  Per plan: nf_sample_vjp with
+all outputs and with x_out = NULL, the tiled nf_sample and the tiled nf_nll_grad of the same handle and images.  The arms are alternated
+in one process: `--reps` rounds over the three handles, one window of `--launches` launches per call and round; the median of a call's
+windows is reported, all windows are printed.  The workspace is reserved first, so no window contains an allocation.
 """
 import argparse
 import ctypes as C
@@ -37,9 +45,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--width", type=int, default=4, help="4: the shipped model (default); 32: the deep model at width 32")
     ap.add_argument("--kernel", default="scalar", help="with --width 32: 'mfma' = sample_vjp_kernel='mfma'")
-    ap.add_argument("--reps", type=int, default=4)
+    ap.add_argument("--reps", type=int, default=None, help="rounds of alternated arms (default 4; --legs tiled: 3)")
     ap.add_argument("--ab-sides", default="24,16")
+    ap.add_argument("--legs", default="whole", help="'whole' (default): the whole-patch kernels; 'tiled': the tile mode on 256x256 x 16 and 1024x1024 x 1")
     a = ap.parse_args()
+    if a.reps is None:
+        a.reps = 3 if a.legs == "tiled" else 4
+    if a.legs not in ("whole", "tiled"):
+        raise SystemExit("--legs whole or --legs tiled")
     if (a.width, a.kernel) not in ((4, "scalar"), (32, "mfma")):
         raise SystemExit("--width 4 [--kernel scalar] or --width 32 --kernel mfma")
     if a.launches < 200:
@@ -65,6 +78,16 @@ def main():
         window(max(a.launches // 4, 10))
         w = sorted(window(a.launches) for _ in range(3))
         return w[1], w
+
+    if a.legs == "tiled":
+        if (a.width, a.kernel) != (4, "scalar"):
+            raise SystemExit("--legs tiled times the shipped model")
+        res = tiled_legs(a, v, cond, temp)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
 
     res = {"B": B, "temp": temp, "launches_per_window": a.launches, "shapes": {}}
     wide = a.width == 32
@@ -134,6 +157,76 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
+
+
+def tiled_legs(a, v, cond, temp):
+    """--legs tiled (module docstring) → the result record."""
+    import numpy as np
+    import torch
+    from noise_flow_amd import NoiseFlow, _lib, default_hps
+
+    def window(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    res = {"temp": temp, "launches_per_window": a.launches, "rounds": a.reps, "shapes": {}}
+    keep = os.environ.get("NF_GRAD_TILE_SEGMENTS")
+    for side, B in ((256, 16), (1024, 1)):
+        rng = np.random.RandomState(0)
+        y = torch.as_tensor(rng.rand(B, side, side, 4).astype(np.float32)).cuda()
+        eps, g = (torch.as_tensor(rng.randn(B, side, side, 4).astype(np.float32)).cuda() for _ in range(2))
+        x = torch.as_tensor((rng.randn(B, side, side, 4) * 0.02).astype(np.float32)).cuda()
+        nll, gt = (torch.empty((B,), device="cuda") for _ in range(2))
+        o1, o2, o3 = (torch.empty_like(y) for _ in range(3))
+        arms = {}
+        for S in (8, 4, 3):
+            os.environ["NF_GRAD_TILE_SEGMENTS"] = str(S)
+            m = NoiseFlow([side, side, 4], False, default_hps(), variables=v, device=0, sample_vjp_tiles=True)
+            lib, h, st = m._flow.lib, m._flow.ptr, m._dev.stream_ptr()
+            assert lib.nf_sample_vjp_path(h) == _lib.NF_SVJP_PATH_TILED and lib.nf_grad_path(h) == _lib.NF_GRAD_PATH_TILED
+            _lib.check(lib.nf_reserve_workspace(h, B, 1))
+            _lib.check(lib.nf_reserve_grad_workspace(h, B, 1))
+            _lib.check(lib.nf_reserve_sample_vjp_workspace(h, B, 1))
+            calls = {
+                "sample": lambda lib=lib, h=h, st=st: _lib.check(lib.nf_sample(h, y.data_ptr(), eps.data_ptr(), 0, 0, temp, B, C.byref(cond),
+                                                                               o1.data_ptr(), st)),
+                "nll_grad": lambda lib=lib, h=h, st=st: _lib.check(lib.nf_nll_grad(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), None, nll.data_ptr(),
+                                                                                   o1.data_ptr(), o2.data_ptr(), st)),
+                "vjp": lambda lib=lib, h=h, st=st: _lib.check(lib.nf_sample_vjp(h, y.data_ptr(), eps.data_ptr(), 0, 0, temp, B, C.byref(cond), None,
+                                                                                g.data_ptr(), o1.data_ptr(), o2.data_ptr(), o3.data_ptr(), gt.data_ptr(), st)),
+                "vjp_no_x": lambda lib=lib, h=h, st=st: _lib.check(lib.nf_sample_vjp(h, y.data_ptr(), eps.data_ptr(), 0, 0, temp, B, C.byref(cond), None,
+                                                                                     g.data_ptr(), None, o2.data_ptr(), o3.data_ptr(), gt.data_ptr(), st)),
+            }
+            for fn in calls.values():
+                window(fn, max(a.launches // 4, 10))
+            arms[S] = (m, calls, {k: [] for k in calls})
+        for _ in range(a.reps):      # the arms alternated
+            for S, (m, calls, w) in arms.items():
+                for k, fn in calls.items():
+                    w[k].append(window(fn, a.launches))
+        shape = {}
+        for S, (m, calls, w) in arms.items():
+            med = {k: sorted(q)[len(q) // 2] for k, q in w.items()}
+            shape["S=%d" % S] = {"median_ms": med, "windows_ms": w, "vjp_over_nll_grad": med["vjp"] / med["nll_grad"],
+                                 "vjp_no_x_over_nll_grad": med["vjp_no_x"] / med["nll_grad"], "vjp_over_sample": med["vjp"] / med["sample"],
+                                 "pixels_per_s": B * side * side / med["vjp"] * 1e3}
+            fmt = lambda q: "/".join("%.4f" % t for t in q)   # noqa: E731
+            print("%dx%d x %d  S = %d  nf_sample %.4f ms [%s]   nf_nll_grad %.4f ms [%s]\n"
+                  "       nf_sample_vjp %.4f ms [%s] (%.3e pixels/s), x_out = NULL %.4f ms [%s]   vjp / nll_grad %.3f   x_out = NULL / nll_grad %.3f   "
+                  "vjp / sample %.2f" % (side, side, B, S, med["sample"], fmt(w["sample"]), med["nll_grad"], fmt(w["nll_grad"]), med["vjp"], fmt(w["vjp"]),
+                                         shape["S=%d" % S]["pixels_per_s"], med["vjp_no_x"], fmt(w["vjp_no_x"]), shape["S=%d" % S]["vjp_over_nll_grad"],
+                                         shape["S=%d" % S]["vjp_no_x_over_nll_grad"], shape["S=%d" % S]["vjp_over_sample"]), flush=True)
+        res["shapes"]["%dx%d x %d" % (side, side, B)] = shape
+    if keep is None:
+        os.environ.pop("NF_GRAD_TILE_SEGMENTS", None)
+    else:
+        os.environ["NF_GRAD_TILE_SEGMENTS"] = keep
+    return res
 
 
 FULL_ARCH = "sdn5|unc|unc|unc|unc|gain4|unc|unc|unc|unc"
