@@ -172,6 +172,12 @@ typedef struct nf_config {
                               other shape on overlapping 32-pixel tiles of that kernel, the program cut into segments
                               (NF_GRAD_PATH_TILED_GEMM).  No effect at widths up to 32; NF_CFG_FP16_CNN handles stay refused;
                               NF_CFG_GRAD_GEMM with NF_CFG_GRAD_TILED / _TILED_WIDE but without this bit stays refused beyond 32x32. */
+#define NF_CFG_SVJP_GEMM 1024 /* nf_sample_vjp at coupling widths 33 .. 512 on whole patches of every H, W <= 32: the GEMM kernel
+                              (csrc/nf_sample_grad_gemm.hip, NF_SVJP_PATH_GEMM).  Includes NF_CFG_GRAD_GEMM: the handle is treated
+                              exactly as if that bit were set, one gradient block serves nf_nll_grad and nf_sample_vjp, and nf_nll_grad
+                              returns the bits of a handle built with NF_CFG_GRAD_GEMM alone.  The flag only adds: at widths up to 32
+                              it has no effect (the same path, the same bits).  fp32 handles only; no tile mode, with or without
+                              NF_CFG_GRAD_TILED_GEMM.  (Bit 8 stays unassigned.) */
 
 /* Per-call conditioning: ONE value per call, not per patch — the reference
  * feeds length-1 lists (MiniBatchSampler.py:61-64, NoiseFlowWrapper.py:85-86).
@@ -402,8 +408,15 @@ int nf_grad_fold(const nf_config *cfg, const nf_layer_desc *layers, const float 
  * any earlier one (nf_workspace_bytes(h, 3, B), nf_reserve_sample_vjp_workspace make it allocation-free).  A shape held whole runs the
  * whole-patch kernel, bit for bit; widths 17 and beyond keep their refusals.
  * A handle with NF_CFG_GRAD_TILED alone is supported on the shapes held whole; without NF_CFG_SVJP_MFMA, handles whose gradient block is in
- * the matrix-core layout (NF_CFG_GRAD_MFMA, NF_CFG_GRAD_TILED_WIDE at padded width 32) are refused, and those in the GEMM layout
- * (NF_CFG_GRAD_GEMM, NF_CFG_GRAD_TILED_GEMM beyond width 32) always are.
+ * the matrix-core layout (NF_CFG_GRAD_MFMA, NF_CFG_GRAD_TILED_WIDE at padded width 32) are refused, and without NF_CFG_SVJP_GEMM so are
+ * those in the GEMM layout (NF_CFG_GRAD_GEMM, NF_CFG_GRAD_TILED_GEMM beyond width 32).
+ * With NF_CFG_SVJP_GEMM, coupling widths 33 .. 512 (zero-padded to 64 / 128 / 256 / 512) run the same contract on
+ * v_mfma_f32_32x32x2_f32 (csrc/nf_sample_grad_gemm.hip, NF_SVJP_PATH_GEMM) over the handle's GEMM gradient block, on every shape
+ * nf_nll_grad sends to NF_GRAD_PATH_GEMM: whole patches of H, W <= 32, at most 32 couplings, the whole layer vocabulary.  The ReLU
+ * gates of a call live in device scratch, one record per launched workgroup, in a buffer of the handle's workspace set: a call
+ * allocates only when it needs more than any earlier one (nf_workspace_bytes(h, 3, B) — the figure nf_workspace_bytes(h, 2, B) gives
+ * for nf_nll_grad on the same handle — and nf_reserve_sample_vjp_workspace make it allocation-free).  Measured, 8 couplings on 1024
+ * patches of 32x32 at widths 64 / 128 / 512: 4.91 / 11.69 / 114.8 ms, 1.022 x / 1.000 x / 1.000 x nf_nll_grad of the same handle.
  * Not covered: tiles at widths 17 and beyond, NF_CFG_FP16_CNN, batch-statistics mode, host-fed variants, parameter gradients. */
 int nf_sample_vjp(nf_handle *h, const float *y, const float *eps, uint64_t seed, int64_t patch_index_base, float temp, int64_t B,
                   const nf_cond *cond, const nf_cond_row *rows, const float *gx_in, float *x_out, float *gy_out,
@@ -418,6 +431,7 @@ int nf_sample_vjp_supported(const nf_config *cfg, const nf_layer_desc *layers, c
 #define NF_SVJP_PATH_SCALAR 0   /* nf_sample_grad_kernel (csrc/nf_sample_grad.hip) */
 #define NF_SVJP_PATH_WIDE32 1   /* NF_CFG_SVJP_MFMA: nf_sample_grad_wide_kernel (csrc/nf_sample_grad_wide.hip), v_mfma_f32_32x32x2_f32 */
 #define NF_SVJP_PATH_TILED 2    /* NF_CFG_SVJP_TILED: nf_sample_grad_kernel on 32-pixel tiles, one launch per segment */
+#define NF_SVJP_PATH_GEMM 3     /* NF_CFG_SVJP_GEMM: nf_sample_grad_gemm_kernel (csrc/nf_sample_grad_gemm.hip), widths 33 .. 512 */
 int nf_sample_vjp_path(const nf_handle *h);
 
 /* The tile plan of one image axis (see "Patch sizes"): `size` pixels, tiles of `tile` = min(size, 64) pixels, `halo` =
@@ -661,7 +675,8 @@ int nf_reserve_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
  * shape is held whole) and for the gate records of NF_GRAD_PATH_GEMM; NF_GRAD_PATH_TILED_GEMM keeps both in the one buffer */
 int nf_reserve_grad_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
 /* the same for nf_sample_vjp under NF_CFG_SVJP_TILED (nf_workspace_bytes(h, 3, B): what one tiled call of B images needs; 0 for a
- * shape held whole or a handle without the flag, and then there is nothing to do) */
+ * shape held whole or a handle without the flag, and then there is nothing to do) and for the gate records of NF_SVJP_PATH_GEMM
+ * (what one call of B patches needs: one record per launched workgroup) */
 int nf_reserve_sample_vjp_workspace(nf_handle *h, int64_t B, int32_t calls_in_flight);
 
 /* Host-only: the SDN5 scalars the kernels receive for a given (iso, cam):

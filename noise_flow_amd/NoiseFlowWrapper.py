@@ -56,7 +56,7 @@ class NoiseFlowWrapper:
         self.grad_kernel = grad_kernel   # 'scalar' | 'mfma' | 'gemm' (NoiseFlow); None: hps.grad_kernel, else 'scalar'
         self.grad_tiles = grad_tiles     # True: input gradients of images beyond 64x64 (NoiseFlow; with grad_kernel='mfma' also at widths 17 .. 32, with grad_kernel='gemm' beyond 32x32 at widths 33 .. 512); None: hps.grad_tiles, else False
         self.sample_vjp_tiles = sample_vjp_tiles   # True: differentiable sampling on every H x W at widths up to 16 (NoiseFlow; includes grad_tiles); None: hps.sample_vjp_tiles, else False
-        self.sample_vjp_kernel = sample_vjp_kernel   # 'scalar' | 'mfma' (NoiseFlow: differentiable sampling at widths 17 .. 32); None: hps.sample_vjp_kernel, else 'scalar'
+        self.sample_vjp_kernel = sample_vjp_kernel   # 'scalar' | 'mfma' | 'gemm' (NoiseFlow: differentiable sampling at widths 17 .. 32 / 33 .. 512); None: hps.sample_vjp_kernel, else 'scalar'
         self.hps = self.hps_loader(os.path.join(self.nf_path, "hps.txt"))
         if seed is not None:
             self.hps.seed = seed

@@ -30,6 +30,7 @@ NF_CFG_GRAD_TILED_WIDE = 32   # widths 17 .. 32: everything NF_CFG_GRAD_MFMA doe
 NF_CFG_GRAD_GEMM = 64   # widths 33 .. 512: the GEMM gradient kernel, whole patches up to 32x32
 NF_CFG_GRAD_TILED_GEMM = 128   # widths 33 .. 512: everything NF_CFG_GRAD_GEMM does, plus tiles of its kernel beyond 32x32
 NF_CFG_SVJP_MFMA = 256   # nf_sample_vjp at widths 17 .. 32 on the matrix cores; includes NF_CFG_GRAD_MFMA
+NF_CFG_SVJP_GEMM = 1024   # nf_sample_vjp at widths 33 .. 512 on the GEMM kernel (whole patches up to 32x32); includes NF_CFG_GRAD_GEMM
 NF_CFG_SVJP_TILED = 512   # nf_sample_vjp at widths up to 16 on every H, W: tiles and segments of nf_nll_grad's plan; includes NF_CFG_GRAD_TILED
 
 NF_ACCUMULATE = 1
@@ -229,7 +230,7 @@ EXPORTED_SYMBOLS = (
 )
 NF_GRAD_PATH_SCALAR, NF_GRAD_PATH_WIDE32, NF_GRAD_PATH_TILED, NF_GRAD_PATH_TILED_WIDE32, NF_GRAD_PATH_GEMM = 0, 1, 2, 3, 4
 NF_GRAD_PATH_TILED_GEMM = 5
-NF_SVJP_PATH_SCALAR, NF_SVJP_PATH_WIDE32, NF_SVJP_PATH_TILED = 0, 1, 2
+NF_SVJP_PATH_SCALAR, NF_SVJP_PATH_WIDE32, NF_SVJP_PATH_TILED, NF_SVJP_PATH_GEMM = 0, 1, 2, 3
 NF_PATH_SCALAR, NF_PATH_MFMA4, NF_PATH_FP16, NF_PATH_WIDE32, NF_PATH_WIDE16, NF_PATH_WIDE32_FP16, NF_PATH_GEMM, NF_PATH_GEMM_FP16 = 0, 1, 2, 3, 4, 5, 6, 7
 NF_PATH_SPLIT_BF16 = 8
 NF_BS_ROUTE_MFMA4, NF_BS_ROUTE_SCALAR, NF_BS_ROUTE_TRAINER = 0, 1, 2

@@ -782,7 +782,7 @@ int build_program(const nf_config *cfg, const nf_layer_desc *layers, const float
     out.tile_w = tw;
     out.segs.clear();
     if (cfg->n_layers < 1) return fail(NF_EINVAL, "n_layers must be >= 1");
-    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE | NF_CFG_GRAD_GEMM | NF_CFG_GRAD_TILED_GEMM | NF_CFG_SVJP_MFMA | NF_CFG_SVJP_TILED)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
+    if (cfg->flags & ~(NF_CFG_FP16_CNN | NF_CFG_EXACT_FP32 | NF_CFG_GRAD_MFMA | NF_CFG_GRAD_TILED | NF_CFG_GRAD_TILED_WIDE | NF_CFG_GRAD_GEMM | NF_CFG_GRAD_TILED_GEMM | NF_CFG_SVJP_MFMA | NF_CFG_SVJP_TILED | NF_CFG_SVJP_GEMM)) return fail(NF_EINVAL, "nf_config.flags has unknown bits set");
     const double HW = (double)cfg->height * cfg->width;
 
     // intermediate list in NLL order
@@ -1038,8 +1038,9 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
     if (tiles) tiles->clear();
     // NF_CFG_GRAD_GEMM: coupling widths beyond 32 — and nothing else — on the GEMM gradient kernel (nf_grad_gemm.hip): whole patches of
     // up to 32x32, fp32 handles, no tile mode whatever the other tile flags say.  NF_CFG_GRAD_TILED_GEMM: all of that, and every other
-    // shape on 32-pixel tiles of the same kernel, one launch per segment (kGradGemmSegs)
-    if ((cfg->flags & (NF_CFG_GRAD_GEMM | NF_CFG_GRAD_TILED_GEMM)) && fwd.lay[NF_PATH_SCALAR].prog.width > 32) {
+    // shape on 32-pixel tiles of the same kernel, one launch per segment (kGradGemmSegs).  NF_CFG_SVJP_GEMM includes NF_CFG_GRAD_GEMM:
+    // one gradient block serves nf_nll_grad and nf_sample_vjp
+    if ((cfg->flags & (NF_CFG_GRAD_GEMM | NF_CFG_GRAD_TILED_GEMM | NF_CFG_SVJP_GEMM)) && fwd.lay[NF_PATH_SCALAR].prog.width > 32) {
         const NfProgram &gprog = fwd.lay[NF_PATH_SCALAR].prog;
         const bool gemm_tiles = (cfg->flags & NF_CFG_GRAD_TILED_GEMM) != 0;
         if (cfg->flags & NF_CFG_FP16_CNN)
@@ -1133,8 +1134,10 @@ int grad_support(const nf_config *cfg, const Built &fwd, int *path = nullptr, st
 // gradient block on whole patches: whatever grad_support sends to NF_GRAD_PATH_SCALAR for this model, shape and flags.  With
 // NF_CFG_SVJP_MFMA, nf_sample_grad_wide.hip interprets the matrix-core block: whatever grad_support sends to NF_GRAD_PATH_WIDE32
 // (that kernel keeps inside nfgw_lds_floats).  With NF_CFG_SVJP_TILED, whatever grad_support sends to NF_GRAD_PATH_TILED (padded widths
-// 4 / 8 / 16) runs nf_sample_grad_kernel<.., TILED> on the gradient plan's tiles and segments (sample_vjp_tiled).  Either way the
-// width, register and LDS limits are nf_nll_grad's: no arithmetic here.
+// 4 / 8 / 16) runs nf_sample_grad_kernel<.., TILED> on the gradient plan's tiles and segments (sample_vjp_tiled).  With
+// NF_CFG_SVJP_GEMM, nf_sample_grad_gemm.hip interprets the GEMM block: whatever grad_support sends to NF_GRAD_PATH_GEMM (widths
+// 33 .. 512, whole patches up to 32x32, at most NFGG_MAX_COUPLINGS couplings); it has no tile mode.  Either way the width, register
+// and LDS limits are nf_nll_grad's: no arithmetic here.
 static int sample_vjp_support_(const nf_config *cfg, const Built &fwd, int *svjp_path)
 {
     if (svjp_path) *svjp_path = NF_SVJP_PATH_SCALAR;
@@ -1160,6 +1163,13 @@ static int sample_vjp_support_(const nf_config *cfg, const Built &fwd, int *svjp
         if (svjp_path) *svjp_path = NF_SVJP_PATH_WIDE32;
         return NF_OK;
     }
+    if (path == NF_GRAD_PATH_GEMM && (cfg->flags & NF_CFG_SVJP_GEMM)) {
+        if (svjp_path) *svjp_path = NF_SVJP_PATH_GEMM;
+        return NF_OK;
+    }
+    if (path == NF_GRAD_PATH_TILED_GEMM && (cfg->flags & NF_CFG_SVJP_GEMM))
+        return fail(NF_EINVAL, "nf_sample_vjp: coupling width %d under NF_CFG_SVJP_GEMM covers whole patches of up to 32x32 (a %dx%d patch is cut "
+                               "into tiles under NF_CFG_GRAD_TILED_GEMM; no tile mode yet)", fwd.raw_width, cfg->height, cfg->width);
     if (path == NF_GRAD_PATH_TILED)
         return fail(NF_EINVAL, "nf_sample_vjp: shapes the scalar gradient kernel holds whole (a %dx%d patch at coupling width %d is cut into "
                                "tiles under NF_CFG_GRAD_TILED; no tile mode yet)", cfg->height, cfg->width, fwd.raw_width);
@@ -1983,7 +1993,7 @@ int64_t nf_workspace_bytes(const nf_handle *h, int32_t direction, int64_t B)
 {
     if (!h || direction < 0 || direction > 3 || B < 0) return fail(NF_EINVAL, "bad argument");
     if (direction == 2) return (int64_t)grad_workspace_bytes(h, B);   // one tiled nf_nll_grad call
-    if (direction == 3) return (int64_t)svjp_workspace_bytes(h, B);   // one tiled nf_sample_vjp call
+    if (direction == 3) return (int64_t)svjp_workspace_bytes(h, B);   // one tiled nf_sample_vjp call, or the gate records of NF_SVJP_PATH_GEMM
     return (int64_t)tiled_workspace_bytes(h, direction, B, direction == 0);
 }
 
@@ -2423,10 +2433,14 @@ static Built::TileSeg svjp_fwd_seg(const nf_handle *h, int j)
 }
 
 // scratch of one call: the tile sums of the NLL-last segment's launch (gtemp), the S - 1 tensors between two segments, two gradient
-// tensors (ping-pong)
+// tensors (ping-pong).  NF_SVJP_PATH_GEMM: the gate records of the launch's workgroups — one per WORKGROUP, not per patch, the count
+// from the function the launcher takes its grid from (what grad_workspace_bytes gives for nf_nll_grad on the same handle)
 static size_t svjp_workspace_bytes(const nf_handle *h, int64_t B)
 {
-    if (h->svjp_rc != NF_OK || h->svjp_path != NF_SVJP_PATH_TILED || B <= 0) return 0;
+    if (h->svjp_rc != NF_OK || B <= 0) return 0;
+    if (h->svjp_path == NF_SVJP_PATH_GEMM)
+        return round_up_256((size_t)nf_grad_gemm_groups(B, h->n_cu) * nfgg_gate_halves(h->cfg.height * h->cfg.width, h->gprog.width, h->grad_n_cpl) * sizeof(uint16_t));
+    if (h->svjp_path != NF_SVJP_PATH_TILED) return 0;
     const int S = (int)h->grad_segs.size();
     const Built::TileSeg &last = h->grad_segs[S - 1];
     return round_up_256((size_t)B * last.ny * last.nx * sizeof(float)) + grad_img_bytes(h, B) * (size_t)(S - 1 + (S - 1 < 2 ? S - 1 : 2));
@@ -2610,11 +2624,21 @@ int nf_sample_vjp(nf_handle *h, const float *y, const float *eps, uint64_t seed,
     a.W = h->cfg.width;
     a.last_cpl = h->svjp_last_cpl;
     a.n_cpl = h->grad_n_cpl;
-    const bool wide = h->svjp_path == NF_SVJP_PATH_WIDE32;
-    a.gate_words = wide ? nfgw_tpw(a.H) * h->grad_n_cpl : nf_grad_gate_words(h->grad_n_cpl, h->gprog.width);
+    const bool wide = h->svjp_path == NF_SVJP_PATH_WIDE32, gemm = h->svjp_path == NF_SVJP_PATH_GEMM;
+    a.gate_words = gemm ? 0 : wide ? nfgw_tpw(a.H) * h->grad_n_cpl : nf_grad_gate_words(h->grad_n_cpl, h->gprog.width);   // (GEMM: device scratch)
     NfDeviceGuard guard;
     int rc = guard.enter(h->device);
     if (rc != NF_OK) return rc;
+    if (gemm) {
+        // the gate records live in a buffer of the handle's workspace set, as nf_nll_grad's on NF_GRAD_PATH_GEMM: one per call in
+        // flight, grown only by a call that needs more than any earlier one (nf_reserve_sample_vjp_workspace sizes it up front)
+        nf_handle::Workspace *wsp = nullptr;
+        if ((rc = ws_acquire(h, svjp_workspace_bytes(h, B), (hipStream_t)stream, &wsp)) != NF_OK) return rc;
+        const hipError_t eg = nf_launch_sample_grad_gemm(h->gprog, a, h->n_cu, wsp ? wsp->p : nullptr, wsp ? wsp->bytes : 0, (hipStream_t)stream);
+        ws_release(h, wsp, (hipStream_t)stream);
+        if (eg != hipSuccess) return fail_hip(eg, "nf_sample_vjp launch (GEMM)");
+        return NF_OK;
+    }
     const hipError_t e = wide ? nf_launch_sample_grad_wide(h->gprog, a, h->n_cu, (hipStream_t)stream)
                               : nf_launch_sample_grad(h->gprog, a, h->n_cu, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "nf_sample_vjp launch");

@@ -62,7 +62,8 @@ int nf_bs_wide_create(const nf_config *cfg, const nf_layer_desc *layers, const f
 int64_t nf_bs_wide_capacity(const nf_trainer *t);
 int nf_bs_wide_run(nf_trainer *t, const nf_bs_wide_args &a, hipStream_t st);
 
-// The gradient kernels' launchers (nf_grad.hip, nf_grad_wide.hip, nf_grad_gemm.hip, nf_sample_grad.hip, nf_sample_grad_wide.hip), called by nf_host.hip, which has
+// The gradient kernels' launchers (nf_grad.hip, nf_grad_wide.hip, nf_grad_gemm.hip, nf_sample_grad.hip, nf_sample_grad_wide.hip,
+// nf_sample_grad_gemm.hip), called by nf_host.hip, which has
 // checked the supported set (grad_support, sample_vjp_support).  `tiled`: one segment of a tiled call (nf_device.h, "gradient tiles") —
 // `prog` = the segment's ops, a.H x a.W = the tile, a.B = images x tiles, n_cpl = the couplings of the call's largest segment (what
 // a.gate_words / the scratch were sized by); otherwise whole patches and n_cpl = the program's couplings.
@@ -83,3 +84,6 @@ hipError_t nf_launch_sample_grad_tiled(const NfProgram &prog, const NfSampleGrad
 hipError_t nf_launch_tile_sum(const float *part, int nt, int64_t B, float *out, hipStream_t stream);
 // NF_SVJP_PATH_WIDE32: programs over the NFGW_* block, a.gate_words = nfgw_tpw(a.H) x a.n_cpl
 hipError_t nf_launch_sample_grad_wide(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, hipStream_t stream);
+// NF_SVJP_PATH_GEMM (nf_sample_grad_gemm.hip): programs over the NFGG_* block; `scratch` as nf_launch_grad_gemm's, sized by a.n_cpl
+hipError_t nf_launch_sample_grad_gemm(const NfProgram &prog, const NfSampleGradLaunch &a, int n_cu, void *scratch, size_t scratch_bytes,
+                                      hipStream_t stream);

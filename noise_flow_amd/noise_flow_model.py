@@ -199,19 +199,23 @@ class FlowHandle:
             raise ValueError("grad_kernel must be 'scalar', 'mfma' or 'gemm'")
         if grad_kernel in ("mfma", "gemm") and cnn_dtype == "fp16":
             raise ValueError("grad_kernel='%s' needs an fp32 handle (cnn_dtype='fp16' has no gradient kernel)" % grad_kernel)
-        if sample_vjp_kernel not in ("scalar", "mfma"):
-            raise ValueError("sample_vjp_kernel must be 'scalar' or 'mfma'")
-        if sample_vjp_kernel == "mfma" and cnn_dtype == "fp16":
-            raise ValueError("sample_vjp_kernel='mfma' needs an fp32 handle (cnn_dtype='fp16' has no gradient kernel)")
+        if sample_vjp_kernel not in ("scalar", "mfma", "gemm"):
+            raise ValueError("sample_vjp_kernel must be 'scalar', 'mfma' or 'gemm'")
+        if sample_vjp_kernel in ("mfma", "gemm") and cnn_dtype == "fp16":
+            raise ValueError("sample_vjp_kernel='%s' needs an fp32 handle (cnn_dtype='fp16' has no gradient kernel)" % sample_vjp_kernel)
+        if sample_vjp_kernel == "gemm" and int(width) <= 32:
+            raise ValueError("sample_vjp_kernel='gemm' is the kernel of coupling widths 33 .. 512 (width %d given: 'scalar' or 'mfma')" % int(width))
         flags = {"fp32": 0, "fp16": _lib.NF_CFG_FP16_CNN, "fp32_exact": _lib.NF_CFG_EXACT_FP32}[cnn_dtype]
         flags |= _lib.NF_CFG_SVJP_MFMA if sample_vjp_kernel == "mfma" else 0   # includes NF_CFG_GRAD_MFMA
         flags |= _lib.NF_CFG_GRAD_MFMA if grad_kernel == "mfma" else 0
         flags |= _lib.NF_CFG_GRAD_GEMM if grad_kernel == "gemm" else 0   # widths 33 .. 512: the GEMM gradient kernel
+        flags |= _lib.NF_CFG_SVJP_GEMM if sample_vjp_kernel == "gemm" else 0   # widths 33 .. 512; includes NF_CFG_GRAD_GEMM
         flags |= _lib.NF_CFG_GRAD_TILED if grad_tiles else 0
         flags |= _lib.NF_CFG_SVJP_TILED if sample_vjp_tiles else 0   # includes NF_CFG_GRAD_TILED
         wide = grad_kernel == "mfma" or (sample_vjp_kernel == "mfma" and grad_kernel == "scalar")   # NF_CFG_SVJP_MFMA includes NF_CFG_GRAD_MFMA
         flags |= _lib.NF_CFG_GRAD_TILED_WIDE if (grad_tiles and wide) else 0   # width 32: tiles of the matrix-core kernel
-        flags |= _lib.NF_CFG_GRAD_TILED_GEMM if (grad_tiles and grad_kernel == "gemm") else 0   # widths 33 .. 512: tiles of the GEMM kernel
+        gemm = grad_kernel == "gemm" or (sample_vjp_kernel == "gemm" and grad_kernel == "scalar")   # NF_CFG_SVJP_GEMM includes NF_CFG_GRAD_GEMM
+        flags |= _lib.NF_CFG_GRAD_TILED_GEMM if (grad_tiles and gemm) else 0   # widths 33 .. 512: tiles of the GEMM kernel
         cfg = _lib.nf_config(H, W, Cc, len(self.layers), -1 if device is None else int(device), flags)
         self._model_args = (cfg, descs, flat)   # what nf_cond_rows takes (kept alive with the handle)
         h = C.c_void_p()
@@ -282,12 +286,15 @@ class NoiseFlow(object):
           the matrix-core gradient kernel (``NF_CFG_GRAD_TILED_WIDE``), and together with grad_kernel='gemm' at coupling widths
           33 .. 512, on tiles of the GEMM gradient kernel (``NF_CFG_GRAD_TILED_GEMM``; without grad_tiles those widths stay at
           patches of up to 32x32).  Default ``False``; also selectable as ``hps.grad_tiles``.
-    sample_vjp_kernel : 'scalar' (default) | 'mfma' — which kernel ``sample_and_vjp`` / ``sample_torch`` run at coupling widths
+    sample_vjp_kernel : 'scalar' (default) | 'mfma' | 'gemm' — which kernel ``sample_and_vjp`` / ``sample_torch`` run at coupling widths
           17 .. 32: 'mfma' is the matrix-core kernel (patches up to 32x32, ``NF_CFG_SVJP_MFMA``), the only one that holds the
           paper's width 32 on 32x32 patches (the scalar kernel's LDS tile ends near 24x24 there).  It includes
           grad_kernel='mfma': one gradient block serves ``nll_torch`` and ``sample_torch``.  No effect on narrower models.
           Where both kernels hold the shape the matrix-core one was the faster (1.36 x at 24x24, 1.10 x at 16x16, width 32 x 8
           couplings; smaller shapes were not measured).
+          'gemm' is the GEMM kernel of coupling widths 33 .. 512 (whole patches up to 32x32, ``NF_CFG_SVJP_GEMM``), which have no
+          differentiable sampling without it; it includes grad_kernel='gemm' and is accepted only for a model whose coupling
+          width is beyond 32 (``ValueError`` otherwise).
           Also selectable as ``hps.sample_vjp_kernel``; not with cnn_dtype='fp16'.
     sample_vjp_tiles : ``True`` lets ``sample_and_vjp`` / ``sample_torch`` take every H, W up to 4096 at coupling widths up to 16:
           a shape the whole-patch kernel does not hold runs on the tiles and segments of ``nll_and_grad``'s plan

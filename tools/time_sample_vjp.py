@@ -18,6 +18,15 @@ the same three CNN evaluations per coupling) and nf_sample of the same handle.  
 nf_sample_vjp of a handle without the flag, arms alternated `--reps` times; per arm the median and the spread (max - min) of its
 `--reps` medians, and the difference read against twice the larger spread.
 
+    python tools/time_sample_vjp.py --kernel gemm [--widths 64,128,512] [--reps 3] [--launches 20] [--batch 1024]
+
+The GEMM kernel (csrc/nf_sample_grad_gemm.hip, sample_vjp_kernel="gemm", NF_SVJP_PATH_GEMM) on FULL_ARCH (8 couplings) at each width,
+32x32, temp 0.6, weights of `default_hps` initialisation.  nf_sample_vjp (all outputs), nf_nll_grad (NF_GRAD_PATH_GEMM: the same three CNN
+evaluations per coupling) and nf_sample of the same handle, ALTERNATED: `--reps` rounds, one window of `--launches` launches per call
+and round after a warm-up window; per call the median of its windows and their spread (max - min), the two ratios, and the fraction
+of the fp32 matrix peak (157.3 TFLOP/s) at three CNN evaluations per coupling.  The workspace is reserved first.  (`--launches` may be
+below 200 here: a launch is 5 .. 120 ms.)
+
     python tools/time_sample_vjp.py --legs tiled [--reps 3]
 
 The tile mode (sample_vjp_tiles=True, NF_SVJP_PATH_TILED) on the shipped model at 256x256 x 16 and 1024x1024 x 1, temp 0.6, under the
@@ -39,6 +48,67 @@ if os.environ.get("NF_TOOL_LIB"):   # A/B a differently-built library (this tool
     _nf_lib.LIB_PATH = os.path.abspath(os.environ["NF_TOOL_LIB"])
 
 
+def gemm_legs(a):
+    import numpy as np
+    import torch
+    from noise_flow_amd import NoiseFlow, _lib, default_hps
+    torch.cuda.set_device(0)
+    B, temp, side = a.batch, 0.6, 32
+    reps = a.reps or 3
+    cond = _lib.nf_cond(800.0, 2.0, 0.0, 0.0)
+    res = {"B": B, "temp": temp, "launches_per_window": a.launches, "reps": reps, "widths": {}}
+    rng = np.random.RandomState(0)
+    y = torch.as_tensor(rng.rand(B, side, side, 4).astype(np.float32)).cuda()
+    eps, g = (torch.as_tensor(rng.randn(B, side, side, 4).astype(np.float32)).cuda() for _ in range(2))
+    x = torch.as_tensor((rng.randn(B, side, side, 4) * 0.02).astype(np.float32)).cuda()
+    nll, gt = (torch.empty((B,), device="cuda") for _ in range(2))
+    o1, o2, o3 = (torch.empty_like(y) for _ in range(3))
+
+    def window(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    for width in [int(q) for q in a.widths.split(",") if q]:
+        m = NoiseFlow([side, side, 4], False, default_hps(arch=FULL_ARCH, width=width), device=0, sample_vjp_kernel="gemm")
+        lib, h, st = m._flow.lib, m._flow.ptr, m._dev.stream_ptr()
+        assert lib.nf_sample_vjp_path(h) == _lib.NF_SVJP_PATH_GEMM and lib.nf_grad_path(h) == _lib.NF_GRAD_PATH_GEMM
+        _lib.check(lib.nf_reserve_sample_vjp_workspace(h, B, 1))
+        calls = {
+            "sample": lambda: _lib.check(lib.nf_sample(h, y.data_ptr(), eps.data_ptr(), 0, 0, temp, B, C.byref(cond), o1.data_ptr(), st)),
+            "nll_grad": lambda: _lib.check(lib.nf_nll_grad(h, x.data_ptr(), y.data_ptr(), B, C.byref(cond), None, nll.data_ptr(), o1.data_ptr(),
+                                                           o2.data_ptr(), st)),
+            "vjp": lambda: _lib.check(lib.nf_sample_vjp(h, y.data_ptr(), eps.data_ptr(), 0, 0, temp, B, C.byref(cond), None, g.data_ptr(),
+                                                        o1.data_ptr(), o2.data_ptr(), o3.data_ptr(), gt.data_ptr(), st)),
+        }
+        for fn in calls.values():
+            window(fn, max(a.launches // 4, 2))
+        wins = {k: [] for k in calls}
+        for _ in range(reps):
+            for k, fn in calls.items():
+                wins[k].append(window(fn, a.launches))
+        med = {k: sorted(w)[len(w) // 2] for k, w in wins.items()}
+        wp = 64 if width <= 64 else 128 if width <= 128 else 256 if width <= 256 else 512
+        flop = 3.0 * 8 * B * side * side * 2.0 * (18 * wp + wp * wp + 36 * wp)   # three CNN evaluations per coupling, padded width
+        r = {"ms": med, "windows": wins, "spread_ms": {k: max(w) - min(w) for k, w in wins.items()},
+             "vjp_over_nll_grad": med["vjp"] / med["nll_grad"], "vjp_over_sample": med["vjp"] / med["sample"],
+             "vjp_peak_fraction": flop / (med["vjp"] * 1e-3) / 157.3e12, "nll_grad_peak_fraction": flop / (med["nll_grad"] * 1e-3) / 157.3e12}
+        res["widths"][str(width)] = r
+        fmt = lambda w: "/".join("%.3f" % q for q in w)   # noqa: E731
+        print("width %d  nf_sample %.3f ms [%s]   nf_nll_grad %.3f ms [%s]   nf_sample_vjp %.3f ms [%s]\n"
+              "          vjp / nll_grad %.3f   vjp / sample %.2f   of the fp32 matrix peak: vjp %.2f, nll_grad %.2f"
+              % (width, med["sample"], fmt(wins["sample"]), med["nll_grad"], fmt(wins["nll_grad"]), med["vjp"], fmt(wins["vjp"]),
+                 r["vjp_over_nll_grad"], r["vjp_over_sample"], r["vjp_peak_fraction"], r["nll_grad_peak_fraction"]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=200)
@@ -48,7 +118,11 @@ def main():
     ap.add_argument("--reps", type=int, default=None, help="rounds of alternated arms (default 4; --legs tiled: 3)")
     ap.add_argument("--ab-sides", default="24,16")
     ap.add_argument("--legs", default="whole", help="'whole' (default): the whole-patch kernels; 'tiled': the tile mode on 256x256 x 16 and 1024x1024 x 1")
+    ap.add_argument("--widths", default="64,128,512", help="--kernel gemm: the coupling widths")
+    ap.add_argument("--batch", type=int, default=1024, help="--kernel gemm: patches per launch")
     a = ap.parse_args()
+    if a.kernel == "gemm":
+        return gemm_legs(a)
     if a.reps is None:
         a.reps = 3 if a.legs == "tiled" else 4
     if a.legs not in ("whole", "tiled"):
